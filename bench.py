@@ -7,11 +7,15 @@ in HBM, followed (N_gpus > 1) by the RCCL all-gather of the B log-L values — t
 of BASELINE.json configs[2]/[3] (B = 4096 per GPU; weak scaling: 8 GPUs = 32768 draws).
 
   python bench.py [--gpus N --steps K --warmup W] [--batch B] [--n N] [--basis SHO|DRWCelerite]
+                  [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task description; DESIGN.md section 7 explains the
-roofline and cpu_baseline objects).  At N_gpus = 1 the line also carries a `secondary` object with
-the other BASELINE.json configurations, each event- or wall-timed in this same process:
+Prints ONE JSON line on rank 0 (DESIGN.md section 7 explains the roofline and cpu_baseline objects).
+A plain run sets up, warms up, times the K steps and prints the line; --dump-outputs DIR writes the
+last timed step's log L and status flags as .npy files (seeded inputs: identical from run to run).
+With --full at N_gpus = 1 the line also carries the CPU baseline with the parity figures against the
+oracle, the FMA-ceiling probe and a `secondary` object with the other BASELINE.json configurations,
+each event- or wall-timed in this same process:
 DRWCelerite-20 at B = 4096 (the model BASELINE's configs name; roofline fraction on the rows the
 kernel EXECUTES and on the reference's count), the single evaluation (configs[0], [1]: N = 1e3 and
 1e4, B = 1), the dense path (configs[4]: N = 4096, J = 40) and the PCIe-inclusive host-pointer entries.
@@ -236,8 +240,14 @@ def main():
     ap.add_argument("--n", type=int, default=10_000)
     ap.add_argument("--components", type=int, default=20)
     ap.add_argument("--basis", default="SHO", choices=["SHO", "DRWCelerite"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the other BASELINE configurations (N_gpus = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the FMA-ceiling probe and (N_gpus = 1) the CPU baseline with the parity figures and the other "
+                         "BASELINE configurations; without it a run does only what the headline figure needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity figures")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the other BASELINE configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy: logl (float64; the gathered vector when N_gpus > 1) "
+                         "and status (rank 0's status flags as float64)")
     ap.add_argument("--verify-gather", action="store_true",
                     help="N_gpus > 1: rank 0 re-evaluates every rank's batch on its own GPU and compares with the gathered vector")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
@@ -251,6 +261,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     import torch
 
@@ -391,6 +403,12 @@ def main():
 
     out_host = dout.cpu().numpy()
     st_host = dst.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step (the inputs are seeded: two builds compare value for value)
+        dump = Path(args.dump_outputs)
+        dump.mkdir(parents=True, exist_ok=True)
+        np.save(dump / "logl.npy", (gathered.cpu().numpy() if use_dist else out_host).astype(np.float64))
+        np.save(dump / "status.npy", st_host.astype(np.float64))
     ms_per_step = 1e3 * elapsed / args.steps
     value = B * world * args.steps / elapsed
     kern_ms = kernel_ms / args.steps
@@ -406,7 +424,7 @@ def main():
     # SIMD), measured straight after the timed loop while the chip is warm: the ceiling of any FP64 vector kernel here (the vendor peak
     # assumes one FMA per SIMD every 4 cycles at 2.4 GHz; the chip issues one every ~4.6 at ~1.9-2.2 GHz under this load)
     fma_ceiling = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             fma_ceiling = float(np.median([ctx.fp64_probe(2, 20.0) for _ in range(3)]))
         except Exception as exc:      # an older library without the probe entry
@@ -445,10 +463,10 @@ def main():
         "status_ok_frac": float((st_host == 0).mean()),
     }
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import oracle as O  # checker + CPU baseline only
         result.update(cpu_baseline_leg(O, A, Bc, C, Dd, t, y, yerr, mu, nu, out_host, st_host, N, Jt))
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if rank == 0 and world == 1 and args.full and not args.no_secondary:
         from oracle import oracle as O  # checker only
         result["secondary"] = secondary_configs(pj, torch, O, dev, stream, ctx, t, y, yerr, theta, f_min, f_max, args)
         for k, g in result["secondary"].items():

@@ -29,7 +29,7 @@ for tag, basis in (("sho", "SHO"), ("drwcelerite", "DRWCelerite")):
     krow = max((r for r in rows if "celerite_scan_kernel" in r["Name"] or "celerite_tile_kernel" in r["Name"]), key=lambda r: float(r["TotalDurationNs"]))
     pre = [r for r in rows if "tile_pairs" in r["Name"]]
     kmatch = "celerite_tile_kernel" if "celerite_tile_kernel" in krow["Name"] else "celerite_scan_kernel"
-    out = {"command": f"rocprofv3 --pmc <counters> --output-format csv -- python3 bench.py --no-cpu-baseline --no-secondary --basis {basis} "
+    out = {"command": f"rocprofv3 --pmc <counters> --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-secondary --basis {basis} "
                       "--steps 2 --warmup 1   (one pass per counter group: FETCH_SIZE | WRITE_SIZE | SQ_* | GRBM_*; tools/run_profiles.sh)",
            "kernel": krow["Name"], "kernel_config": plain["config"]["kernel_config"], "scan_source_hash": bench.scan_source_hash(),
            "workload": plain["config"]["workload"],
