@@ -167,7 +167,11 @@ static inline bool launch_pairs_mfma(const ScanParams& p, hipStream_t stream, Ar
 // ST (gradient, round 5): the forward pass of the one-draw-per-wavefront reverse mode — it leaves the lower tiles of T at the START of every window
 // in p.gw ([draw][window][tile][lane][register], NB (NB + 1) / 2 x 2 KB per window) and nothing else: the reverse kernel
 // (celerite_tile_adjoint_kernel) recomputes M', Sigma, the LDL' and Q' from it.  The value is bit-identical to the plain kernel's.
-template <int NB, bool ST = false>
+// KL (round 7): the K-steps of the last row block that hold a state row, ceil((R - 16 (NB - 1)) / 4), 0 .. 4.  U~ is zero on every row r >= R (the y row
+// included: it has state in T but no u), and in M' = U~' T and G = U~' M the K index is the state row: the K-steps ks >= KL of block NB - 1 multiply an
+// exact zero.  They are neither loaded, formed nor issued (SHO-20: 84 -> 76 matrix instructions per window).  They are the last of every chain they
+// belong to, so dropping them changes no rounding.  KL = 0 (R = 16 (NB - 1): the y row alone in the last block) drops that block from M' and G.
+template <int NB, int KL = 4, bool ST = false>
 __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_tile_kernel(const ScanParams p, const double* __restrict__ btab,
                                                                                           const double* __restrict__ pairs)
 {
@@ -222,21 +226,26 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
     // U~ of window k, A-operand order: (row 16 I + 4 ks + q, step c16), from the record's C o v and C o x (coalesced 512-byte reads), one
     // row block at a time: the reads of block I + 1 are on their way while block column I of T is updated
     double cvn[4], cxn[4];
+    auto live_k = [](int I, int ks) constexpr { return I < NB - 1 || ks < KL; };   // K-step ks of row block I holds a state row
     auto fetch_u = [&](int64_t k, int I) __attribute__((always_inline)) {
         const int so = (int)k * rsb8;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
+            if (!live_k(I, ks)) continue;
             cvn[ks] = tile_bload(rs_tab, lane8, so + (I * 4 + ks) * 512);
             cxn[ks] = tile_bload(rs_tab, lane8, so + (NB * 256 + (I * 4 + ks) * 64) * 8);
         }
     };
     auto form_u = [&](int I) __attribute__((always_inline)) {
+        if (I == NB - 1 && KL == 0) return;
         double2 cf[4];          // the four (al, be) reads together, one wait (left to the compiler: read, wait, two FMAs, four times in a row)
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) cf[ks] = sw.albe[16 * I + 4 * ks + q];
+        for (int ks = 0; ks < 4; ++ks)
+            if (live_k(I, ks)) cf[ks] = sw.albe[16 * I + 4 * ks + q];
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) Uf[I][ks] = fma(cf[ks].x, cvn[ks], cf[ks].y * cxn[ks]);
+        for (int ks = 0; ks < 4; ++ks)
+            if (live_k(I, ks)) Uf[I][ks] = fma(cf[ks].x, cvn[ks], cf[ks].y * cxn[ks]);
     };
     // C_K and sigma2 of window k: fetched a window ahead, staged in LDS at the start of the window
     constexpr int NCK = (16 * NB + 16 + 63) / 64;
@@ -350,7 +359,8 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
 #pragma unroll
             for (int I = Jc; I < NB; ++I)
 #pragma unroll
-                for (int ks = 0; ks < 4; ++ks) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Uf[I][ks], T[tix(I, Jc)][ks], acc, 0, 0, 0);
+                for (int ks = 0; ks < 4; ++ks)
+                    if (live_k(I, ks)) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Uf[I][ks], T[tix(I, Jc)][ks], acc, 0, 0, 0);
             x[Jc] = acc;
         }
         PIORAN_TSTAMP(1);
@@ -369,16 +379,21 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
         }
 #pragma unroll
         for (int Jc = 0; Jc < NB; ++Jc) {
+            const bool gk = Jc < NB - 1 || KL > 0;      // block Jc of M' feeds G (KL = 0: the last block holds the y row alone)
+            if (gk) {
 #pragma unroll
-            for (int g = 0; g < 4; ++g) sw.scr[(4 * g + q) * 18 + c16] = x[Jc][g];
+                for (int g = 0; g < 4; ++g) sw.scr[(4 * g + q) * 18 + c16] = x[Jc][g];
+            }
             PIORAN_TILE_FWD_ORDER();
             double mb[4];   // M [row 16 Jc + 4 ks + q][step c16]
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) mb[ks] = sw.scr[c16 * 18 + 4 * ks + q];
+            for (int ks = 0; ks < 4; ++ks)
+                if (live_k(Jc, ks)) mb[ks] = sw.scr[c16 * 18 + 4 * ks + q];
             const double ckc = sw.ck[16 * Jc + c16];
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) G = __builtin_amdgcn_mfma_f64_16x16x4f64(Uf[Jc][ks], mb[ks], G, 0, 0, 0);
+            for (int ks = 0; ks < 4; ++ks)
+                if (live_k(Jc, ks)) G = __builtin_amdgcn_mfma_f64_16x16x4f64(Uf[Jc][ks], mb[ks], G, 0, 0, 0);
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 double v;
@@ -1498,7 +1513,7 @@ __global__ void __launch_bounds__(512) tile_pairs_grad_kernel(const ScanParams p
 template <int NB>
 constexpr size_t tile_lds_bytes() { return kTileWaves * sizeof(TileWave<NB>); }
 
-template <int NB>
+template <int NB, int KL>
 int launch_tile(const ScanParams& p, const double* btab, double* pairs, hipStream_t stream)
 {
     constexpr size_t lds = tile_lds_bytes<NB>();
@@ -1507,7 +1522,7 @@ int launch_tile(const ScanParams& p, const double* btab, double* pairs, hipStrea
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return PIORAN_ERR_HIP;
     if (!granted[dev]) {
-        if (hipFuncSetAttribute((const void*)celerite_tile_kernel<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return PIORAN_ERR_HIP;
+        if (hipFuncSetAttribute((const void*)celerite_tile_kernel<NB, KL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return PIORAN_ERR_HIP;
         granted[dev] = true;
     }
     const int64_t groups = (p.B + kTileWaves - 1) / kTileWaves;
@@ -1515,8 +1530,22 @@ int launch_tile(const ScanParams& p, const double* btab, double* pairs, hipStrea
     const int64_t NW = (p.N + KW - 1) / KW;
     if (NW > 0x7fffffffLL) return PIORAN_ERR_UNSUPPORTED;
     if (!launch_pairs_mfma(p, stream, btab, (int64_t)block_rec_doubles(NB, p.J), (int64_t)block_tile_doubles(NB), pairs)) return PIORAN_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL((celerite_tile_kernel<NB>), dim3((unsigned)groups), dim3(64 * kTileWaves), lds, stream, p, btab, (const double*)pairs);
+    hipLaunchKernelGGL((celerite_tile_kernel<NB, KL>), dim3((unsigned)groups), dim3(64 * kTileWaves), lds, stream, p, btab, (const double*)pairs);
     return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;
+}
+
+// the kernel for R rows: NB = ceil((R + 1) / 16) block columns, KL = ceil((R - 16 (NB - 1)) / 4) live K-steps in the last row block (NB = 1: R >= 1, KL >= 1)
+template <int NB>
+int launch_tile_rows(const ScanParams& p, const double* btab, double* pairs, hipStream_t stream)
+{
+    switch ((p.R - 16 * (NB - 1) + 3) / 4) {
+        case 0: if constexpr (NB > 1) return launch_tile<NB, 0>(p, btab, pairs, stream); break;
+        case 1: return launch_tile<NB, 1>(p, btab, pairs, stream);
+        case 2: return launch_tile<NB, 2>(p, btab, pairs, stream);
+        case 3: return launch_tile<NB, 3>(p, btab, pairs, stream);
+        case 4: return launch_tile<NB, 4>(p, btab, pairs, stream);
+    }
+    return PIORAN_ERR_UNSUPPORTED;
 }
 
 template <int NB>
@@ -1535,7 +1564,7 @@ int launch_tile_grad(const ScanParams& p, const double* btab, const double* gtab
     const bool cd = grad_c && grad_d;
     if ((grad_c != nullptr) != (grad_d != nullptr)) return PIORAN_ERR_ARG;
     if (!granted[dev]) {
-        if (hipFuncSetAttribute((const void*)celerite_tile_kernel<NB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f) != hipSuccess) return PIORAN_ERR_HIP;
+        if (hipFuncSetAttribute((const void*)celerite_tile_kernel<NB, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f) != hipSuccess) return PIORAN_ERR_HIP;
         if (hipFuncSetAttribute((const void*)celerite_tile_adjoint_kernel<NB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r) != hipSuccess) return PIORAN_ERR_HIP;
         if (hipFuncSetAttribute((const void*)celerite_tile_adjoint_kernel<NB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rc) != hipSuccess) return PIORAN_ERR_HIP;
         granted[dev] = true;
@@ -1545,7 +1574,7 @@ int launch_tile_grad(const ScanParams& p, const double* btab, const double* gtab
     if (groups > 0x7fffffffLL || NW > 0x7fffffffLL) return PIORAN_ERR_UNSUPPORTED;
     const int64_t rsb = block_rec_doubles(NB, p.J), tsp = block_tile_doubles(NB);
     if (!launch_pairs_mfma(p, stream, btab, rsb, tsp, pairs)) return PIORAN_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL((celerite_tile_kernel<NB, true>), dim3((unsigned)groups), dim3(64 * kTileWaves), lds_f, stream, p, btab, (const double*)pairs);
+    hipLaunchKernelGGL((celerite_tile_kernel<NB, 4, true>), dim3((unsigned)groups), dim3(64 * kTileWaves), lds_f, stream, p, btab, (const double*)pairs);   // (all four K-steps: KL = 4)
     const unsigned agroups = (unsigned)((p.B + AW - 1) / AW);
     if (cd) {
         hipLaunchKernelGGL((celerite_tile_adjoint_kernel<NB, true>), dim3((unsigned)((p.B + AWC - 1) / AWC)), dim3(64 * AWC), lds_rc, stream, p, btab, gtab, pairs, grad_a, grad_b,
@@ -1614,12 +1643,12 @@ int pioran_launch_scan_tile(const ScanParams& p, const double* btab, double* wor
     if (!btab || p.B < 1 || p.N < 1 || p.npd_rows != 0 || !pioran_tile_fits(p.R, p.J)) return PIORAN_ERR_UNSUPPORTED;
     if ((p.Y == nullptr) != (p.S2 == nullptr)) return PIORAN_ERR_ARG;
     switch ((p.R + 1 + 15) / 16) {
-        case 1: return launch_tile<1>(p, btab, work, stream);
-        case 2: return launch_tile<2>(p, btab, work, stream);
-        case 3: return launch_tile<3>(p, btab, work, stream);
-        case 4: return launch_tile<4>(p, btab, work, stream);
-        case 5: return launch_tile<5>(p, btab, work, stream);
-        case 6: return launch_tile<6>(p, btab, work, stream);
+        case 1: return launch_tile_rows<1>(p, btab, work, stream);
+        case 2: return launch_tile_rows<2>(p, btab, work, stream);
+        case 3: return launch_tile_rows<3>(p, btab, work, stream);
+        case 4: return launch_tile_rows<4>(p, btab, work, stream);
+        case 5: return launch_tile_rows<5>(p, btab, work, stream);
+        case 6: return launch_tile_rows<6>(p, btab, work, stream);
     }
     return PIORAN_ERR_UNSUPPORTED;
 }
