@@ -56,9 +56,6 @@ namespace {
 #ifndef PIORAN_TILE_RAGFIX4
 #define PIORAN_TILE_RAGFIX4 1     // ... at four block columns and more as a fix-up after the loop with the values loaded again: DRWCelerite-20 -1.5 %, same box
 #endif
-#ifndef PIORAN_TILE_QUADALL
-#define PIORAN_TILE_QUADALL 1     // a quadratic-form accumulator per block column, the y row's picked after the loop: -0.8 %, same box
-#endif
 #ifndef PIORAN_TILE_RAGFIX
 #define PIORAN_TILE_RAGFIX 1      // the ragged window's mask once per window under its wave-uniform test: -0.9 %, same box
 #endif
@@ -171,11 +168,17 @@ static inline bool launch_pairs_mfma(const ScanParams& p, hipStream_t stream, Ar
 // included: it has state in T but no u), and in M' = U~' T and G = U~' M the K index is the state row: the K-steps ks >= KL of block NB - 1 multiply an
 // exact zero.  They are neither loaded, formed nor issued (SHO-20: 84 -> 76 matrix instructions per window).  They are the last of every chain they
 // belong to, so dropping them changes no rounding.  KL = 0 (R = 16 (NB - 1): the y row alone in the last block) drops that block from M' and G.
-template <int NB, int KL = 4, bool ST = false>
+// The y row (row R of the state) always lies in the LAST block column: every launcher takes NB = ceil((R + 1) / 16), so 16 (NB - 1) <= R <= 16 NB - 1 and
+// R >> 4 == NB - 1 (the launchers check it).  The kernel knows it at compile time (round 8): mu, the quadratic form and the per-draw series touch block column
+// NB - 1 alone, the others carry none of the y row's special cases.
+// SER (round 8): the launch has per-draw series (p.Y, p.S2).  Without, their fetch, their staging in LDS and the fix-up of X' do not exist, and p.Y, p.S2 and
+// their tests hold no scalar registers through the window loop.  The gradient's forward pass (ST) never has one (pioran_launch_tile_grad refuses p.Y).
+template <int NB, int KL = 4, bool ST = false, bool SER = false>
 __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_tile_kernel(const ScanParams p, const double* __restrict__ btab,
                                                                                           const double* __restrict__ pairs)
 {
     constexpr int TS = 3 * NB * 256 + 16 * NB + 16, TSP = (TS + 127) & ~127;
+    static_assert(!(ST && SER), "the gradient's forward pass takes the shared series only");
     extern __shared__ double lds_[];
     const int tid = threadIdx.x;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -192,7 +195,8 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
     const __amdgpu_buffer_rsrc_t rs_pw = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(pairs + b * NW * 128), 0, 0x7ffffffc, 0x00020000);
     const int lane8 = lane * 8;
     const int rsb8 = (int)(RSB * 8);
-    const int Jy = R >> 4, ry = R & 15;            // block column / lane column of the y row
+    constexpr int Jy = NB - 1;                     // block column of the y row: R >> 4 == NB - 1 in every launch
+    const int ry = R & 15;                         // ... its lane column
     const double mu = p.mu ? p.mu[b] : 0.0;
     const double nu = p.nu ? p.nu[b] : 1.0;
     const bool has_nu = p.nu != nullptr;
@@ -271,10 +275,9 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
         for (int g = 0; g < 4; ++g) apre[g] = tile_bload(rs_pw, pidx[g], (int)k * 1024);
     };
     // per-draw series (y, sigma2) [B][N]: lanes 0 .. 15 fetch the window's sixteen steps a window ahead (clamped past the end: those steps are masked)
-    const bool has_series = p.Y != nullptr;
-    double ypre = 0.0, spre = 0.0;
+    [[maybe_unused]] double ypre = 0.0, spre = 0.0;
     auto fetch_series = [&](int64_t k) __attribute__((always_inline)) {
-        if (has_series) {
+        if constexpr (SER) {
             int64_t n = k * KW + c16;
             n = n < N ? n : N - 1;
             ypre = p.Y[b * N + n];
@@ -289,17 +292,10 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
         fetch_u(0, I);
         form_u(I);
     }
-    // the y row's column of X': v = y_n - mu in the lane column ry of block Jy (z_n = y_n - u'f, :141); elsewhere mu_sel = 0
-    double mu_sel[NB];
-#pragma unroll
-    for (int Jc = 0; Jc < NB; ++Jc) mu_sel[Jc] = (Jc == Jy && c16 == ry) ? mu : 0.0;
+    // the y row's column of X': v = y_n - mu in the lane column ry of block Jy (z_n = y_n - u'f, :141); the other lane columns of that block take mu_y = 0
+    const double mu_y = c16 == ry ? mu : 0.0;
     const int64_t k_ragged = (N % KW) ? NW - 1 : NW;   // the window whose steps past N are padding (none if N is a multiple of 16)
-    double quad = 0.0;                 // meaningful in the y-row lanes
-#if PIORAN_TILE_QUADALL
-    double quadb[NB];
-#pragma unroll
-    for (int I = 0; I < NB; ++I) quadb[I] = 0.0;
-#endif
+    double quad = 0.0;                 // block column Jy's; meaningful in the y-row lanes
     double Pm = 1.0;                   // per lane (step c16 of every window): running product of |D| (sign of D_1 kept: :126)
     int Pe = 0;
     bool nonpd = false;
@@ -312,7 +308,7 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
 #pragma unroll
         for (int i = 0; i < NCK; ++i)
             if (lane + 64 * i < 16 * NB + 16) sw.ck[lane + 64 * i] = ckpre[i];
-        if (has_series) {
+        if constexpr (SER) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             if (lane < 16) { sw.ys[lane] = ypre; sw.ck[16 * NB + lane] = spre; }
         }
@@ -339,7 +335,7 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
                 for (int I = 0; I < NB; ++I)
 #pragma unroll
                     for (int g = 0; g < 4; ++g)
-                        if (k * KW + 4 * g + q >= N) vha[I][g] = mu_sel[I];
+                        if (k * KW + 4 * g + q >= N) vha[I][g] = I == Jy ? mu_y : 0.0;
             }
 #endif
         }
@@ -372,8 +368,8 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
 #pragma unroll
             for (int g = 0; g < 4; ++g) vh[g] = tile_bload(rs_tab, lane8, wso + (2 * NB * 256 + g * 64) * 8);
         }
-        double ysv[4] = {0.0, 0.0, 0.0, 0.0};     // per-draw series: read here, under the wave-uniform test (inside the block-column loop the compiler turns the
-        if (has_series) {                         // test into a select and reads sw.ys for every block column, a wait each — also when there is no series)
+        [[maybe_unused]] double ysv[4] = {0.0, 0.0, 0.0, 0.0};     // per-draw series: read here, once per window
+        if constexpr (SER) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) ysv[g] = sw.ys[4 * g + q];
         }
@@ -399,9 +395,9 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
                 double v;
                 if constexpr (VHA) v = vha[Jc][g]; else v = vh[g];
 #if !PIORAN_TILE_YSFIX
-                if (has_series && Jc == Jy && c16 == ry) v = ysv[g];     // (the table's y row holds the shared series)
+                if (SER && Jc == Jy && c16 == ry) v = ysv[g];     // (the table's y row holds the shared series)
 #endif
-                v -= mu_sel[Jc];
+                if (Jc == Jy) v -= mu_y;
 #if PIORAN_TILE_RAGFIX && !PIORAN_TILE_RAGFIX4
                 if constexpr (!VHA)      // (four block columns and more: (C_K / C) o v arrives a block ahead; a forced branch per block there costs more than the selects — 16.7 -> 21.9 ms)
 #endif
@@ -429,27 +425,22 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
                         const double vt = tile_bload(rs_tab, lane8, wso + (2 * NB * 256 + (Jc * 4 + g) * 64) * 8);
-                        if (k * KW + 4 * g + q >= N) x[Jc][g] -= vt - mu_sel[Jc];
+                        if (k * KW + 4 * g + q >= N) x[Jc][g] -= Jc == Jy ? vt - mu_y : vt;
                     }
             }
         }
 #endif
 #if PIORAN_TILE_YSFIX
-        // per-draw series: X' = V^' - C_K o M' took the table's (shared) series in the y row; the draw's own replaces it here, under the wave-uniform test — as a
-        // select inside the block-column loop it cost 24 v_cndmask per window whether there is a series or not
-        if (has_series) {
-            static_for<0, NB>([&](auto Jcc) __attribute__((always_inline)) {
-                constexpr int Jc = decltype(Jcc)::value;
-                if (Jc == Jy) {
+        // per-draw series: X' = V^' - C_K o M' took the table's (shared) series in the y row; the draw's own replaces it here, in block column Jy alone — as a
+        // select inside the block-column loop it cost 24 v_cndmask per window
+        if constexpr (SER) {
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        double vt;
-                        if constexpr (VHA) vt = vha[Jc][g]; else vt = tile_bload(rs_tab, lane8, wso + (2 * NB * 256 + (Jc * 4 + g) * 64) * 8);
-                        const bool pad = k == k_ragged && k * KW + 4 * g + q >= N;
-                        if (c16 == ry && !pad) x[Jc][g] += ysv[g] - vt;
-                    }
-                }
-            });
+            for (int g = 0; g < 4; ++g) {
+                double vt;
+                if constexpr (VHA) vt = vha[Jy][g]; else vt = tile_bload(rs_tab, lane8, wso + (2 * NB * 256 + (Jy * 4 + g) * 64) * 8);
+                const bool pad = k == k_ragged && k * KW + 4 * g + q >= N;
+                if (c16 == ry && !pad) x[Jy][g] += ysv[g] - vt;
+            }
         }
 #endif
         PIORAN_TSTAMP(2);
@@ -537,11 +528,7 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 ysc[g] = yt[Jc][g] * idv[g];
-#if PIORAN_TILE_QUADALL
-                quadb[Jc] = fma(yt[Jc][g], ysc[g], quadb[Jc]);         // z_n^2 / D_n (== y'K^-1 y, :333) of EVERY block column; the y row's is picked after the loop
-#else                                                                  // (picked here — `if (Jc == Jy)` — it is an FMA and two v_cndmask per block column and step)
                 if (Jc == Jy) quad = fma(yt[Jc][g], ysc[g], quad);     // z_n^2 / D_n (== y'K^-1 y, :333), in the y-row lanes
-#endif
             }
 #pragma unroll
             for (int I = Jc; I < NB; ++I) {
@@ -563,11 +550,6 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
     PIORAN_TSTAMP_FLUSH
     // ---- result ------------------------------------------------------------------------------------------------------------
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#if PIORAN_TILE_QUADALL
-#pragma unroll
-    for (int I = 0; I < NB; ++I)
-        if (I == Jy) quad = quadb[I];
-#endif
     if (c16 == ry) sw.scr[q] = quad;
     if (q == 0) sw.scr[16 + c16] = log(Pm) + (double)Pe * 0.6931471805599453094;
     const bool any_nonpd = __builtin_amdgcn_ballot_w64(nonpd) != 0;
@@ -650,7 +632,8 @@ __global__ void __launch_bounds__((64 * tile_adj_waves<NB, CD>()), 1) celerite_t
     const double* const gtb = p.gw + b * NW * NT * 256;       // T_k of this draw
     const int lane8 = lane * 8;
     const int rsb8 = (int)(RSB * 8), gs8 = (int)(GS * 8);
-    const int Jy = R >> 4, ry = R & 15;
+    constexpr int Jy = NB - 1;       // R >> 4 == NB - 1 in every launch (celerite_tile_kernel); the masked arithmetic below stays as it is: dropping a product
+    const int ry = R & 15;           // with ymask = 0 would change the result where its other factor is not finite
     const double mu = p.mu ? p.mu[b] : 0.0;
     const double nu = p.nu ? p.nu[b] : 1.0;
     const bool has_nu = p.nu != nullptr;
@@ -1513,16 +1496,17 @@ __global__ void __launch_bounds__(512) tile_pairs_grad_kernel(const ScanParams p
 template <int NB>
 constexpr size_t tile_lds_bytes() { return kTileWaves * sizeof(TileWave<NB>); }
 
-template <int NB, int KL>
+template <int NB, int KL, bool SER>
 int launch_tile(const ScanParams& p, const double* btab, double* pairs, hipStream_t stream)
 {
+    if ((p.R >> 4) != NB - 1) return PIORAN_ERR_UNSUPPORTED;   // the kernel's compile-time y block column
     constexpr size_t lds = tile_lds_bytes<NB>();
     static_assert(lds <= 160 * 1024, "one workgroup must fit a CU");
     static bool granted[64] = {};   // (function, device): one process may drive several devices (pioran_farm_*); racing threads at worst set it twice
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return PIORAN_ERR_HIP;
     if (!granted[dev]) {
-        if (hipFuncSetAttribute((const void*)celerite_tile_kernel<NB, KL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return PIORAN_ERR_HIP;
+        if (hipFuncSetAttribute((const void*)celerite_tile_kernel<NB, KL, false, SER>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return PIORAN_ERR_HIP;
         granted[dev] = true;
     }
     const int64_t groups = (p.B + kTileWaves - 1) / kTileWaves;
@@ -1530,22 +1514,27 @@ int launch_tile(const ScanParams& p, const double* btab, double* pairs, hipStrea
     const int64_t NW = (p.N + KW - 1) / KW;
     if (NW > 0x7fffffffLL) return PIORAN_ERR_UNSUPPORTED;
     if (!launch_pairs_mfma(p, stream, btab, (int64_t)block_rec_doubles(NB, p.J), (int64_t)block_tile_doubles(NB), pairs)) return PIORAN_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL((celerite_tile_kernel<NB, KL>), dim3((unsigned)groups), dim3(64 * kTileWaves), lds, stream, p, btab, (const double*)pairs);
+    hipLaunchKernelGGL((celerite_tile_kernel<NB, KL, false, SER>), dim3((unsigned)groups), dim3(64 * kTileWaves), lds, stream, p, btab, (const double*)pairs);
     return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;
 }
 
 // the kernel for R rows: NB = ceil((R + 1) / 16) block columns, KL = ceil((R - 16 (NB - 1)) / 4) live K-steps in the last row block (NB = 1: R >= 1, KL >= 1)
-template <int NB>
+template <int NB, bool SER>
 int launch_tile_rows(const ScanParams& p, const double* btab, double* pairs, hipStream_t stream)
 {
     switch ((p.R - 16 * (NB - 1) + 3) / 4) {
-        case 0: if constexpr (NB > 1) return launch_tile<NB, 0>(p, btab, pairs, stream); break;
-        case 1: return launch_tile<NB, 1>(p, btab, pairs, stream);
-        case 2: return launch_tile<NB, 2>(p, btab, pairs, stream);
-        case 3: return launch_tile<NB, 3>(p, btab, pairs, stream);
-        case 4: return launch_tile<NB, 4>(p, btab, pairs, stream);
+        case 0: if constexpr (NB > 1) return launch_tile<NB, 0, SER>(p, btab, pairs, stream); break;
+        case 1: return launch_tile<NB, 1, SER>(p, btab, pairs, stream);
+        case 2: return launch_tile<NB, 2, SER>(p, btab, pairs, stream);
+        case 3: return launch_tile<NB, 3, SER>(p, btab, pairs, stream);
+        case 4: return launch_tile<NB, 4, SER>(p, btab, pairs, stream);
     }
     return PIORAN_ERR_UNSUPPORTED;
+}
+template <int NB>
+int launch_tile_rows(const ScanParams& p, const double* btab, double* pairs, hipStream_t stream)
+{
+    return p.Y ? launch_tile_rows<NB, true>(p, btab, pairs, stream) : launch_tile_rows<NB, false>(p, btab, pairs, stream);
 }
 
 template <int NB>
@@ -1560,11 +1549,12 @@ int launch_tile_grad(const ScanParams& p, const double* btab, const double* gtab
     static_assert(lds_f <= 160 * 1024 && lds_r <= 160 * 1024 && lds_rc <= 160 * 1024, "one workgroup must fit a CU");
     static bool granted[64] = {};
     int dev = 0;
+    if ((p.R >> 4) != NB - 1) return PIORAN_ERR_UNSUPPORTED;   // the kernels' compile-time y block column
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return PIORAN_ERR_HIP;
     const bool cd = grad_c && grad_d;
     if ((grad_c != nullptr) != (grad_d != nullptr)) return PIORAN_ERR_ARG;
     if (!granted[dev]) {
-        if (hipFuncSetAttribute((const void*)celerite_tile_kernel<NB, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f) != hipSuccess) return PIORAN_ERR_HIP;
+        if (hipFuncSetAttribute((const void*)celerite_tile_kernel<NB, 4, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f) != hipSuccess) return PIORAN_ERR_HIP;
         if (hipFuncSetAttribute((const void*)celerite_tile_adjoint_kernel<NB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r) != hipSuccess) return PIORAN_ERR_HIP;
         if (hipFuncSetAttribute((const void*)celerite_tile_adjoint_kernel<NB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rc) != hipSuccess) return PIORAN_ERR_HIP;
         granted[dev] = true;
@@ -1574,7 +1564,7 @@ int launch_tile_grad(const ScanParams& p, const double* btab, const double* gtab
     if (groups > 0x7fffffffLL || NW > 0x7fffffffLL) return PIORAN_ERR_UNSUPPORTED;
     const int64_t rsb = block_rec_doubles(NB, p.J), tsp = block_tile_doubles(NB);
     if (!launch_pairs_mfma(p, stream, btab, rsb, tsp, pairs)) return PIORAN_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL((celerite_tile_kernel<NB, 4, true>), dim3((unsigned)groups), dim3(64 * kTileWaves), lds_f, stream, p, btab, (const double*)pairs);   // (all four K-steps: KL = 4)
+    hipLaunchKernelGGL((celerite_tile_kernel<NB, 4, true, false>), dim3((unsigned)groups), dim3(64 * kTileWaves), lds_f, stream, p, btab, (const double*)pairs);   // (all four K-steps: KL = 4)
     const unsigned agroups = (unsigned)((p.B + AW - 1) / AW);
     if (cd) {
         hipLaunchKernelGGL((celerite_tile_adjoint_kernel<NB, true>), dim3((unsigned)((p.B + AWC - 1) / AWC)), dim3(64 * AWC), lds_rc, stream, p, btab, gtab, pairs, grad_a, grad_b,
