@@ -224,6 +224,24 @@ int pioran_logpdf_batch_theta(pioran_ds* ds, int64_t B, int model, int64_t n_com
 int pioran_celerite_predict(pioran_ds* ds, int64_t B, int64_t J, const double* A, const double* Bc, const double* C,
                             const double* Dd, int cd_shared, const double* mu, const double* nu, int64_t M, const double* tau,
                             double* mean_out, int32_t* status);
+/* Posterior variance of the latent process at new times (what sqrt.(diag(predict_cov(...))) of src/scalable_GP.jl:103-104 obtains from a dense
+ * (N + M) x (N + M) Cholesky), through the celerite factorisation in O((N + M) R^2) per draw:
+ *     var_out[b][m] = k_b(0) - k*' K_b^-1 k*,   k*_n = k_b(|tau_m - t_n|),  K_b = kernel_b + diag(nu_b sigma2),  k_b(0) = sum_j a_j
+ * (no measurement noise added, as predict_cov gives it; mu does not enter and the data set's y is ignored).  The factor (W_n, D_n) is stored by the
+ * latency kernel as for the step-by-step prediction; a forward walk carries S+_n = S_n + D_n W_n W_n' and a backward walk
+ * B_n = U~_n U~_n'/D_n + A_n' B_{n+1} A_n, A_n = diag(phi_{n+1}) (I - W_n U~_n'), one wavefront per draw with the R x R matrix in registers
+ * (celerite_predict.hip); no R x R matrix goes to memory: the workspace beyond the factor is M (R rounded up to 16, + 1) doubles per draw,
+ * draws are processed in chunks sized to the free memory.
+ * The result is a difference of numbers of the size of k(0): its error is ABSOLUTE on the scale of k(0) (measured: 3e-12 k(0) at N = 2000 against
+ * the dense formula, which has the same property with a smaller constant; docs/EXPERIMENTS.md section 16) — a variance far below k(0) carries a correspondingly larger relative error.
+ * tau: M >= 0 evaluation times in any order (an index is sorted on the host and the result scattered back); a non-finite tau: PIORAN_ERR_ARG.
+ * A tau equal to a data time is an ordinary point.  nu [B] (may be NULL) scales sigma2.  C, Dd: [J] (cd_shared != 0) or [B][J] (each draw then
+ * evaluated as its own one-draw batch with its own table).  status (may be NULL): 0, or 2 with NaN in the draw's row where a D_n is not positive.
+ * At most 64 active rows; more: PIORAN_ERR_UNSUPPORTED before any workspace is taken.  NULL ds / tau / var_out (with M > 0): PIORAN_ERR_ARG before
+ * any GPU call.  Host pointers, blocking.  pioran_celerite_config_name(-1) afterwards: "wide (step-by-step variance)". */
+int pioran_celerite_predict_var(pioran_ds* ds, int64_t B, int64_t J, const double* A, const double* Bc, const double* C,
+                                const double* Dd, int cd_shared, const double* nu, int64_t M, const double* tau, double* var_out,
+                                int32_t* status);
 /* log L and its gradient (what ForwardDiff obtains through the generic `logl`,
  * src/celerite_solver.jl:316, test/test_likelihood.jl:55-60) by reverse mode through the recurrence, for B draws:
  *   grad_a, grad_b [B][J] = dlogL/da_j, dlogL/db_j;
@@ -275,7 +293,7 @@ int pioran_celerite_simulate(pioran_ctx* ctx, int64_t N, int64_t B, int64_t J, c
  * calling thread's last launch — "tile" (windowed form, one draw per wavefront: large batches from 49 rows on and batch sizes between the
  * passes of the throughput layouts), "block" (windowed kernel), "block+pd" (with per-draw rows), "block (per-draw tables)", "wide"
  * (latency layout), "scan" (throughput layouts), "fallback", "block (windowed gradient[, per-draw tables])",
- * "wide (step-by-step gradient)" (diagnostics). */
+ * "wide (step-by-step gradient)", "wide (step-by-step variance)" (diagnostics). */
 const char* pioran_celerite_config_name(int64_t R);
 /* Diagnostics (no GPU needed): the automatic choice between the windowed form with one draw per wavefront (1, "tile") and the other families (0)
  * for a shared-table batch of B draws with R active rows; `pass` = draws per pass of the step-by-step layout of these rows (0 = unknown:

@@ -17,6 +17,7 @@ int pioran_launch_predict_from_gy(ScanParams p, double* work, double* tau_work, 
 
 
 #include <cmath>
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <functional>
@@ -1751,6 +1752,99 @@ int pioran_celerite_predict(pioran_ds* ds, int64_t B, int64_t J, const double* A
                                       M, tau, mean_out + b * M, status ? status + b : nullptr);
         if (rc) return rc;
     }
+    return PIORAN_OK;
+}
+
+// ---- posterior variance at new times through the factorisation (celerite_predict.hip) ------------------------------------------------
+// shared (c, d), tau ASCENDING (the caller below sorts); draws in chunks of at most 256 sized to the free memory
+static int predict_var_shared(pioran_ds* ds, int64_t B, int64_t J, const double* A, const double* Bc, const double* C, const double* Dd,
+                              const double* nu, int64_t M, const double* tau, double* var_out, int32_t* status)
+{
+    pioran_ctx* ctx = ds->ctx;
+    PrepState& s = ds->host;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    PendingGuard pending_guard(ctx);
+    int rc;
+    if ((rc = prepare_shared(ds, B, J, Bc, C, Dd))) return rc;
+    if (s.R > 64 || s.npd_terms) return PIORAN_ERR_UNSUPPORTED;   // before any upload / workspace
+    if (M == 0) {
+        if (status) for (int64_t b = 0; b < B; ++b) status[b] = 0;
+        return PIORAN_OK;
+    }
+    int64_t chunk = B < 256 ? B : 256;
+    {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
+            while (chunk > 1 && pioran_predict_var_workspace_doubles(chunk, ds->N, s.R, M) * sizeof(double) > ws_allow(ctx, free_b) + ctx->bwork.cap) chunk /= 2;
+    }
+    for (;;) {
+        rc = ensure(ctx, ctx->bwork, pioran_predict_var_workspace_doubles(chunk, ds->N, s.R, M) * sizeof(double));
+        if (!rc) rc = ensure(ctx, ctx->bY, (size_t)chunk * (size_t)M * sizeof(double));
+        if (rc != PIORAN_ERR_ALLOC || chunk == 1) break;
+        chunk /= 2;
+    }
+    if (rc) return rc;
+    if ((rc = ensure(ctx, ctx->bK, pioran_predict_tau_workspace_doubles(M, s.R, 1) * sizeof(double)))) return rc;
+    if ((rc = upload(ctx, ctx->bshift, tau, (size_t)M * sizeof(double)))) return rc;
+    if ((rc = ensure(ctx, ctx->bout, chunk * sizeof(double)))) return rc;
+    if ((rc = ensure(ctx, ctx->bst, chunk * sizeof(int32_t)))) return rc;
+    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+        const int64_t nb = B - b0 < chunk ? B - b0 : chunk;
+        if ((rc = upload(ctx, ctx->bA, A + b0 * J, (size_t)nb * J * sizeof(double)))) return rc;
+        if ((rc = upload(ctx, ctx->bB, Bc + b0 * J, (size_t)nb * J * sizeof(double)))) return rc;
+        if (nu && (rc = upload(ctx, ctx->bnu, nu + b0, nb * sizeof(double)))) return rc;
+        ScanParams p{};
+        p.N = ds->N; p.J = s.J; p.R = s.R; p.B = nb;
+        p.standard_rows = s.row_layout; p.n_complex = s.n_complex;
+        p.rec_stride = 3 * (int64_t)(s.R + 2) + 2;
+        p.tab = s.tab; p.rowmap = s.rowmap; p.t = ds->t; p.y = ds->y; p.s2 = ds->s2;
+        p.A = (const double*)ctx->bA.p; p.Bc = (const double*)ctx->bB.p; p.C = s.dc; p.D = s.dd;
+        p.nu = nu ? (const double*)ctx->bnu.p : nullptr;
+        p.out = (double*)ctx->bout.p;
+        p.opt = &ctx->opt;
+        g_last_kernel = "wide (step-by-step variance)";
+        rc = pioran_launch_predict_var(p, (double*)ctx->bwork.p, (double*)ctx->bK.p, ds->t, M, (const double*)ctx->bshift.p, (double*)ctx->bY.p,
+                                       (int32_t*)ctx->bst.p, ctx->stream);
+        if (rc) { ctx->last_err = "variance launch failed"; return rc; }
+        if ((rc = download(ctx, var_out + b0 * M, ctx->bY.p, (size_t)nb * M * sizeof(double)))) return rc;
+        if (status) if ((rc = download(ctx, status + b0, ctx->bst.p, nb * sizeof(int32_t)))) return rc;
+        SYNC(ctx);
+    }
+    return PIORAN_OK;
+}
+
+int pioran_celerite_predict_var(pioran_ds* ds, int64_t B, int64_t J, const double* A, const double* Bc, const double* C, const double* Dd,
+                                int cd_shared, const double* nu, int64_t M, const double* tau, double* var_out, int32_t* status)
+{
+    if (!ds || B < 1 || J < 1 || M < 0 || !A || !Bc || !C || !Dd || (M > 0 && (!tau || !var_out))) return PIORAN_ERR_ARG;
+    for (int64_t m = 0; m < M; ++m)
+        if (!std::isfinite(tau[m])) return PIORAN_ERR_ARG;
+    // the kernels walk the evaluation times in ascending order: sort an index, scatter the result back
+    const bool sorted = is_sorted(tau, M);
+    std::vector<int64_t> idx;
+    std::vector<double> ts, vs;
+    if (!sorted) {
+        idx.resize((size_t)M);
+        for (int64_t m = 0; m < M; ++m) idx[(size_t)m] = m;
+        std::stable_sort(idx.begin(), idx.end(), [&](int64_t x, int64_t y) { return tau[x] < tau[y]; });
+        ts.resize((size_t)M);
+        for (int64_t m = 0; m < M; ++m) ts[(size_t)m] = tau[idx[(size_t)m]];
+        vs.resize((size_t)B * (size_t)M);
+    }
+    const double* tq = sorted ? tau : ts.data();
+    double* vq = sorted ? var_out : vs.data();
+    int rc = PIORAN_OK;
+    if (cd_shared || B == 1) {
+        rc = predict_var_shared(ds, B, J, A, Bc, C, Dd, nu, M, tq, vq, status);
+    } else {
+        for (int64_t b = 0; b < B && !rc; ++b)   // per-draw (c, d): every draw is its own one-draw batch with its own table
+            rc = predict_var_shared(ds, 1, J, A + b * J, Bc + b * J, C + b * J, Dd + b * J, nu ? nu + b : nullptr, M, tq, vq + b * M,
+                                    status ? status + b : nullptr);
+    }
+    if (rc) return rc;
+    if (!sorted)
+        for (int64_t b = 0; b < B; ++b)
+            for (int64_t m = 0; m < M; ++m) var_out[b * M + idx[(size_t)m]] = vs[(size_t)(b * M + m)];
     return PIORAN_OK;
 }
 

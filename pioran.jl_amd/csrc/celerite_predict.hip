@@ -581,3 +581,329 @@ int pioran_launch_predict(ScanParams p, double* work, const double* t, int64_t M
                            Qb, M, tau, mean_out);
     return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;
 }
+
+namespace {
+
+// ---- posterior variance at new times through the factorisation ("Posterior variance through the factorisation") ----
+//   var(tau) = k(0) - k*' K^-1 k*,  K = L D L' with the (W_n, D_n) that celerite_wide_kernel<MODE 1> leaves in st_w / st_d.
+// With n0 = #{t_n < tau}, alpha = e^{-c (tau - t_{n0-1})} U~(tau) (al Wc + be Ws of predict_tau_kernel) and
+// beta = e^{-c (t_{n0} - tau)} V(tau) (Wv), the entries of k* are V_n' P alpha for n < n0 and U~_n' P beta for n >= n0 (P: the phi products),
+// and L^-1 k* splits at n0:
+//   forward   S+_n = phi_n phi_n' o S+_{n-1} + D_n W_n W_n'                       g = S+_{n0-1} alpha,  q1 = alpha'g
+//   backward  B_n = B' - U~_n h' - h U~_n' + (1/D_n + W_n'h) U~_n U~_n',  B' = phi_{n+1} phi_{n+1}' o B_{n+1},  h = B' W_n
+//             (= U~ U~'/D_n + A' B_{n+1} A with A = diag(phi_{n+1}) (I - W_n U~_n'))     e = beta - phi_{n0} o g,  q2 = e' B_{n0} e
+//   var(tau) = k(0) - q1 - q2.
+// One wavefront per draw, lane = column of the symmetric R x R matrix, the column (H = R rounded up to 16 entries) in registers; what
+// is uniform over the wavefront (W_n, U~_n, phi_n, h, alpha, e) goes through LDS and is read back as broadcasts.  tau ascending: the
+// evaluation times of step n are a contiguous run (as in q_eval_fused_kernel).  No R x R matrix goes to HBM: the forward kernel
+// leaves q1 [B][M] and e [B][M][H], the backward kernel reads them and writes the variance.
+constexpr int VD = 4;   // steps whose (W_n, table record, D_n) are in flight ahead of their use
+
+__device__ __forceinline__ double readlane_f64(double x, int k)
+{
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), k), __builtin_amdgcn_readlane(__double2loint(x), k));
+}
+// sum over the 64 lanes, uniform result: four DPP rotations inside the 16-lane rows, then the four row sums by v_readlane
+__device__ __forceinline__ double wave_sum_uniform(double x)
+{
+    x += dpp_move<0x128>(x);   // row_ror:8
+    x += dpp_move<0x124>(x);   // row_ror:4
+    x += dpp_move<0x122>(x);   // row_ror:2
+    x += dpp_move<0x121>(x);   // row_ror:1
+    return (readlane_f64(x, 0) + readlane_f64(x, 16)) + (readlane_f64(x, 32) + readlane_f64(x, 48));
+}
+
+// f(i, x) for i < H with x[v] = src[v][i], NV uniform vectors in LDS.  A lone wavefront has nothing to hide the LDS round trip behind, and left to
+// itself the compiler keeps three or four reads in flight (the step then waits for LDS three times as long as it computes): the vectors are
+// read sixteen entries at a time, the next sixteen requested before the current ones are used (the empty asm is a compiler-only fence that keeps
+// the requests above the arithmetic).
+template <int NV, int H, typename F>
+__device__ __forceinline__ void lds_rows(const double* const (&src)[NV], F&& f)
+{
+    constexpr int CH = 16, NC = H / CH;
+    double buf[2][NV][CH];
+#pragma unroll
+    for (int v = 0; v < NV; ++v)
+#pragma unroll
+        for (int i = 0; i < CH; ++i) buf[0][v][i] = src[v][i];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        if (c + 1 < NC) {
+#pragma unroll
+            for (int v = 0; v < NV; ++v)
+#pragma unroll
+                for (int i = 0; i < CH; ++i) buf[(c + 1) & 1][v][i] = src[v][CH * (c + 1) + i];
+        }
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int i = 0; i < CH; ++i) {
+            double x[NV];
+#pragma unroll
+            for (int v = 0; v < NV; ++v) x[v] = buf[c & 1][v][i];
+            f(CH * c + i, x);
+        }
+    }
+}
+
+template <int H>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) predict_var_fwd_kernel(const ScanParams p, int64_t M, const int32_t* __restrict__ n0s,
+                                                             const double* __restrict__ Wt, double* __restrict__ q1, double* __restrict__ E)
+{
+    const int64_t b = blockIdx.x, N = p.N;
+    const int lane = threadIdx.x, R = p.R, Rp = R + 2, J = p.J;
+    const bool live = lane < R, inH = lane < H;
+    const int rl = live ? lane : 0;
+    const int64_t rec = p.rec_stride;
+    const int rm0 = p.rowmap[rl];
+    const bool sinrow = (rm0 >> 30) & 1;
+    const int term = rm0 & 0xfffff;
+    const double a_ = p.A[b * J + term], b_ = p.Bc[b * J + term];
+    const double ae = live ? (sinrow ? -b_ : a_) : 0.0, bee = live ? (sinrow ? a_ : b_) : 0.0;   // U~_r(tau) = ae cos + bee sin
+    const double* Wf = p.st_w + b * N * R + rl;
+    const double* Df = p.st_d + b * N;
+    const double* phs = p.tab + 2 * Rp + rl;
+    const double* Wl = Wt + rl;
+    double* q1b = q1 + b * M;
+    double* Eb = E + b * M * H + lane;
+    __shared__ double sh[2][2 * H];   // by step parity: W_n | phi_n
+    __shared__ double sh_a[H];
+
+    int64_t mp = 0;
+    while (mp < M && n0s[mp] == 0) {   // before the first data point: g = 0, e = beta
+        if (inH) Eb[mp * H] = live ? Wl[mp * 3 * H + 2 * H] : 0.0;
+        if (lane == 0) q1b[mp] = 0.0;
+        ++mp;
+    }
+    // the evaluation time the walk meets next: its step and its tau-only factors, fetched when the one before it is done
+    int64_t nn;
+    double qc, qs, qv;
+    auto fetch_q = [&]() __attribute__((always_inline)) {
+        const int64_t m = mp < M ? mp : M - 1;
+        nn = mp < M ? (int64_t)n0s[m] - 1 : N;
+        qc = Wl[m * 3 * H]; qs = Wl[m * 3 * H + H]; qv = Wl[m * 3 * H + 2 * H];
+    };
+    fetch_q();
+
+    double S[H];
+#pragma unroll
+    for (int i = 0; i < H; ++i) S[i] = 0.0;
+    double wr[VD], pr[VD], pn[VD], dr[VD];   // W_n, phi_n, phi_{n+1} of this lane's row; D_n
+    auto fetch = [&](int64_t n, int k) __attribute__((always_inline)) {
+        const int64_t m = n < N ? n : N - 1;
+        wr[k] = Wf[m * R];
+        pr[k] = phs[m * rec];
+        pn[k] = phs[(m + 1) * rec];      // (record N is a readable copy of N - 1)
+        dr[k] = Df[m];
+    };
+#pragma unroll
+    for (int k = 0; k < VD; ++k) fetch(k, k);
+    for (int64_t nb = 0; nb < N; nb += VD) {
+#pragma unroll
+        for (int k = 0; k < VD; ++k) {
+            const int64_t n = nb + k;
+            if (n < N) {   // (uniform)
+                const int par = (int)(n & 1);
+                const double w = live ? wr[k] : 0.0, ph = live && n > 0 ? pr[k] : 0.0, phn = pn[k];
+                if (inH) { sh[par][lane] = w; sh[par][H + lane] = ph; }
+                __syncthreads();
+                const double dw = dr[k] * w;
+                {
+                    const double* const src[2] = {sh[par], sh[par] + H};
+                    lds_rows<2, H>(src, [&](int i, const double (&x)[2]) __attribute__((always_inline)) {
+                        S[i] = fma(x[1] * ph, S[i], dw * x[0]);              // column `lane` of S+_n
+                    });
+                }
+                auto eval = [&]() __attribute__((always_inline)) {
+                    const double alpha = fma(ae, qc, bee * qs);
+                    if (inH) sh_a[lane] = alpha;
+                    __syncthreads();
+                    double gp[4] = {0.0, 0.0, 0.0, 0.0};                     // four chains: a lone wavefront has only its own ILP
+                    {
+                        const double* const src[1] = {sh_a};
+                        lds_rows<1, H>(src, [&](int i, const double (&x)[1]) __attribute__((always_inline)) {
+                            gp[i & 3] = fma(S[i], x[0], gp[i & 3]);          // S+ is symmetric: its column is its row
+                        });
+                    }
+                    const double g = (gp[0] + gp[1]) + (gp[2] + gp[3]);
+                    const double s = wave_sum_lane0(alpha * g);
+                    if (lane == 0) q1b[mp] = s;
+                    if (inH) Eb[mp * H] = live ? qv - phn * g : 0.0;
+                    __syncthreads();
+                    ++mp;
+                    fetch_q();
+                };
+                // the first evaluation time of a step apart from the others: its factors were fetched at least a step ago, and only the
+                // loop behind it has to wait for loads it issued itself
+                if (nn == n) {
+                    eval();
+                    while (nn == n) eval();
+                }
+            }
+            fetch(n + VD, k);
+        }
+    }
+}
+
+template <int H>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) predict_var_bwd_kernel(const ScanParams p, int64_t M, const int32_t* __restrict__ n0s,
+                                                             const double* __restrict__ q1, const double* __restrict__ E,
+                                                             double* __restrict__ var_out, int32_t* __restrict__ status)
+{
+    const int64_t b = blockIdx.x, N = p.N;
+    const int lane = threadIdx.x, R = p.R, Rp = R + 2, J = p.J;
+    const bool live = lane < R, inH = lane < H;
+    const int rl = live ? lane : 0;
+    const int64_t rec = p.rec_stride;
+    const int rm0 = p.rowmap[rl];
+    const bool sinrow = (rm0 >> 30) & 1;
+    const int term = rm0 & 0xfffff;
+    const double al = live ? p.A[b * J + term] : 0.0;                                             // U~_n = al v + be x
+    const double be = live ? (sinrow ? -p.Bc[b * J + term] : p.Bc[b * J + term]) : 0.0;
+    double k0 = 0.0;
+    for (int j = 0; j < J; ++j) k0 += p.A[b * J + j];
+    const double* Wf = p.st_w + b * N * R + rl;
+    const double* Df = p.st_d + b * N;
+    const double* tabl = p.tab + rl;
+    const double* q1b = q1 + b * M;
+    const double* Eb = E + b * M * H + (inH ? lane : 0);
+    double* vb = var_out + b * M;
+    __shared__ double sh[2][3 * H];   // by step parity: phi_{n+1} o W_n | U~_n | phi_{n+1}
+    __shared__ double sh_h[2][H];
+    __shared__ double sh_e[H];
+
+    int64_t m_top = 0;                 // first evaluation time after the last data point: q2 = 0 there
+    {
+        int64_t lo = 0, hi = M;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (n0s[mid] < N) lo = mid + 1; else hi = mid;
+        }
+        m_top = lo;
+    }
+    for (int64_t m = m_top + lane; m < M; m += 64) vb[m] = k0 - q1b[m];
+    int64_t mp = m_top - 1, nn;
+    double qe, qq;
+    auto fetch_q = [&]() __attribute__((always_inline)) {
+        const int64_t m = mp >= 0 ? mp : 0;
+        nn = mp >= 0 ? (int64_t)n0s[m] : -1;
+        qe = Eb[m * H];
+        qq = q1b[m];
+    };
+    fetch_q();
+
+    double Bm[H];
+#pragma unroll
+    for (int i = 0; i < H; ++i) Bm[i] = 0.0;
+    bool bad = false;
+    double wr[VD], vr[VD], xr[VD], pn[VD], dr[VD];
+    auto fetch = [&](int64_t n, int k) __attribute__((always_inline)) {
+        const int64_t m = n > 0 ? n : 0;
+        wr[k] = Wf[m * R];
+        vr[k] = tabl[m * rec];
+        xr[k] = tabl[m * rec + Rp];
+        pn[k] = tabl[(m + 1) * rec + 2 * Rp];   // phi between t_n and t_{n+1} (record N: a readable copy, multiplies B = 0)
+        dr[k] = Df[m];
+    };
+#pragma unroll
+    for (int k = 0; k < VD; ++k) fetch(N - 1 - k, k);
+    for (int64_t nb = N - 1; nb >= 0; nb -= VD) {
+#pragma unroll
+        for (int k = 0; k < VD; ++k) {
+            const int64_t n = nb - k;
+            if (n >= 0) {   // (uniform)
+                const int par = (int)(n & 1);
+                const double w = live ? wr[k] : 0.0, ph = live ? pn[k] : 0.0, u = fma(al, vr[k], be * xr[k]), Dn = dr[k];
+                bad |= !(Dn > 0.0);
+                if (inH) { sh[par][lane] = ph * w; sh[par][H + lane] = u; sh[par][2 * H + lane] = ph; }
+                __syncthreads();
+                double hp[4] = {0.0, 0.0, 0.0, 0.0};                        // four chains: a lone wavefront has only its own ILP
+                {
+                    const double* const src[1] = {sh[par]};
+                    lds_rows<1, H>(src, [&](int i, const double (&x)[1]) __attribute__((always_inline)) { hp[i & 3] = fma(Bm[i], x[0], hp[i & 3]); });
+                }
+                const double h = ph * ((hp[0] + hp[1]) + (hp[2] + hp[3]));   // (B' W_n) of this column
+                if (inH) sh_h[par][lane] = h;
+                const double s = 1.0 / Dn + wave_sum_uniform(w * h);
+                __syncthreads();
+                const double cj = fma(s, u, -h);
+                {
+                    const double* const src[3] = {sh[par] + 2 * H, sh[par] + H, sh_h[par]};
+                    lds_rows<3, H>(src, [&](int i, const double (&x)[3]) __attribute__((always_inline)) {
+                        Bm[i] = fma(x[0] * ph, Bm[i], fma(x[1], cj, -x[2] * u));
+                    });
+                }
+                auto eval = [&]() __attribute__((always_inline)) {
+                    if (inH) sh_e[lane] = qe;
+                    __syncthreads();
+                    double ap[4] = {0.0, 0.0, 0.0, 0.0};
+                    {
+                        const double* const src[1] = {sh_e};
+                        lds_rows<1, H>(src, [&](int i, const double (&x)[1]) __attribute__((always_inline)) { ap[i & 3] = fma(Bm[i], x[0], ap[i & 3]); });
+                    }
+                    const double q2 = wave_sum_lane0(inH ? qe * ((ap[0] + ap[1]) + (ap[2] + ap[3])) : 0.0);
+                    if (lane == 0) vb[mp] = k0 - qq - q2;
+                    __syncthreads();
+                    --mp;
+                    fetch_q();
+                };
+                if (nn == n) {   // (the first one apart from the others, as in the forward kernel)
+                    eval();
+                    while (nn == n) eval();
+                }
+            }
+            fetch(n - VD, k);
+        }
+    }
+    if (bad)   // a non-positive D_n: no factorisation, no variance
+        for (int64_t m = lane; m < M; m += 64) vb[m] = __builtin_nan("");
+    if (status && lane == 0) status[b] = bad ? 2 : 0;
+}
+
+}  // namespace
+
+// W [B][N][R], D [B][N], z' [B][N] of the factor; q1 [B][M], e [B][M][H]
+size_t pioran_predict_var_workspace_doubles(int64_t B, int64_t N, int32_t R, int64_t M)
+{
+    return (size_t)B * ((size_t)N * ((size_t)R + 2) + (size_t)M * ((size_t)((R + 15) & ~15) + 1));
+}
+
+// p: a shared-table launch description as for pioran_launch_predict (y is not read for the result; p.out [B] receives the store pass's log L).
+// tau: device [M], ASCENDING.  tau_work: pioran_predict_tau_workspace_doubles(M, R, 1).  var_out: device [B][M]; status: device [B] or nullptr.
+int pioran_launch_predict_var(ScanParams p, double* work, double* tau_work, const double* t, int64_t M, const double* tau, double* var_out,
+                              int32_t* status, hipStream_t stream)
+{
+    if (!p.tab || p.npd_rows != 0 || p.R > 64 || p.R < 1 || M < 1 || p.N > 0x7fffffff) return PIORAN_ERR_UNSUPPORTED;
+    const size_t BN = (size_t)p.B * (size_t)p.N;
+    const int H = (p.R + 15) & ~15;
+    p.st_w = work;
+    p.st_d = work + BN * p.R;
+    p.st_z = p.st_d + BN;
+    double* q1 = p.st_z + BN;
+    double* E = q1 + (size_t)p.B * (size_t)M;
+    p.status = nullptr;   // (the backward kernel reports: it sees every D_n)
+    int rc = pioran_launch_scan_wide_store(p, stream);
+    if (rc) return rc;
+    int32_t* n0s = (int32_t*)(tau_work + (size_t)M * 3 * (size_t)H);
+    hipLaunchKernelGGL(predict_tau_kernel, dim3((unsigned)((M + 255) / 256), 1), dim3(256), 0, stream, p, t, M, tau, n0s, tau_work, (int64_t)0,
+                       (int64_t)0);
+    const dim3 grid((unsigned)p.B), block(64);
+    switch (H) {
+    case 16:
+        hipLaunchKernelGGL(predict_var_fwd_kernel<16>, grid, block, 0, stream, p, M, n0s, tau_work, q1, E);
+        hipLaunchKernelGGL(predict_var_bwd_kernel<16>, grid, block, 0, stream, p, M, n0s, q1, E, var_out, status);
+        break;
+    case 32:
+        hipLaunchKernelGGL(predict_var_fwd_kernel<32>, grid, block, 0, stream, p, M, n0s, tau_work, q1, E);
+        hipLaunchKernelGGL(predict_var_bwd_kernel<32>, grid, block, 0, stream, p, M, n0s, q1, E, var_out, status);
+        break;
+    case 48:
+        hipLaunchKernelGGL(predict_var_fwd_kernel<48>, grid, block, 0, stream, p, M, n0s, tau_work, q1, E);
+        hipLaunchKernelGGL(predict_var_bwd_kernel<48>, grid, block, 0, stream, p, M, n0s, q1, E, var_out, status);
+        break;
+    default:
+        hipLaunchKernelGGL(predict_var_fwd_kernel<64>, grid, block, 0, stream, p, M, n0s, tau_work, q1, E);
+        hipLaunchKernelGGL(predict_var_bwd_kernel<64>, grid, block, 0, stream, p, M, n0s, q1, E, var_out, status);
+        break;
+    }
+    return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;
+}

@@ -201,6 +201,11 @@ int pioran_launch_block_table_reference(int64_t N, int32_t R, int32_t J, const i
 size_t pioran_predict_workspace_doubles(int64_t B, int64_t N, int32_t R);
 int pioran_launch_predict(ScanParams p, double* work, const double* t, int64_t M, const double* tau, double* mean_out,
                           hipStream_t stream);
+// ... posterior variance at new times through the stored factor (at most 64 rows; tau ascending)
+size_t pioran_predict_tau_workspace_doubles(int64_t M, int32_t R, int64_t ntab);
+size_t pioran_predict_var_workspace_doubles(int64_t B, int64_t N, int32_t R, int64_t M);
+int pioran_launch_predict_var(ScanParams p, double* work, double* tau_work, const double* t, int64_t M, const double* tau, double* var_out,
+                              int32_t* status, hipStream_t stream);
 // celerite_fallback.hip
 int pioran_launch_scan_fallback(const ScanParams& p, hipStream_t stream);
 size_t pioran_fallback_scratch_doubles(int R);

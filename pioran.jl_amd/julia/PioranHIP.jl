@@ -331,6 +331,29 @@ function predict_batch(ds::Dataset, A::Matrix{Float64}, B::Matrix{Float64}, c::V
     return out, status
 end
 
+"""
+    predict_var(ds, A, B, c, d, τ; ν)
+
+Posterior variance of the latent process at the times `τ` (any order) for every draw (column) of `A`, `B`, through the celerite
+factorisation in O((N + M) R²): the diagonal that `std(posterior(f(t, σ²), y), τ)` (src/scalable_GP.jl:103-104) takes from a dense
+`predict_cov`.  At most 64 active rows.  The error is absolute on the scale of `k(0) = sum(a)`.  Returns an `length(τ) × nbatch`
+matrix and the status vector (2 and NaN where a draw's factorisation is not positive definite).
+"""
+function predict_var(ds::Dataset, A::Matrix{Float64}, B::Matrix{Float64}, c::VecOrMat{Float64}, d::VecOrMat{Float64},
+                     τ::Vector{Float64}; ν::Union{Nothing, Vector{Float64}} = nothing)
+    J, nb = size(A)
+    out = Matrix{Float64}(undef, length(τ), nb)      # column-major = the ABI's [B][M]
+    status = zeros(Int32, nb)
+    p(x) = x === nothing ? Ptr{Cdouble}(C_NULL) : pointer(x)
+    GC.@preserve A B c d ν τ out status begin
+        check(ccall((:pioran_celerite_predict_var, LIB), Cint,
+                    (Ptr{Cvoid}, Int64, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble},
+                     Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}),
+                    ds.h, nb, J, A, B, c, d, c isa Vector ? 1 : 0, p(ν), length(τ), τ, out, status))
+    end
+    return out, status
+end
+
 # Float64 drop-in for Pioran.pred (predict(cov, τ, t, y, σ²) reaches it for every covariance type, :348-361)
 function pred_hip(a::Vector{Float64}, b::Vector{Float64}, c::Vector{Float64}, d::Vector{Float64}, τ::Vector{Float64},
                   t::Vector{Float64}, y::Vector{Float64}, σ²::Vector{Float64}; ctx = default_context())
