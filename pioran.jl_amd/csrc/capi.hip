@@ -113,14 +113,23 @@ static size_t ws_allow(const pioran_ctx* ctx, size_t free_b)
     return free_b / 2 < cap ? free_b / 2 : cap;
 }
 
+// The device memory that is free right now; false when the runtime cannot tell (its error is cleared: the callers go on without the figure,
+// and a later launch wrapper must not read it as its own)
+static bool device_free_bytes(size_t& free_b)
+{
+    size_t total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) return true;
+    (void)hipGetLastError();
+    return false;
+}
+
 // May `b` hold `bytes` under the workspace budget?  The runtime is asked for the free memory only when the buffer would have to GROW: the
 // asynchronous *_dev entries run this on every launch, and a launch that fits what is already allocated must not block on the host.
 static bool ws_fits(pioran_ctx* ctx, const pioran_ctx::Buf& b, size_t bytes)
 {
     if (bytes <= b.cap) return true;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return bytes <= ws_allow(ctx, free_b) + b.cap;
+    size_t free_b = 0;
+    return device_free_bytes(free_b) && bytes <= ws_allow(ctx, free_b) + b.cap;
 }
 
 int ensure(pioran_ctx* ctx, pioran_ctx::Buf& b, size_t bytes)
@@ -228,6 +237,178 @@ int download(pioran_ctx* ctx, void* host, const void* dev, size_t bytes)
     }
     return PIORAN_OK;
 }
+
+// ---- what the batched entries share: launch descriptions, one chunk of draws up and down, the size of a chunk ------------------------------------
+// doubles of one step record of the shared table (table.hip): (v, x, phi) of R + 2 rows, then (y_n, sigma2_n)
+constexpr int64_t rec_stride_of(int64_t R) { return 3 * (int64_t)(R + 2) + 2; }
+
+// Device pointers of one chunk of draws: A, Bc, C, D [nb][J]; mu, nu [nb] or nullptr; Y, S2 [nb][N] or nullptr
+struct DrawChunk { const double *A, *Bc, *C, *D, *mu, *nu, *Y, *S2; };
+
+// Launch description of the nb draws `m` on a prepared shared-(c, d) state: everything the data set, the state and the chunk decide (m.C, m.D:
+// not used).  out / status and what only one entry uses (gw, g_y, noise, npd_rows, ...) are the caller's.
+ScanParams shared_params(const pioran_ds* ds, const PrepState& s, int64_t nb, const DrawChunk& m)
+{
+    ScanParams p{};
+    p.opt = &ds->ctx->opt;
+    p.A = m.A; p.Bc = m.Bc; p.mu = m.mu; p.nu = m.nu; p.Y = m.Y; p.S2 = m.S2;
+    p.N = ds->N; p.J = s.J; p.R = s.R; p.B = nb;
+    p.standard_rows = s.row_layout; p.n_complex = s.n_complex;
+    p.rec_stride = rec_stride_of(s.R);
+    p.tab = s.tab; p.rowmap = s.rowmap; p.t = ds->t; p.y = ds->y; p.s2 = ds->s2;
+    p.C = s.dc; p.D = s.dd;
+    return p;
+}
+
+// ... of nb draws with (c, d) of their own in every term (m.C, m.D; both rows of each of the J terms: R = 2 J, rowmap the full map): no shared
+// table; the per-draw tables are tab_stride (reverse pass: gtab_stride) doubles apart, 0 where the entry has none
+ScanParams perdraw_params(const pioran_ds* ds, int32_t J, int32_t R, const int32_t* rowmap, int64_t nb, const DrawChunk& m, int64_t tab_stride,
+                          int64_t gtab_stride)
+{
+    ScanParams p{};
+    p.opt = &ds->ctx->opt;
+    p.A = m.A; p.Bc = m.Bc; p.mu = m.mu; p.nu = m.nu; p.Y = m.Y; p.S2 = m.S2;
+    p.N = ds->N; p.J = J; p.R = R; p.B = nb; p.standard_rows = 1;
+    p.rec_stride = rec_stride_of(R);
+    p.tab_draw_stride = tab_stride; p.gtab_draw_stride = gtab_stride;
+    p.rowmap = rowmap; p.t = ds->t; p.y = ds->y; p.s2 = ds->s2;
+    p.C = m.C; p.D = m.D;
+    return p;
+}
+
+// Draws [b0, b0 + nb) of the caller's host arrays into the context's staging buffers bA .. bnu.  C / Dd, mu, nu: nullptr = not part of the
+// call (a shared (c, d) lives in the prepared state), and the chunk's pointer is nullptr then.
+int upload_draws(pioran_ctx* ctx, int64_t J, int64_t b0, int64_t nb, const double* A, const double* Bc, const double* C, const double* Dd,
+                 const double* mu, const double* nu, DrawChunk& m)
+{
+    int rc;
+    const size_t bj = (size_t)nb * (size_t)J * sizeof(double);
+    if ((rc = upload(ctx, ctx->bA, A + b0 * J, bj))) return rc;
+    if ((rc = upload(ctx, ctx->bB, Bc + b0 * J, bj))) return rc;
+    if (C && (rc = upload(ctx, ctx->bC, C + b0 * J, bj))) return rc;
+    if (C && (rc = upload(ctx, ctx->bD, Dd + b0 * J, bj))) return rc;
+    if (mu && (rc = upload(ctx, ctx->bmu, mu + b0, nb * sizeof(double)))) return rc;
+    if (nu && (rc = upload(ctx, ctx->bnu, nu + b0, nb * sizeof(double)))) return rc;
+    m = DrawChunk{};
+    m.A = (const double*)ctx->bA.p; m.Bc = (const double*)ctx->bB.p;
+    if (C) { m.C = (const double*)ctx->bC.p; m.D = (const double*)ctx->bD.p; }
+    m.mu = mu ? (const double*)ctx->bmu.p : nullptr; m.nu = nu ? (const double*)ctx->bnu.p : nullptr;
+    return PIORAN_OK;
+}
+
+// log L and status of n draws land in bout / bst ...
+int ensure_results(pioran_ctx* ctx, int64_t n)
+{
+    const int rc = ensure(ctx, ctx->bout, n * sizeof(double));
+    return rc ? rc : ensure(ctx, ctx->bst, n * sizeof(int32_t));
+}
+
+// ... and go from there to the caller's arrays at draw b0 (out, status: nullptr = not wanted)
+int download_results(pioran_ctx* ctx, double* out, int32_t* status, int64_t b0, int64_t nb)
+{
+    int rc;
+    if (out && (rc = download(ctx, out + b0, ctx->bout.p, nb * sizeof(double)))) return rc;
+    if (status && (rc = download(ctx, status + b0, ctx->bst.p, nb * sizeof(int32_t)))) return rc;
+    return PIORAN_OK;
+}
+
+// Gradient arrays, the caller's or a chunk's on the device: a, b, c, d [.][J]; nu, mu [.]; y, s2 [.][N].  In the caller's set everything but
+// a and b may be nullptr (not wanted).
+struct GradPtrs {
+    double *a, *b, *c, *d, *nu, *mu, *y, *s2;
+    GradPtrs from_draw(int64_t b0, int64_t J, int64_t N) const
+    {
+        return {a + b0 * J, b + b0 * J, c ? c + b0 * J : nullptr, d ? d + b0 * J : nullptr, nu ? nu + b0 : nullptr, mu ? mu + b0 : nullptr,
+                y ? y + b0 * N : nullptr, s2 ? s2 + b0 * N : nullptr};
+    }
+};
+
+// the device side of a chunk: grad_a | grad_b | grad_c | grad_d ([chunk][J] each) in `terms`, grad_nu | grad_mu ([chunk] each) in `scalars`,
+// the series gradients in bY / bS2
+GradPtrs grad_chunk(pioran_ctx* ctx, const pioran_ctx::Buf& terms, const pioran_ctx::Buf& scalars, int64_t chunk, int64_t J)
+{
+    double* ga = (double*)terms.p; double* gn = (double*)scalars.p;
+    const size_t cj = (size_t)chunk * (size_t)J;
+    return {ga, ga + cj, ga + 2 * cj, ga + 3 * cj, gn, gn + chunk, (double*)ctx->bY.p, (double*)ctx->bS2.p};
+}
+
+// nb draws of a chunk's gradients to the caller's arrays (host: already at the chunk's first draw)
+int download_grads(pioran_ctx* ctx, const GradPtrs& host, const GradPtrs& dev, int64_t nb, int64_t J, int64_t N)
+{
+    int rc;
+    const size_t nbj = (size_t)nb * J * sizeof(double), nbn = (size_t)nb * N * sizeof(double);
+    if ((rc = download(ctx, host.a, dev.a, nbj))) return rc;
+    if ((rc = download(ctx, host.b, dev.b, nbj))) return rc;
+    if (host.c && (rc = download(ctx, host.c, dev.c, nbj))) return rc;
+    if (host.d && (rc = download(ctx, host.d, dev.d, nbj))) return rc;
+    if (host.nu && (rc = download(ctx, host.nu, dev.nu, nb * sizeof(double)))) return rc;
+    if (host.mu && (rc = download(ctx, host.mu, dev.mu, nb * sizeof(double)))) return rc;
+    if (host.y && (rc = download(ctx, host.y, dev.y, nbn))) return rc;
+    if (host.s2 && (rc = download(ctx, host.s2, dev.s2, nbn))) return rc;
+    return PIORAN_OK;
+}
+
+// Sizing a chunk of draws.  `chunk` is halved while need(chunk) bytes of workspace exceed what the call may newly take (ws_allow) plus what
+// the buffers in `held`, the ones need() counts, hold already ...
+using BufList = std::initializer_list<const pioran_ctx::Buf*>;
+template <class Need>
+int64_t budget_chunk(pioran_ctx* ctx, int64_t chunk, BufList held, Need need)
+{
+    size_t free_b = 0;
+    if (!device_free_bytes(free_b)) return chunk;
+    size_t allowed = ws_allow(ctx, free_b);
+    for (const pioran_ctx::Buf* b : held) allowed += b->cap;
+    while (chunk > 1 && need(chunk) > allowed) chunk /= 2;
+    return chunk;
+}
+
+// ... and halved again while ensure_all(chunk), which grows every buffer the chunk needs, cannot allocate.  Returns ensure_all's code for the
+// chunk it leaves in `chunk`.  (The entries that leave the windowed kernels when memory is short, instead of shrinking, use budget_chunk alone.)
+template <class Need, class EnsureAll>
+int size_chunk(pioran_ctx* ctx, int64_t& chunk, BufList held, Need need, EnsureAll ensure_all)
+{
+    chunk = budget_chunk(ctx, chunk, held, need);
+    for (;;) {
+        const int rc = ensure_all(chunk);
+        if (rc != PIORAN_ERR_ALLOC || chunk == 1) return rc;
+        chunk /= 2;
+    }
+}
+
+struct BufNeed { pioran_ctx::Buf* b; size_t bytes; };
+int ensure_each(pioran_ctx* ctx, std::initializer_list<BufNeed> needs)
+{
+    for (const BufNeed& n : needs)
+        if (int rc = ensure(ctx, *n.b, n.bytes)) return rc;
+    return PIORAN_OK;
+}
+
+// second stream + events of the gradient's reverse pass and of the remainder launch (split_dispatch): created on first use
+int ensure_aux(pioran_ctx* ctx)
+{
+    if (ctx->aux) return PIORAN_OK;
+    HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->aux, hipStreamNonBlocking));
+    for (auto& e : ctx->gev) HIPCHK(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return PIORAN_OK;
+}
+
+// May an entry (prediction, gradient, simulation) run on the windowed kernels (celerite_block.hip) with R rows of J terms?
+bool windowed_allowed(const ScanOptions& o, int32_t R, int32_t J)
+{
+    return !o.no_block && !o.force_fallback && !o.scan_config[0] && pioran_block_fits(R, J);
+}
+
+// A data set that lives for one call: the simulation's series of zeros on the caller's time stamps
+struct ScopedDataset {
+    pioran_ds* ds = nullptr;
+    std::vector<double> zeros;
+    ~ScopedDataset() { if (ds) pioran_dataset_destroy(ds); }
+    int create_zeros(pioran_ctx* ctx, int64_t N, const double* t, const double* sigma2)
+    {
+        zeros.assign((size_t)N, 0.0);
+        return pioran_dataset_create(ctx, N, t, zeros.data(), sigma2, &ds);
+    }
+};
 
 // rows kept for a term list.  kind[j]: 0 = shared (c, d): cos + sin row from the shared table;
 //   1 = "real" term (b = d = 0 for every draw): cos row only; 2 = per-draw (c, d): cos + sin row from the per-draw table.
@@ -350,7 +531,7 @@ int block_dispatch(pioran_ds* ds, const ScanParams& p)
                                 : (p.B <= 512 || (p.B <= 768 && p.R >= 32 && p.R <= 47) || (p.B <= 1024 && p.R >= 36 && p.R <= 47)));
     if (!(force || automatic) || !p.tab || p.npd_rows != 0 || !pioran_block_fits_value(p.R, p.J)) return PIORAN_ERR_UNSUPPORTED;
     PrepState* s = p.tab == ds->user.tab ? &ds->user : (p.tab == ds->host.tab ? &ds->host : nullptr);
-    if (!s || !s->prepared || s->npd_terms != 0 || p.rec_stride != 3 * (int64_t)(s->R + 2) + 2) return PIORAN_ERR_UNSUPPORTED;
+    if (!s || !s->prepared || s->npd_terms != 0 || p.rec_stride != rec_stride_of(s->R)) return PIORAN_ERR_UNSUPPORTED;
     int rc = ensure_btab(ds, *s);
     if (rc) return rc;
     g_last_kernel = "block";
@@ -502,7 +683,7 @@ int tp_dispatch(pioran_ds* ds, const ScanParams& p)
     // or the walk ALONE is wrong by more than 1e-8 on a few per thousand of the latter — tools/tp_scan_accept.py, tp_walk_accuracy.py) is evaluated again by the
     // serial-chain windowed kernel (celerite_block_kernel with ScanParams::only_if: its workgroups leave at once for every draw that passed).
     bool repair = !o.tp_walk_repair && !o.tp_unchecked && !o.no_block && pioran_block_fits_value(p.R, p.J) &&
-                  p.rec_stride == 3 * (int64_t)(s->R + 2) + 2 && (p.Y == nullptr) == (p.S2 == nullptr);
+                  p.rec_stride == rec_stride_of(s->R) && (p.Y == nullptr) == (p.S2 == nullptr);
     if (repair) {
         rc = ensure_btab(ds, *s);
         if (rc == PIORAN_ERR_UNSUPPORTED) repair = false;
@@ -574,7 +755,7 @@ int tile_dispatch(pioran_ds* ds, const ScanParams& p)
     }
     if (!(force || automatic) || !p.tab || p.npd_rows != 0 || !pioran_tile_fits(p.R, p.J)) return PIORAN_ERR_UNSUPPORTED;
     PrepState* s = p.tab == ds->user.tab ? &ds->user : (p.tab == ds->host.tab ? &ds->host : nullptr);
-    if (!s || !s->prepared || s->npd_terms != 0 || p.rec_stride != 3 * (int64_t)(s->R + 2) + 2) return PIORAN_ERR_UNSUPPORTED;
+    if (!s || !s->prepared || s->npd_terms != 0 || p.rec_stride != rec_stride_of(s->R)) return PIORAN_ERR_UNSUPPORTED;
     int rc = ensure_btab(ds, *s);
     if (rc) return rc;
     // workspace: 1 KB per draw and window (the windows' own covariance blocks); large batches in chunks of whole passes
@@ -602,7 +783,7 @@ static int split_dispatch(pioran_ds* ds, const ScanParams& p)
         !pioran_block_fits_value(p.R, p.J))
         return PIORAN_ERR_UNSUPPORTED;
     PrepState* s = p.tab == ds->user.tab ? &ds->user : (p.tab == ds->host.tab ? &ds->host : nullptr);
-    if (!s || !s->prepared || s->npd_terms != 0 || p.rec_stride != 3 * (int64_t)(s->R + 2) + 2) return PIORAN_ERR_UNSUPPORTED;
+    if (!s || !s->prepared || s->npd_terms != 0 || p.rec_stride != rec_stride_of(s->R)) return PIORAN_ERR_UNSUPPORTED;
     int wps = 0;
     const int64_t pass = pioran_scan_pass_draws(p, &wps);
     if (pass < 1024) return PIORAN_ERR_UNSUPPORTED;
@@ -624,10 +805,7 @@ static int split_dispatch(pioran_ds* ds, const ScanParams& p)
     }
     int rc = ensure_btab(ds, *s);
     if (rc) return rc;
-    if (!ctx->aux) {
-        HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->aux, hipStreamNonBlocking));
-        for (auto& e : ctx->gev) HIPCHK(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
+    if ((rc = ensure_aux(ctx))) return rc;
     // fork: the second stream sees everything the main stream has queued so far (inputs, tables)
     HIPCHK(ctx, hipEventRecord(ctx->gev[3], ctx->stream));
     HIPCHK(ctx, hipStreamWaitEvent(ctx->aux, ctx->gev[3], 0));
@@ -996,7 +1174,7 @@ static int prepare_state(pioran_ds* ds, PrepState& s, int64_t J, const double* c
         s.tab_cap = need;
     }
     rc = pioran_launch_table(ds->N, s.R, s.rowmap, ds->t, s.dc, s.dd, ds->y, ds->s2, s.tab,
-                             3 * (int64_t)(s.R + 2) + 2, ctx->stream);
+                             rec_stride_of(s.R), ctx->stream);
     if (rc) return rc;
     s.J = (int32_t)J;
     s.real_host = real;
@@ -1026,13 +1204,8 @@ static int batch_dev_impl(pioran_ds* ds, const PrepState& s, int64_t B, const do
     if ((dY == nullptr) != (dS2 == nullptr)) return PIORAN_ERR_ARG;
     pioran_ctx* ctx = ds->ctx;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    ScanParams p{};
-    p.N = ds->N; p.J = s.J; p.R = s.R; p.B = B;
-    p.standard_rows = s.row_layout; p.n_complex = s.n_complex;
-    p.rec_stride = 3 * (int64_t)(s.R + 2) + 2;
-    p.tab = s.tab; p.rowmap = s.rowmap; p.t = ds->t; p.y = ds->y; p.s2 = ds->s2;
-    p.Y = dY; p.S2 = dS2; p.A = dA; p.Bc = dBc; p.C = s.dc; p.D = s.dd;
-    p.mu = dmu; p.nu = dnu; p.out = dout; p.status = dstatus;
+    ScanParams p = shared_params(ds, s, B, {dA, dBc, nullptr, nullptr, dmu, dnu, dY, dS2});
+    p.out = dout; p.status = dstatus;
     return launch(ds, p);
 }
 
@@ -1060,35 +1233,36 @@ int pioran_celerite_logl_batch_dev_cd(pioran_ds* ds, int64_t B, int64_t J, const
     drm = (int32_t*)ctx->bwork.p;
     HIPCHK(ctx, hipMemcpyAsync(drm, rm.data(), rm.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     SYNC(ctx);
-    if ((int64_t)rm.size() > pioran_scan_supported_rows() && (int64_t)rm.size() <= pioran_wide_supported_rows() && !ctx->opt.force_fallback) {
+    const int32_t R = (int32_t)rm.size();
+    // draws [b0, b0 + nb) of the caller's device arrays, on per-draw tables tab_stride doubles apart (0: no tables)
+    auto draws = [&](int64_t b0, int64_t nb, int64_t tab_stride) {
+        const DrawChunk m{dA + b0 * J, dBc + b0 * J, dC + b0 * J, dDd + b0 * J, dmu ? dmu + b0 : nullptr, dnu ? dnu + b0 : nullptr,
+                          dY ? dY + b0 * ds->N : nullptr, dS2 ? dS2 + b0 * ds->N : nullptr};
+        ScanParams q = perdraw_params(ds, (int32_t)J, R, drm, nb, m, tab_stride, 0);
+        q.out = dout + b0; q.status = dstatus ? dstatus + b0 : nullptr;
+        return q;
+    };
+    // a chunk of at most 256 per-draw tables of tdoubles doubles each in bscratch
+    auto size_tables = [&](int64_t tdoubles, int64_t& chunk) {
+        chunk = B < 256 ? B : 256;
+        auto bytes = [&](int64_t nb) { return (size_t)nb * (size_t)tdoubles * sizeof(double); };
+        return size_chunk(ctx, chunk, {&ctx->bscratch}, bytes, [&](int64_t nb) { return ensure(ctx, ctx->bscratch, bytes(nb)); });
+    };
+    if (R > pioran_scan_supported_rows() && R <= pioran_wide_supported_rows() && !ctx->opt.force_fallback) {
         // More rows than the throughput layouts hold (which evaluate per-draw transcendentals in the kernel): every draw gets its
         // OWN table, built for a chunk of draws at a time, and the lean latency kernel walks it (one draw per workgroup) — the
         // reference benchmark's j = 64 with the reference's call pattern (one random (a, b, c, d) per call,
         // benchmark/benchmarks.jl:74-91): 16 k instead of 0.8 k evaluations per second (any-rank kernel, S in HBM).
-        const int32_t R = (int32_t)rm.size();
-        const int64_t rec = 3 * (int64_t)(R + 2) + 2, tdoubles = (int64_t)pioran_table_doubles(ds->N, R);
-        int64_t chunk = B < 256 ? B : 256;
-        {
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-                while (chunk > 1 && (size_t)chunk * (size_t)tdoubles * sizeof(double) > ws_allow(ctx, free_b) + ctx->bscratch.cap) chunk /= 2;
-        }
-        while ((rc = ensure(ctx, ctx->bscratch, (size_t)chunk * (size_t)tdoubles * sizeof(double))) == PIORAN_ERR_ALLOC && chunk > 1) chunk /= 2;
-        if (rc) return rc;
+        const int64_t tdoubles = (int64_t)pioran_table_doubles(ds->N, R);
+        int64_t chunk;
+        if ((rc = size_tables(tdoubles, chunk))) return rc;
         for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-            const int64_t nb = B - b0 < chunk ? B - b0 : chunk;
-            rc = pioran_launch_table_batch(ds->N, R, (int32_t)J, nb, drm, ds->t, dC + b0 * J, dDd + b0 * J, ds->y, ds->s2,
-                                           (double*)ctx->bscratch.p, rec, tdoubles, ctx->stream);
+            const int64_t nb = std::min(B - b0, chunk);
+            ScanParams q = draws(b0, nb, tdoubles);
+            q.tab = (const double*)ctx->bscratch.p;
+            rc = pioran_launch_table_batch(ds->N, R, (int32_t)J, nb, drm, ds->t, q.C, q.D, ds->y, ds->s2, (double*)ctx->bscratch.p, q.rec_stride, tdoubles,
+                                           ctx->stream);
             if (rc) return rc;
-            ScanParams q{};
-            q.opt = &ctx->opt;
-            q.N = ds->N; q.J = (int32_t)J; q.R = R; q.B = nb; q.standard_rows = 1;
-            q.rec_stride = rec; q.tab_draw_stride = tdoubles;
-            q.tab = (const double*)ctx->bscratch.p; q.rowmap = drm; q.t = ds->t; q.y = ds->y; q.s2 = ds->s2;
-            q.Y = dY ? dY + b0 * ds->N : nullptr; q.S2 = dS2 ? dS2 + b0 * ds->N : nullptr;
-            q.A = dA + b0 * J; q.Bc = dBc + b0 * J; q.C = dC + b0 * J; q.D = dDd + b0 * J;
-            q.mu = dmu ? dmu + b0 : nullptr; q.nu = dnu ? dnu + b0 : nullptr;
-            q.out = dout + b0; q.status = dstatus ? dstatus + b0 : nullptr;
             g_last_kernel = "wide (per-draw tables)";
             rc = pioran_launch_scan_wide(q, ctx->stream);
             if (rc) { if (rc == PIORAN_ERR_HIP) ctx->last_err = "per-draw-table latency kernel launch failed"; return rc; }
@@ -1101,33 +1275,18 @@ int pioran_celerite_logl_batch_dev_cd(pioran_ds* ds, int64_t B, int64_t J, const
         // the throughput layout (14.7 ms per launch at N = 1e4, J = 20 whatever the batch): free Celerite / CARMA terms under a sampler
         // (src/CARMA.jl:98-143).  tools/bench_per_draw_small.py.
         const ScanOptions& o = ctx->opt;
-        const int32_t R = (int32_t)rm.size();
         const bool automatic = !o.scan_config[0] && !o.no_block && B <= 768 && R >= 6;
         const bool force = !std::strcmp(o.scan_config, "block");
         if ((automatic || force) && !o.force_fallback && pioran_block_fits(R, (int32_t)J)) {
             const int64_t tdoubles = (int64_t)pioran_block_table_doubles(ds->N, R, (int32_t)J);
-            int64_t chunk = B < 256 ? B : 256;
-            {
-                size_t free_b = 0, total_b = 0;
-                if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-                    while (chunk > 1 && (size_t)chunk * (size_t)tdoubles * sizeof(double) > ws_allow(ctx, free_b) + ctx->bscratch.cap) chunk /= 2;
-            }
-            while ((rc = ensure(ctx, ctx->bscratch, (size_t)chunk * (size_t)tdoubles * sizeof(double))) == PIORAN_ERR_ALLOC && chunk > 1) chunk /= 2;
-            if (rc) return rc;
+            int64_t chunk;
+            if ((rc = size_tables(tdoubles, chunk))) return rc;
             for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-                const int64_t nb = B - b0 < chunk ? B - b0 : chunk;
-                rc = pioran_launch_block_table_batch(ds->N, R, (int32_t)J, nb, drm, ds->t, dC + b0 * J, dDd + b0 * J, ds->y, ds->s2,
-                                                     (double*)ctx->bscratch.p, tdoubles, ctx->stream);
+                const int64_t nb = std::min(B - b0, chunk);
+                const ScanParams q = draws(b0, nb, tdoubles);
+                rc = pioran_launch_block_table_batch(ds->N, R, (int32_t)J, nb, drm, ds->t, q.C, q.D, ds->y, ds->s2, (double*)ctx->bscratch.p, tdoubles,
+                                                     ctx->stream);
                 if (rc) return rc;
-                ScanParams q{};
-                q.opt = &ctx->opt;
-                q.N = ds->N; q.J = (int32_t)J; q.R = R; q.B = nb; q.standard_rows = 1;
-                q.rec_stride = 3 * (int64_t)(R + 2) + 2; q.tab_draw_stride = tdoubles;
-                q.rowmap = drm; q.t = ds->t; q.y = ds->y; q.s2 = ds->s2;
-                q.Y = dY ? dY + b0 * ds->N : nullptr; q.S2 = dS2 ? dS2 + b0 * ds->N : nullptr;
-                q.A = dA + b0 * J; q.Bc = dBc + b0 * J; q.C = dC + b0 * J; q.D = dDd + b0 * J;
-                q.mu = dmu ? dmu + b0 : nullptr; q.nu = dnu ? dnu + b0 : nullptr;
-                q.out = dout + b0; q.status = dstatus ? dstatus + b0 : nullptr;
                 g_last_kernel = "block (per-draw tables)";
                 rc = pioran_launch_scan_block(q, (const double*)ctx->bscratch.p, ctx->stream);
                 if (rc) { if (rc == PIORAN_ERR_HIP) ctx->last_err = "windowed kernel (per-draw tables) launch failed"; return rc; }
@@ -1135,13 +1294,8 @@ int pioran_celerite_logl_batch_dev_cd(pioran_ds* ds, int64_t B, int64_t J, const
             return PIORAN_OK;
         }
     }
-    ScanParams p{};
-    p.N = ds->N; p.J = (int32_t)J; p.R = (int32_t)rm.size(); p.B = B;
-    p.standard_rows = 1;
-    p.rec_stride = 0;
-    p.tab = nullptr; p.rowmap = drm; p.t = ds->t; p.y = ds->y; p.s2 = ds->s2;
-    p.Y = dY; p.S2 = dS2; p.A = dA; p.Bc = dBc; p.C = dC; p.D = dDd;
-    p.mu = dmu; p.nu = dnu; p.out = dout; p.status = dstatus;
+    ScanParams p = draws(0, B, 0);
+    p.rec_stride = 0;   // no table at all: the kernels evaluate the per-draw transcendentals themselves
     return launch(ds, p);
 }
 
@@ -1167,9 +1321,8 @@ static int prepare_shared(pioran_ds* ds, int64_t B, int64_t J, const double* Bc,
 // per-draw terms ignored) declare the layout; `fetch(b0, nb, ptrs)` hands the DEVICE pointers of one chunk of draws
 // (A, Bc, C, D as [nb][J]; mu, nu [nb] or nullptr; Y, S2 [nb][N] or nullptr).  Results go to the caller's host arrays.
 // Returns 1 if it handled the batch, 0 if this layout is not worth / not able to run mixed (caller takes the generic path).
-struct MixedChunk { const double *A, *Bc, *C, *D, *mu, *nu, *Y, *S2; };
 static int mixed_core(pioran_ds* ds, int64_t B, int64_t J, const std::vector<int32_t>& kind, const double* C0, const double* D0,
-                      const std::function<int(int64_t, int64_t, MixedChunk&)>& fetch, double* out, int32_t* status,
+                      const std::function<int(int64_t, int64_t, DrawChunk&)>& fetch, double* out, int32_t* status,
                       bool must_run = false)
 {
     pioran_ctx* ctx = ds->ctx;
@@ -1192,7 +1345,7 @@ static int mixed_core(pioran_ds* ds, int64_t B, int64_t J, const std::vector<int
     }
     if (npd == 0 || npd > 8 || (!must_run && !blk_ok && npd * 2 > J)) return 0;
     if (rows > pioran_scan_supported_rows()) return 0;
-    const int64_t rs_shared = 3 * (rows + 2) + 2;               // shared part of a step record (doubles)
+    const int64_t rs_shared = rec_stride_of(rows);              // shared part of a step record (doubles)
     // combined table: (N+1) records of rs_shared + chunk * 2 npd * 3 doubles, addressed with 32-bit byte offsets
     int64_t chunk = ((int64_t)0x7fff0000 / ((ds->N + 1) * 8) - rs_shared) / (6 * npd);
     chunk = chunk > B ? B : (chunk >= 16 ? chunk & ~(int64_t)15 : chunk);
@@ -1208,30 +1361,21 @@ static int mixed_core(pioran_ds* ds, int64_t B, int64_t J, const std::vector<int
             const int64_t cb = B < 4096 ? B : 4096;
             const size_t trig_bytes = pioran_block_pd_trig_doubles(ds->N, cb, s.npd_terms) * sizeof(double);
             if ((rc = ensure(ctx, ctx->bscratch, trig_bytes))) return rc;
-            if ((rc = ensure(ctx, ctx->bout, cb * sizeof(double)))) return rc;
-            if ((rc = ensure(ctx, ctx->bst, cb * sizeof(int32_t)))) return rc;
+            if ((rc = ensure_results(ctx, cb))) return rc;
             for (int64_t b0 = 0; b0 < B; b0 += cb) {
-                const int64_t nb = B - b0 < cb ? B - b0 : cb;
-                MixedChunk m{};
+                const int64_t nb = std::min(B - b0, cb);
+                DrawChunk m{};
                 if ((rc = fetch(b0, nb, m))) return rc;
                 if ((rc = pioran_launch_block_pd_trig(ds->N, nb, (int32_t)J, s.npd_terms, s.dpd_terms, ds->t, m.D, (double*)ctx->bscratch.p, ctx->stream)))
                     return rc;
-                ScanParams p{};
-                p.N = ds->N; p.J = s.J; p.R = s.R; p.B = nb;
-                p.standard_rows = s.row_layout; p.n_complex = s.n_complex;
-                p.rec_stride = 3 * (int64_t)(s.R + 2) + 2;
-                p.tab = s.tab; p.rowmap = s.rowmap; p.t = ds->t; p.y = ds->y; p.s2 = ds->s2;
-                p.Y = m.Y; p.S2 = m.S2; p.A = m.A; p.Bc = m.Bc; p.C = s.dc; p.D = s.dd;
-                p.mu = m.mu; p.nu = m.nu;
+                ScanParams p = shared_params(ds, s, nb, m);
                 p.out = (double*)ctx->bout.p; p.status = (int32_t*)ctx->bst.p;
                 p.npd_rows = 2 * s.npd_terms;
                 p.pd_C = m.C; p.pd_trig = (const double*)ctx->bscratch.p; p.pd_npad = (ds->N + 15) / 16 * 16;
-                p.opt = &ctx->opt;
                 g_last_kernel = "block+pd";
                 rc = pioran_launch_scan_block(p, s.btab, ctx->stream);
                 if (rc) { ctx->last_err = "windowed kernel (per-draw rows) launch failed"; return rc; }
-                if ((rc = download(ctx, out + b0, ctx->bout.p, nb * sizeof(double)))) return rc;
-                if (status) if ((rc = download(ctx, status + b0, ctx->bst.p, nb * sizeof(int32_t)))) return rc;
+                if ((rc = download_results(ctx, out, status, b0, nb))) return rc;
                 SYNC(ctx);
             }
             return 1;
@@ -1243,29 +1387,21 @@ static int mixed_core(pioran_ds* ds, int64_t B, int64_t J, const std::vector<int
     // shared rows into the combined layout (same kernel as the plain table, wider record stride)
     if ((rc = pioran_launch_table(ds->N, s.R, s.rowmap, ds->t, s.dc, s.dd, ds->y, ds->s2, ctab, rec_stride, ctx->stream)))
         return rc;
-    if ((rc = ensure(ctx, ctx->bout, chunk * sizeof(double)))) return rc;
-    if ((rc = ensure(ctx, ctx->bst, chunk * sizeof(int32_t)))) return rc;
+    if ((rc = ensure_results(ctx, chunk))) return rc;
     for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-        const int64_t nb = B - b0 < chunk ? B - b0 : chunk;
-        MixedChunk m{};
+        const int64_t nb = std::min(B - b0, chunk);
+        DrawChunk m{};
         if ((rc = fetch(b0, nb, m))) return rc;
         rc = pioran_launch_pd_table(ds->N, nb, (int32_t)J, s.npd_terms, s.dpd_terms, ds->t, m.C, m.D, ctab, rec_stride, rs_shared,
                                     ctx->stream);
         if (rc) return rc;
-        ScanParams p{};
-        p.N = ds->N; p.J = s.J; p.R = s.R; p.B = nb;
-        p.standard_rows = s.row_layout; p.n_complex = s.n_complex;
-        p.rec_stride = rec_stride;
-        p.tab = ctab; p.rowmap = s.rowmap; p.t = ds->t; p.y = ds->y; p.s2 = ds->s2;
-        p.Y = m.Y; p.S2 = m.S2; p.A = m.A; p.Bc = m.Bc; p.C = s.dc; p.D = s.dd;
-        p.mu = m.mu; p.nu = m.nu;
+        ScanParams p = shared_params(ds, s, nb, m);
+        p.tab = ctab; p.rec_stride = rec_stride;   // the combined table: the shared records widened by the chunk's per-draw rows
         p.out = (double*)ctx->bout.p; p.status = (int32_t*)ctx->bst.p;
         p.npd_rows = 2 * s.npd_terms;
-        p.opt = &ctx->opt;
         rc = scan_dispatch(p, ctx->stream);
         if (rc) { ctx->last_err = "mixed-mode scan launch failed"; return rc; }
-        if ((rc = download(ctx, out + b0, ctx->bout.p, nb * sizeof(double)))) return rc;
-        if (status) if ((rc = download(ctx, status + b0, ctx->bst.p, nb * sizeof(int32_t)))) return rc;
+        if ((rc = download_results(ctx, out, status, b0, nb))) return rc;
         SYNC(ctx);
     }
     return 1;
@@ -1288,17 +1424,9 @@ static int batch_host_mixed(pioran_ds* ds, int64_t B, int64_t J, const double* A
             kind[j] = allzero ? 1 : 0;
         }
     }
-    auto fetch = [&](int64_t b0, int64_t nb, MixedChunk& m) -> int {
+    auto fetch = [&](int64_t b0, int64_t nb, DrawChunk& m) -> int {
         int rc;
-        const size_t bj = (size_t)nb * (size_t)J * sizeof(double);
-        if ((rc = upload(ctx, ctx->bA, A + b0 * J, bj))) return rc;
-        if ((rc = upload(ctx, ctx->bB, Bc + b0 * J, bj))) return rc;
-        if ((rc = upload(ctx, ctx->bC, C + b0 * J, bj))) return rc;
-        if ((rc = upload(ctx, ctx->bD, Dd + b0 * J, bj))) return rc;
-        if (mu && (rc = upload(ctx, ctx->bmu, mu + b0, nb * sizeof(double)))) return rc;
-        if (nu && (rc = upload(ctx, ctx->bnu, nu + b0, nb * sizeof(double)))) return rc;
-        m.A = (const double*)ctx->bA.p; m.Bc = (const double*)ctx->bB.p; m.C = (const double*)ctx->bC.p; m.D = (const double*)ctx->bD.p;
-        m.mu = mu ? (const double*)ctx->bmu.p : nullptr; m.nu = nu ? (const double*)ctx->bnu.p : nullptr;
+        if ((rc = upload_draws(ctx, J, b0, nb, A, Bc, C, Dd, mu, nu, m))) return rc;
         if (Y) {
             const size_t bn = (size_t)nb * (size_t)ds->N * sizeof(double);
             if ((rc = upload(ctx, ctx->bY, Y + b0 * ds->N, bn))) return rc;
@@ -1374,35 +1502,21 @@ static int batch_host_impl(pioran_ds* ds, int64_t B, int64_t J, const double* A,
         SYNC(ctx);
         return PIORAN_OK;
     }
-    if ((rc = upload(ctx, ctx->bA, A, bj))) return rc;
-    if ((rc = upload(ctx, ctx->bB, Bc, bj))) return rc;
-    if (!cd_shared) {
-        if ((rc = upload(ctx, ctx->bC, C, bj))) return rc;
-        if ((rc = upload(ctx, ctx->bD, Dd, bj))) return rc;
-    }
-    if (mu && (rc = upload(ctx, ctx->bmu, mu, B * sizeof(double)))) return rc;
-    if (nu && (rc = upload(ctx, ctx->bnu, nu, B * sizeof(double)))) return rc;
+    DrawChunk m;
+    if ((rc = upload_draws(ctx, J, 0, B, A, Bc, cd_shared ? nullptr : C, Dd, mu, nu, m))) return rc;
     if (Y) {
         if ((rc = upload(ctx, ctx->bY, Y, bn))) return rc;
         if ((rc = upload(ctx, ctx->bS2, S2, bn))) return rc;
     }
-    if ((rc = ensure(ctx, ctx->bout, B * sizeof(double)))) return rc;
-    if ((rc = ensure(ctx, ctx->bst, B * sizeof(int32_t)))) return rc;
-    const double* dmu = mu ? (const double*)ctx->bmu.p : nullptr;
-    const double* dnu = nu ? (const double*)ctx->bnu.p : nullptr;
+    if ((rc = ensure_results(ctx, B))) return rc;
     const double* dY = (Y || series_on_device) ? (const double*)ctx->bY.p : nullptr;
     const double* dS2 = (Y || series_on_device) ? (const double*)ctx->bS2.p : nullptr;
     if (cd_shared)
-        rc = batch_dev_impl(ds, ds->host, B, (const double*)ctx->bA.p, (const double*)ctx->bB.p, dmu, dnu, dY,
-                                            dS2, (double*)ctx->bout.p, (int32_t*)ctx->bst.p);
+        rc = batch_dev_impl(ds, ds->host, B, m.A, m.Bc, m.mu, m.nu, dY, dS2, (double*)ctx->bout.p, (int32_t*)ctx->bst.p);
     else
-        rc = pioran_celerite_logl_batch_dev_cd(ds, B, J, (const double*)ctx->bA.p, (const double*)ctx->bB.p,
-                                               (const double*)ctx->bC.p, (const double*)ctx->bD.p, dmu, dnu, dY, dS2,
-                                               (double*)ctx->bout.p, (int32_t*)ctx->bst.p);
+        rc = pioran_celerite_logl_batch_dev_cd(ds, B, J, m.A, m.Bc, m.C, m.D, m.mu, m.nu, dY, dS2, (double*)ctx->bout.p, (int32_t*)ctx->bst.p);
     if (rc) return rc;
-    if ((rc = download(ctx, out, ctx->bout.p, B * sizeof(double)))) return rc;
-    if (status)
-        if ((rc = download(ctx, status, ctx->bst.p, B * sizeof(int32_t)))) return rc;
+    if ((rc = download_results(ctx, out, status, 0, B))) return rc;
     SYNC(ctx);
     return PIORAN_OK;
 }
@@ -1527,7 +1641,7 @@ int pioran_logpdf_batch_theta(pioran_ds* ds, int64_t B, int model, int64_t n_com
         std::vector<double> c0((size_t)Jt, 0.0), d0((size_t)Jt, 0.0);
         for (int64_t j = 0; j < Jc; ++j) { kind[j] = real[j] ? 1 : 0; c0[j] = c[j]; d0[j] = d[j]; }
         for (int64_t q = 0; q < n_qpo; ++q) kind[Jc + q] = 2;
-        auto fetch = [&](int64_t b0, int64_t nb, MixedChunk& m) -> int {
+        auto fetch = [&](int64_t b0, int64_t nb, DrawChunk& m) -> int {
             (void)nb;
             m.A = (const double*)ctx->bA.p + b0 * Jt; m.Bc = (const double*)ctx->bB.p + b0 * Jt;
             m.C = dCq + b0 * Jt; m.D = dDq + b0 * Jt;
@@ -1540,8 +1654,7 @@ int pioran_logpdf_batch_theta(pioran_ds* ds, int64_t B, int model, int64_t n_com
         if (rc == 0) return PIORAN_ERR_UNSUPPORTED;   // too many rows for the register-resident kernels
     } else {
         if ((rc = prepare_state(ds, ds->host, Jc, c.data(), d.data(), real.data()))) return rc;
-        if ((rc = ensure(ctx, ctx->bout, B * sizeof(double)))) return rc;
-        if ((rc = ensure(ctx, ctx->bst, B * sizeof(int32_t)))) return rc;
+        if ((rc = ensure_results(ctx, B))) return rc;
         if (shift)
             rc = batch_shift_dev_impl(ds, ds->host, B, (const double*)ctx->bA.p, (const double*)ctx->bB.p, dmu, dnu,
                                       (const double*)ctx->bshift.p, (double*)ctx->bout.p, (int32_t*)ctx->bst.p);
@@ -1549,8 +1662,7 @@ int pioran_logpdf_batch_theta(pioran_ds* ds, int64_t B, int model, int64_t n_com
             rc = batch_dev_impl(ds, ds->host, B, (const double*)ctx->bA.p, (const double*)ctx->bB.p, dmu, dnu, nullptr,
                                 nullptr, (double*)ctx->bout.p, (int32_t*)ctx->bst.p);
         if (rc) return rc;
-        if ((rc = download(ctx, out, ctx->bout.p, B * sizeof(double)))) return rc;
-        if (status) if ((rc = download(ctx, status, ctx->bst.p, B * sizeof(int32_t)))) return rc;
+        if ((rc = download_results(ctx, out, status, 0, B))) return rc;
     }
     if (A_out) if ((rc = download(ctx, A_out, ctx->bA.p, bj))) return rc;
     if (Bc_out) if ((rc = download(ctx, Bc_out, ctx->bB.p, bj))) return rc;
@@ -1598,24 +1710,22 @@ static int predict_shared(pioran_ds* ds, int64_t B, int64_t J, const double* A, 
     int64_t chunk = B < 256 ? B : 256;
     // Windowed path (round 3): z = K^-1 (y - mu) from the windowed factorisation and a block back-substitution (celerite_block.hip),
     // then the two Q recurrences segment-parallel (celerite_predict.hip) — no step-by-step factor, no per-step wave reduction
-    bool windowed = !ctx->opt.no_block && !ctx->opt.force_fallback && !ctx->opt.scan_config[0] && s.R <= 63 &&
-                    pioran_block_fits(s.R, s.J);
+    bool windowed = windowed_allowed(ctx->opt, s.R, s.J) && s.R <= 63;
     if (windowed) {
         rc = ensure_btab(ds, s);
         if (rc == PIORAN_ERR_UNSUPPORTED) windowed = false;
         else if (rc) return rc;
     }
     if (windowed) {
-        size_t free_b = 0, total_b = 0;
         auto need = [&](int64_t nb) {
             return (pioran_block_store_workspace_doubles(nb, ds->N, s.R, 2) + pioran_predict_q_workspace_doubles(nb, ds->N, s.R)) * sizeof(double);
         };
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-            while (chunk > 1 && need(chunk) > ws_allow(ctx, free_b) + ctx->bwork.cap + ctx->bscratch.cap) chunk /= 2;
-        rc = ensure(ctx, ctx->bwork, pioran_block_store_workspace_doubles(chunk, ds->N, s.R, 2) * sizeof(double));
-        if (!rc) rc = ensure(ctx, ctx->bscratch, pioran_predict_q_workspace_doubles(chunk, ds->N, s.R) * sizeof(double));
-        if (!rc) rc = ensure(ctx, ctx->bgtab, pioran_block_gtab_doubles(ds->N, s.R) * sizeof(double));
-        if (!rc) rc = ensure(ctx, ctx->bK, pioran_predict_tau_workspace_doubles(M, s.R, 1) * sizeof(double));
+        chunk = budget_chunk(ctx, chunk, {&ctx->bwork, &ctx->bscratch}, need);
+        // (no memory for the chunk the budget admits: not a smaller chunk, the step-by-step kernels)
+        rc = ensure_each(ctx, {{&ctx->bwork, pioran_block_store_workspace_doubles(chunk, ds->N, s.R, 2) * sizeof(double)},
+                               {&ctx->bscratch, pioran_predict_q_workspace_doubles(chunk, ds->N, s.R) * sizeof(double)},
+                               {&ctx->bgtab, pioran_block_gtab_doubles(ds->N, s.R) * sizeof(double)},
+                               {&ctx->bK, pioran_predict_tau_workspace_doubles(M, s.R, 1) * sizeof(double)}});
         if (rc == PIORAN_ERR_ALLOC) { windowed = false; chunk = B < 256 ? B : 256; }
         else if (rc) return rc;
         if (windowed && (rc = pioran_launch_block_gtab(ds->N, s.R, s.J, s.rowmap, ds->t, s.dc, s.dd, ds->s2, (double*)ctx->bgtab.p, ctx->stream)))
@@ -1624,23 +1734,13 @@ static int predict_shared(pioran_ds* ds, int64_t B, int64_t J, const double* A, 
     if (!windowed && (rc = ensure(ctx, ctx->bwork, pioran_predict_workspace_doubles(chunk, ds->N, s.R) * sizeof(double)))) return rc;
     if ((rc = upload(ctx, ctx->bshift, tau, (size_t)M * sizeof(double)))) return rc;          // tau
     if ((rc = ensure(ctx, ctx->bY, (size_t)chunk * (size_t)M * sizeof(double)))) return rc;   // mean [chunk][M]
-    if ((rc = ensure(ctx, ctx->bout, chunk * sizeof(double)))) return rc;
-    if ((rc = ensure(ctx, ctx->bst, chunk * sizeof(int32_t)))) return rc;
+    if ((rc = ensure_results(ctx, chunk))) return rc;
     for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-        const int64_t nb = B - b0 < chunk ? B - b0 : chunk;
-        if ((rc = upload(ctx, ctx->bA, A + b0 * J, (size_t)nb * J * sizeof(double)))) return rc;
-        if ((rc = upload(ctx, ctx->bB, Bc + b0 * J, (size_t)nb * J * sizeof(double)))) return rc;
-        if (mu && (rc = upload(ctx, ctx->bmu, mu + b0, nb * sizeof(double)))) return rc;
-        if (nu && (rc = upload(ctx, ctx->bnu, nu + b0, nb * sizeof(double)))) return rc;
-        ScanParams p{};
-        p.N = ds->N; p.J = s.J; p.R = s.R; p.B = nb;
-        p.standard_rows = s.row_layout; p.n_complex = s.n_complex;
-        p.rec_stride = 3 * (int64_t)(s.R + 2) + 2;
-        p.tab = s.tab; p.rowmap = s.rowmap; p.t = ds->t; p.y = ds->y; p.s2 = ds->s2;
-        p.A = (const double*)ctx->bA.p; p.Bc = (const double*)ctx->bB.p; p.C = s.dc; p.D = s.dd;
-        p.mu = mu ? (const double*)ctx->bmu.p : nullptr; p.nu = nu ? (const double*)ctx->bnu.p : nullptr;
+        const int64_t nb = std::min(B - b0, chunk);
+        DrawChunk m;
+        if ((rc = upload_draws(ctx, J, b0, nb, A, Bc, nullptr, nullptr, mu, nu, m))) return rc;
+        ScanParams p = shared_params(ds, s, nb, m);
         p.out = (double*)ctx->bout.p; p.status = (int32_t*)ctx->bst.p;
-        p.opt = &ctx->opt;
         if (windowed) {
             p.gw = (double*)ctx->bwork.p;
             g_last_kernel = "block (windowed prediction)";
@@ -1655,7 +1755,7 @@ static int predict_shared(pioran_ds* ds, int64_t B, int64_t J, const double* A, 
         }
         if (rc) { ctx->last_err = "prediction launch failed"; return rc; }
         if ((rc = download(ctx, mean_out + b0 * M, ctx->bY.p, (size_t)nb * M * sizeof(double)))) return rc;
-        if (status) if ((rc = download(ctx, status + b0, ctx->bst.p, nb * sizeof(int32_t)))) return rc;
+        if ((rc = download_results(ctx, nullptr, status, b0, nb))) return rc;
         SYNC(ctx);
     }
     return PIORAN_OK;
@@ -1669,8 +1769,7 @@ static int predict_perdraw_windowed(pioran_ds* ds, int64_t B, int64_t J, const d
 {
     pioran_ctx* ctx = ds->ctx;
     PrepState& s = ds->host;
-    if (ctx->opt.no_block || ctx->opt.force_fallback || ctx->opt.scan_config[0] || !pioran_block_fits((int32_t)(2 * J), (int32_t)J))
-        return PIORAN_ERR_UNSUPPORTED;
+    if (!windowed_allowed(ctx->opt, (int32_t)(2 * J), (int32_t)J)) return PIORAN_ERR_UNSUPPORTED;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     PendingGuard pending_guard(ctx);
     int rc;
@@ -1682,47 +1781,25 @@ static int predict_perdraw_windowed(pioran_ds* ds, int64_t B, int64_t J, const d
                 pioran_predict_tau_workspace_doubles(M, s.R, nb) + (size_t)nb * (size_t)M) * sizeof(double);
     };
     int64_t chunk = B < 256 ? B : 256;
-    {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-            while (chunk > 1 && per_chunk(chunk) > ws_allow(ctx, free_b) + ctx->bwork.cap + ctx->bscratch.cap + ctx->bgtab.cap + ctx->bK.cap + ctx->bq.cap) chunk /= 2;
-    }
-    for (;;) {
-        rc = ensure(ctx, ctx->bwork, pioran_block_store_workspace_doubles(chunk, N, s.R, 2) * sizeof(double));
-        if (!rc) rc = ensure(ctx, ctx->bscratch, (size_t)chunk * (size_t)bt * sizeof(double));
-        if (!rc) rc = ensure(ctx, ctx->bgtab, (size_t)chunk * (size_t)gt * sizeof(double));
-        if (!rc) rc = ensure(ctx, ctx->bq, pioran_predict_q_workspace_doubles(chunk, N, s.R) * sizeof(double));
-        if (!rc) rc = ensure(ctx, ctx->bK, pioran_predict_tau_workspace_doubles(M, s.R, chunk) * sizeof(double));
-        if (!rc) rc = ensure(ctx, ctx->bY, (size_t)chunk * (size_t)M * sizeof(double));
-        if (rc != PIORAN_ERR_ALLOC || chunk == 1) break;
-        chunk /= 2;
-    }
+    rc = size_chunk(ctx, chunk, {&ctx->bwork, &ctx->bscratch, &ctx->bgtab, &ctx->bK, &ctx->bq}, per_chunk, [&](int64_t nb) {
+        return ensure_each(ctx, {{&ctx->bwork, pioran_block_store_workspace_doubles(nb, N, s.R, 2) * sizeof(double)},
+                                 {&ctx->bscratch, (size_t)nb * (size_t)bt * sizeof(double)},
+                                 {&ctx->bgtab, (size_t)nb * (size_t)gt * sizeof(double)},
+                                 {&ctx->bq, pioran_predict_q_workspace_doubles(nb, N, s.R) * sizeof(double)},
+                                 {&ctx->bK, pioran_predict_tau_workspace_doubles(M, s.R, nb) * sizeof(double)},
+                                 {&ctx->bY, (size_t)nb * (size_t)M * sizeof(double)}});
+    });
     if (rc) return rc;
     if ((rc = upload(ctx, ctx->bshift, tau, (size_t)M * sizeof(double)))) return rc;
-    if ((rc = ensure(ctx, ctx->bout, chunk * sizeof(double)))) return rc;
-    if ((rc = ensure(ctx, ctx->bst, chunk * sizeof(int32_t)))) return rc;
+    if ((rc = ensure_results(ctx, chunk))) return rc;
     for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-        const int64_t nb = B - b0 < chunk ? B - b0 : chunk;
-        const size_t nbj = (size_t)nb * J * sizeof(double);
-        if ((rc = upload(ctx, ctx->bA, A + b0 * J, nbj))) return rc;
-        if ((rc = upload(ctx, ctx->bB, Bc + b0 * J, nbj))) return rc;
-        if ((rc = upload(ctx, ctx->bC, C + b0 * J, nbj))) return rc;
-        if ((rc = upload(ctx, ctx->bD, Dd + b0 * J, nbj))) return rc;
-        if (mu && (rc = upload(ctx, ctx->bmu, mu + b0, nb * sizeof(double)))) return rc;
-        if (nu && (rc = upload(ctx, ctx->bnu, nu + b0, nb * sizeof(double)))) return rc;
+        const int64_t nb = std::min(B - b0, chunk);
+        DrawChunk m;
+        if ((rc = upload_draws(ctx, J, b0, nb, A, Bc, C, Dd, mu, nu, m))) return rc;
         double* btab = (double*)ctx->bscratch.p; double* gtab = (double*)ctx->bgtab.p;
-        if ((rc = pioran_launch_block_table_batch(N, s.R, s.J, nb, s.rowmap, ds->t, (const double*)ctx->bC.p, (const double*)ctx->bD.p, ds->y, ds->s2,
-                                                  btab, bt, ctx->stream))) return rc;
-        if ((rc = pioran_launch_block_gtab_batch(N, s.R, s.J, nb, s.rowmap, ds->t, (const double*)ctx->bC.p, (const double*)ctx->bD.p, ds->s2, gtab,
-                                                 gt, ctx->stream))) return rc;
-        ScanParams p{};
-        p.opt = &ctx->opt;
-        p.N = N; p.J = s.J; p.R = s.R; p.B = nb; p.standard_rows = 1;
-        p.rec_stride = 3 * (int64_t)(s.R + 2) + 2;
-        p.tab_draw_stride = bt; p.gtab_draw_stride = gt;
-        p.rowmap = s.rowmap; p.t = ds->t; p.y = ds->y; p.s2 = ds->s2;
-        p.A = (const double*)ctx->bA.p; p.Bc = (const double*)ctx->bB.p; p.C = (const double*)ctx->bC.p; p.D = (const double*)ctx->bD.p;
-        p.mu = mu ? (const double*)ctx->bmu.p : nullptr; p.nu = nu ? (const double*)ctx->bnu.p : nullptr;
+        if ((rc = pioran_launch_block_table_batch(N, s.R, s.J, nb, s.rowmap, ds->t, m.C, m.D, ds->y, ds->s2, btab, bt, ctx->stream))) return rc;
+        if ((rc = pioran_launch_block_gtab_batch(N, s.R, s.J, nb, s.rowmap, ds->t, m.C, m.D, ds->s2, gtab, gt, ctx->stream))) return rc;
+        ScanParams p = perdraw_params(ds, s.J, s.R, s.rowmap, nb, m, bt, gt);
         p.out = (double*)ctx->bout.p; p.status = (int32_t*)ctx->bst.p;
         p.gw = (double*)ctx->bwork.p;
         g_last_kernel = "block (windowed prediction, per-draw tables)";
@@ -1731,7 +1808,7 @@ static int predict_perdraw_windowed(pioran_ds* ds, int64_t B, int64_t J, const d
                                                     (double*)ctx->bY.p, ctx->stream, 1, is_sorted(tau, M));
         if (rc) { ctx->last_err = "windowed prediction launch failed"; return rc; }
         if ((rc = download(ctx, mean_out + b0 * M, ctx->bY.p, (size_t)nb * M * sizeof(double)))) return rc;
-        if (status) if ((rc = download(ctx, status + b0, ctx->bst.p, nb * sizeof(int32_t)))) return rc;
+        if ((rc = download_results(ctx, nullptr, status, b0, nb))) return rc;
         SYNC(ctx);
     }
     return PIORAN_OK;
@@ -1772,42 +1849,26 @@ static int predict_var_shared(pioran_ds* ds, int64_t B, int64_t J, const double*
         return PIORAN_OK;
     }
     int64_t chunk = B < 256 ? B : 256;
-    {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-            while (chunk > 1 && pioran_predict_var_workspace_doubles(chunk, ds->N, s.R, M) * sizeof(double) > ws_allow(ctx, free_b) + ctx->bwork.cap) chunk /= 2;
-    }
-    for (;;) {
-        rc = ensure(ctx, ctx->bwork, pioran_predict_var_workspace_doubles(chunk, ds->N, s.R, M) * sizeof(double));
-        if (!rc) rc = ensure(ctx, ctx->bY, (size_t)chunk * (size_t)M * sizeof(double));
-        if (rc != PIORAN_ERR_ALLOC || chunk == 1) break;
-        chunk /= 2;
-    }
+    auto need = [&](int64_t nb) { return pioran_predict_var_workspace_doubles(nb, ds->N, s.R, M) * sizeof(double); };
+    rc = size_chunk(ctx, chunk, {&ctx->bwork}, need, [&](int64_t nb) {
+        return ensure_each(ctx, {{&ctx->bwork, need(nb)}, {&ctx->bY, (size_t)nb * (size_t)M * sizeof(double)}});
+    });
     if (rc) return rc;
     if ((rc = ensure(ctx, ctx->bK, pioran_predict_tau_workspace_doubles(M, s.R, 1) * sizeof(double)))) return rc;
     if ((rc = upload(ctx, ctx->bshift, tau, (size_t)M * sizeof(double)))) return rc;
-    if ((rc = ensure(ctx, ctx->bout, chunk * sizeof(double)))) return rc;
-    if ((rc = ensure(ctx, ctx->bst, chunk * sizeof(int32_t)))) return rc;
+    if ((rc = ensure_results(ctx, chunk))) return rc;
     for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-        const int64_t nb = B - b0 < chunk ? B - b0 : chunk;
-        if ((rc = upload(ctx, ctx->bA, A + b0 * J, (size_t)nb * J * sizeof(double)))) return rc;
-        if ((rc = upload(ctx, ctx->bB, Bc + b0 * J, (size_t)nb * J * sizeof(double)))) return rc;
-        if (nu && (rc = upload(ctx, ctx->bnu, nu + b0, nb * sizeof(double)))) return rc;
-        ScanParams p{};
-        p.N = ds->N; p.J = s.J; p.R = s.R; p.B = nb;
-        p.standard_rows = s.row_layout; p.n_complex = s.n_complex;
-        p.rec_stride = 3 * (int64_t)(s.R + 2) + 2;
-        p.tab = s.tab; p.rowmap = s.rowmap; p.t = ds->t; p.y = ds->y; p.s2 = ds->s2;
-        p.A = (const double*)ctx->bA.p; p.Bc = (const double*)ctx->bB.p; p.C = s.dc; p.D = s.dd;
-        p.nu = nu ? (const double*)ctx->bnu.p : nullptr;
-        p.out = (double*)ctx->bout.p;
-        p.opt = &ctx->opt;
+        const int64_t nb = std::min(B - b0, chunk);
+        DrawChunk m;
+        if ((rc = upload_draws(ctx, J, b0, nb, A, Bc, nullptr, nullptr, nullptr, nu, m))) return rc;
+        ScanParams p = shared_params(ds, s, nb, m);
+        p.out = (double*)ctx->bout.p;     // (the status comes from the variance kernel itself: bst below)
         g_last_kernel = "wide (step-by-step variance)";
         rc = pioran_launch_predict_var(p, (double*)ctx->bwork.p, (double*)ctx->bK.p, ds->t, M, (const double*)ctx->bshift.p, (double*)ctx->bY.p,
                                        (int32_t*)ctx->bst.p, ctx->stream);
         if (rc) { ctx->last_err = "variance launch failed"; return rc; }
         if ((rc = download(ctx, var_out + b0 * M, ctx->bY.p, (size_t)nb * M * sizeof(double)))) return rc;
-        if (status) if ((rc = download(ctx, status + b0, ctx->bst.p, nb * sizeof(int32_t)))) return rc;
+        if ((rc = download_results(ctx, nullptr, status, b0, nb))) return rc;
         SYNC(ctx);
     }
     return PIORAN_OK;
@@ -1852,8 +1913,7 @@ int pioran_celerite_predict_var(pioran_ds* ds, int64_t B, int64_t J, const doubl
 // then refer to the TRANSFORMED series of each draw.  Shared (c, d) [J] only; per-draw (c, d) are looped over by the callers below.
 static int logl_grad_shared(pioran_ds* ds, int64_t B, int64_t J, const double* A, const double* Bc, const double* C,
                             const double* Dd, const double* mu, const double* nu, const double* shift, double* out,
-                            int32_t* status, double* grad_a, double* grad_b, double* grad_c, double* grad_d, double* grad_nu,
-                            double* grad_mu, double* grad_y, double* grad_sigma2, double* grad_shift)
+                            int32_t* status, const GradPtrs& grad, double* grad_shift)
 {
     pioran_ctx* ctx = ds->ctx;
     PrepState& s = ds->host;
@@ -1864,8 +1924,7 @@ static int logl_grad_shared(pioran_ds* ds, int64_t B, int64_t J, const double* A
     if (s.R > pioran_wide_supported_rows_grad() || s.npd_terms) return PIORAN_ERR_UNSUPPORTED;
     // Windowed reverse mode (celerite_block.hip, round 3) whenever the rows fit the windowed kernel, with or without d/d(c, d):
     // 6.3 ms (7.0 with d/d(c, d)) instead of 25 at N = 1e4, J = 20 (series gradients and the shifted log-flux models included).
-    bool windowed = !ctx->opt.no_block && !ctx->opt.force_fallback && !ctx->opt.scan_config[0] &&
-                    pioran_block_fits(s.R, s.J);
+    bool windowed = windowed_allowed(ctx->opt, s.R, s.J);
     if (windowed) {
         rc = ensure_btab(ds, s);
         if (rc == PIORAN_ERR_UNSUPPORTED) windowed = false;
@@ -1877,33 +1936,36 @@ static int logl_grad_shared(pioran_ds* ds, int64_t B, int64_t J, const double* A
     // small-batch kernels keep 41 KB per window and chain and hold one chain per CU.  scan_config = "tile" forces it for any chain count.
     // From 513 chains on (measured, SHO-20 / SHO-12 at N = 1e4: 512 chains 15.1 / 9.3 ms against the small-batch kernels' 11.0 / 9.2; 640 chains 15.2 /
     // 9.4 against 16.6 / 14.0; 2048 chains 27 / 16 against 44 / 36).
-    const bool tilegrad = windowed && (grad_c != nullptr) == (grad_d != nullptr) && !grad_y && !grad_sigma2 && !shift && s.R <= pioran_tile_grad_supported_rows() &&
+    const bool tilegrad = windowed && (grad.c != nullptr) == (grad.d != nullptr) && !grad.y && !grad.s2 && !shift && s.R <= pioran_tile_grad_supported_rows() &&
                           (ctx->opt.force_tile || (!ctx->opt.no_tile && B > 512 && s.R >= 17));
     // (48 .. 63 rows — DRWCelerite-20 is 60: three draws per workgroup there (two with d/d(c, d)); 4096 chains take 126 ms (163 with d/d(c, d)) against 166 (175)
     //  in 512-chain launches of the small-batch kernels: tools/ab_tile_grad_nb4.py, profiles/r06_tile_grad_four_block_columns.txt.  Until the reverse kernel
     //  stopped spilling at four block columns — T_k and the window's U operands loaded at the head of their own window instead of a window ahead — it was 177 (208).)
-    auto ws_doubles = [&](int64_t nb) {
-        return tilegrad ? pioran_tile_grad_workspace_doubles(nb, ds->N, s.R)
-                        : (windowed ? pioran_block_grad_workspace_doubles(nb, ds->N, s.R) : pioran_grad_workspace_doubles(nb, ds->N, s.R));
+    auto ws_bytes = [&](int64_t nb) {
+        return (tilegrad ? pioran_tile_grad_workspace_doubles(nb, ds->N, s.R)
+                         : (windowed ? pioran_block_grad_workspace_doubles(nb, ds->N, s.R) : pioran_grad_workspace_doubles(nb, ds->N, s.R))) * sizeof(double);
     };
+    auto ensure_ws = [&](int64_t nb) { return ensure(ctx, ctx->bwork, ws_bytes(nb)); };
     // Workspace per draw: (m, D) of every step + S at the checkpoints + two replayed segments (celerite_wide.hip): ~15 MB at
     // N = 1e4, R = 40.  The chunk is bounded by half of the memory that is free right now (plus what this buffer already
     // holds) and halved again if the allocation still fails.
     int64_t chunk = B < 1024 ? B : 1024;
     // windowed: 512 chains per launch pair (the forward pass then runs two workgroups per CU, the reverse pass two rounds of one)
     if (windowed && chunk > 512) chunk = 512;
-    if (tilegrad) chunk = B < 4096 ? B : 4096;      // whole passes of 2048 (1024) chains: 7.7 GB of T per 1024 chains at N = 1e4, three block columns
-    {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            // (tile: the limit holds for the buffer as a whole — "limit + what it holds" let the second call grow a 16 GB buffer to 31 GB)
-            const size_t allowed = tilegrad ? ws_allow(ctx, free_b + ctx->bwork.cap) : ws_allow(ctx, free_b) + ctx->bwork.cap;
-            while (chunk > 1 && ws_doubles(chunk) * sizeof(double) > allowed) chunk = tilegrad && chunk > 1024 ? chunk - 1024 : chunk / 2;
+    if (tilegrad) {
+        // whole passes of 2048 (1024) chains: 7.7 GB of T per 1024 chains at N = 1e4, three block columns.  A sizing rule of its own: the limit holds for
+        // the buffer as a whole ("limit + what it holds" let the second call grow a 16 GB buffer to 31 GB), and the chunk is cut by 1024 chains, then halved
+        chunk = B < 4096 ? B : 4096;
+        size_t free_b = 0;
+        if (device_free_bytes(free_b)) {
+            const size_t allowed = ws_allow(ctx, free_b + ctx->bwork.cap);
+            while (chunk > 1 && ws_bytes(chunk) > allowed) chunk = chunk > 1024 ? chunk - 1024 : chunk / 2;
         }
+        if ((rc = ensure(ctx, ctx->bpair, pioran_tile_workspace_doubles(chunk, ds->N) * sizeof(double)))) return rc;
+        while ((rc = ensure_ws(chunk)) == PIORAN_ERR_ALLOC && chunk > 1) chunk /= 2;
+    } else {
+        rc = size_chunk(ctx, chunk, {&ctx->bwork}, ws_bytes, ensure_ws);
     }
-    if (tilegrad && (rc = ensure(ctx, ctx->bpair, pioran_tile_workspace_doubles(chunk, ds->N) * sizeof(double)))) return rc;
-    while ((rc = ensure(ctx, ctx->bwork, ws_doubles(chunk) * sizeof(double))) == PIORAN_ERR_ALLOC && chunk > 1)
-        chunk /= 2;
     if (rc) return rc;
     double* gtab = nullptr;
     if (windowed) {   // the reverse pass's table (C o v, C o x in C/D order, C_K, sigma2): 13 KB per window, rebuilt per call (10 us)
@@ -1914,26 +1976,19 @@ static int logl_grad_shared(pioran_ds* ds, int64_t B, int64_t J, const double* A
     const size_t cj = (size_t)chunk * (size_t)J * sizeof(double), cn = (size_t)chunk * (size_t)ds->N * sizeof(double);
     if ((rc = ensure(ctx, ctx->bC, 4 * cj))) return rc;              // grad_a | grad_b | grad_c | grad_d
     if ((rc = ensure(ctx, ctx->bD, 2 * chunk * sizeof(double)))) return rc;   // grad_nu | grad_mu
-    const bool want_series = grad_y || grad_sigma2 || shift;   // the shift's chain rule needs both series gradients
+    const bool want_series = grad.y || grad.s2 || shift;   // the shift's chain rule needs both series gradients
     if (want_series && (rc = ensure(ctx, ctx->bY, cn))) return rc;
     if (want_series && (rc = ensure(ctx, ctx->bS2, cn))) return rc;
     if (shift && (rc = ensure(ctx, ctx->bscratch, 2 * cn))) return rc;           // transformed Y | S2 of the chunk
     if (shift && (rc = ensure(ctx, ctx->bshift, 2 * chunk * sizeof(double)))) return rc;   // shift | grad_shift
-    if ((rc = ensure(ctx, ctx->bout, chunk * sizeof(double)))) return rc;
-    if ((rc = ensure(ctx, ctx->bst, chunk * sizeof(int32_t)))) return rc;
+    if ((rc = ensure_results(ctx, chunk))) return rc;
+    if ((rc = ensure_aux(ctx))) return rc;
+    const GradPtrs dev = grad_chunk(ctx, ctx->bC, ctx->bD, chunk, J);
     for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-        const int64_t nb = B - b0 < chunk ? B - b0 : chunk;
-        if ((rc = upload(ctx, ctx->bA, A + b0 * J, (size_t)nb * J * sizeof(double)))) return rc;
-        if ((rc = upload(ctx, ctx->bB, Bc + b0 * J, (size_t)nb * J * sizeof(double)))) return rc;
-        if (mu && (rc = upload(ctx, ctx->bmu, mu + b0, nb * sizeof(double)))) return rc;
-        if (nu && (rc = upload(ctx, ctx->bnu, nu + b0, nb * sizeof(double)))) return rc;
-        ScanParams p{};
-        p.N = ds->N; p.J = s.J; p.R = s.R; p.B = nb;
-        p.standard_rows = s.row_layout; p.n_complex = s.n_complex;
-        p.rec_stride = 3 * (int64_t)(s.R + 2) + 2;
-        p.tab = s.tab; p.rowmap = s.rowmap; p.t = ds->t; p.y = ds->y; p.s2 = ds->s2;
-        p.A = (const double*)ctx->bA.p; p.Bc = (const double*)ctx->bB.p; p.C = s.dc; p.D = s.dd;
-        p.mu = mu ? (const double*)ctx->bmu.p : nullptr; p.nu = nu ? (const double*)ctx->bnu.p : nullptr;
+        const int64_t nb = std::min(B - b0, chunk);
+        DrawChunk m;
+        if ((rc = upload_draws(ctx, J, b0, nb, A, Bc, nullptr, nullptr, mu, nu, m))) return rc;
+        ScanParams p = shared_params(ds, s, nb, m);
         p.out = (double*)ctx->bout.p; p.status = (int32_t*)ctx->bst.p;
         p.g_y = want_series ? (double*)ctx->bY.p : nullptr;
         p.g_s2 = want_series ? (double*)ctx->bS2.p : nullptr;
@@ -1944,26 +1999,18 @@ static int logl_grad_shared(pioran_ds* ds, int64_t B, int64_t J, const double* A
             if ((rc = pioran_launch_shift_transform(ds->N, nb, ds->y, ds->s2, dshift, dYt, dSt, ctx->stream))) return rc;
             p.Y = dYt; p.S2 = dSt;
         }
-        double* dga = (double*)ctx->bC.p; double* dgb = dga + (size_t)chunk * J;
-        double* dgc = dgb + (size_t)chunk * J; double* dgd = dgc + (size_t)chunk * J;
-        double* dgn = (double*)ctx->bD.p; double* dgm = dgn + chunk;
-        if (!ctx->aux) {
-            HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->aux, hipStreamNonBlocking));
-            for (auto& e : ctx->gev) HIPCHK(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        }
-        p.opt = &ctx->opt;
+        double* const dgc = grad.c ? dev.c : nullptr; double* const dgd = grad.d ? dev.d : nullptr;
         if (tilegrad) {
             p.gw = (double*)ctx->bwork.p;
             g_last_kernel = "tile (windowed gradient, one draw per wavefront)";
-            rc = pioran_launch_tile_grad(p, s.btab, gtab, (double*)ctx->bpair.p, dga, dgb, dgn, dgm, grad_c ? dgc : nullptr, grad_d ? dgd : nullptr, ctx->stream);
+            rc = pioran_launch_tile_grad(p, s.btab, gtab, (double*)ctx->bpair.p, dev.a, dev.b, dev.nu, dev.mu, dgc, dgd, ctx->stream);
         } else if (windowed) {
             p.gw = (double*)ctx->bwork.p;
             g_last_kernel = "block (windowed gradient)";
-            rc = pioran_launch_block_grad(p, s.btab, gtab, dga, dgb, dgn, dgm, grad_c ? dgc : nullptr, grad_d ? dgd : nullptr, ctx->stream);
+            rc = pioran_launch_block_grad(p, s.btab, gtab, dev.a, dev.b, dev.nu, dev.mu, dgc, dgd, ctx->stream);
         } else {
             g_last_kernel = "wide (step-by-step gradient)";
-            rc = pioran_launch_scan_wide_grad(p, (double*)ctx->bwork.p, dga, dgb, grad_c ? dgc : nullptr, grad_d ? dgd : nullptr, dgn, dgm,
-                                              ctx->stream, ctx->aux, ctx->gev);
+            rc = pioran_launch_scan_wide_grad(p, (double*)ctx->bwork.p, dev.a, dev.b, dgc, dgd, dev.nu, dev.mu, ctx->stream, ctx->aux, ctx->gev);
         }
         if (rc) { ctx->last_err = "gradient launch failed"; return rc; }
         if (shift) {
@@ -1971,17 +2018,8 @@ static int logl_grad_shared(pioran_ds* ds, int64_t B, int64_t J, const double* A
             if (rc) return rc;
             if ((rc = download(ctx, grad_shift + b0, dshift + chunk, nb * sizeof(double)))) return rc;
         }
-        const size_t nbj = (size_t)nb * J * sizeof(double);
-        if ((rc = download(ctx, out + b0, ctx->bout.p, nb * sizeof(double)))) return rc;
-        if (status) if ((rc = download(ctx, status + b0, ctx->bst.p, nb * sizeof(int32_t)))) return rc;
-        if ((rc = download(ctx, grad_a + b0 * J, dga, nbj))) return rc;
-        if ((rc = download(ctx, grad_b + b0 * J, dgb, nbj))) return rc;
-        if (grad_c) if ((rc = download(ctx, grad_c + b0 * J, dgc, nbj))) return rc;
-        if (grad_d) if ((rc = download(ctx, grad_d + b0 * J, dgd, nbj))) return rc;
-        if (grad_nu) if ((rc = download(ctx, grad_nu + b0, dgn, nb * sizeof(double)))) return rc;
-        if (grad_mu) if ((rc = download(ctx, grad_mu + b0, dgm, nb * sizeof(double)))) return rc;
-        if (grad_y) if ((rc = download(ctx, grad_y + b0 * ds->N, ctx->bY.p, (size_t)nb * ds->N * sizeof(double)))) return rc;
-        if (grad_sigma2) if ((rc = download(ctx, grad_sigma2 + b0 * ds->N, ctx->bS2.p, (size_t)nb * ds->N * sizeof(double)))) return rc;
+        if ((rc = download_results(ctx, out, status, b0, nb))) return rc;
+        if ((rc = download_grads(ctx, grad.from_draw(b0, J, ds->N), dev, nb, J, ds->N))) return rc;
         // Chunks follow each other on the stream without a host synchronisation in between (round 4): every transfer is stream-ordered
         // and staged through pinned memory, which drains itself when it fills (pin_reserve); only the large series gradients, which go
         // straight to the caller's pageable memory, are waited for per chunk.  (No change in time: 4096 chains are 16 launches of 7.5 ms, 122 ms.)
@@ -1997,13 +2035,11 @@ static int logl_grad_shared(pioran_ds* ds, int64_t B, int64_t J, const double* A
 // fit the windowed kernel (the caller then evaluates draw by draw).
 static int logl_grad_perdraw_windowed(pioran_ds* ds, int64_t B, int64_t J, const double* A, const double* Bc, const double* C,
                                       const double* Dd, const double* mu, const double* nu, double* out, int32_t* status,
-                                      double* grad_a, double* grad_b, double* grad_c, double* grad_d, double* grad_nu, double* grad_mu,
-                                      double* grad_y, double* grad_sigma2)
+                                      const GradPtrs& grad)
 {
     pioran_ctx* ctx = ds->ctx;
     PrepState& s = ds->host;
-    if (ctx->opt.no_block || ctx->opt.force_fallback || ctx->opt.scan_config[0] || !pioran_block_fits((int32_t)(2 * J), (int32_t)J))
-        return PIORAN_ERR_UNSUPPORTED;
+    if (!windowed_allowed(ctx->opt, (int32_t)(2 * J), (int32_t)J)) return PIORAN_ERR_UNSUPPORTED;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     PendingGuard pending_guard(ctx);
     int rc;
@@ -2012,69 +2048,37 @@ static int logl_grad_perdraw_windowed(pioran_ds* ds, int64_t B, int64_t J, const
     const int64_t bt = (int64_t)pioran_block_table_doubles(N, s.R, s.J), gt = (int64_t)pioran_block_gtab_doubles(N, s.R);
     const size_t per_draw = ((size_t)bt + (size_t)gt + pioran_block_grad_workspace_doubles(1, N, s.R)) * sizeof(double);
     int64_t chunk = B < 256 ? B : 256;
-    {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-            while (chunk > 1 && (size_t)chunk * per_draw > ws_allow(ctx, free_b) + ctx->bwork.cap + ctx->bscratch.cap + ctx->bgtab.cap) chunk /= 2;
-    }
-    for (;;) {
-        rc = ensure(ctx, ctx->bwork, pioran_block_grad_workspace_doubles(chunk, N, s.R) * sizeof(double));
-        if (!rc) rc = ensure(ctx, ctx->bscratch, (size_t)chunk * (size_t)bt * sizeof(double));
-        if (!rc) rc = ensure(ctx, ctx->bgtab, (size_t)chunk * (size_t)gt * sizeof(double));
-        if (rc != PIORAN_ERR_ALLOC || chunk == 1) break;
-        chunk /= 2;
-    }
+    rc = size_chunk(ctx, chunk, {&ctx->bwork, &ctx->bscratch, &ctx->bgtab}, [&](int64_t nb) { return (size_t)nb * per_draw; }, [&](int64_t nb) {
+        return ensure_each(ctx, {{&ctx->bwork, pioran_block_grad_workspace_doubles(nb, N, s.R) * sizeof(double)},
+                                 {&ctx->bscratch, (size_t)nb * (size_t)bt * sizeof(double)},
+                                 {&ctx->bgtab, (size_t)nb * (size_t)gt * sizeof(double)}});
+    });
     if (rc) return rc;
     const size_t cj = (size_t)chunk * (size_t)J * sizeof(double), cn = (size_t)chunk * (size_t)N * sizeof(double);
     if ((rc = ensure(ctx, ctx->bK, 4 * cj))) return rc;                   // grad_a | grad_b | grad_c | grad_d of the chunk
     if ((rc = ensure(ctx, ctx->bshift, 2 * chunk * sizeof(double)))) return rc;   // grad_nu | grad_mu
-    const bool want_series = grad_y || grad_sigma2;
+    const bool want_series = grad.y || grad.s2;
     if (want_series && (rc = ensure(ctx, ctx->bY, cn))) return rc;
     if (want_series && (rc = ensure(ctx, ctx->bS2, cn))) return rc;
-    if ((rc = ensure(ctx, ctx->bout, chunk * sizeof(double)))) return rc;
-    if ((rc = ensure(ctx, ctx->bst, chunk * sizeof(int32_t)))) return rc;
+    if ((rc = ensure_results(ctx, chunk))) return rc;
+    const GradPtrs dev = grad_chunk(ctx, ctx->bK, ctx->bshift, chunk, J);
     for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-        const int64_t nb = B - b0 < chunk ? B - b0 : chunk;
-        const size_t nbj = (size_t)nb * J * sizeof(double);
-        if ((rc = upload(ctx, ctx->bA, A + b0 * J, nbj))) return rc;
-        if ((rc = upload(ctx, ctx->bB, Bc + b0 * J, nbj))) return rc;
-        if ((rc = upload(ctx, ctx->bC, C + b0 * J, nbj))) return rc;
-        if ((rc = upload(ctx, ctx->bD, Dd + b0 * J, nbj))) return rc;
-        if (mu && (rc = upload(ctx, ctx->bmu, mu + b0, nb * sizeof(double)))) return rc;
-        if (nu && (rc = upload(ctx, ctx->bnu, nu + b0, nb * sizeof(double)))) return rc;
+        const int64_t nb = std::min(B - b0, chunk);
+        DrawChunk m;
+        if ((rc = upload_draws(ctx, J, b0, nb, A, Bc, C, Dd, mu, nu, m))) return rc;
         double* btab = (double*)ctx->bscratch.p; double* gtab = (double*)ctx->bgtab.p;
-        if ((rc = pioran_launch_block_table_batch(N, s.R, s.J, nb, s.rowmap, ds->t, (const double*)ctx->bC.p, (const double*)ctx->bD.p, ds->y, ds->s2,
-                                                  btab, bt, ctx->stream))) return rc;
-        if ((rc = pioran_launch_block_gtab_batch(N, s.R, s.J, nb, s.rowmap, ds->t, (const double*)ctx->bC.p, (const double*)ctx->bD.p, ds->s2, gtab,
-                                                 gt, ctx->stream))) return rc;
-        ScanParams p{};
-        p.opt = &ctx->opt;
-        p.N = N; p.J = s.J; p.R = s.R; p.B = nb; p.standard_rows = 1;
-        p.rec_stride = 3 * (int64_t)(s.R + 2) + 2;
-        p.tab_draw_stride = bt; p.gtab_draw_stride = gt;
-        p.rowmap = s.rowmap; p.t = ds->t; p.y = ds->y; p.s2 = ds->s2;
-        p.A = (const double*)ctx->bA.p; p.Bc = (const double*)ctx->bB.p; p.C = (const double*)ctx->bC.p; p.D = (const double*)ctx->bD.p;
-        p.mu = mu ? (const double*)ctx->bmu.p : nullptr; p.nu = nu ? (const double*)ctx->bnu.p : nullptr;
+        if ((rc = pioran_launch_block_table_batch(N, s.R, s.J, nb, s.rowmap, ds->t, m.C, m.D, ds->y, ds->s2, btab, bt, ctx->stream))) return rc;
+        if ((rc = pioran_launch_block_gtab_batch(N, s.R, s.J, nb, s.rowmap, ds->t, m.C, m.D, ds->s2, gtab, gt, ctx->stream))) return rc;
+        ScanParams p = perdraw_params(ds, s.J, s.R, s.rowmap, nb, m, bt, gt);
         p.out = (double*)ctx->bout.p; p.status = (int32_t*)ctx->bst.p;
         p.g_y = want_series ? (double*)ctx->bY.p : nullptr;
         p.g_s2 = want_series ? (double*)ctx->bS2.p : nullptr;
         p.gw = (double*)ctx->bwork.p;
-        double* dga = (double*)ctx->bK.p; double* dgb = dga + (size_t)chunk * J;
-        double* dgc = dgb + (size_t)chunk * J; double* dgd = dgc + (size_t)chunk * J;
-        double* dgn = (double*)ctx->bshift.p; double* dgm = dgn + chunk;
         g_last_kernel = "block (windowed gradient, per-draw tables)";
-        rc = pioran_launch_block_grad(p, btab, gtab, dga, dgb, dgn, dgm, grad_c ? dgc : nullptr, grad_d ? dgd : nullptr, ctx->stream);
+        rc = pioran_launch_block_grad(p, btab, gtab, dev.a, dev.b, dev.nu, dev.mu, grad.c ? dev.c : nullptr, grad.d ? dev.d : nullptr, ctx->stream);
         if (rc) { ctx->last_err = "windowed gradient launch failed"; return rc; }
-        if ((rc = download(ctx, out + b0, ctx->bout.p, nb * sizeof(double)))) return rc;
-        if (status) if ((rc = download(ctx, status + b0, ctx->bst.p, nb * sizeof(int32_t)))) return rc;
-        if ((rc = download(ctx, grad_a + b0 * J, dga, nbj))) return rc;
-        if ((rc = download(ctx, grad_b + b0 * J, dgb, nbj))) return rc;
-        if (grad_c) if ((rc = download(ctx, grad_c + b0 * J, dgc, nbj))) return rc;
-        if (grad_d) if ((rc = download(ctx, grad_d + b0 * J, dgd, nbj))) return rc;
-        if (grad_nu) if ((rc = download(ctx, grad_nu + b0, dgn, nb * sizeof(double)))) return rc;
-        if (grad_mu) if ((rc = download(ctx, grad_mu + b0, dgm, nb * sizeof(double)))) return rc;
-        if (grad_y) if ((rc = download(ctx, grad_y + b0 * N, ctx->bY.p, (size_t)nb * N * sizeof(double)))) return rc;
-        if (grad_sigma2) if ((rc = download(ctx, grad_sigma2 + b0 * N, ctx->bS2.p, (size_t)nb * N * sizeof(double)))) return rc;
+        if ((rc = download_results(ctx, out, status, b0, nb))) return rc;
+        if ((rc = download_grads(ctx, grad.from_draw(b0, J, N), dev, nb, J, N))) return rc;
         SYNC(ctx);
     }
     return PIORAN_OK;
@@ -2082,29 +2086,22 @@ static int logl_grad_perdraw_windowed(pioran_ds* ds, int64_t B, int64_t J, const
 
 static int logl_grad_impl(pioran_ds* ds, int64_t B, int64_t J, const double* A, const double* Bc, const double* C,
                           const double* Dd, int cd_shared, const double* mu, const double* nu, const double* shift, double* out,
-                          int32_t* status, double* grad_a, double* grad_b, double* grad_c, double* grad_d, double* grad_nu,
-                          double* grad_mu, double* grad_y, double* grad_sigma2, double* grad_shift)
+                          int32_t* status, const GradPtrs& grad, double* grad_shift)
 {
-    if (!ds || B < 1 || J < 1 || !A || !Bc || !C || !Dd || !out || !grad_a || !grad_b) return PIORAN_ERR_ARG;
+    if (!ds || B < 1 || J < 1 || !A || !Bc || !C || !Dd || !out || !grad.a || !grad.b) return PIORAN_ERR_ARG;
     if ((shift == nullptr) != (grad_shift == nullptr)) return PIORAN_ERR_ARG;
-    if (cd_shared || B == 1)
-        return logl_grad_shared(ds, B, J, A, Bc, C, Dd, mu, nu, shift, out, status, grad_a, grad_b, grad_c, grad_d, grad_nu, grad_mu,
-                                grad_y, grad_sigma2, grad_shift);
+    if (cd_shared || B == 1) return logl_grad_shared(ds, B, J, A, Bc, C, Dd, mu, nu, shift, out, status, grad, grad_shift);
     // per-draw (c, d) — CARMA, QPO features, free Celerite sums under NUTS (a handful of chains): all chains in one launch of the
     // windowed reverse mode where the shape fits it, else every draw is its own one-draw batch with its own table
     if (!shift) {
-        const int rc = logl_grad_perdraw_windowed(ds, B, J, A, Bc, C, Dd, mu, nu, out, status, grad_a, grad_b, grad_c, grad_d, grad_nu, grad_mu,
-                                                  grad_y, grad_sigma2);
+        const int rc = logl_grad_perdraw_windowed(ds, B, J, A, Bc, C, Dd, mu, nu, out, status, grad);
         if (rc != PIORAN_ERR_UNSUPPORTED) return rc;
     }
     const int64_t N = ds->N;
     for (int64_t b = 0; b < B; ++b) {
         const int rc = logl_grad_shared(ds, 1, J, A + b * J, Bc + b * J, C + b * J, Dd + b * J, mu ? mu + b : nullptr,
                                         nu ? nu + b : nullptr, shift ? shift + b : nullptr, out + b, status ? status + b : nullptr,
-                                        grad_a + b * J, grad_b + b * J, grad_c ? grad_c + b * J : nullptr,
-                                        grad_d ? grad_d + b * J : nullptr, grad_nu ? grad_nu + b : nullptr,
-                                        grad_mu ? grad_mu + b : nullptr, grad_y ? grad_y + b * N : nullptr,
-                                        grad_sigma2 ? grad_sigma2 + b * N : nullptr, grad_shift ? grad_shift + b : nullptr);
+                                        grad.from_draw(b, J, N), grad_shift ? grad_shift + b : nullptr);
         if (rc) return rc;
     }
     return PIORAN_OK;
@@ -2115,8 +2112,8 @@ int pioran_celerite_logl_grad(pioran_ds* ds, int64_t B, int64_t J, const double*
                               double* grad_a, double* grad_b, double* grad_c, double* grad_d, double* grad_nu, double* grad_mu,
                               double* grad_y, double* grad_sigma2)
 {
-    return logl_grad_impl(ds, B, J, A, Bc, C, Dd, cd_shared, mu, nu, nullptr, out, status, grad_a, grad_b, grad_c, grad_d, grad_nu,
-                          grad_mu, grad_y, grad_sigma2, nullptr);
+    return logl_grad_impl(ds, B, J, A, Bc, C, Dd, cd_shared, mu, nu, nullptr, out, status,
+                          {grad_a, grad_b, grad_c, grad_d, grad_nu, grad_mu, grad_y, grad_sigma2}, nullptr);
 }
 
 int pioran_celerite_logl_grad_shift(pioran_ds* ds, int64_t B, int64_t J, const double* A, const double* Bc, const double* C,
@@ -2125,8 +2122,18 @@ int pioran_celerite_logl_grad_shift(pioran_ds* ds, int64_t B, int64_t J, const d
                                     double* grad_nu, double* grad_mu, double* grad_shift)
 {
     if (!shift || !grad_shift) return PIORAN_ERR_ARG;
-    return logl_grad_impl(ds, B, J, A, Bc, C, Dd, cd_shared, mu, nu, shift, out, status, grad_a, grad_b, grad_c, grad_d, grad_nu,
-                          grad_mu, nullptr, nullptr, grad_shift);
+    return logl_grad_impl(ds, B, J, A, Bc, C, Dd, cd_shared, mu, nu, shift, out, status,
+                          {grad_a, grad_b, grad_c, grad_d, grad_nu, grad_mu, nullptr, nullptr}, grad_shift);
+}
+
+// n doubles of a chunk's realisations (bS2) straight into the caller's array, and wait for them
+static int download_realisations(pioran_ctx* ctx, double* y_out, int64_t n)
+{
+    if (hipMemcpyAsync(y_out, ctx->bS2.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || ctx_sync(ctx) != PIORAN_OK) {
+        ctx->last_err = "simulation copy-back failed";
+        return PIORAN_ERR_HIP;
+    }
+    return PIORAN_OK;
 }
 
 static int simulate_shared(pioran_ctx* ctx, int64_t N, int64_t B, int64_t J, const double* A, const double* Bc,
@@ -2135,51 +2142,42 @@ static int simulate_shared(pioran_ctx* ctx, int64_t N, int64_t B, int64_t J, con
 {
     if (!ctx || N < 1 || B < 1 || J < 1 || !A || !Bc || !C || !Dd || !t || !sigma2 || !q || !y_out) return PIORAN_ERR_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    pioran_ds* ds = nullptr;
-    std::vector<double> zeros((size_t)N, 0.0);
-    int rc = pioran_dataset_create(ctx, N, t, zeros.data(), sigma2, &ds);
+    ScopedDataset series;
+    int rc = series.create_zeros(ctx, N, t, sigma2);
     if (rc) return rc;
-    auto done = [&](int code) { pioran_dataset_destroy(ds); return code; };
-    if ((rc = prepare_shared(ds, B, J, Bc, C, Dd))) return done(rc);
+    pioran_ds* ds = series.ds;
+    if ((rc = prepare_shared(ds, B, J, Bc, C, Dd))) return rc;
     PrepState& s = ds->host;
-    if (s.R > pioran_wide_supported_rows_modes() || s.npd_terms) return done(PIORAN_ERR_UNSUPPORTED);   // before any upload / workspace
+    if (s.R > pioran_wide_supported_rows_modes() || s.npd_terms) return PIORAN_ERR_UNSUPPORTED;   // before any upload / workspace
     int64_t chunk = B < 256 ? B : 256;
     // Windowed path (round 3; 6 .. 63 rows): the windowed factorisation with its per-window stores, then L applied window by window
-    bool windowed = !ctx->opt.no_block && !ctx->opt.force_fallback && !ctx->opt.scan_config[0] && s.R <= 63 &&
-                    pioran_block_fits(s.R, s.J);
+    bool windowed = windowed_allowed(ctx->opt, s.R, s.J) && s.R <= 63;
     if (windowed) {
         rc = ensure_btab(ds, s);
         if (rc == PIORAN_ERR_UNSUPPORTED) windowed = false;
-        else if (rc) return done(rc);
+        else if (rc) return rc;
     }
     if (windowed) {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-            while (chunk > 1 && pioran_block_store_workspace_doubles(chunk, N, s.R, 3) * sizeof(double) > ws_allow(ctx, free_b) + ctx->bwork.cap) chunk /= 2;
-        rc = ensure(ctx, ctx->bwork, pioran_block_store_workspace_doubles(chunk, N, s.R, 3) * sizeof(double));
-        if (!rc) rc = ensure(ctx, ctx->bscratch, (size_t)chunk * (size_t)N * sizeof(double));   // xi
-        if (!rc) rc = ensure(ctx, ctx->bst, chunk * sizeof(int32_t));
+        auto need = [&](int64_t nb) { return pioran_block_store_workspace_doubles(nb, N, s.R, 3) * sizeof(double); };
+        chunk = budget_chunk(ctx, chunk, {&ctx->bwork}, need);
+        // (no memory for the chunk the budget admits: not a smaller chunk, the step-by-step kernel)
+        rc = ensure_each(ctx, {{&ctx->bwork, need(chunk)}, {&ctx->bscratch, (size_t)chunk * (size_t)N * sizeof(double)},   // bscratch: xi
+                               {&ctx->bst, chunk * sizeof(int32_t)}});
         if (rc == PIORAN_ERR_ALLOC) { windowed = false; chunk = B < 256 ? B : 256; }
-        else if (rc) return done(rc);
+        else if (rc) return rc;
     }
     const size_t cn = (size_t)chunk * (size_t)N * sizeof(double);
-    if ((rc = ensure(ctx, ctx->bY, cn))) return done(rc);     // noise
-    if ((rc = ensure(ctx, ctx->bS2, cn))) return done(rc);    // realisations
-    if ((rc = ensure(ctx, ctx->bout, chunk * sizeof(double)))) return done(rc);
+    if ((rc = ensure(ctx, ctx->bY, cn))) return rc;     // noise
+    if ((rc = ensure(ctx, ctx->bS2, cn))) return rc;    // realisations
+    if ((rc = ensure(ctx, ctx->bout, chunk * sizeof(double)))) return rc;
     for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-        const int64_t nb = B - b0 < chunk ? B - b0 : chunk;
-        if ((rc = upload(ctx, ctx->bA, A + b0 * J, (size_t)nb * J * sizeof(double)))) return done(rc);
-        if ((rc = upload(ctx, ctx->bB, Bc + b0 * J, (size_t)nb * J * sizeof(double)))) return done(rc);
-        if ((rc = upload(ctx, ctx->bY, q + b0 * N, (size_t)nb * N * sizeof(double)))) return done(rc);
-        ScanParams p{};
-        p.N = ds->N; p.J = s.J; p.R = s.R; p.B = nb;
-        p.standard_rows = s.row_layout; p.n_complex = s.n_complex;
-        p.rec_stride = 3 * (int64_t)(s.R + 2) + 2;
-        p.tab = s.tab; p.rowmap = s.rowmap; p.t = ds->t; p.y = ds->y; p.s2 = ds->s2;
-        p.A = (const double*)ctx->bA.p; p.Bc = (const double*)ctx->bB.p; p.C = s.dc; p.D = s.dd;
+        const int64_t nb = std::min(B - b0, chunk);
+        DrawChunk m;
+        if ((rc = upload_draws(ctx, J, b0, nb, A, Bc, nullptr, nullptr, nullptr, nullptr, m))) return rc;
+        if ((rc = upload(ctx, ctx->bY, q + b0 * N, (size_t)nb * N * sizeof(double)))) return rc;
+        ScanParams p = shared_params(ds, s, nb, m);
         p.out = (double*)ctx->bout.p;
         p.noise = (const double*)ctx->bY.p; p.ysim = (double*)ctx->bS2.p;
-        p.opt = &ctx->opt;
         if (windowed) {
             p.gw = (double*)ctx->bwork.p;
             p.status = (int32_t*)ctx->bst.p;
@@ -2189,14 +2187,10 @@ static int simulate_shared(pioran_ctx* ctx, int64_t N, int64_t B, int64_t J, con
             g_last_kernel = "wide (step-by-step simulation)";
             rc = pioran_launch_scan_wide_sim(p, ctx->stream);
         }
-        if (rc) { ctx->last_err = "simulation launch failed"; return done(rc); }
-        if (hipMemcpyAsync(y_out + b0 * N, ctx->bS2.p, (size_t)nb * N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-            ctx_sync(ctx) != PIORAN_OK) {
-            ctx->last_err = "simulation copy-back failed";
-            return done(PIORAN_ERR_HIP);
-        }
+        if (rc) { ctx->last_err = "simulation launch failed"; return rc; }
+        if ((rc = download_realisations(ctx, y_out + b0 * N, nb * N))) return rc;
     }
-    return done(PIORAN_OK);
+    return PIORAN_OK;
 }
 
 // (c, d) per draw in every term, several draws: per-draw windowed tables, all draws of a chunk in one launch of every kernel
@@ -2204,68 +2198,44 @@ static int simulate_shared(pioran_ctx* ctx, int64_t N, int64_t B, int64_t J, con
 static int simulate_perdraw_windowed(pioran_ctx* ctx, int64_t N, int64_t B, int64_t J, const double* A, const double* Bc, const double* C,
                                      const double* Dd, const double* t, const double* sigma2, const double* q, double* y_out)
 {
-    if (ctx->opt.no_block || ctx->opt.force_fallback || ctx->opt.scan_config[0] || !pioran_block_fits((int32_t)(2 * J), (int32_t)J))
-        return PIORAN_ERR_UNSUPPORTED;
+    if (!windowed_allowed(ctx->opt, (int32_t)(2 * J), (int32_t)J)) return PIORAN_ERR_UNSUPPORTED;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    pioran_ds* ds = nullptr;
-    std::vector<double> zeros((size_t)N, 0.0);
-    int rc = pioran_dataset_create(ctx, N, t, zeros.data(), sigma2, &ds);
+    ScopedDataset series;
+    int rc = series.create_zeros(ctx, N, t, sigma2);
     if (rc) return rc;
-    auto done = [&](int code) { pioran_dataset_destroy(ds); return code; };
+    pioran_ds* ds = series.ds;
     PrepState& s = ds->host;
-    if ((rc = prepare_state(ds, s, J, C, Dd, nullptr))) return done(rc);    // row map with both rows of every term
+    if ((rc = prepare_state(ds, s, J, C, Dd, nullptr))) return rc;    // row map with both rows of every term
     const int64_t bt = (int64_t)pioran_block_table_doubles(N, s.R, s.J);
     int64_t chunk = B < 256 ? B : 256;
-    {
-        size_t free_b = 0, total_b = 0;
-        auto need = [&](int64_t nb) { return ((size_t)nb * (size_t)bt + pioran_block_store_workspace_doubles(nb, N, s.R, 3) + 3 * (size_t)nb * (size_t)N) * sizeof(double); };
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-            while (chunk > 1 && need(chunk) > ws_allow(ctx, free_b) + ctx->bwork.cap + ctx->bscratch.cap + ctx->bq.cap) chunk /= 2;
-    }
-    for (;;) {
-        rc = ensure(ctx, ctx->bwork, pioran_block_store_workspace_doubles(chunk, N, s.R, 3) * sizeof(double));
-        if (!rc) rc = ensure(ctx, ctx->bscratch, (size_t)chunk * (size_t)bt * sizeof(double));
-        if (!rc) rc = ensure(ctx, ctx->bq, (size_t)chunk * (size_t)N * sizeof(double));     // xi
-        if (rc != PIORAN_ERR_ALLOC || chunk == 1) break;
-        chunk /= 2;
-    }
-    if (rc) return done(rc);
+    auto need = [&](int64_t nb) { return ((size_t)nb * (size_t)bt + pioran_block_store_workspace_doubles(nb, N, s.R, 3) + 3 * (size_t)nb * (size_t)N) * sizeof(double); };
+    rc = size_chunk(ctx, chunk, {&ctx->bwork, &ctx->bscratch, &ctx->bq}, need, [&](int64_t nb) {
+        return ensure_each(ctx, {{&ctx->bwork, pioran_block_store_workspace_doubles(nb, N, s.R, 3) * sizeof(double)},
+                                 {&ctx->bscratch, (size_t)nb * (size_t)bt * sizeof(double)},
+                                 {&ctx->bq, (size_t)nb * (size_t)N * sizeof(double)}});     // bq: xi
+    });
+    if (rc) return rc;
     const size_t cn = (size_t)chunk * (size_t)N * sizeof(double);
-    if ((rc = ensure(ctx, ctx->bY, cn))) return done(rc);     // noise
-    if ((rc = ensure(ctx, ctx->bS2, cn))) return done(rc);    // realisations
-    if ((rc = ensure(ctx, ctx->bout, chunk * sizeof(double)))) return done(rc);
-    if ((rc = ensure(ctx, ctx->bst, chunk * sizeof(int32_t)))) return done(rc);
+    if ((rc = ensure(ctx, ctx->bY, cn))) return rc;     // noise
+    if ((rc = ensure(ctx, ctx->bS2, cn))) return rc;    // realisations
+    if ((rc = ensure_results(ctx, chunk))) return rc;
     for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-        const int64_t nb = B - b0 < chunk ? B - b0 : chunk;
-        const size_t nbj = (size_t)nb * J * sizeof(double);
-        if ((rc = upload(ctx, ctx->bA, A + b0 * J, nbj))) return done(rc);
-        if ((rc = upload(ctx, ctx->bB, Bc + b0 * J, nbj))) return done(rc);
-        if ((rc = upload(ctx, ctx->bC, C + b0 * J, nbj))) return done(rc);
-        if ((rc = upload(ctx, ctx->bD, Dd + b0 * J, nbj))) return done(rc);
-        if ((rc = upload(ctx, ctx->bY, q + b0 * N, (size_t)nb * N * sizeof(double)))) return done(rc);
+        const int64_t nb = std::min(B - b0, chunk);
+        DrawChunk m;
+        if ((rc = upload_draws(ctx, J, b0, nb, A, Bc, C, Dd, nullptr, nullptr, m))) return rc;
+        if ((rc = upload(ctx, ctx->bY, q + b0 * N, (size_t)nb * N * sizeof(double)))) return rc;
         double* btab = (double*)ctx->bscratch.p;
-        if ((rc = pioran_launch_block_table_batch(N, s.R, s.J, nb, s.rowmap, ds->t, (const double*)ctx->bC.p, (const double*)ctx->bD.p, ds->y, ds->s2,
-                                                  btab, bt, ctx->stream))) return done(rc);
-        ScanParams p{};
-        p.opt = &ctx->opt;
-        p.N = N; p.J = s.J; p.R = s.R; p.B = nb; p.standard_rows = 1;
-        p.rec_stride = 3 * (int64_t)(s.R + 2) + 2;
-        p.tab_draw_stride = bt;
-        p.rowmap = s.rowmap; p.t = ds->t; p.y = ds->y; p.s2 = ds->s2;
-        p.A = (const double*)ctx->bA.p; p.Bc = (const double*)ctx->bB.p; p.C = (const double*)ctx->bC.p; p.D = (const double*)ctx->bD.p;
+        if ((rc = pioran_launch_block_table_batch(N, s.R, s.J, nb, s.rowmap, ds->t, m.C, m.D, ds->y, ds->s2, btab, bt, ctx->stream))) return rc;
+        ScanParams p = perdraw_params(ds, s.J, s.R, s.rowmap, nb, m, bt, 0);
         p.out = (double*)ctx->bout.p; p.status = (int32_t*)ctx->bst.p;
         p.noise = (const double*)ctx->bY.p; p.ysim = (double*)ctx->bS2.p;
         p.gw = (double*)ctx->bwork.p;
         g_last_kernel = "block (windowed simulation, per-draw tables)";
         rc = pioran_launch_block_sim(p, btab, (double*)ctx->bq.p, ctx->stream);
-        if (rc) { ctx->last_err = "windowed simulation launch failed"; return done(rc); }
-        if (hipMemcpyAsync(y_out + b0 * N, ctx->bS2.p, (size_t)nb * N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-            ctx_sync(ctx) != PIORAN_OK) {
-            ctx->last_err = "simulation copy-back failed";
-            return done(PIORAN_ERR_HIP);
-        }
+        if (rc) { ctx->last_err = "windowed simulation launch failed"; return rc; }
+        if ((rc = download_realisations(ctx, y_out + b0 * N, nb * N))) return rc;
     }
-    return done(PIORAN_OK);
+    return PIORAN_OK;
 }
 
 int pioran_celerite_simulate(pioran_ctx* ctx, int64_t N, int64_t B, int64_t J, const double* A, const double* Bc,
