@@ -288,15 +288,7 @@ __host__ __device__ constexpr int block_ws_off_q(int NB, int ST) { return ST == 
 __host__ __device__ constexpr int block_ws_off_qf(int NB, int ST) { return ST == 2 ? 0 : NB * NB * 256 + 2 * NB * 256; }
 __host__ __device__ constexpr int block_ws_off_li(int NB, int ST) { return ST == 3 ? NB * 256 : NB * NB * 256 + 3 * NB * 256 + 256; }
 // Between a wavefront's LDS writes and its OWN reads of the same addresses (or the other way round) the LDS's in-order service of a wavefront is the ordering;
-// only the compiler has to be kept from moving them (a counter wait stood here before)
-#ifndef PIORAN_BLK_NOWAIT
-#define PIORAN_BLK_NOWAIT 1      // 256 draws of SHO-20: 1.859 -> 1.834 ms, same box
-#endif
-#if PIORAN_BLK_NOWAIT
-#define PIORAN_BLK_SAMEWAVE() asm volatile("" ::: "memory")
-#else
-#define PIORAN_BLK_SAMEWAVE() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#endif
+// only the compiler has to be kept from moving them: asm volatile("" ::: "memory") below (a counter wait stood there before; 256 draws of SHO-20: 1.859 -> 1.834 ms, same box)
 template <int NB, int EM, int PDM = 0, int ST = 0>   // ST: 0 no stores, 1 everything the reverse pass needs, 2 Q in A-operand order (prediction), 3 Q in C/D order and L^-1, D (simulation)
 __global__ void __launch_bounds__(NB < 4 ? (PDM == 1 ? 320 : 256) : 512, (NB < 4 && PDM != 1 && (!ST || (ST == 1 && EM == 2))) ? 2 : 1) celerite_block_kernel(const ScanParams p, const double* __restrict__ btab)
 {
@@ -650,7 +642,7 @@ __global__ void __launch_bounds__(NB < 4 ? (PDM == 1 ? 320 : 256) : 512, (NB < 4
             double* mg = sh.MG[w];
 #pragma unroll
             for (int g = 0; g < 4; ++g) mg[(4 * g + q) * 18 + c16] = acc[g];
-            PIORAN_BLK_SAMEWAVE();
+            asm volatile("" ::: "memory");
             double mb[4];   // the same block transposed: M [row 16 w + 4 ks + q][step c16], the B operand of U~_w' M_w
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) mb[ks] = mg[c16 * 18 + 4 * ks + q];
@@ -667,7 +659,7 @@ __global__ void __launch_bounds__(NB < 4 ? (PDM == 1 ? 320 : 256) : 512, (NB < 4
             d4 G = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) G = __builtin_amdgcn_mfma_f64_16x16x4f64(uw[ks], mb[ks], G, 0, 0, 0);
-            PIORAN_BLK_SAMEWAVE();   // the read-back comes first: the block's storage is reused
+            asm volatile("" ::: "memory");   // the read-back comes first: the block's storage is reused
 #pragma unroll
             for (int g = 0; g < 4; ++g) mg[g * 64 + lane] = G[g];
         }
@@ -698,7 +690,7 @@ __global__ void __launch_bounds__(NB < 4 ? (PDM == 1 ? 320 : 256) : 512, (NB < 4
             }
 #pragma unroll
             for (int g = 0; g < 4; ++g) sh.Li[(4 * g + q) * 16 + c16] = sg[g];
-            PIORAN_BLK_SAMEWAVE();
+            asm volatile("" ::: "memory");
             PIORAN_BSTAMP(3);
             double m[16];
 #pragma unroll

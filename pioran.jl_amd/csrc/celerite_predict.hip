@@ -17,6 +17,7 @@
 //      with U~_r(tau) = (a cos + b sin | a sin - b cos)(d tau), V_r(tau) = (cos | sin)(d tau)             (:412-413, :457-458).
 // tau must be ascending for the reference; here any order works (each tau is independent).
 #include "common.h"
+#include "device_util.h"
 
 #include <cmath>
 
@@ -32,20 +33,12 @@ __device__ __forceinline__ double wave_sum(double x)
 
 // The same sum, valid in lane 0 only, with the four stages inside a 16-lane row as DPP rotations (row_ror 8, 4, 2, 1: register moves,
 // no LDS crossbar) and the three other rows fetched at once: 6 dependent exchange rounds become 4 short ones + 1.
-template <int CTRL>
-__device__ __forceinline__ double dpp_move(double x)
-{
-    int lo = __double2loint(x), hi = __double2hiint(x);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, false);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
 __device__ __forceinline__ double wave_sum_lane0(double x)
 {
-    x += dpp_move<0x128>(x);   // row_ror:8
-    x += dpp_move<0x124>(x);   // row_ror:4
-    x += dpp_move<0x122>(x);   // row_ror:2
-    x += dpp_move<0x121>(x);   // row_ror:1   -> every lane holds its row's sum
+    x += dpp_perm<0x128, false>(x);   // row_ror:8
+    x += dpp_perm<0x124, false>(x);   // row_ror:4
+    x += dpp_perm<0x122, false>(x);   // row_ror:2
+    x += dpp_perm<0x121, false>(x);   // row_ror:1   -> every lane holds its row's sum
     const double r1 = __shfl(x, 16), r2 = __shfl(x, 32), r3 = __shfl(x, 48);
     return (x + r1) + (r2 + r3);
 }
@@ -599,17 +592,13 @@ namespace {
 // leaves q1 [B][M] and e [B][M][H], the backward kernel reads them and writes the variance.
 constexpr int VD = 4;   // steps whose (W_n, table record, D_n) are in flight ahead of their use
 
-__device__ __forceinline__ double readlane_f64(double x, int k)
-{
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), k), __builtin_amdgcn_readlane(__double2loint(x), k));
-}
 // sum over the 64 lanes, uniform result: four DPP rotations inside the 16-lane rows, then the four row sums by v_readlane
 __device__ __forceinline__ double wave_sum_uniform(double x)
 {
-    x += dpp_move<0x128>(x);   // row_ror:8
-    x += dpp_move<0x124>(x);   // row_ror:4
-    x += dpp_move<0x122>(x);   // row_ror:2
-    x += dpp_move<0x121>(x);   // row_ror:1
+    x += dpp_perm<0x128, false>(x);   // row_ror:8
+    x += dpp_perm<0x124, false>(x);   // row_ror:4
+    x += dpp_perm<0x122, false>(x);   // row_ror:2
+    x += dpp_perm<0x121, false>(x);   // row_ror:1
     return (readlane_f64(x, 0) + readlane_f64(x, 16)) + (readlane_f64(x, 32) + readlane_f64(x, 48));
 }
 

@@ -42,52 +42,14 @@
 
 namespace {
 
-#ifndef PIORAN_TILE_FWD_NOWAIT
-#define PIORAN_TILE_FWD_NOWAIT 1      // no counter wait between a wavefront's LDS writes and its own reads of them (the LDS serves a wavefront in order): -0.3 %, same box
-#endif
-#if PIORAN_TILE_FWD_NOWAIT
-#define PIORAN_TILE_FWD_ORDER() asm volatile("" ::: "memory")
-#else
-#define PIORAN_TILE_FWD_ORDER() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#endif
-#ifndef PIORAN_TILE_ADJ_RAGFIX
-#define PIORAN_TILE_ADJ_RAGFIX 1   // the same in the reverse kernel: 4096 chains of SHO-20 45.60 -> 45.33 ms, same box
-#endif
-#ifndef PIORAN_TILE_RAGFIX4
-#define PIORAN_TILE_RAGFIX4 1     // ... at four block columns and more as a fix-up after the loop with the values loaded again: DRWCelerite-20 -1.5 %, same box
-#endif
-#ifndef PIORAN_TILE_RAGFIX
-#define PIORAN_TILE_RAGFIX 1      // the ragged window's mask once per window under its wave-uniform test: -0.9 %, same box
-#endif
-#ifndef PIORAN_TILE_YSFIX
-#define PIORAN_TILE_YSFIX 1       // the per-draw series as a fix-up of X' under its wave-uniform test instead of a select per block column and step: -0.7 %, same box
-#endif
-#ifndef PIORAN_TILE_BIG_VHA
-#define PIORAN_TILE_BIG_VHA 1      // five and six block columns (one wavefront per SIMD, 512 registers): both preloads, SHO-40 38.0 -> 32.4 ms per 4096 draws, same box
-#endif
-#ifndef PIORAN_TILE_BIG_CKP
-#define PIORAN_TILE_BIG_CKP 1
-#endif
-#ifndef PIORAN_TILE_VHA      // compile-time switches of measured choices (tools/ab_variant_lib.py builds the other side for a same-box A/B)
-#define PIORAN_TILE_VHA 1
-#endif
 constexpr int kTileMaxTerms = 64;
 constexpr int kTileWaves = 4;      // wavefronts (= draws) per workgroup
 // ... of the reverse mode: T_k and T- of a draw are 45 KB (53 with d/d(c, d)) of LDS at four block columns — three draws fit a CU, not four
 // Between a wavefront's LDS writes and its own reads of the same addresses no counter wait is needed — the LDS executes a wavefront's instructions in order —
-// only the compiler has to keep the order:
+// only the compiler has to keep the order (forward kernel: -0.3 % against a wait, same box):
 #define PIORAN_LDS_ORDER() asm volatile("" ::: "memory")
 template <int NB, bool CD = false>
 constexpr int tile_adj_waves() { return NB <= 3 ? 4 : (CD ? 2 : 3); }
-
-typedef unsigned int tile_u32x2 __attribute__((ext_vector_type(2)));
-// 8 bytes through a buffer resource: per-lane byte offset in a VGPR (constant over the kernel), everything that moves (window, block, register
-// of the fragment) in the scalar offset — no vector address arithmetic in the window loop
-__device__ __forceinline__ double tile_bload(__amdgpu_buffer_rsrc_t rs, int voff, int soff)
-{
-    const tile_u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, 0);
-    return __hiloint2double((int)v.y, (int)v.x);
-}
 
 template <int NB>
 struct TileWave {                  // LDS of one wavefront
@@ -236,8 +198,8 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             if (!live_k(I, ks)) continue;
-            cvn[ks] = tile_bload(rs_tab, lane8, so + (I * 4 + ks) * 512);
-            cxn[ks] = tile_bload(rs_tab, lane8, so + (NB * 256 + (I * 4 + ks) * 64) * 8);
+            cvn[ks] = buf_load_f64(rs_tab, lane8, so + (I * 4 + ks) * 512);
+            cxn[ks] = buf_load_f64(rs_tab, lane8, so + (NB * 256 + (I * 4 + ks) * 64) * 8);
         }
     };
     auto form_u = [&](int I) __attribute__((always_inline)) {
@@ -257,7 +219,7 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
     auto fetch_ck = [&](int64_t k) __attribute__((always_inline)) {
         const int so = (int)k * rsb8 + 3 * NB * 256 * 8;
 #pragma unroll
-        for (int i = 0; i < NCK; ++i) ckpre[i] = tile_bload(rs_tab, lane8, so + 512 * i);   // (past 16 NB + 16 doubles: padding / the pair table, not used)
+        for (int i = 0; i < NCK; ++i) ckpre[i] = buf_load_f64(rs_tab, lane8, so + 512 * i);   // (past 16 NB + 16 doubles: padding / the pair table, not used)
     };
     // A of window k, C/D order (row 4 g + q, column c16): the off-diagonal entries from the workspace of tile_pairs_mfma_kernel (pair p =
     // nn (nn - 1) / 2 + jj, jj < nn), fetched one window ahead; the diagonal sum(a) + nu sigma2_n here (:92)
@@ -272,7 +234,7 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
     double apre[4];
     auto fetch_A = [&](int64_t k) __attribute__((always_inline)) {
 #pragma unroll
-        for (int g = 0; g < 4; ++g) apre[g] = tile_bload(rs_pw, pidx[g], (int)k * 1024);
+        for (int g = 0; g < 4; ++g) apre[g] = buf_load_f64(rs_pw, pidx[g], (int)k * 1024);
     };
     // per-draw series (y, sigma2) [B][N]: lanes 0 .. 15 fetch the window's sixteen steps a window ahead (clamped past the end: those steps are masked)
     [[maybe_unused]] double ypre = 0.0, spre = 0.0;
@@ -320,16 +282,16 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
         }
         // (C_K / C) o v of the window: up to three block columns all of it now, behind the matrix instructions of M' (round 6: fetched a block ahead inside the
         // G phase before, its wait stood right behind the issue); more block columns: a block ahead as before (registers)
-        constexpr bool VHA = PIORAN_TILE_VHA && (NB <= 3 || (PIORAN_TILE_BIG_VHA && NB >= 5));
+        // (five and six block columns — one wavefront per SIMD, 512 registers — take this preload and the one of C_K below: SHO-40 38.0 -> 32.4 ms per 4096 draws, same box)
+        constexpr bool VHA = NB <= 3 || NB >= 5;
         [[maybe_unused]] double vha[VHA ? NB : 1][4];
         if constexpr (VHA) {
 #pragma unroll
             for (int I = 0; I < NB; ++I)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) vha[I][g] = tile_bload(rs_tab, lane8, wso + (2 * NB * 256 + (I * 4 + g) * 64) * 8);
-#if PIORAN_TILE_RAGFIX
+                for (int g = 0; g < 4; ++g) vha[I][g] = buf_load_f64(rs_tab, lane8, wso + (2 * NB * 256 + (I * 4 + g) * 64) * 8);
             // the padded steps of the last, ragged window: V^' - mu = 0 there.  Once, under the wave-uniform test, on the loaded values (as a select inside the
-            // block-column loop: four v_cndmask per block column and step in EVERY window, 48 of the ~520 vector instructions)
+            // block-column loop: four v_cndmask per block column and step in EVERY window, 48 of the ~520 vector instructions; -0.9 %, same box)
             if (k == k_ragged) {
 #pragma unroll
                 for (int I = 0; I < NB; ++I)
@@ -337,7 +299,6 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
                     for (int g = 0; g < 4; ++g)
                         if (k * KW + 4 * g + q >= N) vha[I][g] = I == Jy ? mu_y : 0.0;
             }
-#endif
         }
         // ---- M' = U~' T: the lower tiles from registers, the upper ones as transposed reads of their LDS copies -------------------
         d4 x[NB];
@@ -366,7 +327,7 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
         double vh[4];
         if constexpr (!VHA) {
 #pragma unroll
-            for (int g = 0; g < 4; ++g) vh[g] = tile_bload(rs_tab, lane8, wso + (2 * NB * 256 + g * 64) * 8);
+            for (int g = 0; g < 4; ++g) vh[g] = buf_load_f64(rs_tab, lane8, wso + (2 * NB * 256 + g * 64) * 8);
         }
         [[maybe_unused]] double ysv[4] = {0.0, 0.0, 0.0, 0.0};     // per-draw series: read here, once per window
         if constexpr (SER) {
@@ -380,7 +341,7 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
 #pragma unroll
                 for (int g = 0; g < 4; ++g) sw.scr[(4 * g + q) * 18 + c16] = x[Jc][g];
             }
-            PIORAN_TILE_FWD_ORDER();
+            PIORAN_LDS_ORDER();
             double mb[4];   // M [row 16 Jc + 4 ks + q][step c16]
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks)
@@ -394,55 +355,43 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
             for (int g = 0; g < 4; ++g) {
                 double v;
                 if constexpr (VHA) v = vha[Jc][g]; else v = vh[g];
-#if !PIORAN_TILE_YSFIX
-                if (SER && Jc == Jy && c16 == ry) v = ysv[g];     // (the table's y row holds the shared series)
-#endif
                 if (Jc == Jy) v -= mu_y;
-#if PIORAN_TILE_RAGFIX && !PIORAN_TILE_RAGFIX4
-                if constexpr (!VHA)      // (four block columns and more: (C_K / C) o v arrives a block ahead; a forced branch per block there costs more than the selects — 16.7 -> 21.9 ms)
-#endif
-#if !PIORAN_TILE_RAGFIX4
-                if (k == k_ragged && k * KW + 4 * g + q >= N) v = 0.0;
-#endif
                 x[Jc][g] = fma(-ckc, x[Jc][g], v);
                 asm volatile("" : "+v"(x[Jc][g]));   // formed HERE: left to itself the compiler sinks these FMAs below the LDL' and keeps (C_K / C) o v live across it
             }
             if constexpr (!VHA) {
                 if (Jc + 1 < NB) {
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) vh[g] = tile_bload(rs_tab, lane8, wso + (2 * NB * 256 + ((Jc + 1) * 4 + g) * 64) * 8);
+                    for (int g = 0; g < 4; ++g) vh[g] = buf_load_f64(rs_tab, lane8, wso + (2 * NB * 256 + ((Jc + 1) * 4 + g) * 64) * 8);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-#if PIORAN_TILE_RAGFIX4
-        // four block columns and more: the padded steps of the last, ragged window took V^' - mu like the others; taken back here, once, with the table's values
-        // loaded again (a load cannot be speculated: this stays a branch)
+        // four block columns: (C_K / C) o v arrives a block ahead, and the padded steps of the last, ragged window took V^' - mu like the others; taken back here, once,
+        // with the table's values loaded again (a load cannot be speculated: this stays a branch; a branch per block costs more than the selects it saves,
+        // 16.7 -> 21.9 ms; this form against the selects: DRWCelerite-20 -1.5 %, same box)
         if constexpr (!VHA) {
             if (k == k_ragged) {
 #pragma unroll
                 for (int Jc = 0; Jc < NB; ++Jc)
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
-                        const double vt = tile_bload(rs_tab, lane8, wso + (2 * NB * 256 + (Jc * 4 + g) * 64) * 8);
+                        const double vt = buf_load_f64(rs_tab, lane8, wso + (2 * NB * 256 + (Jc * 4 + g) * 64) * 8);
                         if (k * KW + 4 * g + q >= N) x[Jc][g] -= Jc == Jy ? vt - mu_y : vt;
                     }
             }
         }
-#endif
-#if PIORAN_TILE_YSFIX
         // per-draw series: X' = V^' - C_K o M' took the table's (shared) series in the y row; the draw's own replaces it here, in block column Jy alone — as a
-        // select inside the block-column loop it cost 24 v_cndmask per window
+        // select inside the block-column loop it cost 24 v_cndmask per window (-0.7 %, same box)
         if constexpr (SER) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 double vt;
-                if constexpr (VHA) vt = vha[Jy][g]; else vt = tile_bload(rs_tab, lane8, wso + (2 * NB * 256 + (Jy * 4 + g) * 64) * 8);
+                if constexpr (VHA) vt = vha[Jy][g]; else vt = buf_load_f64(rs_tab, lane8, wso + (2 * NB * 256 + (Jy * 4 + g) * 64) * 8);
                 const bool pad = k == k_ragged && k * KW + 4 * g + q >= N;
                 if (c16 == ry && !pad) x[Jy][g] += ysv[g] - vt;
             }
         }
-#endif
         PIORAN_TSTAMP(2);
         PIORAN_TSTAMP(3);
         // ---- Sigma = A - G, Sigma = L D L', L^-1 ----------------------------------------------------------------------------
@@ -453,7 +402,7 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
             for (int g = 0; g < 4; ++g) sw.scr[(4 * g + q) * 16 + c16] = ((on_diag && g == gd) ? dg : apre[g]) - G[g];
         }
         if (k + 1 < NW) fetch_A(k + 1);
-        PIORAN_TILE_FWD_ORDER();
+        PIORAN_LDS_ORDER();
         double m[16];
 #pragma unroll
         for (int j = 0; j < 16; ++j) m[j] = sw.scr[j * 16 + c16];
@@ -469,7 +418,7 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
 #pragma unroll
             for (int j = 0; j < 16; j += 2) dst[j / 2] = double2{m[j], m[j + 1]};
         }
-        PIORAN_TILE_FWD_ORDER();
+        PIORAN_LDS_ORDER();
         double li[4], idv[4];
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
@@ -503,7 +452,7 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
         // C_K of the tiles' rows and columns: up to three block columns read once, in front of the tiles (round 6: left at its uses, every tile starts with an
         // LDS read and a wait for it; SHO-20 10.18 -> 9.97 ms per 4096 draws).  With four block columns the 20 values cost spilled registers (DRWCelerite-20
         // 15.99 -> 16.33 ms): read per tile there, as before.
-        constexpr bool CKP = NB <= 3 || (PIORAN_TILE_BIG_CKP && NB >= 5);
+        constexpr bool CKP = NB <= 3 || NB >= 5;
         [[maybe_unused]] double ckrow[CKP ? NB : 1][4], ckcol[CKP ? NB : 1];
         if constexpr (CKP) {
 #pragma unroll
@@ -544,7 +493,7 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
             __builtin_amdgcn_sched_barrier(0);
         }
         PIORAN_TSTAMP(8);
-        PIORAN_TILE_FWD_ORDER();
+        PIORAN_LDS_ORDER();
     }
 
     PIORAN_TSTAMP_FLUSH
@@ -736,12 +685,12 @@ __global__ void __launch_bounds__((64 * tile_adj_waves<NB, CD>()), 1) celerite_t
             for (int I = 0; I < NB; ++I)
 #pragma unroll
                 for (int ks = 0; ks < 4; ++ks) {
-                    wi.cva[I][ks] = tile_bload(rs_tab, lane8, wso + (I * 4 + ks) * 512);
-                    wi.cxa[I][ks] = tile_bload(rs_tab, lane8, wso + (NB * 256 + (I * 4 + ks) * 64) * 8);
+                    wi.cva[I][ks] = buf_load_f64(rs_tab, lane8, wso + (I * 4 + ks) * 512);
+                    wi.cxa[I][ks] = buf_load_f64(rs_tab, lane8, wso + (NB * 256 + (I * 4 + ks) * 64) * 8);
                 }
         }
 #pragma unroll
-        for (int i = 0; i < NCK; ++i) wi.ckp[i] = tile_bload(rs_tab, lane8, wso + 3 * NB * 256 * 8 + 512 * i);
+        for (int i = 0; i < NCK; ++i) wi.ckp[i] = buf_load_f64(rs_tab, lane8, wso + 3 * NB * 256 * 8 + 512 * i);
 #pragma unroll
         for (int g = 0; g < 4; ++g) wi.ap[g] = pw[kk * 128 + pidx[g]];
     };
@@ -761,8 +710,8 @@ __global__ void __launch_bounds__((64 * tile_adj_waves<NB, CD>()), 1) celerite_t
             for (int I = 0; I < NB; ++I)
 #pragma unroll
                 for (int ks = 0; ks < 4; ++ks) {
-                    cvh[I][ks] = tile_bload(rs_tab, lane8, wso + (I * 4 + ks) * 512);
-                    cxh[I][ks] = tile_bload(rs_tab, lane8, wso + (NB * 256 + (I * 4 + ks) * 64) * 8);
+                    cvh[I][ks] = buf_load_f64(rs_tab, lane8, wso + (I * 4 + ks) * 512);
+                    cxh[I][ks] = buf_load_f64(rs_tab, lane8, wso + (NB * 256 + (I * 4 + ks) * 64) * 8);
                 }
             const d4* tkg = reinterpret_cast<const d4*>(gtb + k * NT * 256);
 #pragma unroll
@@ -774,16 +723,15 @@ __global__ void __launch_bounds__((64 * tile_adj_waves<NB, CD>()), 1) celerite_t
 #pragma unroll
         for (int I = 0; I < NB; ++I)
 #pragma unroll
-            for (int g = 0; g < 4; ++g) vhs[I][g] = tile_bload(rs_tab, lane8, wso + (2 * NB * 256 + (I * 4 + g) * 64) * 8);
-#if PIORAN_TILE_ADJ_RAGFIX
-        if (k == k_ragged) {        // the padded steps of the last, ragged window: V^' - mu = 0 there — once, on the loaded values (celerite_tile_kernel, PIORAN_TILE_RAGFIX)
+            for (int g = 0; g < 4; ++g) vhs[I][g] = buf_load_f64(rs_tab, lane8, wso + (2 * NB * 256 + (I * 4 + g) * 64) * 8);
+        if (k == k_ragged) {        // the padded steps of the last, ragged window: V^' - mu = 0 there — once, on the loaded values as in celerite_tile_kernel
+                                    // (4096 chains of SHO-20 45.60 -> 45.33 ms, same box)
 #pragma unroll
             for (int I = 0; I < NB; ++I)
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
                     if (k * KW + 4 * g + q >= N) vhs[I][g] = mu_sel[I];
         }
-#endif
         // ---- this window's inputs ---------------------------------------------------------------------------------------------
 #pragma unroll
         for (int i = 0; i < NCK; ++i)
@@ -865,9 +813,6 @@ __global__ void __launch_bounds__((64 * tile_adj_waves<NB, CD>()), 1) celerite_t
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     double v = vhs[Jc][g] - mu_sel[Jc];
-#if !PIORAN_TILE_ADJ_RAGFIX
-                    if (k == k_ragged && k * KW + 4 * g + q >= N) v = 0.0;
-#endif
                     x[Jc][g] = fma(-ckc[Jc], x[Jc][g], v);
                     asm volatile("" : "+v"(x[Jc][g]));
                 }
@@ -891,9 +836,6 @@ __global__ void __launch_bounds__((64 * tile_adj_waves<NB, CD>()), 1) celerite_t
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 double v = vhs[Jc][g] - mu_sel[Jc];
-#if !PIORAN_TILE_ADJ_RAGFIX
-                if (k == k_ragged && k * KW + 4 * g + q >= N) v = 0.0;
-#endif
                 x[Jc][g] = fma(-ckc, x[Jc][g], v);
                 asm volatile("" : "+v"(x[Jc][g]));
             }
@@ -987,8 +929,8 @@ __global__ void __launch_bounds__((64 * tile_adj_waves<NB, CD>()), 1) celerite_t
         for (int I = 0; I < NB; ++I)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                cvs[I][g] = tile_bload(rs_gt, lane8, gso + ((I * 4 + g) * 64) * 8);
-                cxs[I][g] = tile_bload(rs_gt, lane8, gso + (NB * 256 + (I * 4 + g) * 64) * 8);
+                cvs[I][g] = buf_load_f64(rs_gt, lane8, gso + ((I * 4 + g) * 64) * 8);
+                cxs[I][g] = buf_load_f64(rs_gt, lane8, gso + (NB * 256 + (I * 4 + g) * 64) * 8);
             }
         __builtin_amdgcn_sched_barrier(0);
         // ---- A: Q in A-operand order; X-' = 2 Q' T- (- q_y in the y column); P = Q' T- Q -----------------------------------------------
@@ -1122,7 +1064,7 @@ __global__ void __launch_bounds__((64 * tile_adj_waves<NB, CD>()), 1) celerite_t
         // d/d(c, d), round 6: the three groups of terms sit where their factor is consumed anyway — X-' here, U~-' in phase D, T- o T_k in the update — so
         // that no operand's life grows (all of them in phase D: 334 spilled registers, the reverse kernel twice as slow)
         if constexpr (CD) {
-            if (lane < 18) sw.tm[lane] = tile_bload(rs_gt, lane8, gso + OFF_TM * 8);
+            if (lane < 18) sw.tm[lane] = buf_load_f64(rs_gt, lane8, gso + OFF_TM * 8);
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         }
         if constexpr (BT) {      // (never with d/d(c, d): tile_adj_batched)
@@ -1156,8 +1098,8 @@ __global__ void __launch_bounds__((64 * tile_adj_waves<NB, CD>()), 1) celerite_t
             if constexpr (CD) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    hvw[g] = tile_bload(rs_gt, lane8, gso + (OFF_H + (Jc * 4 + g) * 64) * 8);
-                    hxw[g] = tile_bload(rs_gt, lane8, gso + (OFF_H + NB * 256 + (Jc * 4 + g) * 64) * 8);
+                    hvw[g] = buf_load_f64(rs_gt, lane8, gso + (OFF_H + (Jc * 4 + g) * 64) * 8);
+                    hxw[g] = buf_load_f64(rs_gt, lane8, gso + (OFF_H + NB * 256 + (Jc * 4 + g) * 64) * 8);
                 }
             }
             d4 su = {0.0, 0.0, 0.0, 0.0};

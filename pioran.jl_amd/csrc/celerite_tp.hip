@@ -27,6 +27,7 @@
 #include <cstdint>
 
 #include "common.h"
+#include "device_util.h"
 
 int pioran_tp_scan_rows(int RP);
 double pioran_tp_scan_tol(const ScanOptions* opt);
@@ -60,49 +61,25 @@ __device__ unsigned long long tp_stamp_buf[32];
 #define TP_STAMP(i) do { } while (0)
 #endif
 
-__device__ __forceinline__ double tp_readlane(double x, int l)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), l), hi = __builtin_amdgcn_readlane(__double2hiint(x), l);
-    return __hiloint2double(hi, lo);
-}
-
-template <int CTRL>
-__device__ __forceinline__ double tp_dpp(double x)
-{
-    int lo = __double2loint(x), hi = __double2hiint(x);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, true);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-
 // the neighbour lane of a row pair (lane ^ 1): quad_perm [1, 0, 3, 2]
-__device__ __forceinline__ double tp_partner(double x) { return tp_dpp<0xB1>(x); }
+__device__ __forceinline__ double tp_partner(double x) { return dpp_perm<0xB1>(x); }
 
 // sums over the wavefront, two at a time: four DPP rounds inside the rows of 16 lanes, then the four row totals as scalar operands
 // (ds_bpermute-based shuffles cost ~700 cycles for the same: the first version of these kernels spent a third of a step there)
 template <bool ROW0 = false>      // ROW0: every contributing lane sits in the first row of 16 lanes (up to 16 state rows): the row total is the total
 __device__ __forceinline__ void tp_sum2(double& a, double& b)
 {
-    a += tp_dpp<0xB1>(a);  b += tp_dpp<0xB1>(b);
-    a += tp_dpp<0x4E>(a);  b += tp_dpp<0x4E>(b);
-    a += tp_dpp<0x141>(a); b += tp_dpp<0x141>(b);
-    a += tp_dpp<0x140>(a); b += tp_dpp<0x140>(b);
+    a += dpp_perm<0xB1>(a);  b += dpp_perm<0xB1>(b);
+    a += dpp_perm<0x4E>(a);  b += dpp_perm<0x4E>(b);
+    a += dpp_perm<0x141>(a); b += dpp_perm<0x141>(b);
+    a += dpp_perm<0x140>(a); b += dpp_perm<0x140>(b);
     if constexpr (ROW0) {
-        a = tp_readlane(a, 0);
-        b = tp_readlane(b, 0);
+        a = readlane_f64(a, 0);
+        b = readlane_f64(b, 0);
     } else {
-        a = (tp_readlane(a, 0) + tp_readlane(a, 16)) + (tp_readlane(a, 32) + tp_readlane(a, 48));
-        b = (tp_readlane(b, 0) + tp_readlane(b, 16)) + (tp_readlane(b, 32) + tp_readlane(b, 48));
+        a = (readlane_f64(a, 0) + readlane_f64(a, 16)) + (readlane_f64(a, 32) + readlane_f64(a, 48));
+        b = (readlane_f64(b, 0) + readlane_f64(b, 16)) + (readlane_f64(b, 32) + readlane_f64(b, 48));
     }
-}
-
-// 1 / x to fp64 accuracy: v_rcp_f64 and two Newton steps (as in celerite_scan.hip)
-__device__ __forceinline__ double tp_rcp(double x)
-{
-    double r = __builtin_amdgcn_rcp(x);
-    r = fma(fma(-x, r, 1.0), r, r);
-    r = fma(fma(-x, r, 1.0), r, r);
-    return r;
 }
 
 // max over the wavefront of non-negative 32-bit keys (the high words of |x|: monotonic for non-negative doubles), DPP folded into v_max_u32
@@ -119,11 +96,11 @@ __device__ __forceinline__ unsigned tp_max_u32(unsigned a)
 
 __device__ __forceinline__ double tp_max(double a)
 {
-    a = fmax(a, tp_dpp<0xB1>(a));
-    a = fmax(a, tp_dpp<0x4E>(a));
-    a = fmax(a, tp_dpp<0x141>(a));
-    a = fmax(a, tp_dpp<0x140>(a));
-    return fmax(fmax(tp_readlane(a, 0), tp_readlane(a, 16)), fmax(tp_readlane(a, 32), tp_readlane(a, 48)));
+    a = fmax(a, dpp_perm<0xB1>(a));
+    a = fmax(a, dpp_perm<0x4E>(a));
+    a = fmax(a, dpp_perm<0x141>(a));
+    a = fmax(a, dpp_perm<0x140>(a));
+    return fmax(fmax(readlane_f64(a, 0), readlane_f64(a, 16)), fmax(readlane_f64(a, 32), readlane_f64(a, 48)));
 }
 
 // ---- phase 0 ---------------------------------------------------------------------------------------------------------------------------------
@@ -285,7 +262,7 @@ __global__ void __launch_bounds__(64 * NWV) tp_filter_kernel(int64_t N, int RP, 
         double sS = hh * Ph, sm = hh * m;
         tp_sum2<NWV == 1>(sS, sm);
         const double S = sbuf[buf][si * 2 + 1].x + sS, v = s0.y - sm;
-        const double iS = tp_rcp(S);
+        const double iS = recip_f64(S);
         Slast = S;
         if (threadIdx.x == 0) sring[k & 255] = S;
         quad = fma(v * v, iS, quad);
@@ -486,7 +463,7 @@ __global__ void __launch_bounds__(64 * NWV) tp_element_kernel(int64_t N, int RP,
         for (int s = 0; s < NP; ++s) { uc[s] = uni[w][0][NWV * s + w]; agc[s] = uni[w][1][NWV * s + w]; }
         double gu = mg * u, gb = mg * bv;
         tp_sum2<NWV == 1>(gu, gb);
-        const double delta = st_s + gu, idel = tp_rcp(delta);
+        const double delta = st_s + gu, idel = recip_f64(delta);
         const double agd = ag * idel, ud = u * idel;
         double xf[NP][2], yv[NP][2];
         double hfx = 0.0, yh = 0.0;
@@ -719,14 +696,14 @@ __global__ void __launch_bounds__(64 * TW) tp_boundary_kernel(int RP, int nseg, 
                 const unsigned mx = tp_max_u32(cand);
                 const unsigned long long bal = __ballot(cand == mx);
                 pr[j] = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(bal));
-                const double ipv = tp_rcp(tp_readlane(xp[j], pr[j]));
+                const double ipv = recip_f64(readlane_f64(xp[j], pr[j]));
                 f[j] = (lane == pr[j] || lane >= RP) ? 0.0 : xp[j] * ipv;
                 if (lane == pr[j]) { used = true; mycol = k0 + j; mypiv = ipv; }
 #pragma unroll
-                for (int jj = j + 1; jj < 4; ++jj) xp[jj] = fma(-f[j], tp_readlane(xp[jj], pr[j]), xp[jj]);
+                for (int jj = j + 1; jj < 4; ++jj) xp[jj] = fma(-f[j], readlane_f64(xp[jj], pr[j]), xp[jj]);
             }
-            const double f01 = tp_readlane(f[0], pr[1]), f02 = tp_readlane(f[0], pr[2]), f03 = tp_readlane(f[0], pr[3]);
-            const double f12 = tp_readlane(f[1], pr[2]), f13 = tp_readlane(f[1], pr[3]), f23 = tp_readlane(f[2], pr[3]);
+            const double f01 = readlane_f64(f[0], pr[1]), f02 = readlane_f64(f[0], pr[2]), f03 = readlane_f64(f[0], pr[3]);
+            const double f12 = readlane_f64(f[1], pr[2]), f13 = readlane_f64(f[1], pr[3]), f23 = readlane_f64(f[2], pr[3]);
             // the rank-4 update of the other columns on the matrix cores: X[:, cols] -= F U, F = (f_0 .. f_3) (rows x 4), U = the four pivot rows as they
             // stand after the earlier pivots of the block (4 x cols).  A wavefront owns whole column tiles of 16 (every row tile of them): the pivot
             // rows of a column are read before any wavefront writes that column.  (As vector FMAs, lane = row: 14 of a boundary's 33 us at 40 rows.)
@@ -930,15 +907,15 @@ __global__ void __launch_bounds__(64 * TW) tp_combine_kernel(int RP, int nseg, i
             const unsigned mx = tp_max_u32(cand);
             const unsigned long long bal = __ballot(cand == mx);
             pr[j] = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(bal));
-            const double ipv = tp_rcp(tp_readlane(xp[j], pr[j]));
+            const double ipv = recip_f64(readlane_f64(xp[j], pr[j]));
             f[j] = (lane == pr[j] || lane >= RP) ? 0.0 : xp[j] * ipv;
             if (lane == pr[j]) { used = true; mycol = k0 + j; mypiv = ipv; }
 #pragma unroll
-            for (int jj = j + 1; jj < 4; ++jj) xp[jj] = fma(-f[j], tp_readlane(xp[jj], pr[j]), xp[jj]);
+            for (int jj = j + 1; jj < 4; ++jj) xp[jj] = fma(-f[j], readlane_f64(xp[jj], pr[j]), xp[jj]);
         }
         if (k0 == 0) TP_STAMP(10);
-        const double f01 = tp_readlane(f[0], pr[1]), f02 = tp_readlane(f[0], pr[2]), f03 = tp_readlane(f[0], pr[3]);
-        const double f12 = tp_readlane(f[1], pr[2]), f13 = tp_readlane(f[1], pr[3]), f23 = tp_readlane(f[2], pr[3]);
+        const double f01 = readlane_f64(f[0], pr[1]), f02 = readlane_f64(f[0], pr[2]), f03 = readlane_f64(f[0], pr[3]);
+        const double f12 = readlane_f64(f[1], pr[2]), f13 = readlane_f64(f[1], pr[3]), f23 = readlane_f64(f[2], pr[3]);
 #pragma unroll
         for (int j = 0; j < 4; ++j) fneg[(w * 4 + j) * 64 + lane] = -f[j];
         if (k0 == 0) TP_STAMP(11);
@@ -1208,14 +1185,14 @@ __global__ void __launch_bounds__(64 * TW) tp_combine_lean_kernel(int RP, int ns
             const unsigned mx = tp_max_u32(cand);
             const unsigned long long bal = __ballot(cand == mx);
             pr[j] = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(bal));
-            const double ipv = tp_rcp(tp_readlane(xp[j], pr[j]));
+            const double ipv = recip_f64(readlane_f64(xp[j], pr[j]));
             f[j] = (lane == pr[j] || lane >= RP) ? 0.0 : xp[j] * ipv;
             if (lane == pr[j]) { used = true; mycol = k0 + j; mypiv = ipv; }
 #pragma unroll
-            for (int jj = j + 1; jj < 4; ++jj) xp[jj] = fma(-f[j], tp_readlane(xp[jj], pr[j]), xp[jj]);
+            for (int jj = j + 1; jj < 4; ++jj) xp[jj] = fma(-f[j], readlane_f64(xp[jj], pr[j]), xp[jj]);
         }
-        const double f01 = tp_readlane(f[0], pr[1]), f02 = tp_readlane(f[0], pr[2]), f03 = tp_readlane(f[0], pr[3]);
-        const double f12 = tp_readlane(f[1], pr[2]), f13 = tp_readlane(f[1], pr[3]), f23 = tp_readlane(f[2], pr[3]);
+        const double f01 = readlane_f64(f[0], pr[1]), f02 = readlane_f64(f[0], pr[2]), f03 = readlane_f64(f[0], pr[3]);
+        const double f12 = readlane_f64(f[1], pr[2]), f13 = readlane_f64(f[1], pr[3]), f23 = readlane_f64(f[2], pr[3]);
 #pragma unroll
         for (int j = 0; j < 4; ++j) fneg[(w * 4 + j) * 64 + lane] = -f[j];
         for (int ct = w; k0 + 4 + 16 * ct < NC; ct += TW) {
@@ -1432,7 +1409,7 @@ __global__ void __launch_bounds__(64) tp_boundary_small_kernel(int nseg, int J, 
                     X[i][c] = sw ? a0 : a1;
                 }
             }
-            const double ipv = tp_rcp(X[k][k]);
+            const double ipv = recip_f64(X[k][k]);
 #pragma unroll
             for (int c = k + 1; c < 2 * R + 1; ++c) X[k][c] *= ipv;
 #pragma unroll
@@ -1546,9 +1523,9 @@ __global__ void __launch_bounds__(64) tp_boundary_wave_kernel(int nseg, int J, c
 #pragma unroll
             for (int k = 0; k < R; ++k) {
                 const double pk = P[k];
-                z = fma(pk, tp_readlane(cur.eta, k), z);
+                z = fma(pk, readlane_f64(cur.eta, k), z);
 #pragma unroll
-                for (int c = 0; c < R; ++c) X[c] = fma(pk, tp_readlane(cur.Jm[c], k), X[c]);      // J[k][c]: lane k's entry c
+                for (int c = 0; c < R; ++c) X[c] = fma(pk, readlane_f64(cur.Jm[c], k), X[c]);      // J[k][c]: lane k's entry c
             }
             X[R] = z;
 #pragma unroll
@@ -1561,18 +1538,18 @@ __global__ void __launch_bounds__(64) tp_boundary_wave_kernel(int nseg, int J, c
         for (int k = 0; k < R; ++k) {
             const double cand = used ? -1.0 : fabs(X[k]);
             double mx = cand;
-            mx = fmax(mx, tp_dpp<0xB1>(mx));
-            mx = fmax(mx, tp_dpp<0x4E>(mx));
-            mx = fmax(mx, tp_dpp<0x141>(mx));
-            mx = fmax(mx, tp_dpp<0x140>(mx));
-            mx = tp_readlane(mx, 0);                       // (the live lanes sit in the first row of 16)
+            mx = fmax(mx, dpp_perm<0xB1>(mx));
+            mx = fmax(mx, dpp_perm<0x4E>(mx));
+            mx = fmax(mx, dpp_perm<0x141>(mx));
+            mx = fmax(mx, dpp_perm<0x140>(mx));
+            mx = readlane_f64(mx, 0);                       // (the live lanes sit in the first row of 16)
             const unsigned long long bal = __ballot(cand == mx);
             const int pr = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(bal));
-            const double ipv = tp_rcp(tp_readlane(X[k], pr));
+            const double ipv = recip_f64(readlane_f64(X[k], pr));
             const double f = (lane == pr || !live) ? 0.0 : X[k] * ipv;
             if (lane == pr) { used = true; mycol = k; mypiv = ipv; }
 #pragma unroll
-            for (int c = k + 1; c < 2 * R + 1; ++c) X[c] = fma(-f, tp_readlane(X[c], pr), X[c]);
+            for (int c = k + 1; c < 2 * R + 1; ++c) X[c] = fma(-f, readlane_f64(X[c], pr), X[c]);
         }
         // the row this lane solved is row `mycol` of [z | Z]: back into natural order through LDS
         if (live) inv[mycol] = lane;
@@ -1588,15 +1565,15 @@ __global__ void __launch_bounds__(64) tp_boundary_wave_kernel(int nseg, int J, c
 #pragma unroll
         for (int k = 0; k < R; ++k) {
             const double ak = cur.A[k];
-            mn = fma(ak, tp_readlane(zn, k), mn);
+            mn = fma(ak, readlane_f64(zn, k), mn);
 #pragma unroll
-            for (int c = 0; c < R; ++c) T[c] = fma(ak, tp_readlane(Z[c], k), T[c]);
+            for (int c = 0; c < R; ++c) T[c] = fma(ak, readlane_f64(Z[c], k), T[c]);
         }
 #pragma unroll
         for (int c = 0; c < R; ++c) {
             double acc = cur.C[c];
 #pragma unroll
-            for (int k = 0; k < R; ++k) acc = fma(T[k], tp_readlane(cur.A[k], c), acc);          // A[c][k]: lane c's entry k
+            for (int k = 0; k < R; ++k) acc = fma(T[k], readlane_f64(cur.A[k], c), acc);          // A[c][k]: lane c's entry k
             Pn[c] = acc;
         }
         // symmetrise (the two products round differently): the transpose through LDS

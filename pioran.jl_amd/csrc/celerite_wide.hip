@@ -30,6 +30,7 @@
 // (celerite_predict.hip); 2 = simulate (the extra row applies L instead of L^-1); 3 = also store S_n, v - q and D_n for
 // celerite_adjoint_kernel below, which walks the recurrence backwards and returns the gradient of log L.
 #include "common.h"
+#include "device_util.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -44,46 +45,7 @@
 
 namespace {
 
-template <int I>
-using ic = std::integral_constant<int, I>;
-template <int B, int E, class F>
-__device__ __forceinline__ void static_for(F&& f)
-{
-    if constexpr (B < E) {
-        f(ic<B>{});
-        static_for<B + 1, E>(f);
-    }
-}
-
-template <int CTRL>
-__device__ __forceinline__ double dpp_perm(double x)
-{
-    int lo = __double2loint(x), hi = __double2hiint(x);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, true);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-
-// sum over the 16 lanes of a DPP row; every lane gets the bit-identical total
-__device__ __forceinline__ double row16_sum(double x)
-{
-    x += dpp_perm<0xB1>(x);   // quad_perm [1,0,3,2]
-    x += dpp_perm<0x4E>(x);   // quad_perm [2,3,0,1]
-    x += dpp_perm<0x141>(x);  // row_half_mirror
-    x += dpp_perm<0x140>(x);  // row_mirror
-    return x;
-}
-
 typedef double d2 __attribute__((ext_vector_type(2)));
-
-// 1/x to fp64 accuracy: v_rcp_f64 seed + two Newton steps (same sequence as celerite_scan.hip)
-__device__ __forceinline__ double recip_f64(double x)
-{
-    double r = __builtin_amdgcn_rcp(x);
-    r = fma(fma(-x, r, 1.0), r, r);
-    r = fma(fma(-x, r, 1.0), r, r);
-    return r;
-}
 
 template <int RPL>
 struct WideIn {   // what one time step reads: (v, x, phi) of the lane's row block and of its column block, y_n, sigma2_n

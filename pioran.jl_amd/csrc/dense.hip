@@ -26,6 +26,7 @@
 //   dense_finish     logdet + z'z reduction -> +NLL.
 #include "../../include/pioran_hip.h"
 #include "common.h"
+#include "device_util.h"
 
 #include <cmath>
 #include <type_traits>
@@ -313,19 +314,6 @@ __global__ void __launch_bounds__(256) dense_build_diag_batch_kernel(int64_t N, 
     }
 }
 
-template <int I>
-using icd = std::integral_constant<int, I>;
-template <class F, int... Is>
-__device__ __forceinline__ void static_for16_impl(F&& f, std::integer_sequence<int, Is...>)
-{
-    (f(icd<Is>{}), ...);
-}
-template <class F>
-__device__ __forceinline__ void static_for16(F&& f)
-{
-    static_for16_impl(f, std::make_integer_sequence<int, 16>{});
-}
-
 // 1/sqrt(x) to fp64 accuracy: v_rsq_f64 + ONE third-order step, y (1 + e/2 + 3e^2/8) with e = 1 - x y^2.
 // Four dependent operations instead of the six of two Newton steps: this sits on the per-column critical path of
 // the diagonal-tile factorisation.  (|e| <= 2^-22 after v_rsq_f64 leaves a relative error ~ e^3 < 2^-66.)
@@ -359,14 +347,6 @@ __device__ __forceinline__ double bcast16(double x)
 }
 
 // ---- the 64 x 64 diagonal factor (round 6) -----------------------------------------------------------------------------------------
-// 1 / x to fp64 accuracy: v_rcp_f64 + two Newton steps.
-__device__ __forceinline__ double recip_f64d(double x)
-{
-    double r = __builtin_amdgcn_rcp(x);
-    r = fma(fma(-x, r, 1.0), r, r);
-    return fma(fma(-x, r, 1.0), r, r);
-}
-
 // The 16 x 16 LDL' + L^-1 of one diagonal tile as an in-place Gauss-Jordan sweep on DPP broadcasts — the form of the windowed celerite
 // kernels (window_common.h), restated here for a tile that lives in the dense slab.  Lane (q, n) holds column n of the (symmetric) tile
 // in m[0..15]; the four DPP rows q hold copies.  Step P: d_P = m[P] of lane P; mult_n = -m[P]_n / d_P (lane P: -2);
@@ -380,19 +360,6 @@ __device__ __forceinline__ double recip_f64d(double x)
 // is the row's own register m[j], last written by the PREVIOUS step's update of that row — at least the seven instructions of the
 // multiplier chain earlier — so the updates need no s_nop (window_common.h's form pays one per group of four: 168 s_nop per sweep in
 // the ISA); only the broadcast of the next pivot, which reads the register the instruction before it wrote, keeps its s_nop 1.
-// multiplier -m / d without a finished reciprocal: r0 = v_rcp_f64(d), e = 1 - d r0, t0 = -m r0, mult = t0 (1 + e + e^2) (relative error e^3 < 1e-22)
-__device__ __forceinline__ double gj_mult_of(double dn, double mrow)
-{
-    double r0, e, t0, pq, mn;
-    asm volatile("v_rcp_f64 %0, %1" : "=v"(r0) : "v"(dn));
-    asm volatile("s_nop 0\n\tv_fma_f64 %0, -%2, %3, 1.0\n\tv_mul_f64 %1, -%4, %2" : "=&v"(e), "=&v"(t0) : "v"(r0), "v"(dn), "v"(mrow));
-    asm volatile("v_fma_f64 %0, %1, %1, %1" : "=v"(pq) : "v"(e));
-    asm volatile("v_fma_f64 %0, %1, %2, %1" : "=v"(mn) : "v"(t0), "v"(pq));
-    return mn;
-}
-// one elimination step = ONE inline-assembly statement (ldl_steps.inc, generated by tools/gen_ldl_steps.py; shared with the windowed celerite kernels):
-// as separate statements per piece the compiler put an `s_nop 0` at most of their boundaries (111 s_nop per sweep, on a chain that waits for every one)
-#include "ldl_steps.inc"
 template <int P>
 __device__ __forceinline__ void gj_sweep(double (&m)[16], double& mult, int c16)
 {
@@ -500,7 +467,7 @@ __device__ __forceinline__ int factor_block64(double* __restrict__ Ls, double* _
 #pragma unroll
         for (int g = 0; g < 4; ++g) Ls[(16 * rt + lr) * LP + 16 * ct + lk + 4 * g] = c[g];
     };
-    static_for16([&](auto sc) {
+    static_for<0, 16>([&](auto sc) {
         constexpr int s = decltype(sc)::value;
         if constexpr (s < 4) {
             constexpr int c0 = 16 * s;
@@ -515,7 +482,7 @@ __device__ __forceinline__ int factor_block64(double* __restrict__ Ls, double* _
                 double d0;
                 asm volatile("s_nop 1\n\tv_mov_b64_dpp %0, %1 row_newbcast:0 row_mask:0xf bank_mask:0xf" : "=v"(d0) : "v"(m[0]));
                 asm volatile("s_nop 0");
-                double mult = gj_mult_of(d0, m[0]);
+                double mult = ldl_mult_of(d0, m[0]);
                 mult = lr == 0 ? -2.0 : mult;
                 gj_sweep<0>(m, mult, lr);
                 PIORAN_STAMP(8 * s + 1);

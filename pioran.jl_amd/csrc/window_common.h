@@ -3,32 +3,11 @@
 // (moved out of celerite_block.hip unchanged in round 5; every item keeps internal linkage)
 #pragma once
 #include "common.h"
-
-#include <cmath>
-#include <type_traits>
+#include "device_util.h"
 
 namespace {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
-
-template <int I>
-using ic = std::integral_constant<int, I>;
-template <int B, int E, class F>
-__device__ __forceinline__ void static_for(F&& f)
-{
-    if constexpr (B < E) {
-        f(ic<B>{});
-        static_for<B + 1, E>(f);
-    }
-}
-
-__device__ __forceinline__ double recip_f64(double x)
-{
-    double r = __builtin_amdgcn_rcp(x);
-    r = fma(fma(-x, r, 1.0), r, r);
-    r = fma(fma(-x, r, 1.0), r, r);
-    return r;
-}
 
 constexpr int KW = 16;   // time steps per window
 
@@ -57,20 +36,8 @@ __host__ __device__ inline int64_t block_rec_doubles(int NB, int J) { return ((3
 // window in the ISA); only the broadcast of the next pivot, which reads the register the instruction before it wrote, keeps its s_nop 1.  At the end lane n holds d_n in m[n] and d_n (L^-1)_jn in m[j], j > n; m[j]_n
 // with j < n is left-over Sigma (the readers mask it).
 // One elimination step with the NEXT pivot's multiplier chain spread between the rank-1 updates of this step, which do not depend on it: the
-// wavefront issues in order, so the order of the instructions is the schedule.  The multiplier -m / d is formed without a finished reciprocal:
-// r0 = v_rcp_f64(d) (24 bits), e = 1 - d r0, t0 = -m r0, mult = t0 (1 + e + e^2) — third order, relative error e^3 < 1e-22 before rounding — four
-// dependent DP operations after the broadcast instead of the seven of "two Newton steps, then multiply".  `mult` is this step's multiplier, on
-// return the next step's; D_P stays in m[P] of lane P.
-// Since round 6 a step is ONE inline-assembly statement (ldl_steps.inc, generated by tools/gen_ldl_steps.py): as separate statements per piece the
-// compiler, which cannot see into them, put an `s_nop 0` at most of their boundaries (~5 per step, 80 per window of the headline kernel).
-__device__ __forceinline__ void blk_rcp(double& r, double d) { asm volatile("v_rcp_f64 %0, %1" : "=v"(r) : "v"(d)); }
-__device__ __forceinline__ void blk_e_t0(double& e, double& t0, double r0, double d, double mrow)
-{
-    asm volatile("s_nop 0\n\tv_fma_f64 %0, -%2, %3, 1.0\n\tv_mul_f64 %1, -%4, %2" : "=&v"(e), "=&v"(t0) : "v"(r0), "v"(d), "v"(mrow));
-}
-__device__ __forceinline__ void blk_poly(double& pq, double e) { asm volatile("v_fma_f64 %0, %1, %1, %1" : "=v"(pq) : "v"(e)); }
-__device__ __forceinline__ void blk_mult(double& mu_, double t0, double pq) { asm volatile("v_fma_f64 %0, %1, %2, %1" : "=v"(mu_) : "v"(t0), "v"(pq)); }
-#include "ldl_steps.inc"
+// wavefront issues in order, so the order of the instructions is the schedule.  `mult` is this step's multiplier (ldl_mult_of, device_util.h), on return the next step's; D_P stays
+// in m[P] of lane P.  The steps themselves are ldl_step_fused<P> (ldl_steps.inc through device_util.h).
 template <int P>
 __device__ __forceinline__ void ldl_step(double (&m)[16], double& mult, int c16)
 {
@@ -78,13 +45,10 @@ __device__ __forceinline__ void ldl_step(double (&m)[16], double& mult, int c16)
 }
 __device__ __forceinline__ double ldl_first_mult(double (&m)[16], int c16)
 {
-    double d0, r0, e, t0, pq, mn;
+    double d0;
     asm volatile("s_nop 1\n\tv_mov_b64_dpp %0, %1 row_newbcast:0 row_mask:0xf bank_mask:0xf" : "=v"(d0) : "v"(m[0]));
     asm volatile("s_nop 0");
-    blk_rcp(r0, d0);
-    blk_e_t0(e, t0, r0, d0, m[0]);
-    blk_poly(pq, e);
-    blk_mult(mn, t0, pq);
+    const double mn = ldl_mult_of(d0, m[0]);
     return c16 == 0 ? -2.0 : mn;
 }
 
