@@ -11,8 +11,10 @@
 //                          tiles are kept: an off-diagonal tile serves twice, as B operand and — transposed for free — as A operand)
 //   G   = U~' M            4 NB   (one transposing LDS round trip per block of M')
 //   Sigma = A - G ; Sigma = L D L' ; L^-1    on v_fmac_f64_dpp row_newbcast (window_common.h), no LDS inside the factorisation
+//   exchange: D_n L^-1 -> A-operand fragments through LDS; 1 / D_n formed once per step and handed over the same way (round 9)
 //   Y^' = L^-1 X'          4 NB
-//   T  <- (C_K C_K') o T + Y^ D^-1 Y^'       2 NB (NB + 1)
+//   T  <- (C_K C_K') o T + Y^ D^-1 Y^'       2 NB (NB + 1)   (up to three block columns the rescaling (C_K C_K') o T stands in the two LDS waits around the
+//                          LDL', round 9: the update is matrix instructions, the Y^ D^-1 products, the LDS copies of the off-diagonal tiles and U~ of the next window)
 // No exchange between wavefronts at all: the four wavefronts of a workgroup (four draws) only share the LDS copy of the window's
 // record (LDS DMA, two buffers, one barrier per window); two workgroups share a CU up to four block columns (<= 256 registers), so
 // every SIMD holds two independent instruction streams — one can run its vector phase (the LDL', the rescaling of T, the pair
@@ -53,7 +55,7 @@ constexpr int tile_adj_waves() { return NB <= 3 ? 4 : (CD ? 2 : 3); }
 
 template <int NB>
 struct TileWave {                  // LDS of one wavefront
-    double scr[16 * 18];           // in turn: a block of M' for the transposing read-back; Sigma [j][n]; D_k (L^-1)_ik at [k * 18 + i]
+    double scr[16 * 18];           // in turn: a block of M' for the transposing read-back; Sigma [j][n]; D_k (L^-1)_ik at [k * 18 + i], 1 / D_k at [k * 18 + 16]
     double2 albe[16 * NB];         // per row: u = al v + be x (:59-63)
     double ck[16 * NB + 16];       // the window's C_K per row, then sigma2 per step (staged from the record: read again and again by the update)
     double ys[16];                 // per-draw series (p.Y: the shifted log-flux models, docs/src/ultranest.md:199-205): y_n of the window's steps
@@ -262,6 +264,21 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
     int Pe = 0;
     bool nonpd = false;
 
+    // PRE (round 9, up to three block columns): the rescaling (C_K C_K') o T of the update does not depend on the window's LDL'.  It stands in two waits instead of
+    // between the update's matrix instructions, where every product cost its full issue time: the tiles of the last row block in the entrance wait of Sigma (the
+    // columns' LDS round trip), the others in the exchange behind the chain (the reciprocals' round trip) — all of it at the entrance takes 218 registers.  The same
+    // product ck_row ck_col multiplies the same T before the same accumulation: the same bits.  Four block columns and more keep it in the update (DRWCelerite-20
+    // +0.7 %, SHO-40 +0.7 % with it here, same box).
+    constexpr bool PRE = NB <= 3;
+    [[maybe_unused]] double ckl[4], ckcl[NB], cku[NB > 1 ? NB - 1 : 1][4];
+    [[maybe_unused]] auto rescale_tile = [&](int I, int Jc, const double (&row)[4]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            T[tix(I, Jc)][g] *= row[g] * ckcl[Jc];
+            if (!(KL == 0 && I == NB - 1 && Jc == NB - 1)) asm volatile("" : "+v"(T[tix(I, Jc)][g]));   // formed HERE (KL = 0: nothing reads that tile, it stays dead)
+        }
+    };
+
     PIORAN_TSTAMP_DECL
     for (int64_t k = 0; k < NW; ++k) {
         PIORAN_TSTAMP(0);
@@ -395,6 +412,12 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
         PIORAN_TSTAMP(2);
         PIORAN_TSTAMP(3);
         // ---- Sigma = A - G, Sigma = L D L', L^-1 ----------------------------------------------------------------------------
+        if constexpr (PRE) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) ckl[g] = sw.ck[16 * (NB - 1) + 4 * g + q];
+#pragma unroll
+            for (int Jc = 0; Jc < NB; ++Jc) ckcl[Jc] = sw.ck[16 * Jc + c16];
+        }
         {
             const double s2n = sw.ck[16 * NB + c16];
             const double dg = k * KW + c16 < N ? suma + (has_nu ? nu * s2n : s2n) : 1.0;   // :92; padded steps of the last window: D = 1
@@ -406,6 +429,12 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
         double m[16];
 #pragma unroll
         for (int j = 0; j < 16; ++j) m[j] = sw.scr[j * 16 + c16];
+        if constexpr (PRE) {     // the last row block's tiles of (C_K C_K') o T, while Sigma's columns are on their way
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int Jc = 0; Jc < NB; ++Jc) rescale_tile(NB - 1, Jc, ckl);
+            __builtin_amdgcn_sched_barrier(0);
+        }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         PIORAN_TSTAMP(4);
         __builtin_amdgcn_s_setprio(2);     // the dependent chain of the window: ahead of the SIMD's other wavefront's matrix work (+1 .. 2 %)
@@ -420,25 +449,46 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
         }
         PIORAN_LDS_ORDER();
         double li[4], idv[4];
+        // 1 / D_n once per step, not once per use: every lane of lane column n forms it from its copy of D_n (the four DPP rows hold copies), row 0 hands it over in
+        // the padding column of scr's row n, and the four a lane needs come back with one more LDS round trip — one v_rcp_f64 (16 port cycles) and four FMAs per
+        // lane and window instead of four of each.  recip_f64 of the same value: the same bits.  The table reads of the next window's U~ and the
+        // log-determinant bookkeeping stand in front of that round trip, the upper tiles' rescaling inside it.
+        const double dj = sw.scr[c16 * 18 + c16];              // D_n sits on the diagonal; this lane follows step c16 of every window
+        double lv[4];
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) lv[ks] = sw.scr[(4 * ks + q) * 18 + c16];
+        if constexpr (PRE) {
+#pragma unroll
+            for (int I = 0; I < NB - 1; ++I)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) cku[I][g] = sw.ck[16 * I + 4 * g + q];
+        }
+        if (more) fetch_u(k + 1, 0);
+        const double rj = recip_f64(dj);
+        if (q == 0) sw.scr[c16 * 18 + 16] = rj;
+        PIORAN_LDS_ORDER();
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) idv[ks] = sw.scr[(4 * ks + q) * 18 + 16];
+        nonpd |= !(dj > 0.0);
+        Pm *= (k == 0 && c16 == 0) ? dj : fabs(dj);    // log(D[1]) :126, log(abs(D[n])) :140
+        int ex;
+        Pm = frexp(Pm, &ex);
+        Pe += ex;
+        if constexpr (PRE && NB > 1) {     // (C_K C_K') o T of the tiles above the last row block, while the reciprocals are on their way
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int Jc = 0; Jc < NB - 1; ++Jc)
+#pragma unroll
+                for (int I = Jc; I < NB - 1; ++I) rescale_tile(I, Jc, cku[I]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             const int kk = 4 * ks + q;                             // L^-1 [i = c16][k = kk]: unit lower triangular
-            const double lv = sw.scr[kk * 18 + c16];
-            idv[ks] = recip_f64(sw.scr[kk * 18 + kk]);             // D_n sits on the diagonal
-            li[ks] = kk < c16 ? lv * idv[ks] : (kk == c16 ? 1.0 : 0.0);   // the column arrives scaled by D_kk
+            li[ks] = kk < c16 ? lv[ks] * idv[ks] : (kk == c16 ? 1.0 : 0.0);   // the column arrives scaled by D_kk
         }
-        {   // log-determinant bookkeeping: this lane follows step c16 of every window
-            const double dj = sw.scr[c16 * 18 + c16];
-            nonpd |= !(dj > 0.0);
-            Pm *= (k == 0 && c16 == 0) ? dj : fabs(dj);    // log(D[1]) :126, log(abs(D[n])) :140
-            int ex;
-            Pm = frexp(Pm, &ex);
-            Pe += ex;
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         PIORAN_TSTAMP(6);
         // ---- Y^' = L^-1 X' ------------------------------------------------------------------------------------------------
-        if (more) fetch_u(k + 1, 0);
         __builtin_amdgcn_sched_barrier(0);
         d4 yt[NB];
 #pragma unroll
@@ -449,10 +499,10 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
             yt[Jc] = a;
         }
         PIORAN_TSTAMP(7);
-        // C_K of the tiles' rows and columns: up to three block columns read once, in front of the tiles (round 6: left at its uses, every tile starts with an
-        // LDS read and a wait for it; SHO-20 10.18 -> 9.97 ms per 4096 draws).  With four block columns the 20 values cost spilled registers (DRWCelerite-20
-        // 15.99 -> 16.33 ms): read per tile there, as before.
-        constexpr bool CKP = NB <= 3 || NB >= 5;
+        // C_K of the tiles' rows and columns where the rescaling is still part of the update (four block columns and more): five and six block columns read them once, in
+        // front of the tiles (round 6: left at its uses, every tile starts with an LDS read and a wait for it).  With four block columns the 20 values cost spilled
+        // registers (DRWCelerite-20 15.99 -> 16.33 ms): read per tile there.
+        constexpr bool CKP = NB >= 5;
         [[maybe_unused]] double ckrow[CKP ? NB : 1][4], ckcol[CKP ? NB : 1];
         if constexpr (CKP) {
 #pragma unroll
@@ -462,7 +512,7 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
                 ckcol[I] = sw.ck[16 * I + c16];
             }
         }
-        auto ck_row = [&](int I, int g) __attribute__((always_inline)) -> double { if constexpr (CKP) return ckrow[I][g]; else return sw.ck[16 * I + 4 * g + q]; };
+        [[maybe_unused]] auto ck_row = [&](int I, int g) __attribute__((always_inline)) -> double { if constexpr (CKP) return ckrow[I][g]; else return sw.ck[16 * I + 4 * g + q]; };
         // ---- T <- (C_K C_K') o T + Y^ D^-1 Y^', lower tiles, one block column at a time; the off-diagonal ones are copied to LDS for the
         //      next window's M'; U~ of the next window is formed on the way ------------------------------------------------------
 #pragma unroll
@@ -472,8 +522,8 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
                 if (Jc + 1 < NB) fetch_u(k + 1, Jc + 1);
             }
             double ysc[4];
-            double ckc;
-            if constexpr (CKP) ckc = ckcol[Jc]; else ckc = sw.ck[16 * Jc + c16];
+            [[maybe_unused]] double ckc = 0.0;
+            if constexpr (CKP) ckc = ckcol[Jc]; else if constexpr (!PRE) ckc = sw.ck[16 * Jc + c16];
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 ysc[g] = yt[Jc][g] * idv[g];
@@ -481,8 +531,10 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
             }
 #pragma unroll
             for (int I = Jc; I < NB; ++I) {
+                if constexpr (!PRE) {
 #pragma unroll
-                for (int g = 0; g < 4; ++g) T[tix(I, Jc)][g] *= ck_row(I, g) * ckc;
+                    for (int g = 0; g < 4; ++g) T[tix(I, Jc)][g] *= ck_row(I, g) * ckc;
+                }
 #pragma unroll
                 for (int ks = 0; ks < 4; ++ks) T[tix(I, Jc)] = __builtin_amdgcn_mfma_f64_16x16x4f64(yt[I][ks], ysc[ks], T[tix(I, Jc)], 0, 0, 0);
                 if (Jc < I) {
