@@ -288,6 +288,39 @@ int pioran_celerite_logl_grad_shift(pioran_ds* ds, int64_t B, int64_t J, const d
 int pioran_celerite_simulate(pioran_ctx* ctx, int64_t N, int64_t B, int64_t J, const double* A, const double* Bc,
                              const double* C, const double* Dd, int cd_shared, const double* t, const double* sigma2,
                              const double* q, double* y_out);
+/* ---- batched Lomb-Scargle periodogram (the per-draw loop of plot_lsp_ppc, src/plots_diagnostics.jl:514-571) --------------------------
+ * The generalised Lomb-Scargle periodogram (Zechmeister & Kuerster 2009, time-shift-free form) of B series on one sampling, at F frequencies —
+ * what LombScargle.jl evaluates with its defaults fit_mean = true, center_data = true, normalization = :standard:
+ *     w_n = yerr_n^-2 / sum yerr^-2  (1/N when yerr is NULL),   omega = 2 pi freq,
+ *     C = sum w cos(omega t), S = sum w sin, C^ = sum w cos^2, CS^ = sum w cos sin,   CC = C^ - C^2, SS = (1 - C^) - S^2, CS = CS^ - C S, D = CC SS - CS^2,
+ *     y~_b = y_b - sum w y_b when center_data (else y_b),   Y = sum w y~, YY = sum w y~^2 - Y^2,   YC = sum w y~ cos - Y C, YS = sum w y~ sin - Y S,
+ *     power[b][f] = (SS YC^2 + CC YS^2 - 2 CS YC YS) / (YY D)   in [0, 1].
+ * fit_mean == 0: C, S and Y are taken as zero in CC, SS, CS, YC, YS, YY (the classical periodogram).
+ * With fit_mean != 0 the power does not depend on a constant added to a series, and the weighted mean is subtracted before projecting whatever
+ * center_data says (the result is the same function of the inputs, evaluated without the cancellation an offset causes).
+ * The weights and the cos/sin factors are shared by the draws: a table of w cos, w sin is built once per chunk of frequencies (phase formed in cycles and
+ * reduced exactly, so its error does not grow with |omega t|) and the projections are one [B x N].[N x 2F] fp64 matrix product on the matrix cores, the
+ * weighted mean subtracted as the series is loaded (centre before projecting); only the powers go to memory.  Results do not depend on how the call is
+ * chunked.  t need not be sorted.
+ *   t [N], Y [B][N], yerr [N] or NULL, freq [F] in cycles per unit time, power [B][F], status [B] or NULL.
+ * PIORAN_ERR_ARG, before any GPU call: NULL ctx / t / Y / freq / power; N < 3, B < 1, F < 1; and in the host form a non-finite t, a freq or yerr
+ * that is non-finite or not positive (the device form cannot look at its arrays: such values give NaN there).
+ * status[b]: 2, with NaN in the draw's row, for a non-finite value in the series or a series that is constant (YY <= 0; to rounding: YY <= 1e-28 sum w y^2);
+ * 0 otherwise.  The other draws of the call are not affected.
+ * Degenerate frequencies: a frequency whose D is not positive or not finite gives NaN in its column.  Sampling on a regular grid makes sin(omega t)
+ * vanish at multiples of the grid's Nyquist frequency — which is why the reference drops the last point of its frequency grid (:545).
+ * Memory: the table of a frequency chunk (2 N doubles per frequency, N and F rounded up to 64: 165 MB at N = 1e4, F = 1000) and, in the host form, the staged series
+ * and powers of a draw chunk each take at most half of what the context may newly take ("workspace_limit_mb", the free memory); pioran_ctx_trim
+ * releases them.  Context option "ls_tile" (64 / 128) pins the output tile of the product per workgroup (default 64; same results).  "ls_only" is for timing tools ONLY: it
+ * runs single phases on the workspace the previous call left, and the powers of a call made while it is set are NOT a result.
+ * The host form uploads, runs and downloads chunk by chunk and blocks; the device form takes device pointers and is asynchronous on the context's
+ * stream.  pioran_celerite_config_name(-1) afterwards: "periodogram (fp64 matrix product)". */
+int pioran_lombscargle_batch(pioran_ctx* ctx, int64_t N, int64_t B, int64_t F, const double* t, const double* Y,
+                             const double* yerr, const double* freq, int fit_mean, int center_data, double* power,
+                             int32_t* status);
+int pioran_lombscargle_batch_dev(pioran_ctx* ctx, int64_t N, int64_t B, int64_t F, const double* dt, const double* dY,
+                                 const double* dyerr, const double* dfreq, int fit_mean, int center_data, double* dpower,
+                                 int32_t* dstatus);
 /* Name of the kernel configuration a large batch with R active rows (all terms with both rows when R is even) runs on;
  * R == 0: the configuration the calling thread's last throughput-layout launch actually ran on; R < 0: the kernel FAMILY of the
  * calling thread's last launch — "tile" (windowed form, one draw per wavefront: large batches from 49 rows on and batch sizes between the

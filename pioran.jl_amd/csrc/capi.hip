@@ -54,6 +54,7 @@ struct pioran_ctx {
         size_t cap = 0;
     };
     Buf bA, bB, bC, bD, bmu, bnu, bY, bS2, bout, bst, bscratch, bK, bwork, bshift, bgtab, bq, bpair, btp, btprow;
+    Buf blstab, blsaux;   // periodogram: the cos/sin table of a frequency chunk | weights and per-draw scalars
     // scalar entry point: the last series' time stamps stay resident (samplers call logl with the same t)
     pioran_ds* scalar_ds = nullptr;
     std::vector<double> scalar_t;
@@ -958,6 +959,8 @@ int pioran_ctx_set_option(pioran_ctx* ctx, const char* key, const char* value)
     else if (!std::strcmp(key, "dense_streams")) o.dense_streams = (value && value[0]) ? std::atoi(value) : 0;
     else if (!std::strcmp(key, "gsum")) o.gsum = (value && value[0]) ? std::atoi(value) : -1;
     else if (!std::strcmp(key, "exp")) o.exp = (value && value[0]) ? std::atoi(value) : 0;
+    else if (!std::strcmp(key, "ls_tile")) o.ls_tile = (value && value[0]) ? std::atoi(value) : 0;
+    else if (!std::strcmp(key, "ls_only")) o.ls_only = (value && value[0]) ? std::atoi(value) : 0;
     else if (!std::strcmp(key, "wide2")) o.wide2 = on;
     else if (!std::strcmp(key, "no_wide2")) o.no_wide2 = on;
     else return PIORAN_ERR_ARG;
@@ -1043,7 +1046,8 @@ int pioran_ctx_trim(pioran_ctx* ctx)
     HIPCHK(ctx, hipSetDevice(ctx->device));
     SYNC(ctx);
     pioran_ctx::Buf* bufs[] = {&ctx->bA, &ctx->bB, &ctx->bC, &ctx->bD, &ctx->bmu, &ctx->bnu, &ctx->bY,
-                               &ctx->bS2, &ctx->bout, &ctx->bst, &ctx->bscratch, &ctx->bK, &ctx->bwork, &ctx->bshift, &ctx->bgtab, &ctx->bq, &ctx->bpair, &ctx->btp, &ctx->btprow};
+                               &ctx->bS2, &ctx->bout, &ctx->bst, &ctx->bscratch, &ctx->bK, &ctx->bwork, &ctx->bshift, &ctx->bgtab, &ctx->bq, &ctx->bpair, &ctx->btp, &ctx->btprow,
+                               &ctx->blstab, &ctx->blsaux};
     for (auto* b : bufs) {
         if (b->p) (void)hipFree(b->p);
         b->p = nullptr;
@@ -2251,6 +2255,102 @@ int pioran_celerite_simulate(pioran_ctx* ctx, int64_t N, int64_t B, int64_t J, c
     for (int64_t b = 0; b < B; ++b) {
         const int rc = simulate_shared(ctx, N, 1, J, A + b * J, Bc + b * J, C + b * J, Dd + b * J, t, sigma2, q + b * N, y_out + b * N);
         if (rc) return rc;
+    }
+    return PIORAN_OK;
+}
+
+// ---- batched Lomb-Scargle periodogram (periodogram.hip) --------------------------------------------------------------------------
+// The staged series of a draw chunk and the table of a frequency chunk are alive together, so each may take half of what the call may newly
+// take (ws_allow): need() of both chunk sizers counts its bytes twice.
+// The frequency chunk of a call, sized ONCE per call, and its workspace in blstab.  The free memory is asked for only when the table of all
+// frequencies is not allocated already (the asynchronous entry must not block on the host).
+static int ls_size_fchunk(pioran_ctx* ctx, int64_t N, int64_t F, int64_t& fchunk)
+{
+    auto need = [&](int64_t fc) { return 2 * pioran_ls_chunk_doubles(N, fc) * sizeof(double); };
+    fchunk = std::min(F, pioran_ls_max_fchunk());
+    if (need(fchunk) / 2 <= ctx->blstab.cap) return PIORAN_OK;
+    int rc = size_chunk(ctx, fchunk, {&ctx->blstab}, need, [&](int64_t fc) { return ensure(ctx, ctx->blstab, need(fc) / 2); });
+    if (rc) return rc;
+    fchunk = std::min(F, pioran_ls_fpad(fchunk));   // the padded table of the chunk the budget admits holds this many
+    return ensure(ctx, ctx->blstab, need(fchunk) / 2);
+}
+
+// blsaux = weights [N] | per-draw scalars [3][Bmax]; the weights are computed here, once per call
+static int ls_weights(pioran_ctx* ctx, int64_t N, int64_t Bmax, const double* dyerr)
+{
+    if (int rc = ensure(ctx, ctx->blsaux, (size_t)(N + 3 * Bmax) * sizeof(double))) return rc;
+    if (ctx->opt.ls_only && !(ctx->opt.ls_only & 1)) return PIORAN_OK;
+    return pioran_launch_ls_weights(N, dyerr, (double*)ctx->blsaux.p, ctx->stream);
+}
+
+// B draws against all F frequencies in chunks of fchunk, on the weights and the workspace the two functions above left.  table_ready: blstab
+// holds the table of every frequency already — meaningful only with fchunk == F, and only the caller that built it in this call may say so.
+static int ls_run(pioran_ctx* ctx, int64_t N, int64_t B, int64_t F, int64_t fchunk, bool table_ready, const double* dt, const double* dY,
+                  const double* dfreq, int fit_mean, int center_data, double* dpower, int32_t* dstatus)
+{
+    int rc;
+    const int only = ctx->opt.ls_only ? ctx->opt.ls_only : 7;
+    double* w = (double*)ctx->blsaux.p;
+    double* dr = w + N;
+    double* work = (double*)ctx->blstab.p;
+    table_ready = table_ready && fchunk == F;
+    g_last_kernel = "periodogram (fp64 matrix product)";
+    if ((only & 2) && (rc = pioran_launch_ls_series(N, B, dY, w, fit_mean, center_data, dr, dstatus, ctx->stream))) return rc;
+    for (int64_t f0 = 0; f0 < F; f0 += fchunk) {
+        const int64_t fc = std::min(F - f0, fchunk);
+        if ((only & 1) && !table_ready && (rc = pioran_launch_ls_table(N, fc, dt, w, dfreq + f0, fit_mean, work, ctx->stream))) return rc;
+        if ((only & 4) && (rc = pioran_launch_ls_product(N, B, fc, dY, work, dr, dpower + f0, F, ctx->opt.ls_tile, ctx->stream))) return rc;
+    }
+    return PIORAN_OK;
+}
+
+int pioran_lombscargle_batch_dev(pioran_ctx* ctx, int64_t N, int64_t B, int64_t F, const double* dt, const double* dY, const double* dyerr,
+                                 const double* dfreq, int fit_mean, int center_data, double* dpower, int32_t* dstatus)
+{
+    if (!ctx || !dt || !dY || !dfreq || !dpower || N < 3 || B < 1 || F < 1) return PIORAN_ERR_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc;
+    int64_t fchunk;
+    if ((rc = ls_size_fchunk(ctx, N, F, fchunk))) return rc;
+    if ((rc = ls_weights(ctx, N, B, dyerr))) return rc;
+    return ls_run(ctx, N, B, F, fchunk, false, dt, dY, dfreq, fit_mean, center_data, dpower, dstatus);
+}
+
+int pioran_lombscargle_batch(pioran_ctx* ctx, int64_t N, int64_t B, int64_t F, const double* t, const double* Y, const double* yerr,
+                             const double* freq, int fit_mean, int center_data, double* power, int32_t* status)
+{
+    if (!ctx || !t || !Y || !freq || !power || N < 3 || B < 1 || F < 1) return PIORAN_ERR_ARG;
+    for (int64_t n = 0; n < N; ++n)
+        if (!std::isfinite(t[n]) || (yerr && !(std::isfinite(yerr[n]) && yerr[n] > 0.0))) return PIORAN_ERR_ARG;
+    for (int64_t f = 0; f < F; ++f)
+        if (!(std::isfinite(freq[f]) && freq[f] > 0.0)) return PIORAN_ERR_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    PendingGuard guard(ctx);
+    int rc;
+    if ((rc = upload(ctx, ctx->bA, t, N * sizeof(double)))) return rc;
+    if (yerr && (rc = upload(ctx, ctx->bB, yerr, N * sizeof(double)))) return rc;
+    if ((rc = upload(ctx, ctx->bC, freq, F * sizeof(double)))) return rc;
+    const double *dt = (const double*)ctx->bA.p, *dyerr = yerr ? (const double*)ctx->bB.p : nullptr, *dfreq = (const double*)ctx->bC.p;
+    int64_t chunk = B;
+    rc = size_chunk(ctx, chunk, {&ctx->bY, &ctx->bS2}, [&](int64_t nb) { return 2 * (size_t)nb * (size_t)(N + F) * sizeof(double); },
+                    [&](int64_t nb) {
+                        return ensure_each(ctx, {{&ctx->bY, (size_t)nb * (size_t)N * sizeof(double)}, {&ctx->bS2, (size_t)nb * (size_t)F * sizeof(double)},
+                                                 {&ctx->bst, (size_t)nb * sizeof(int32_t)}});
+                    });
+    if (rc) return rc;
+    // the frequency chunk, its workspace and the weights: once, in front of the draw chunks — no buffer of theirs is touched inside the loop
+    int64_t fchunk;
+    if ((rc = ls_size_fchunk(ctx, N, F, fchunk))) return rc;
+    if ((rc = ls_weights(ctx, N, chunk, dyerr))) return rc;
+    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+        const int64_t nb = std::min(B - b0, chunk);
+        if ((rc = upload(ctx, ctx->bY, Y + b0 * N, (size_t)nb * N * sizeof(double)))) return rc;
+        // with one frequency chunk the first draw chunk's table serves the others
+        rc = ls_run(ctx, N, nb, F, fchunk, b0 > 0, dt, (const double*)ctx->bY.p, dfreq, fit_mean, center_data, (double*)ctx->bS2.p, (int32_t*)ctx->bst.p);
+        if (rc) { if (rc == PIORAN_ERR_HIP && ctx->last_err.empty()) ctx->last_err = "periodogram launch failed"; return rc; }
+        if ((rc = download(ctx, power + b0 * F, ctx->bS2.p, (size_t)nb * F * sizeof(double)))) return rc;
+        if (status && (rc = download(ctx, status + b0, ctx->bst.p, nb * sizeof(int32_t)))) return rc;
+        SYNC(ctx);   // the staging buffers are reused by the next chunk
     }
     return PIORAN_OK;
 }

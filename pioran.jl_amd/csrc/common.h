@@ -52,6 +52,9 @@ struct ScanOptions {
     bool btab_reference;  // windowed kernel: build its table with the entry-per-thread kernel of round 2 (cross-check of the windowed table kernel)
     int exp;              // diagnostics: experiment selector of the kernel under study (0 in the product; tools/ only)
     bool wide2, no_wide2; // latency layout: force / forbid the lean form (celerite_wide2_kernel; default from 48 rows on)
+    int ls_tile = 0;      // periodogram.hip: output tile of the product per workgroup, 64 or 128 (0 = automatic; tools)
+    int ls_only = 0;      // periodogram.hip, timing tools ONLY: run only these phases (1 weights + table, 2 series, 4 product; 0 = all) on the workspace the previous
+                          // call left — the powers of such a call are not a result (stale or undefined)
 };
 
 struct ScanParams {
@@ -224,6 +227,17 @@ int pioran_launch_shift_transform(int64_t N, int64_t B, const double* y, const d
                                   double* Y, double* S2, hipStream_t stream);
 int pioran_launch_shift_grad(int64_t N, int64_t B, const double* y, const double* s2, const double* shift, const double* gY,
                              const double* gS, double* gshift, hipStream_t stream);
+// periodogram.hip: batched generalised Lomb-Scargle periodogram (fp64 matrix product of the series with a cos/sin table)
+int64_t pioran_ls_fpad(int64_t Fc);                       // frequencies a chunk's table is padded to (memory is the same for every Fc with the same value)
+int64_t pioran_ls_max_fchunk();                           // most frequencies of one chunk (grid limits)
+size_t pioran_ls_chunk_doubles(int64_t N, int64_t Fc);    // workspace of one frequency chunk: table | partial sums | per-frequency scalars
+int pioran_launch_ls_weights(int64_t N, const double* yerr /*nullptr: 1/N*/, double* w, hipStream_t stream);
+int pioran_launch_ls_series(int64_t N, int64_t B, const double* Y, const double* w, int fit_mean, int center, double* dr /*[3][B]*/,
+                            int32_t* status, hipStream_t stream);
+int pioran_launch_ls_table(int64_t N, int64_t Fc, const double* t, const double* w, const double* freq, int fit_mean, double* work,
+                           hipStream_t stream);
+int pioran_launch_ls_product(int64_t N, int64_t B, int64_t Fc, const double* Y, const double* work, const double* dr, double* power,
+                             int64_t ldp, int tile /*0: automatic; 64, 128*/, hipStream_t stream);
 // approx.hip
 #ifdef __cplusplus
 #include <vector>

@@ -113,6 +113,30 @@ class Context:
                                                        _ptr(sigma2), _ptr(q), _ptr(out)), self._h)
         return out
 
+    # -- batched Lomb-Scargle periodogram ------------------------------------------------------
+    def lombscargle(self, t, Y, yerr, freq, fit_mean=True, center_data=True, return_status=False):
+        """Generalised Lomb-Scargle power (standard normalisation) of the B series Y (B, N) sampled at t (N,) at the frequencies freq (F,)
+        in cycles per unit time, weights yerr^-2 (None: equal weights): pioran_lombscargle_batch.  Returns (B, F) [, status (B,)]:
+        status 2 and a NaN row for a series that is constant or holds a non-finite value."""
+        t, Y, freq = _f64(t), _f64(Y), _f64(freq)
+        yerr = None if yerr is None else _f64(yerr)
+        if t.ndim != 1 or Y.ndim != 2 or Y.shape[1] != len(t) or freq.ndim != 1 or (yerr is not None and yerr.shape != t.shape):
+            raise ValueError("t, yerr must be (N,), Y (B, N) and freq (F,)")
+        B, N = Y.shape
+        F = len(freq)
+        power = np.empty((B, F))
+        st = np.zeros(B, dtype=np.int32)
+        _lib.check(_lib.lib().pioran_lombscargle_batch(self._h, N, B, F, _ptr(t), _ptr(Y), _ptr(yerr), _ptr(freq), int(bool(fit_mean)),
+                                                       int(bool(center_data)), _ptr(power), _ptr(st)), self._h)
+        return (power, st) if return_status else power
+
+    def lombscargle_dev(self, N, B, F, dt, dY, dyerr=0, dfreq=0, fit_mean=True, center_data=True, dpower=0, dstatus=0):
+        """Device-pointer (int addresses) asynchronous variant: dt, dyerr (N,), dY (B, N), dfreq (F,), dpower (B, F), dstatus (B,) int32 in
+        HBM; enqueues on the context's stream (pioran_lombscargle_batch_dev).  dyerr, dstatus may be 0."""
+        v = ctypes.c_void_p
+        _lib.check(_lib.lib().pioran_lombscargle_batch_dev(self._h, int(N), int(B), int(F), v(dt), v(dY), v(dyerr or None), v(dfreq),
+                                                           int(bool(fit_mean)), int(bool(center_data)), v(dpower), v(dstatus or None)), self._h)
+
     def dense_nll(self, a, b, c, d, t, y, sigma2, return_info=False):
         a, b, c, d, t, y, sigma2 = map(_f64, (a, b, c, d, t, y, sigma2))
         out = ctypes.c_double()
@@ -651,3 +675,60 @@ def log_likelihood_direct(cov: SemiSeparable, t, y, sigma2, ctx: Context | None 
 def logpdf_batch(ds: Dataset, A, Bc, C, Dd, mu=None, nu=None, Y=None, S2=None, shift=None, return_status=False):
     """B independent logpdf evaluations on one data set (nested-sampling live points / MCMC walkers)."""
     return ds.logl_batch(A, Bc, C, Dd, mu=mu, nu=nu, Y=Y, S2=S2, shift=shift, return_status=return_status)
+
+
+_LS_NORMALIZATIONS = ("standard", "model", "log")
+
+
+def lombscargle(t, y, yerr=None, frequencies=None, fit_mean=True, center_data=True, normalization="standard", ctx: Context | None = None):
+    """lombscargle(t, y, yerr, frequencies = freq) of LombScargle.jl with its defaults (generalised periodogram, fit_mean, center_data,
+    :standard) as the reference's diagnostics call it (src/plots_diagnostics.jl:544,565), for one series y (N,) -> (F,) or a batch
+    (B, N) -> (B, F) in one device call.  frequencies: cycles per unit time (required).  normalization: "standard" (P in [0, 1]),
+    "model" (P / (1 - P)) or "log" (-log(1 - P)), the latter two formed on the host from the standard power."""
+    normalization = str(normalization).lstrip(":")
+    if normalization not in _LS_NORMALIZATIONS:
+        raise ValueError(f"normalization {normalization!r} not supported, use one of {list(_LS_NORMALIZATIONS)}")
+    if frequencies is None:
+        raise ValueError("frequencies is required")
+    y = _f64(y)
+    if y.ndim not in (1, 2):
+        raise ValueError("y must be (N,) or (B, N)")
+    P = (ctx or default_context()).lombscargle(t, np.atleast_2d(y), yerr, frequencies, fit_mean=fit_mean, center_data=center_data)
+    if normalization == "model":
+        P = P / (1.0 - P)
+    elif normalization == "log":
+        P = -np.log(1.0 - P)
+    return P[0] if y.ndim == 1 else P
+
+
+def lsp_ppc_frequencies(t, n_frequencies=1000, S_low=20, S_high=20):
+    """The frequency grid of plot_lsp_ppc (src/plots_diagnostics.jl:522-528): exp(range(log(f_min / S_low), log(f_max S_high), n_frequencies))
+    with f_min = 1 / (t[end] - t[1]), f_max = 1 / min(diff(t)) / 2.  All n_frequencies points (the check drops the last, :545)."""
+    t = _f64(t).reshape(-1)
+    f_min, f_max = 1.0 / (t[-1] - t[0]), 1.0 / np.min(np.diff(t)) / 2.0
+    return np.exp(np.linspace(np.log(f_min / S_low), np.log(f_max * S_high), int(n_frequencies)))
+
+
+def lsp_ppc(rng, t, yerr, A, Bc, C, Dd, mu=None, nu=None, frequencies=None, S_low=20, S_high=20, n_frequencies=1000,
+            quantiles=(0.025, 0.16, 0.5, 0.84, 0.975), ctx: Context | None = None):
+    """The loop of plot_lsp_ppc (src/plots_diagnostics.jl:530-559) for B posterior draws (A, Bc: (B, J); C, Dd: (J,) or (B, J); mu, nu: (B,)
+    or None) in two device calls: latent realisations at t from Context.simulate with zero variance, mu_b and sqrt(nu_b) yerr q noise added
+    on the host (the simulate entry's sigma2 is shared by the draws), then the periodogram of every series with weights yerr^-2 (like the
+    reference: yerr, not sqrt(nu) yerr).  rng: numpy Generator; it supplies the (B, N) latent normals first, then the (B, N) noise normals.
+    Returns (frequencies[:-1], power (B, F - 1), quantiles (len(quantiles), F - 1)); the default grid is lsp_ppc_frequencies(t, ...), and the
+    last point is dropped as in the reference (:545).
+    The series cross the bus twice (down after the simulation, up for the periodogram: 80 MB each way at B = 1000, N = 1e4);
+    Context.lombscargle_dev on series already in device memory avoids that."""
+    ctx = ctx or default_context()
+    t, yerr, A, Bc = _f64(t).reshape(-1), _f64(yerr).reshape(-1), _f64(A), _f64(Bc)
+    B, N = A.shape[0], len(t)
+    freq = lsp_ppc_frequencies(t, n_frequencies, S_low, S_high) if frequencies is None else _f64(frequencies).reshape(-1)
+    freq = freq[:-1]
+    Y = ctx.simulate(A, Bc, C, Dd, t, np.zeros(N), rng.standard_normal((B, N)))
+    q = rng.standard_normal((B, N))
+    scale = np.ones(B) if nu is None else np.sqrt(_f64(nu).reshape(-1))
+    Y = Y + scale[:, None] * yerr[None, :] * q
+    if mu is not None:
+        Y = Y + _f64(mu).reshape(-1)[:, None]
+    P = ctx.lombscargle(t, Y, yerr, freq)
+    return freq, P, np.quantile(P, np.asarray(quantiles, dtype=np.float64), axis=0)

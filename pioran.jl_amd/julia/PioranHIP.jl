@@ -387,6 +387,31 @@ function simulate_batch(A::Matrix{Float64}, B::Matrix{Float64}, c::VecOrMat{Floa
     return out
 end
 
+"""
+    lombscargle_batch(t, Y, yerr, freq; fit_mean = true, center_data = true)
+
+Generalised Lomb-Scargle power (standard normalisation) of every column of `Y` (`length(t) × nbatch`) at the frequencies `freq` (cycles per
+unit time), weights `yerr.^-2` (`yerr = nothing`: equal weights) — `freqpower(lombscargle(t, Y[:, k], yerr, frequencies = freq))[2]` of
+LombScargle.jl for all `k` in one call, the loop of `plot_lsp_ppc` (src/plots_diagnostics.jl:532-546).  Returns `(power, status)`:
+`power` is `length(freq) × nbatch`; `status[k] == 2` marks a constant or non-finite series (its column is NaN).
+"""
+function lombscargle_batch(t::Vector{Float64}, Y::Matrix{Float64}, yerr::Union{Nothing, Vector{Float64}}, freq::Vector{Float64};
+                           fit_mean::Bool = true, center_data::Bool = true, ctx = default_context())
+    N, nb = size(Y)
+    N == length(t) || error("Y must be length(t) × nbatch")
+    yerr === nothing || length(yerr) == N || error("yerr must have the length of t")
+    power = Matrix{Float64}(undef, length(freq), nb)
+    status = Vector{Int32}(undef, nb)
+    GC.@preserve t Y yerr freq power status begin
+        check(ccall((:pioran_lombscargle_batch, LIB), Cint,
+                    (Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble},
+                     Ptr{Int32}),
+                    ctx.h, N, nb, length(freq), t, Y, yerr === nothing ? Ptr{Cdouble}(C_NULL) : pointer(yerr), freq, fit_mean ? 1 : 0,
+                    center_data ? 1 : 0, power, status))
+    end
+    return power, status
+end
+
 # ---- value and gradient (reverse mode through the recurrence on the GPU) --------------------------------------------------
 """
     logpdf_grad_batch(ds, A, B, c, d; μ, ν, series = false, cd = true)
