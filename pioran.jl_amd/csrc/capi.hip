@@ -243,8 +243,19 @@ int download(pioran_ctx* ctx, void* host, const void* dev, size_t bytes)
 // doubles of one step record of the shared table (table.hip): (v, x, phi) of R + 2 rows, then (y_n, sigma2_n)
 constexpr int64_t rec_stride_of(int64_t R) { return 3 * (int64_t)(R + 2) + 2; }
 
-// Device pointers of one chunk of draws: A, Bc, C, D [nb][J]; mu, nu [nb] or nullptr; Y, S2 [nb][N] or nullptr
-struct DrawChunk { const double *A, *Bc, *C, *D, *mu, *nu, *Y, *S2; };
+// element i of an array that may be absent
+template <class T>
+T* at(T* p, int64_t i) { return p ? p + i : nullptr; }
+
+// Input arrays of some draws, a chunk's on the device or the caller's: A, Bc, C, D [.][J]; mu, nu [.] or nullptr; Y, S2 [.][N] or nullptr.
+// (The caller's C, D are [J] where the draws share them: from_draw is for arrays that hold a row per draw.)
+struct DrawChunk {
+    const double *A, *Bc, *C, *D, *mu, *nu, *Y, *S2;
+    DrawChunk from_draw(int64_t b0, int64_t J, int64_t N) const
+    {
+        return {A + b0 * J, Bc + b0 * J, at(C, b0 * J), at(D, b0 * J), at(mu, b0), at(nu, b0), at(Y, b0 * N), at(S2, b0 * N)};
+    }
+};
 
 // Launch description of the nb draws `m` on a prepared shared-(c, d) state: everything the data set, the state and the chunk decide (m.C, m.D:
 // not used).  out / status and what only one entry uses (gw, g_y, noise, npd_rows, ...) are the caller's.
@@ -275,6 +286,27 @@ ScanParams perdraw_params(const pioran_ds* ds, int32_t J, int32_t R, const int32
     p.rowmap = rowmap; p.t = ds->t; p.y = ds->y; p.s2 = ds->s2;
     p.C = m.C; p.D = m.D;
     return p;
+}
+
+// The windowed kernels' tables of a chunk of draws: the forward table, the reverse pass's (nullptr: the entry has none), and the doubles from one
+// draw's table to the next (0: one table for all draws, shared (c, d)).  Filled by build_tables (below, after ensure_btab).
+struct ChunkTables { const double *btab = nullptr, *gtab = nullptr; int64_t bstride = 0, gstride = 0; };
+
+// Launch description of the nb draws `m` of an entry that serves both forms: on the prepared state `s` (shared (c, d)), or, per_draw, with the
+// row map of `s` and the chunk's own tables
+ScanParams chunk_params(const pioran_ds* ds, const PrepState& s, bool per_draw, int64_t nb, const DrawChunk& m, const ChunkTables& tb)
+{
+    return per_draw ? perdraw_params(ds, s.J, s.R, s.rowmap, nb, m, tb.bstride, tb.gstride) : shared_params(ds, s, nb, m);
+}
+
+// Runs one(b) — draw b as a call of its own — for every draw of a batch; the first error ends it.  Where (c, d) per draw do not fit the windowed
+// kernels with per-draw tables, every draw is a one-draw batch with its own shared table.
+template <class One>
+int each_draw(int64_t B, One one)
+{
+    for (int64_t b = 0; b < B; ++b)
+        if (const int rc = one(b)) return rc;
+    return PIORAN_OK;
 }
 
 // Draws [b0, b0 + nb) of the caller's host arrays into the context's staging buffers bA .. bnu.  C / Dd, mu, nu: nullptr = not part of the
@@ -319,8 +351,7 @@ struct GradPtrs {
     double *a, *b, *c, *d, *nu, *mu, *y, *s2;
     GradPtrs from_draw(int64_t b0, int64_t J, int64_t N) const
     {
-        return {a + b0 * J, b + b0 * J, c ? c + b0 * J : nullptr, d ? d + b0 * J : nullptr, nu ? nu + b0 : nullptr, mu ? mu + b0 : nullptr,
-                y ? y + b0 * N : nullptr, s2 ? s2 + b0 * N : nullptr};
+        return {a + b0 * J, b + b0 * J, at(c, b0 * J), at(d, b0 * J), at(nu, b0), at(mu, b0), at(y, b0 * N), at(s2, b0 * N)};
     }
 };
 
@@ -391,6 +422,14 @@ int ensure_aux(pioran_ctx* ctx)
     HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->aux, hipStreamNonBlocking));
     for (auto& e : ctx->gev) HIPCHK(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     return PIORAN_OK;
+}
+
+// 1: ascending (ties allowed), 0: not — or a NaN among the times
+int is_sorted(const double* t, int64_t N)
+{
+    for (int64_t i = 1; i < N; ++i)
+        if (!(t[i] >= t[i - 1])) return 0;
+    return 1;
 }
 
 // May an entry (prediction, gradient, simulation) run on the windowed kernels (celerite_block.hip) with R rows of J terms?
@@ -507,6 +546,38 @@ int ensure_btab(pioran_ds* ds, PrepState& s)
     return PIORAN_OK;
 }
 
+// An entry whose rows fit the windowed kernels (`windowed`) can run on them with (c, d) per draw, which bring their own tables, and with a shared
+// (c, d) where the state's forward table can be had: it is built here on first use, and `windowed` cleared where it cannot
+int windowed_ready(pioran_ds* ds, PrepState& s, bool per_draw, bool& windowed)
+{
+    if (!windowed || per_draw) return PIORAN_OK;
+    const int rc = ensure_btab(ds, s);
+    if (rc == PIORAN_ERR_UNSUPPORTED) windowed = false;
+    return rc == PIORAN_ERR_UNSUPPORTED ? PIORAN_OK : rc;
+}
+
+// The tables of a windowed launch; a chunk loop calls this for shared (c, d) ONCE PER CALL — the state's forward table
+// (windowed_ready) and the reverse table, built into `gbuf` — and for (c, d) per draw ONCE PER CHUNK: one pair per draw of the nb draws `m`, into `bbuf`
+// and `gbuf`.  gbuf = nullptr: the entry has no reverse pass.  The buffers hold the tables already (the entry's chunk sizing).
+int build_tables(pioran_ds* ds, const PrepState& s, bool per_draw, int64_t nb, const DrawChunk& m, const pioran_ctx::Buf& bbuf, const pioran_ctx::Buf* gbuf,
+                 ChunkTables& tb)
+{
+    hipStream_t stream = ds->ctx->stream;
+    double* const gtab = gbuf ? (double*)gbuf->p : nullptr;
+    tb = ChunkTables{};
+    tb.gtab = gtab;
+    if (!per_draw) {
+        tb.btab = s.btab;
+        return gtab ? pioran_launch_block_gtab(ds->N, s.R, s.J, s.rowmap, ds->t, s.dc, s.dd, ds->s2, gtab, stream) : PIORAN_OK;
+    }
+    tb.btab = (const double*)bbuf.p;
+    tb.bstride = (int64_t)pioran_block_table_doubles(ds->N, s.R, s.J);
+    tb.gstride = gtab ? (int64_t)pioran_block_gtab_doubles(ds->N, s.R) : 0;
+    int rc = pioran_launch_block_table_batch(ds->N, s.R, s.J, nb, s.rowmap, ds->t, m.C, m.D, ds->y, ds->s2, (double*)bbuf.p, tb.bstride, stream);
+    if (!rc && gtab) rc = pioran_launch_block_gtab_batch(ds->N, s.R, s.J, nb, s.rowmap, ds->t, m.C, m.D, ds->s2, gtab, tb.gstride, stream);
+    return rc;
+}
+
 // Small shared-table batches without per-draw rows: the windowed kernel (celerite_block.hip), which needs its own table.
 // Returns PIORAN_ERR_UNSUPPORTED when the launch is not one of those (the caller goes on to the other kernels).
 int block_dispatch(pioran_ds* ds, const ScanParams& p)
@@ -557,6 +628,7 @@ static ScanParams slice_draws(const ScanParams& p, int64_t off, int64_t n)
     if (p.S2) q.S2 = p.S2 + off * p.N;
     q.out = p.out + off;
     if (p.status) q.status = p.status + off;
+    if (p.only_if) q.only_if = p.only_if + off;     // (per draw: celerite_block_kernel)
     return q;
 }
 
@@ -1317,6 +1389,13 @@ static int prepare_shared(pioran_ds* ds, int64_t B, int64_t J, const double* Bc,
     return prepare_state(ds, ds->host, J, C, Dd, real.data());
 }
 
+// The host state of an entry that serves both forms.  per_draw — (C, Dd) [B][J], every term's of its own in every draw: the row map with both rows of
+// every term is what the entry uses (the shared table this builds from draw 0 is not)
+static int prepare_draws(pioran_ds* ds, bool per_draw, int64_t B, int64_t J, const double* Bc, const double* C, const double* Dd)
+{
+    return per_draw ? prepare_state(ds, ds->host, J, C, Dd, nullptr) : prepare_shared(ds, B, J, Bc, C, Dd);
+}
+
 // Mixed mode (host-pointer entry, cd_shared == 0): when only a few terms really differ between draws (QPO features on
 // top of an approx continuum, src/psd.jl:254-261), the shared terms keep using the shared table and only the per-draw
 // terms get a per-draw table, built by a pre-pass kernel for chunks of draws (32-bit buffer offsets).
@@ -1695,123 +1774,87 @@ int pioran_celerite_logl(pioran_ctx* ctx, int64_t N, int64_t J, const double* a,
     return pioran_celerite_logl_batch(ctx->scalar_ds, 1, J, a, b, c, d, 1, nullptr, nullptr, y, sigma2, out, status);
 }
 
-static int is_sorted(const double* t, int64_t N);   // (below, with the dense solver)
-
 // ---- posterior mean / simulation --------------------------------------------------------------------
-// shared (c, d) only; draws are processed in chunks of at most 256 (one workgroup per draw, factor kept in HBM)
-static int predict_shared(pioran_ds* ds, int64_t B, int64_t J, const double* A, const double* Bc, const double* C,
-                          const double* Dd, const double* mu, const double* nu, int64_t M, const double* tau,
-                          double* mean_out, int32_t* status)
+// The three batched entries below (posterior mean, value and gradient, simulation) each serve both forms of (c, d) in ONE body:
+//   shared by the draws — the prepared state's tables; the windowed kernels where the rows fit them, else step by step;
+//   per_draw — (c, d) of their own in every term (posterior draws of QPO / CARMA / free Celerite models), several draws: every draw its own
+//   windowed-kernel tables, built per chunk, all draws of a chunk in one launch of every kernel.  There is no step-by-step leg: a shape the windowed
+//   kernels do not take is PIORAN_ERR_UNSUPPORTED before any upload or allocation, and the public entry goes draw by draw (each_draw).
+// The forms differ in the state they prepare (prepare_draws), in who builds the tables and when (build_tables), in the launch description
+// (chunk_params) and in what happens when memory is short: the per-draw form halves its chunk (size_chunk), the shared prediction and simulation leave
+// the windowed kernels (budget_chunk alone).  The argument checks are the public entries'.
+
+// Posterior mean of B draws at M times; chunks of at most 256 draws
+static int predict_batch(pioran_ds* ds, bool per_draw, int64_t B, int64_t J, const DrawChunk& in, int64_t M, const double* tau, double* mean_out,
+                         int32_t* status)
 {
-    if (!ds || B < 1 || J < 1 || M < 1 || !A || !Bc || !C || !Dd || !tau || !mean_out) return PIORAN_ERR_ARG;
     pioran_ctx* ctx = ds->ctx;
     PrepState& s = ds->host;
+    if (per_draw && !windowed_allowed(ctx->opt, (int32_t)(2 * J), (int32_t)J)) return PIORAN_ERR_UNSUPPORTED;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     PendingGuard pending_guard(ctx);
     int rc;
-    if ((rc = prepare_shared(ds, B, J, Bc, C, Dd))) return rc;
+    if ((rc = prepare_draws(ds, per_draw, B, J, in.Bc, in.C, in.D))) return rc;
     if (s.R > pioran_predict_supported_rows() || s.npd_terms) return PIORAN_ERR_UNSUPPORTED;   // before any upload / workspace
-    int64_t chunk = B < 256 ? B : 256;
+    const int64_t N = ds->N;
+    // buffer roles: the per-window stores (step by step: the factor) | a chunk's forward tables (per_draw only) | the reverse table(s) | -z and the Q
+    // recurrences | the tau-only factors | a chunk's means | tau
+    pioran_ctx::Buf &stores = ctx->bwork, &btabs = ctx->bscratch, &gtabs = ctx->bgtab, &qws = ctx->bq, &tauws = ctx->bK, &mean = ctx->bY, &taus = ctx->bshift;
     // Windowed path (round 3): z = K^-1 (y - mu) from the windowed factorisation and a block back-substitution (celerite_block.hip),
     // then the two Q recurrences segment-parallel (celerite_predict.hip) — no step-by-step factor, no per-step wave reduction
-    bool windowed = windowed_allowed(ctx->opt, s.R, s.J) && s.R <= 63;
+    bool windowed = per_draw || (windowed_allowed(ctx->opt, s.R, s.J) && s.R <= 63);
+    if ((rc = windowed_ready(ds, s, per_draw, windowed))) return rc;
+    int64_t chunk = B < 256 ? B : 256;
     if (windowed) {
-        rc = ensure_btab(ds, s);
-        if (rc == PIORAN_ERR_UNSUPPORTED) windowed = false;
-        else if (rc) return rc;
-    }
-    if (windowed) {
+        const size_t bt = per_draw ? pioran_block_table_doubles(N, s.R, s.J) : 0, gt = pioran_block_gtab_doubles(N, s.R);
+        auto ntab = [&](int64_t nb) { return per_draw ? nb : 1; };      // pairs of tables of nb draws
         auto need = [&](int64_t nb) {
-            return (pioran_block_store_workspace_doubles(nb, ds->N, s.R, 2) + pioran_predict_q_workspace_doubles(nb, ds->N, s.R)) * sizeof(double);
+            size_t d = pioran_block_store_workspace_doubles(nb, N, s.R, 2) + pioran_predict_q_workspace_doubles(nb, N, s.R);
+            if (per_draw) d += (size_t)nb * (bt + gt) + pioran_predict_tau_workspace_doubles(M, s.R, nb) + (size_t)nb * (size_t)M;
+            return d * sizeof(double);
         };
-        chunk = budget_chunk(ctx, chunk, {&ctx->bwork, &ctx->bscratch}, need);
-        // (no memory for the chunk the budget admits: not a smaller chunk, the step-by-step kernels)
-        rc = ensure_each(ctx, {{&ctx->bwork, pioran_block_store_workspace_doubles(chunk, ds->N, s.R, 2) * sizeof(double)},
-                               {&ctx->bscratch, pioran_predict_q_workspace_doubles(chunk, ds->N, s.R) * sizeof(double)},
-                               {&ctx->bgtab, pioran_block_gtab_doubles(ds->N, s.R) * sizeof(double)},
-                               {&ctx->bK, pioran_predict_tau_workspace_doubles(M, s.R, 1) * sizeof(double)}});
-        if (rc == PIORAN_ERR_ALLOC) { windowed = false; chunk = B < 256 ? B : 256; }
-        else if (rc) return rc;
-        if (windowed && (rc = pioran_launch_block_gtab(ds->N, s.R, s.J, s.rowmap, ds->t, s.dc, s.dd, ds->s2, (double*)ctx->bgtab.p, ctx->stream)))
-            return rc;
+        auto grow = [&](int64_t nb) {
+            return ensure_each(ctx, {{&stores, pioran_block_store_workspace_doubles(nb, N, s.R, 2) * sizeof(double)},
+                                     {&btabs, (size_t)nb * bt * sizeof(double)},
+                                     {&gtabs, (size_t)ntab(nb) * gt * sizeof(double)},
+                                     {&qws, pioran_predict_q_workspace_doubles(nb, N, s.R) * sizeof(double)},
+                                     {&tauws, pioran_predict_tau_workspace_doubles(M, s.R, ntab(nb)) * sizeof(double)},
+                                     {&mean, per_draw ? (size_t)nb * (size_t)M * sizeof(double) : 0}});
+        };
+        if (per_draw) {
+            rc = size_chunk(ctx, chunk, {&stores, &btabs, &gtabs, &tauws, &qws}, need, grow);
+        } else {   // (no memory for the chunk the budget admits: not a smaller chunk, the step-by-step kernels)
+            chunk = budget_chunk(ctx, chunk, {&stores, &qws}, need);
+            if ((rc = grow(chunk)) == PIORAN_ERR_ALLOC) { windowed = false; chunk = B < 256 ? B : 256; rc = PIORAN_OK; }
+        }
+        if (rc) return rc;
     }
-    if (!windowed && (rc = ensure(ctx, ctx->bwork, pioran_predict_workspace_doubles(chunk, ds->N, s.R) * sizeof(double)))) return rc;
-    if ((rc = upload(ctx, ctx->bshift, tau, (size_t)M * sizeof(double)))) return rc;          // tau
-    if ((rc = ensure(ctx, ctx->bY, (size_t)chunk * (size_t)M * sizeof(double)))) return rc;   // mean [chunk][M]
+    if (!windowed && (rc = ensure(ctx, stores, pioran_predict_workspace_doubles(chunk, N, s.R) * sizeof(double)))) return rc;
+    if ((rc = upload(ctx, taus, tau, (size_t)M * sizeof(double)))) return rc;
+    if ((rc = ensure(ctx, mean, (size_t)chunk * (size_t)M * sizeof(double)))) return rc;   // [chunk][M]
     if ((rc = ensure_results(ctx, chunk))) return rc;
+    const int tau_sorted = is_sorted(tau, M);
+    ChunkTables tb;
     for (int64_t b0 = 0; b0 < B; b0 += chunk) {
         const int64_t nb = std::min(B - b0, chunk);
         DrawChunk m;
-        if ((rc = upload_draws(ctx, J, b0, nb, A, Bc, nullptr, nullptr, mu, nu, m))) return rc;
-        ScanParams p = shared_params(ds, s, nb, m);
+        if ((rc = upload_draws(ctx, J, b0, nb, in.A, in.Bc, per_draw ? in.C : nullptr, in.D, in.mu, in.nu, m))) return rc;
+        if (windowed && (per_draw || b0 == 0) && (rc = build_tables(ds, s, per_draw, nb, m, btabs, &gtabs, tb))) return rc;
+        ScanParams p = chunk_params(ds, s, per_draw, nb, m, tb);
         p.out = (double*)ctx->bout.p; p.status = (int32_t*)ctx->bst.p;
         if (windowed) {
-            p.gw = (double*)ctx->bwork.p;
-            g_last_kernel = "block (windowed prediction)";
+            p.gw = (double*)stores.p;
+            g_last_kernel = per_draw ? "block (windowed prediction, per-draw tables)" : "block (windowed prediction)";
             // -z = -K^-1 (y - mu) [nb][N] into the head of the Q workspace
-            rc = pioran_launch_block_solve(p, s.btab, (const double*)ctx->bgtab.p, (double*)ctx->bscratch.p, ctx->stream);
-            if (!rc) rc = pioran_launch_predict_from_gy(p, (double*)ctx->bscratch.p, (double*)ctx->bK.p, ds->t, M, (const double*)ctx->bshift.p, (double*)ctx->bY.p,
-                                                        ctx->stream, 0, is_sorted(tau, M));
+            rc = pioran_launch_block_solve(p, tb.btab, tb.gtab, (double*)qws.p, ctx->stream);
+            if (!rc) rc = pioran_launch_predict_from_gy(p, (double*)qws.p, (double*)tauws.p, ds->t, M, (const double*)taus.p, (double*)mean.p, ctx->stream,
+                                                        per_draw, tau_sorted);
         } else {
             g_last_kernel = "wide (step-by-step prediction)";
-            rc = pioran_launch_predict(p, (double*)ctx->bwork.p, ds->t, M, (const double*)ctx->bshift.p, (double*)ctx->bY.p,
-                                       ctx->stream);
+            rc = pioran_launch_predict(p, (double*)stores.p, ds->t, M, (const double*)taus.p, (double*)mean.p, ctx->stream);
         }
         if (rc) { ctx->last_err = "prediction launch failed"; return rc; }
-        if ((rc = download(ctx, mean_out + b0 * M, ctx->bY.p, (size_t)nb * M * sizeof(double)))) return rc;
-        if ((rc = download_results(ctx, nullptr, status, b0, nb))) return rc;
-        SYNC(ctx);
-    }
-    return PIORAN_OK;
-}
-
-// Per-draw (c, d) in every term (posterior draws of QPO / CARMA / free Celerite models), several draws: every draw its own windowed-kernel
-// tables, all draws of a chunk in one launch of every kernel (as logl_grad_perdraw_windowed below).  PIORAN_ERR_UNSUPPORTED when the
-// shape does not fit the windowed kernel (the caller then goes draw by draw).
-static int predict_perdraw_windowed(pioran_ds* ds, int64_t B, int64_t J, const double* A, const double* Bc, const double* C, const double* Dd,
-                                    const double* mu, const double* nu, int64_t M, const double* tau, double* mean_out, int32_t* status)
-{
-    pioran_ctx* ctx = ds->ctx;
-    PrepState& s = ds->host;
-    if (!windowed_allowed(ctx->opt, (int32_t)(2 * J), (int32_t)J)) return PIORAN_ERR_UNSUPPORTED;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    PendingGuard pending_guard(ctx);
-    int rc;
-    if ((rc = prepare_state(ds, s, J, C, Dd, nullptr))) return rc;    // row map with both rows of every term
-    const int64_t N = ds->N;
-    const int64_t bt = (int64_t)pioran_block_table_doubles(N, s.R, s.J), gt = (int64_t)pioran_block_gtab_doubles(N, s.R);
-    auto per_chunk = [&](int64_t nb) {
-        return ((size_t)nb * ((size_t)bt + (size_t)gt) + pioran_block_store_workspace_doubles(nb, N, s.R, 2) + pioran_predict_q_workspace_doubles(nb, N, s.R) +
-                pioran_predict_tau_workspace_doubles(M, s.R, nb) + (size_t)nb * (size_t)M) * sizeof(double);
-    };
-    int64_t chunk = B < 256 ? B : 256;
-    rc = size_chunk(ctx, chunk, {&ctx->bwork, &ctx->bscratch, &ctx->bgtab, &ctx->bK, &ctx->bq}, per_chunk, [&](int64_t nb) {
-        return ensure_each(ctx, {{&ctx->bwork, pioran_block_store_workspace_doubles(nb, N, s.R, 2) * sizeof(double)},
-                                 {&ctx->bscratch, (size_t)nb * (size_t)bt * sizeof(double)},
-                                 {&ctx->bgtab, (size_t)nb * (size_t)gt * sizeof(double)},
-                                 {&ctx->bq, pioran_predict_q_workspace_doubles(nb, N, s.R) * sizeof(double)},
-                                 {&ctx->bK, pioran_predict_tau_workspace_doubles(M, s.R, nb) * sizeof(double)},
-                                 {&ctx->bY, (size_t)nb * (size_t)M * sizeof(double)}});
-    });
-    if (rc) return rc;
-    if ((rc = upload(ctx, ctx->bshift, tau, (size_t)M * sizeof(double)))) return rc;
-    if ((rc = ensure_results(ctx, chunk))) return rc;
-    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-        const int64_t nb = std::min(B - b0, chunk);
-        DrawChunk m;
-        if ((rc = upload_draws(ctx, J, b0, nb, A, Bc, C, Dd, mu, nu, m))) return rc;
-        double* btab = (double*)ctx->bscratch.p; double* gtab = (double*)ctx->bgtab.p;
-        if ((rc = pioran_launch_block_table_batch(N, s.R, s.J, nb, s.rowmap, ds->t, m.C, m.D, ds->y, ds->s2, btab, bt, ctx->stream))) return rc;
-        if ((rc = pioran_launch_block_gtab_batch(N, s.R, s.J, nb, s.rowmap, ds->t, m.C, m.D, ds->s2, gtab, gt, ctx->stream))) return rc;
-        ScanParams p = perdraw_params(ds, s.J, s.R, s.rowmap, nb, m, bt, gt);
-        p.out = (double*)ctx->bout.p; p.status = (int32_t*)ctx->bst.p;
-        p.gw = (double*)ctx->bwork.p;
-        g_last_kernel = "block (windowed prediction, per-draw tables)";
-        rc = pioran_launch_block_solve(p, btab, gtab, (double*)ctx->bq.p, ctx->stream);
-        if (!rc) rc = pioran_launch_predict_from_gy(p, (double*)ctx->bq.p, (double*)ctx->bK.p, ds->t, M, (const double*)ctx->bshift.p,
-                                                    (double*)ctx->bY.p, ctx->stream, 1, is_sorted(tau, M));
-        if (rc) { ctx->last_err = "windowed prediction launch failed"; return rc; }
-        if ((rc = download(ctx, mean_out + b0 * M, ctx->bY.p, (size_t)nb * M * sizeof(double)))) return rc;
+        if ((rc = download(ctx, mean_out + b0 * M, mean.p, (size_t)nb * M * sizeof(double)))) return rc;
         if ((rc = download_results(ctx, nullptr, status, b0, nb))) return rc;
         SYNC(ctx);
     }
@@ -1823,30 +1866,23 @@ int pioran_celerite_predict(pioran_ds* ds, int64_t B, int64_t J, const double* A
                             double* mean_out, int32_t* status)
 {
     if (!ds || B < 1 || J < 1 || M < 1 || !A || !Bc || !C || !Dd || !tau || !mean_out) return PIORAN_ERR_ARG;
-    if (cd_shared || B == 1) return predict_shared(ds, B, J, A, Bc, C, Dd, mu, nu, M, tau, mean_out, status);
-    {
-        const int rc = predict_perdraw_windowed(ds, B, J, A, Bc, C, Dd, mu, nu, M, tau, mean_out, status);
-        if (rc != PIORAN_ERR_UNSUPPORTED) return rc;
-    }
-    for (int64_t b = 0; b < B; ++b) {   // per-draw (c, d): every draw is its own one-draw batch with its own table
-        const int rc = predict_shared(ds, 1, J, A + b * J, Bc + b * J, C + b * J, Dd + b * J, mu ? mu + b : nullptr, nu ? nu + b : nullptr,
-                                      M, tau, mean_out + b * M, status ? status + b : nullptr);
-        if (rc) return rc;
-    }
-    return PIORAN_OK;
+    const DrawChunk in{A, Bc, C, Dd, mu, nu, nullptr, nullptr};
+    if (cd_shared || B == 1) return predict_batch(ds, false, B, J, in, M, tau, mean_out, status);
+    const int rc = predict_batch(ds, true, B, J, in, M, tau, mean_out, status);
+    if (rc != PIORAN_ERR_UNSUPPORTED) return rc;
+    return each_draw(B, [&](int64_t b) { return predict_batch(ds, false, 1, J, in.from_draw(b, J, 0), M, tau, mean_out + b * M, at(status, b)); });
 }
 
 // ---- posterior variance at new times through the factorisation (celerite_predict.hip) ------------------------------------------------
 // shared (c, d), tau ASCENDING (the caller below sorts); draws in chunks of at most 256 sized to the free memory
-static int predict_var_shared(pioran_ds* ds, int64_t B, int64_t J, const double* A, const double* Bc, const double* C, const double* Dd,
-                              const double* nu, int64_t M, const double* tau, double* var_out, int32_t* status)
+static int predict_var_shared(pioran_ds* ds, int64_t B, int64_t J, const DrawChunk& in, int64_t M, const double* tau, double* var_out, int32_t* status)
 {
     pioran_ctx* ctx = ds->ctx;
     PrepState& s = ds->host;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     PendingGuard pending_guard(ctx);
     int rc;
-    if ((rc = prepare_shared(ds, B, J, Bc, C, Dd))) return rc;
+    if ((rc = prepare_shared(ds, B, J, in.Bc, in.C, in.D))) return rc;
     if (s.R > 64 || s.npd_terms) return PIORAN_ERR_UNSUPPORTED;   // before any upload / workspace
     if (M == 0) {
         if (status) for (int64_t b = 0; b < B; ++b) status[b] = 0;
@@ -1864,7 +1900,7 @@ static int predict_var_shared(pioran_ds* ds, int64_t B, int64_t J, const double*
     for (int64_t b0 = 0; b0 < B; b0 += chunk) {
         const int64_t nb = std::min(B - b0, chunk);
         DrawChunk m;
-        if ((rc = upload_draws(ctx, J, b0, nb, A, Bc, nullptr, nullptr, nullptr, nu, m))) return rc;
+        if ((rc = upload_draws(ctx, J, b0, nb, in.A, in.Bc, nullptr, nullptr, nullptr, in.nu, m))) return rc;
         ScanParams p = shared_params(ds, s, nb, m);
         p.out = (double*)ctx->bout.p;     // (the status comes from the variance kernel itself: bst below)
         g_last_kernel = "wide (step-by-step variance)";
@@ -1898,14 +1934,11 @@ int pioran_celerite_predict_var(pioran_ds* ds, int64_t B, int64_t J, const doubl
     }
     const double* tq = sorted ? tau : ts.data();
     double* vq = sorted ? var_out : vs.data();
-    int rc = PIORAN_OK;
-    if (cd_shared || B == 1) {
-        rc = predict_var_shared(ds, B, J, A, Bc, C, Dd, nu, M, tq, vq, status);
-    } else {
-        for (int64_t b = 0; b < B && !rc; ++b)   // per-draw (c, d): every draw is its own one-draw batch with its own table
-            rc = predict_var_shared(ds, 1, J, A + b * J, Bc + b * J, C + b * J, Dd + b * J, nu ? nu + b : nullptr, M, tq, vq + b * M,
-                                    status ? status + b : nullptr);
-    }
+    const DrawChunk in{A, Bc, C, Dd, nullptr, nu, nullptr, nullptr};
+    // (c, d) per draw: there is no per-draw-table form, every draw is its own one-draw batch with its own table
+    const int rc = cd_shared || B == 1
+                       ? predict_var_shared(ds, B, J, in, M, tq, vq, status)
+                       : each_draw(B, [&](int64_t b) { return predict_var_shared(ds, 1, J, in.from_draw(b, J, 0), M, tq, vq + b * M, at(status, b)); });
     if (rc) return rc;
     if (!sorted)
         for (int64_t b = 0; b < B; ++b)
@@ -1913,178 +1946,129 @@ int pioran_celerite_predict_var(pioran_ds* ds, int64_t B, int64_t J, const doubl
     return PIORAN_OK;
 }
 
-// shift / grad_shift != nullptr: the shifted log-flux models (the data set holds raw flux and yerr^2); grad_y / grad_sigma2
-// then refer to the TRANSFORMED series of each draw.  Shared (c, d) [J] only; per-draw (c, d) are looped over by the callers below.
-static int logl_grad_shared(pioran_ds* ds, int64_t B, int64_t J, const double* A, const double* Bc, const double* C,
-                            const double* Dd, const double* mu, const double* nu, const double* shift, double* out,
-                            int32_t* status, const GradPtrs& grad, double* grad_shift)
+// ---- value and gradient ------------------------------------------------------------------------------------------------------------
+// shift / grad_shift != nullptr: the shifted log-flux models (the data set holds raw flux and yerr^2); grad_y / grad_sigma2 then refer to the
+// TRANSFORMED series of each draw.  per_draw (CARMA kernels, QPO features, free Celerite sums under NUTS): the windowed reverse mode with one pair of
+// tables per draw, all chains of a chunk in one launch — 16 chains in the time of one instead of 16 one-draw calls; it has no shifted form.
+static int logl_grad_batch(pioran_ds* ds, bool per_draw, int64_t B, int64_t J, const DrawChunk& in, const double* shift, double* out, int32_t* status,
+                           const GradPtrs& grad, double* grad_shift)
 {
     pioran_ctx* ctx = ds->ctx;
     PrepState& s = ds->host;
+    if (per_draw && (shift || !windowed_allowed(ctx->opt, (int32_t)(2 * J), (int32_t)J))) return PIORAN_ERR_UNSUPPORTED;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     PendingGuard pending_guard(ctx);
     int rc;
-    if ((rc = prepare_shared(ds, B, J, Bc, C, Dd))) return rc;
+    if ((rc = prepare_draws(ds, per_draw, B, J, in.Bc, in.C, in.D))) return rc;
     if (s.R > pioran_wide_supported_rows_grad() || s.npd_terms) return PIORAN_ERR_UNSUPPORTED;
+    const int64_t N = ds->N;
+    // buffer roles: the reverse mode's workspace | a chunk's forward tables (per_draw) or its transformed series Y | S2 (shift): never both | the reverse
+    // table(s) | grad_a | grad_b | grad_c | grad_d of a chunk | grad_nu | grad_mu | shift | grad_shift.  The series gradients: bY, bS2.
+    pioran_ctx::Buf &ws = ctx->bwork, &btabs = ctx->bscratch, &shifted = ctx->bscratch, &gtabs = ctx->bgtab, &terms = ctx->bK, &scalars = ctx->bq,
+                    &shifts = ctx->bshift;
     // Windowed reverse mode (celerite_block.hip, round 3) whenever the rows fit the windowed kernel, with or without d/d(c, d):
     // 6.3 ms (7.0 with d/d(c, d)) instead of 25 at N = 1e4, J = 20 (series gradients and the shifted log-flux models included).
-    bool windowed = windowed_allowed(ctx->opt, s.R, s.J);
-    if (windowed) {
-        rc = ensure_btab(ds, s);
-        if (rc == PIORAN_ERR_UNSUPPORTED) windowed = false;
-        else if (rc) return rc;
-    }
+    bool windowed = per_draw || windowed_allowed(ctx->opt, s.R, s.J);
+    if ((rc = windowed_ready(ds, s, per_draw, windowed))) return rc;
     // Many chains (round 5): the one-draw-per-wavefront reverse mode (celerite_tile.hip) — value and d/d(a, b, mu, nu), since round 6 also d/d(c, d) of the
     // SHARED (c, d) (both or neither), shared series.  Its
     // forward pass keeps the lower tiles of T per window (12 KB at three block columns) and the reverse kernel recomputes the rest, where the
     // small-batch kernels keep 41 KB per window and chain and hold one chain per CU.  scan_config = "tile" forces it for any chain count.
     // From 513 chains on (measured, SHO-20 / SHO-12 at N = 1e4: 512 chains 15.1 / 9.3 ms against the small-batch kernels' 11.0 / 9.2; 640 chains 15.2 /
     // 9.4 against 16.6 / 14.0; 2048 chains 27 / 16 against 44 / 36).
-    const bool tilegrad = windowed && (grad.c != nullptr) == (grad.d != nullptr) && !grad.y && !grad.s2 && !shift && s.R <= pioran_tile_grad_supported_rows() &&
-                          (ctx->opt.force_tile || (!ctx->opt.no_tile && B > 512 && s.R >= 17));
+    const bool tilegrad = !per_draw && windowed && (grad.c != nullptr) == (grad.d != nullptr) && !grad.y && !grad.s2 && !shift &&
+                          s.R <= pioran_tile_grad_supported_rows() && (ctx->opt.force_tile || (!ctx->opt.no_tile && B > 512 && s.R >= 17));
     // (48 .. 63 rows — DRWCelerite-20 is 60: three draws per workgroup there (two with d/d(c, d)); 4096 chains take 126 ms (163 with d/d(c, d)) against 166 (175)
     //  in 512-chain launches of the small-batch kernels: tools/ab_tile_grad_nb4.py, profiles/r06_tile_grad_four_block_columns.txt.  Until the reverse kernel
     //  stopped spilling at four block columns — T_k and the window's U operands loaded at the head of their own window instead of a window ahead — it was 177 (208).)
     auto ws_bytes = [&](int64_t nb) {
-        return (tilegrad ? pioran_tile_grad_workspace_doubles(nb, ds->N, s.R)
-                         : (windowed ? pioran_block_grad_workspace_doubles(nb, ds->N, s.R) : pioran_grad_workspace_doubles(nb, ds->N, s.R))) * sizeof(double);
+        return (tilegrad ? pioran_tile_grad_workspace_doubles(nb, N, s.R)
+                         : (windowed ? pioran_block_grad_workspace_doubles(nb, N, s.R) : pioran_grad_workspace_doubles(nb, N, s.R))) * sizeof(double);
     };
-    auto ensure_ws = [&](int64_t nb) { return ensure(ctx, ctx->bwork, ws_bytes(nb)); };
+    // doubles of a draw's own forward and reverse table (per_draw: they are part of what a chunk needs)
+    const size_t bt = per_draw ? pioran_block_table_doubles(N, s.R, s.J) : 0, gt = per_draw ? pioran_block_gtab_doubles(N, s.R) : 0;
+    auto need = [&](int64_t nb) { return ws_bytes(nb) + (size_t)nb * (bt + gt) * sizeof(double); };
+    auto grow = [&](int64_t nb) {
+        return ensure_each(ctx, {{&ws, ws_bytes(nb)}, {&btabs, (size_t)nb * bt * sizeof(double)}, {&gtabs, (size_t)nb * gt * sizeof(double)}});
+    };
     // Workspace per draw: (m, D) of every step + S at the checkpoints + two replayed segments (celerite_wide.hip): ~15 MB at
-    // N = 1e4, R = 40.  The chunk is bounded by half of the memory that is free right now (plus what this buffer already
-    // holds) and halved again if the allocation still fails.
-    int64_t chunk = B < 1024 ? B : 1024;
-    // windowed: 512 chains per launch pair (the forward pass then runs two workgroups per CU, the reverse pass two rounds of one)
-    if (windowed && chunk > 512) chunk = 512;
+    // N = 1e4, R = 40.  The chunk is bounded by half of the memory that is free right now (plus what the buffers it counts already
+    // hold) and halved again if the allocation still fails.
+    // windowed: 512 chains per launch pair (the forward pass then runs two workgroups per CU, the reverse pass two rounds of one); per-draw tables: 256
+    int64_t chunk = std::min<int64_t>(B, per_draw ? 256 : (windowed ? 512 : 1024));
     if (tilegrad) {
         // whole passes of 2048 (1024) chains: 7.7 GB of T per 1024 chains at N = 1e4, three block columns.  A sizing rule of its own: the limit holds for
         // the buffer as a whole ("limit + what it holds" let the second call grow a 16 GB buffer to 31 GB), and the chunk is cut by 1024 chains, then halved
         chunk = B < 4096 ? B : 4096;
         size_t free_b = 0;
         if (device_free_bytes(free_b)) {
-            const size_t allowed = ws_allow(ctx, free_b + ctx->bwork.cap);
+            const size_t allowed = ws_allow(ctx, free_b + ws.cap);
             while (chunk > 1 && ws_bytes(chunk) > allowed) chunk = chunk > 1024 ? chunk - 1024 : chunk / 2;
         }
-        if ((rc = ensure(ctx, ctx->bpair, pioran_tile_workspace_doubles(chunk, ds->N) * sizeof(double)))) return rc;
-        while ((rc = ensure_ws(chunk)) == PIORAN_ERR_ALLOC && chunk > 1) chunk /= 2;
+        if ((rc = ensure(ctx, ctx->bpair, pioran_tile_workspace_doubles(chunk, N) * sizeof(double)))) return rc;
+        while ((rc = grow(chunk)) == PIORAN_ERR_ALLOC && chunk > 1) chunk /= 2;
     } else {
-        rc = size_chunk(ctx, chunk, {&ctx->bwork}, ws_bytes, ensure_ws);
+        rc = per_draw ? size_chunk(ctx, chunk, {&ws, &btabs, &gtabs}, need, grow) : size_chunk(ctx, chunk, {&ws}, need, grow);
     }
     if (rc) return rc;
-    double* gtab = nullptr;
-    if (windowed) {   // the reverse pass's table (C o v, C o x in C/D order, C_K, sigma2): 13 KB per window, rebuilt per call (10 us)
-        if ((rc = ensure(ctx, ctx->bgtab, pioran_block_gtab_doubles(ds->N, s.R) * sizeof(double)))) return rc;
-        gtab = (double*)ctx->bgtab.p;
-        if ((rc = pioran_launch_block_gtab(ds->N, s.R, s.J, s.rowmap, ds->t, s.dc, s.dd, ds->s2, gtab, ctx->stream))) return rc;
-    }
-    const size_t cj = (size_t)chunk * (size_t)J * sizeof(double), cn = (size_t)chunk * (size_t)ds->N * sizeof(double);
-    if ((rc = ensure(ctx, ctx->bC, 4 * cj))) return rc;              // grad_a | grad_b | grad_c | grad_d
-    if ((rc = ensure(ctx, ctx->bD, 2 * chunk * sizeof(double)))) return rc;   // grad_nu | grad_mu
+    // shared (c, d): the reverse pass's table (C o v, C o x in C/D order, C_K, sigma2): 13 KB per window, rebuilt per call (10 us)
+    if (windowed && !per_draw && (rc = ensure(ctx, gtabs, pioran_block_gtab_doubles(N, s.R) * sizeof(double)))) return rc;
+    const size_t cj = (size_t)chunk * (size_t)J * sizeof(double), cn = (size_t)chunk * (size_t)N * sizeof(double);
+    if ((rc = ensure(ctx, terms, 4 * cj))) return rc;
+    if ((rc = ensure(ctx, scalars, 2 * chunk * sizeof(double)))) return rc;
     const bool want_series = grad.y || grad.s2 || shift;   // the shift's chain rule needs both series gradients
     if (want_series && (rc = ensure(ctx, ctx->bY, cn))) return rc;
     if (want_series && (rc = ensure(ctx, ctx->bS2, cn))) return rc;
-    if (shift && (rc = ensure(ctx, ctx->bscratch, 2 * cn))) return rc;           // transformed Y | S2 of the chunk
-    if (shift && (rc = ensure(ctx, ctx->bshift, 2 * chunk * sizeof(double)))) return rc;   // shift | grad_shift
+    if (shift && (rc = ensure(ctx, shifted, 2 * cn))) return rc;
+    if (shift && (rc = ensure(ctx, shifts, 2 * chunk * sizeof(double)))) return rc;
     if ((rc = ensure_results(ctx, chunk))) return rc;
-    if ((rc = ensure_aux(ctx))) return rc;
-    const GradPtrs dev = grad_chunk(ctx, ctx->bC, ctx->bD, chunk, J);
+    if (!per_draw && (rc = ensure_aux(ctx))) return rc;   // (the step-by-step reverse pass's; the shared form creates it whichever kernel it takes)
+    const GradPtrs dev = grad_chunk(ctx, terms, scalars, chunk, J);
+    ChunkTables tb;
     for (int64_t b0 = 0; b0 < B; b0 += chunk) {
         const int64_t nb = std::min(B - b0, chunk);
         DrawChunk m;
-        if ((rc = upload_draws(ctx, J, b0, nb, A, Bc, nullptr, nullptr, mu, nu, m))) return rc;
-        ScanParams p = shared_params(ds, s, nb, m);
+        if ((rc = upload_draws(ctx, J, b0, nb, in.A, in.Bc, per_draw ? in.C : nullptr, in.D, in.mu, in.nu, m))) return rc;
+        if (windowed && (per_draw || b0 == 0) && (rc = build_tables(ds, s, per_draw, nb, m, btabs, &gtabs, tb))) return rc;
+        ScanParams p = chunk_params(ds, s, per_draw, nb, m, tb);
         p.out = (double*)ctx->bout.p; p.status = (int32_t*)ctx->bst.p;
         p.g_y = want_series ? (double*)ctx->bY.p : nullptr;
         p.g_s2 = want_series ? (double*)ctx->bS2.p : nullptr;
-        double* dshift = (double*)ctx->bshift.p;
+        double* dshift = (double*)shifts.p;
         if (shift) {
             HIPCHK(ctx, hipMemcpyAsync(dshift, shift + b0, nb * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-            double* dYt = (double*)ctx->bscratch.p; double* dSt = dYt + (size_t)chunk * (size_t)ds->N;
-            if ((rc = pioran_launch_shift_transform(ds->N, nb, ds->y, ds->s2, dshift, dYt, dSt, ctx->stream))) return rc;
+            double* dYt = (double*)shifted.p; double* dSt = dYt + (size_t)chunk * (size_t)N;
+            if ((rc = pioran_launch_shift_transform(N, nb, ds->y, ds->s2, dshift, dYt, dSt, ctx->stream))) return rc;
             p.Y = dYt; p.S2 = dSt;
         }
         double* const dgc = grad.c ? dev.c : nullptr; double* const dgd = grad.d ? dev.d : nullptr;
         if (tilegrad) {
-            p.gw = (double*)ctx->bwork.p;
+            p.gw = (double*)ws.p;
             g_last_kernel = "tile (windowed gradient, one draw per wavefront)";
-            rc = pioran_launch_tile_grad(p, s.btab, gtab, (double*)ctx->bpair.p, dev.a, dev.b, dev.nu, dev.mu, dgc, dgd, ctx->stream);
+            rc = pioran_launch_tile_grad(p, tb.btab, tb.gtab, (double*)ctx->bpair.p, dev.a, dev.b, dev.nu, dev.mu, dgc, dgd, ctx->stream);
         } else if (windowed) {
-            p.gw = (double*)ctx->bwork.p;
-            g_last_kernel = "block (windowed gradient)";
-            rc = pioran_launch_block_grad(p, s.btab, gtab, dev.a, dev.b, dev.nu, dev.mu, dgc, dgd, ctx->stream);
+            p.gw = (double*)ws.p;
+            g_last_kernel = per_draw ? "block (windowed gradient, per-draw tables)" : "block (windowed gradient)";
+            rc = pioran_launch_block_grad(p, tb.btab, tb.gtab, dev.a, dev.b, dev.nu, dev.mu, dgc, dgd, ctx->stream);
         } else {
             g_last_kernel = "wide (step-by-step gradient)";
-            rc = pioran_launch_scan_wide_grad(p, (double*)ctx->bwork.p, dev.a, dev.b, dgc, dgd, dev.nu, dev.mu, ctx->stream, ctx->aux, ctx->gev);
+            rc = pioran_launch_scan_wide_grad(p, (double*)ws.p, dev.a, dev.b, dgc, dgd, dev.nu, dev.mu, ctx->stream, ctx->aux, ctx->gev);
         }
         if (rc) { ctx->last_err = "gradient launch failed"; return rc; }
         if (shift) {
-            rc = pioran_launch_shift_grad(ds->N, nb, ds->y, ds->s2, dshift, p.g_y, p.g_s2, dshift + chunk, ctx->stream);
+            rc = pioran_launch_shift_grad(N, nb, ds->y, ds->s2, dshift, p.g_y, p.g_s2, dshift + chunk, ctx->stream);
             if (rc) return rc;
             if ((rc = download(ctx, grad_shift + b0, dshift + chunk, nb * sizeof(double)))) return rc;
         }
         if ((rc = download_results(ctx, out, status, b0, nb))) return rc;
-        if ((rc = download_grads(ctx, grad.from_draw(b0, J, ds->N), dev, nb, J, ds->N))) return rc;
+        if ((rc = download_grads(ctx, grad.from_draw(b0, J, N), dev, nb, J, N))) return rc;
         // Chunks follow each other on the stream without a host synchronisation in between (round 4): every transfer is stream-ordered
         // and staged through pinned memory, which drains itself when it fills (pin_reserve); only the large series gradients, which go
         // straight to the caller's pageable memory, are waited for per chunk.  (No change in time: 4096 chains are 16 launches of 7.5 ms, 122 ms.)
+        // Both forms: a chunk with (c, d) per draw adds uploads of C, D (upload_draws) and two table launches, all on the same stream.
         if (want_series) SYNC(ctx);
     }
     SYNC(ctx);
-    return PIORAN_OK;
-}
-
-// Per-draw (c, d) in every term, several chains (CARMA kernels, QPO features, free Celerite sums under NUTS): the windowed reverse
-// mode with one pair of tables per draw (the forward table of pioran_launch_block_table_batch and the reverse pass's), all chains in
-// one launch — 16 chains in the time of one instead of 16 one-draw calls.  Returns PIORAN_ERR_UNSUPPORTED when the shape does not
-// fit the windowed kernel (the caller then evaluates draw by draw).
-static int logl_grad_perdraw_windowed(pioran_ds* ds, int64_t B, int64_t J, const double* A, const double* Bc, const double* C,
-                                      const double* Dd, const double* mu, const double* nu, double* out, int32_t* status,
-                                      const GradPtrs& grad)
-{
-    pioran_ctx* ctx = ds->ctx;
-    PrepState& s = ds->host;
-    if (!windowed_allowed(ctx->opt, (int32_t)(2 * J), (int32_t)J)) return PIORAN_ERR_UNSUPPORTED;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    PendingGuard pending_guard(ctx);
-    int rc;
-    if ((rc = prepare_state(ds, s, J, C, Dd, nullptr))) return rc;    // row map with both rows of every term (tables of draw 0: unused)
-    const int64_t N = ds->N;
-    const int64_t bt = (int64_t)pioran_block_table_doubles(N, s.R, s.J), gt = (int64_t)pioran_block_gtab_doubles(N, s.R);
-    const size_t per_draw = ((size_t)bt + (size_t)gt + pioran_block_grad_workspace_doubles(1, N, s.R)) * sizeof(double);
-    int64_t chunk = B < 256 ? B : 256;
-    rc = size_chunk(ctx, chunk, {&ctx->bwork, &ctx->bscratch, &ctx->bgtab}, [&](int64_t nb) { return (size_t)nb * per_draw; }, [&](int64_t nb) {
-        return ensure_each(ctx, {{&ctx->bwork, pioran_block_grad_workspace_doubles(nb, N, s.R) * sizeof(double)},
-                                 {&ctx->bscratch, (size_t)nb * (size_t)bt * sizeof(double)},
-                                 {&ctx->bgtab, (size_t)nb * (size_t)gt * sizeof(double)}});
-    });
-    if (rc) return rc;
-    const size_t cj = (size_t)chunk * (size_t)J * sizeof(double), cn = (size_t)chunk * (size_t)N * sizeof(double);
-    if ((rc = ensure(ctx, ctx->bK, 4 * cj))) return rc;                   // grad_a | grad_b | grad_c | grad_d of the chunk
-    if ((rc = ensure(ctx, ctx->bshift, 2 * chunk * sizeof(double)))) return rc;   // grad_nu | grad_mu
-    const bool want_series = grad.y || grad.s2;
-    if (want_series && (rc = ensure(ctx, ctx->bY, cn))) return rc;
-    if (want_series && (rc = ensure(ctx, ctx->bS2, cn))) return rc;
-    if ((rc = ensure_results(ctx, chunk))) return rc;
-    const GradPtrs dev = grad_chunk(ctx, ctx->bK, ctx->bshift, chunk, J);
-    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-        const int64_t nb = std::min(B - b0, chunk);
-        DrawChunk m;
-        if ((rc = upload_draws(ctx, J, b0, nb, A, Bc, C, Dd, mu, nu, m))) return rc;
-        double* btab = (double*)ctx->bscratch.p; double* gtab = (double*)ctx->bgtab.p;
-        if ((rc = pioran_launch_block_table_batch(N, s.R, s.J, nb, s.rowmap, ds->t, m.C, m.D, ds->y, ds->s2, btab, bt, ctx->stream))) return rc;
-        if ((rc = pioran_launch_block_gtab_batch(N, s.R, s.J, nb, s.rowmap, ds->t, m.C, m.D, ds->s2, gtab, gt, ctx->stream))) return rc;
-        ScanParams p = perdraw_params(ds, s.J, s.R, s.rowmap, nb, m, bt, gt);
-        p.out = (double*)ctx->bout.p; p.status = (int32_t*)ctx->bst.p;
-        p.g_y = want_series ? (double*)ctx->bY.p : nullptr;
-        p.g_s2 = want_series ? (double*)ctx->bS2.p : nullptr;
-        p.gw = (double*)ctx->bwork.p;
-        g_last_kernel = "block (windowed gradient, per-draw tables)";
-        rc = pioran_launch_block_grad(p, btab, gtab, dev.a, dev.b, dev.nu, dev.mu, grad.c ? dev.c : nullptr, grad.d ? dev.d : nullptr, ctx->stream);
-        if (rc) { ctx->last_err = "windowed gradient launch failed"; return rc; }
-        if ((rc = download_results(ctx, out, status, b0, nb))) return rc;
-        if ((rc = download_grads(ctx, grad.from_draw(b0, J, N), dev, nb, J, N))) return rc;
-        SYNC(ctx);
-    }
     return PIORAN_OK;
 }
 
@@ -2094,21 +2078,15 @@ static int logl_grad_impl(pioran_ds* ds, int64_t B, int64_t J, const double* A, 
 {
     if (!ds || B < 1 || J < 1 || !A || !Bc || !C || !Dd || !out || !grad.a || !grad.b) return PIORAN_ERR_ARG;
     if ((shift == nullptr) != (grad_shift == nullptr)) return PIORAN_ERR_ARG;
-    if (cd_shared || B == 1) return logl_grad_shared(ds, B, J, A, Bc, C, Dd, mu, nu, shift, out, status, grad, grad_shift);
+    const DrawChunk in{A, Bc, C, Dd, mu, nu, nullptr, nullptr};
+    if (cd_shared || B == 1) return logl_grad_batch(ds, false, B, J, in, shift, out, status, grad, grad_shift);
     // per-draw (c, d) — CARMA, QPO features, free Celerite sums under NUTS (a handful of chains): all chains in one launch of the
     // windowed reverse mode where the shape fits it, else every draw is its own one-draw batch with its own table
-    if (!shift) {
-        const int rc = logl_grad_perdraw_windowed(ds, B, J, A, Bc, C, Dd, mu, nu, out, status, grad);
-        if (rc != PIORAN_ERR_UNSUPPORTED) return rc;
-    }
-    const int64_t N = ds->N;
-    for (int64_t b = 0; b < B; ++b) {
-        const int rc = logl_grad_shared(ds, 1, J, A + b * J, Bc + b * J, C + b * J, Dd + b * J, mu ? mu + b : nullptr,
-                                        nu ? nu + b : nullptr, shift ? shift + b : nullptr, out + b, status ? status + b : nullptr,
-                                        grad.from_draw(b, J, N), grad_shift ? grad_shift + b : nullptr);
-        if (rc) return rc;
-    }
-    return PIORAN_OK;
+    const int rc = logl_grad_batch(ds, true, B, J, in, shift, out, status, grad, grad_shift);
+    if (rc != PIORAN_ERR_UNSUPPORTED) return rc;
+    return each_draw(B, [&](int64_t b) {
+        return logl_grad_batch(ds, false, 1, J, in.from_draw(b, J, 0), at(shift, b), out + b, at(status, b), grad.from_draw(b, J, ds->N), at(grad_shift, b));
+    });
 }
 
 int pioran_celerite_logl_grad(pioran_ds* ds, int64_t B, int64_t J, const double* A, const double* Bc, const double* C,
@@ -2130,6 +2108,7 @@ int pioran_celerite_logl_grad_shift(pioran_ds* ds, int64_t B, int64_t J, const d
                           {grad_a, grad_b, grad_c, grad_d, grad_nu, grad_mu, nullptr, nullptr}, grad_shift);
 }
 
+// ---- simulation ----------------------------------------------------------------------------------------------------------------------
 // n doubles of a chunk's realisations (bS2) straight into the caller's array, and wait for them
 static int download_realisations(pioran_ctx* ctx, double* y_out, int64_t n)
 {
@@ -2140,53 +2119,65 @@ static int download_realisations(pioran_ctx* ctx, double* y_out, int64_t n)
     return PIORAN_OK;
 }
 
-static int simulate_shared(pioran_ctx* ctx, int64_t N, int64_t B, int64_t J, const double* A, const double* Bc,
-                           const double* C, const double* Dd, const double* t, const double* sigma2, const double* q,
-                           double* y_out)
+// B realisations on the caller's time stamps from the normals q [B][N]; chunks of at most 256 draws
+static int simulate_batch(pioran_ctx* ctx, bool per_draw, int64_t N, int64_t B, int64_t J, const DrawChunk& in, const double* t, const double* sigma2,
+                          const double* q, double* y_out)
 {
-    if (!ctx || N < 1 || B < 1 || J < 1 || !A || !Bc || !C || !Dd || !t || !sigma2 || !q || !y_out) return PIORAN_ERR_ARG;
+    if (per_draw && !windowed_allowed(ctx->opt, (int32_t)(2 * J), (int32_t)J)) return PIORAN_ERR_UNSUPPORTED;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     ScopedDataset series;
     int rc = series.create_zeros(ctx, N, t, sigma2);
     if (rc) return rc;
     pioran_ds* ds = series.ds;
-    if ((rc = prepare_shared(ds, B, J, Bc, C, Dd))) return rc;
+    if ((rc = prepare_draws(ds, per_draw, B, J, in.Bc, in.C, in.D))) return rc;
     PrepState& s = ds->host;
     if (s.R > pioran_wide_supported_rows_modes() || s.npd_terms) return PIORAN_ERR_UNSUPPORTED;   // before any upload / workspace
-    int64_t chunk = B < 256 ? B : 256;
+    // buffer roles: the per-window stores | a chunk's forward tables (per_draw only) | xi | the normals | the realisations
+    pioran_ctx::Buf &stores = ctx->bwork, &btabs = ctx->bscratch, &xi = ctx->bq, &noise = ctx->bY, &ysim = ctx->bS2;
     // Windowed path (round 3; 6 .. 63 rows): the windowed factorisation with its per-window stores, then L applied window by window
-    bool windowed = windowed_allowed(ctx->opt, s.R, s.J) && s.R <= 63;
+    bool windowed = per_draw || (windowed_allowed(ctx->opt, s.R, s.J) && s.R <= 63);
+    if ((rc = windowed_ready(ds, s, per_draw, windowed))) return rc;
+    int64_t chunk = B < 256 ? B : 256;
     if (windowed) {
-        rc = ensure_btab(ds, s);
-        if (rc == PIORAN_ERR_UNSUPPORTED) windowed = false;
-        else if (rc) return rc;
-    }
-    if (windowed) {
-        auto need = [&](int64_t nb) { return pioran_block_store_workspace_doubles(nb, N, s.R, 3) * sizeof(double); };
-        chunk = budget_chunk(ctx, chunk, {&ctx->bwork}, need);
-        // (no memory for the chunk the budget admits: not a smaller chunk, the step-by-step kernel)
-        rc = ensure_each(ctx, {{&ctx->bwork, need(chunk)}, {&ctx->bscratch, (size_t)chunk * (size_t)N * sizeof(double)},   // bscratch: xi
-                               {&ctx->bst, chunk * sizeof(int32_t)}});
-        if (rc == PIORAN_ERR_ALLOC) { windowed = false; chunk = B < 256 ? B : 256; }
-        else if (rc) return rc;
+        const size_t bt = per_draw ? pioran_block_table_doubles(N, s.R, s.J) : 0;
+        auto need = [&](int64_t nb) {
+            size_t d = pioran_block_store_workspace_doubles(nb, N, s.R, 3);
+            if (per_draw) d += (size_t)nb * bt + 3 * (size_t)nb * (size_t)N;
+            return d * sizeof(double);
+        };
+        auto grow = [&](int64_t nb) {
+            return ensure_each(ctx, {{&stores, pioran_block_store_workspace_doubles(nb, N, s.R, 3) * sizeof(double)},
+                                     {&btabs, (size_t)nb * bt * sizeof(double)},
+                                     {&xi, (size_t)nb * (size_t)N * sizeof(double)},
+                                     {&ctx->bst, nb * sizeof(int32_t)}});
+        };
+        if (per_draw) {
+            rc = size_chunk(ctx, chunk, {&stores, &btabs, &xi}, need, grow);
+        } else {   // (no memory for the chunk the budget admits: not a smaller chunk, the step-by-step kernel)
+            chunk = budget_chunk(ctx, chunk, {&stores}, need);
+            if ((rc = grow(chunk)) == PIORAN_ERR_ALLOC) { windowed = false; chunk = B < 256 ? B : 256; rc = PIORAN_OK; }
+        }
+        if (rc) return rc;
     }
     const size_t cn = (size_t)chunk * (size_t)N * sizeof(double);
-    if ((rc = ensure(ctx, ctx->bY, cn))) return rc;     // noise
-    if ((rc = ensure(ctx, ctx->bS2, cn))) return rc;    // realisations
+    if ((rc = ensure(ctx, noise, cn))) return rc;
+    if ((rc = ensure(ctx, ysim, cn))) return rc;
     if ((rc = ensure(ctx, ctx->bout, chunk * sizeof(double)))) return rc;
+    ChunkTables tb;
     for (int64_t b0 = 0; b0 < B; b0 += chunk) {
         const int64_t nb = std::min(B - b0, chunk);
         DrawChunk m;
-        if ((rc = upload_draws(ctx, J, b0, nb, A, Bc, nullptr, nullptr, nullptr, nullptr, m))) return rc;
-        if ((rc = upload(ctx, ctx->bY, q + b0 * N, (size_t)nb * N * sizeof(double)))) return rc;
-        ScanParams p = shared_params(ds, s, nb, m);
+        if ((rc = upload_draws(ctx, J, b0, nb, in.A, in.Bc, per_draw ? in.C : nullptr, in.D, nullptr, nullptr, m))) return rc;
+        if ((rc = upload(ctx, noise, q + b0 * N, (size_t)nb * N * sizeof(double)))) return rc;
+        if (windowed && (per_draw || b0 == 0) && (rc = build_tables(ds, s, per_draw, nb, m, btabs, nullptr, tb))) return rc;
+        ScanParams p = chunk_params(ds, s, per_draw, nb, m, tb);
         p.out = (double*)ctx->bout.p;
-        p.noise = (const double*)ctx->bY.p; p.ysim = (double*)ctx->bS2.p;
+        p.noise = (const double*)noise.p; p.ysim = (double*)ysim.p;
         if (windowed) {
-            p.gw = (double*)ctx->bwork.p;
+            p.gw = (double*)stores.p;
             p.status = (int32_t*)ctx->bst.p;
-            g_last_kernel = "block (windowed simulation)";
-            rc = pioran_launch_block_sim(p, s.btab, (double*)ctx->bscratch.p, ctx->stream);
+            g_last_kernel = per_draw ? "block (windowed simulation, per-draw tables)" : "block (windowed simulation)";
+            rc = pioran_launch_block_sim(p, tb.btab, (double*)xi.p, ctx->stream);
         } else {
             g_last_kernel = "wide (step-by-step simulation)";
             rc = pioran_launch_scan_wide_sim(p, ctx->stream);
@@ -2197,66 +2188,16 @@ static int simulate_shared(pioran_ctx* ctx, int64_t N, int64_t B, int64_t J, con
     return PIORAN_OK;
 }
 
-// (c, d) per draw in every term, several draws: per-draw windowed tables, all draws of a chunk in one launch of every kernel
-// (PIORAN_ERR_UNSUPPORTED: the shape does not fit the windowed kernel — the caller goes draw by draw)
-static int simulate_perdraw_windowed(pioran_ctx* ctx, int64_t N, int64_t B, int64_t J, const double* A, const double* Bc, const double* C,
-                                     const double* Dd, const double* t, const double* sigma2, const double* q, double* y_out)
-{
-    if (!windowed_allowed(ctx->opt, (int32_t)(2 * J), (int32_t)J)) return PIORAN_ERR_UNSUPPORTED;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    ScopedDataset series;
-    int rc = series.create_zeros(ctx, N, t, sigma2);
-    if (rc) return rc;
-    pioran_ds* ds = series.ds;
-    PrepState& s = ds->host;
-    if ((rc = prepare_state(ds, s, J, C, Dd, nullptr))) return rc;    // row map with both rows of every term
-    const int64_t bt = (int64_t)pioran_block_table_doubles(N, s.R, s.J);
-    int64_t chunk = B < 256 ? B : 256;
-    auto need = [&](int64_t nb) { return ((size_t)nb * (size_t)bt + pioran_block_store_workspace_doubles(nb, N, s.R, 3) + 3 * (size_t)nb * (size_t)N) * sizeof(double); };
-    rc = size_chunk(ctx, chunk, {&ctx->bwork, &ctx->bscratch, &ctx->bq}, need, [&](int64_t nb) {
-        return ensure_each(ctx, {{&ctx->bwork, pioran_block_store_workspace_doubles(nb, N, s.R, 3) * sizeof(double)},
-                                 {&ctx->bscratch, (size_t)nb * (size_t)bt * sizeof(double)},
-                                 {&ctx->bq, (size_t)nb * (size_t)N * sizeof(double)}});     // bq: xi
-    });
-    if (rc) return rc;
-    const size_t cn = (size_t)chunk * (size_t)N * sizeof(double);
-    if ((rc = ensure(ctx, ctx->bY, cn))) return rc;     // noise
-    if ((rc = ensure(ctx, ctx->bS2, cn))) return rc;    // realisations
-    if ((rc = ensure_results(ctx, chunk))) return rc;
-    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-        const int64_t nb = std::min(B - b0, chunk);
-        DrawChunk m;
-        if ((rc = upload_draws(ctx, J, b0, nb, A, Bc, C, Dd, nullptr, nullptr, m))) return rc;
-        if ((rc = upload(ctx, ctx->bY, q + b0 * N, (size_t)nb * N * sizeof(double)))) return rc;
-        double* btab = (double*)ctx->bscratch.p;
-        if ((rc = pioran_launch_block_table_batch(N, s.R, s.J, nb, s.rowmap, ds->t, m.C, m.D, ds->y, ds->s2, btab, bt, ctx->stream))) return rc;
-        ScanParams p = perdraw_params(ds, s.J, s.R, s.rowmap, nb, m, bt, 0);
-        p.out = (double*)ctx->bout.p; p.status = (int32_t*)ctx->bst.p;
-        p.noise = (const double*)ctx->bY.p; p.ysim = (double*)ctx->bS2.p;
-        p.gw = (double*)ctx->bwork.p;
-        g_last_kernel = "block (windowed simulation, per-draw tables)";
-        rc = pioran_launch_block_sim(p, btab, (double*)ctx->bq.p, ctx->stream);
-        if (rc) { ctx->last_err = "windowed simulation launch failed"; return rc; }
-        if ((rc = download_realisations(ctx, y_out + b0 * N, nb * N))) return rc;
-    }
-    return PIORAN_OK;
-}
-
 int pioran_celerite_simulate(pioran_ctx* ctx, int64_t N, int64_t B, int64_t J, const double* A, const double* Bc,
                              const double* C, const double* Dd, int cd_shared, const double* t, const double* sigma2,
                              const double* q, double* y_out)
 {
     if (!ctx || N < 1 || B < 1 || J < 1 || !A || !Bc || !C || !Dd || !t || !sigma2 || !q || !y_out) return PIORAN_ERR_ARG;
-    if (cd_shared || B == 1) return simulate_shared(ctx, N, B, J, A, Bc, C, Dd, t, sigma2, q, y_out);
-    {
-        const int rc = simulate_perdraw_windowed(ctx, N, B, J, A, Bc, C, Dd, t, sigma2, q, y_out);
-        if (rc != PIORAN_ERR_UNSUPPORTED) return rc;
-    }
-    for (int64_t b = 0; b < B; ++b) {
-        const int rc = simulate_shared(ctx, N, 1, J, A + b * J, Bc + b * J, C + b * J, Dd + b * J, t, sigma2, q + b * N, y_out + b * N);
-        if (rc) return rc;
-    }
-    return PIORAN_OK;
+    const DrawChunk in{A, Bc, C, Dd, nullptr, nullptr, nullptr, nullptr};
+    if (cd_shared || B == 1) return simulate_batch(ctx, false, N, B, J, in, t, sigma2, q, y_out);
+    const int rc = simulate_batch(ctx, true, N, B, J, in, t, sigma2, q, y_out);
+    if (rc != PIORAN_ERR_UNSUPPORTED) return rc;
+    return each_draw(B, [&](int64_t b) { return simulate_batch(ctx, false, N, 1, J, in.from_draw(b, J, 0), t, sigma2, q + b * N, y_out + b * N); });
 }
 
 // ---- batched Lomb-Scargle periodogram (periodogram.hip) --------------------------------------------------------------------------
@@ -2452,13 +2393,7 @@ int pioran_farm_logl_batch_series(pioran_farm* f, int64_t B, int64_t J, const do
 }
 
 // ---- dense solver -------------------------------------------------------------------------------
-// ascending time stamps enable the factorised covariance build (dense.hip); anything else takes the direct one
-static int is_sorted(const double* t, int64_t N)
-{
-    for (int64_t i = 1; i < N; ++i)
-        if (!(t[i] >= t[i - 1])) return 0;
-    return 1;
-}
+// (ascending time stamps — is_sorted — enable the factorised covariance build of dense.hip; anything else takes the direct one)
 
 static int dense_stage(pioran_ctx* ctx, int64_t N, int64_t J, const double* a, const double* b, const double* c,
                        const double* d, const double* t, const double* y, const double* sigma2, double** dv)

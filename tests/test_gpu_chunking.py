@@ -10,7 +10,10 @@ test_gpu_predict_var.py.
 
 Shapes: N = 300 irregular times, J = 10 (R = 20 rows: NB = 2 block columns, 19 windows of 16 steps), B = 23 draws (23 -> 11 -> 5 -> 2 -> 1
 by halving: the last chunk is ragged whatever the entry settles on), M = 37 evaluation times, mu and nu per draw.  1 MB = 131072 doubles;
-next to each case: the doubles per draw from the pioran_*_workspace_doubles formula of its workspace, which 23 draws exceed."""
+next to each case: the doubles per draw from the pioran_*_workspace_doubles formula of its workspace, which 23 draws exceed.
+
+The last five cases cover the other way a call is cut up: (c, d) per draw on a route without per-draw-table kernels runs draw by draw, and must
+return what the same draws return as one-draw calls."""
 import numpy as np
 import pytest
 
@@ -20,7 +23,7 @@ import pioran_jl_amd as pj  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 
 N, J, B, M = 300, 10, 23, 37
-GRAD_KEYS = ("grad_a", "grad_b", "grad_c", "grad_d", "grad_mu", "grad_nu", "grad_y", "grad_sigma2")
+GRAD_KEYS = ("grad_a", "grad_b", "grad_c", "grad_d", "grad_mu", "grad_nu", "grad_y", "grad_sigma2", "grad_shift")
 
 
 @pytest.fixture(scope="module")
@@ -228,3 +231,90 @@ def test_logl_batch_per_draw_tables(ctx, data):
     assert ok.any()
     ref = O.logl_batch(A, Bc, C, Dd, t, y, s2, mu, nu)
     assert np.max(np.abs(whole[0]["logl"][ok] - ref[ok]) / np.abs(ref[ok])) < 1e-11
+
+
+# ---- (c, d) per draw where the windowed per-draw-table kernels do not take the call: draw by draw -------------------------------------------
+# The entries then run every draw as a one-draw call of their own.  One call with three draws of the per-draw set (a first, a middle and a last
+# one: a wrong offset into any of the arrays shows in at least one of them) against the same three draws as three one-draw calls, which take the
+# shared-(c, d) body directly: same kernel family, same status, same values under the rules of same_values.
+FALLBACK_DRAWS = 3
+
+
+def batched_and_one_by_one(ctx, call, options=()):
+    """call(sl) -> dict of arrays with the draws on axis 0: once for all FALLBACK_DRAWS draws, and once per draw, the results joined."""
+    for k in options:
+        ctx.set_option(k, True)
+    try:
+        batched = (call(slice(0, FALLBACK_DRAWS)), name())
+        singles = [call(slice(b, b + 1)) for b in range(FALLBACK_DRAWS)]
+        joined = {k: None if singles[0][k] is None else np.concatenate([r[k] for r in singles]) for k in singles[0]}
+        one_by_one = (joined, name())
+    finally:
+        for k in options:
+            ctx.set_option(k, False)
+    assert set(batched[0]) == set(joined)
+    for k, v in batched[0].items():
+        assert v is None or v.shape == joined[k].shape, k
+    return batched, one_by_one
+
+
+def test_predict_draw_by_draw(ctx, data):
+    t, y, s2, tau = data["t"], data["y"], data["s2"], data["tau"]
+    A, Bc, C, Dd, mu, nu = data["perdraw"]
+    ds = pj.Dataset(t, y, s2, ctx)
+
+    def call(sl):
+        mean, st = ds.predict(A[sl], Bc[sl], C[sl], Dd[sl], tau, mu=mu[sl], nu=nu[sl], return_status=True)
+        return dict(mean=mean, status=st)
+    batched, single = batched_and_one_by_one(ctx, call, ("no_block",))
+    ds.close()
+    same_values("predict draw by draw", batched, single, "wide (step-by-step prediction)")
+    first_good(batched[0]["status"])
+
+
+def test_predict_var_draw_by_draw(ctx, data):
+    t, y, s2, tau = data["t"], data["y"], data["s2"], data["tau_any"]
+    A, Bc, C, Dd, mu, nu = data["perdraw"]
+    ds = pj.Dataset(t, y, s2, ctx)
+
+    def call(sl):
+        var, st = ds.predict_var(A[sl], Bc[sl], C[sl], Dd[sl], tau, nu=nu[sl], return_status=True)
+        return dict(var=var, status=st)
+    batched, single = batched_and_one_by_one(ctx, call)
+    ds.close()
+    same_values("predict_var draw by draw", batched, single, "wide (step-by-step variance)")
+    first_good(batched[0]["status"])
+
+
+def test_simulate_draw_by_draw(ctx, data):
+    t, s2, q = data["t"], data["s2"], data["q"]
+    A, Bc, C, Dd, mu, nu = data["perdraw"]
+    batched, single = batched_and_one_by_one(ctx, lambda sl: dict(y=ctx.simulate(A[sl], Bc[sl], C[sl], Dd[sl], t, s2, q[sl])), ("no_block",))
+    same_values("simulate draw by draw", batched, single, "wide (step-by-step simulation)")
+    assert np.isfinite(batched[0]["y"]).all()
+
+
+def test_logl_grad_draw_by_draw(ctx, data):
+    t, y, s2 = data["t"], data["y"], data["s2"]
+    A, Bc, C, Dd, mu, nu = data["perdraw"]
+    ds = pj.Dataset(t, y, s2, ctx)
+    batched, single = batched_and_one_by_one(ctx, lambda sl: ds.logl_grad(A[sl], Bc[sl], C[sl], Dd[sl], mu=mu[sl], nu=nu[sl], series_grad=True),
+                                             ("no_block",))
+    ds.close()
+    same_values("logl_grad draw by draw", batched, single, "wide (step-by-step gradient)")
+    first_good(batched[0]["status"])
+
+
+# the shifted log-flux form has no per-draw-table kernel: with (c, d) per draw it goes draw by draw under every option.  The data set holds a
+# positive series (raw flux), every shift lies below its minimum
+def test_logl_grad_shift_draw_by_draw(ctx, data):
+    t, s2 = data["t"], data["s2"]
+    A, Bc, C, Dd, mu, nu = data["perdraw"]
+    flux = np.exp(0.5 * data["y"])
+    shift = flux.min() * np.linspace(0.1, 0.9, B)
+    ds = pj.Dataset(t, flux, s2, ctx)
+    batched, single = batched_and_one_by_one(ctx, lambda sl: ds.logl_grad(A[sl], Bc[sl], C[sl], Dd[sl], mu=mu[sl], nu=nu[sl], shift=shift[sl]))
+    ds.close()
+    assert batched[0]["grad_shift"] is not None
+    same_values("logl_grad shift draw by draw", batched, single, "block (windowed gradient)")
+    first_good(batched[0]["status"])
