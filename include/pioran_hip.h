@@ -333,6 +333,17 @@ const char* pioran_celerite_config_name(int64_t R);
  * returns -1 where the choice depends on it), no_split != 0: option "no_split".  The thresholds come from one sweep (profiles/r05_tile_batch_sweep.txt);
  * tests/test_host.py holds this function against that file, tools/retune_thresholds.py prints both side by side. */
 int pioran_tile_choice(int32_t R, int64_t B, int64_t pass, int no_split);
+/* Diagnostics (no GPU needed): the kernel family a log-likelihood launch takes — shared (c, d) of J terms, n_one_row_terms of them with one row
+ * (R = 2 J - n_one_row_terms active rows), B draws of N time stamps, per_draw_series != 0: (y, sigma2) per draw — when every resource it asks
+ * for is granted: the table fits, the workspace is within the budget, the time-parallel family's repair pass is available.  `name` receives one of
+ * the strings pioran_celerite_config_name(-1) reports after such a launch: "tp", "tile", "block", "scan + block (remainder)", "wide", "scan",
+ * "fallback".  `pass` = draws per pass of the step-by-step layout of these rows (0 = unknown: no remainder split; the tile family only where its
+ * choice does not depend on it).  `options`: "key=value;key=value" with the keys of pioran_ctx_set_option, NULL or "" for the defaults (the
+ * environment is not read).  tp, where not NULL and the family is "tp": {1 the boundary phase as a scan / 0 the walk, padded state rows,
+ * segments, steps per segment}; zeros for the other families.  PIORAN_ERR_ARG for inconsistent counts, an unknown key or a NULL name.
+ * The rules are csrc/route.hip; tests/test_route.py holds them, tests/test_gpu_route.py holds the launches to them. */
+int pioran_value_route(int32_t R, int32_t J, int32_t n_one_row_terms, int64_t B, int64_t N, int per_draw_series, int64_t pass,
+                       const char* options, char* name, int name_len, int32_t* tp);
 /* Diagnostics: the FP64 FMA rate (TFLOP/s) the device sustains right now with `waves_per_simd` (1 .. 8) wavefronts on every SIMD — about
  * `ms` milliseconds of a pure stream of independent v_fma_f64, event-timed on the context's stream.  The measured ceiling of any FP64
  * vector kernel on this box at that occupancy (the 78.6 TFLOP/s vendor figure assumes one FMA per SIMD every 4 cycles at 2.4 GHz).

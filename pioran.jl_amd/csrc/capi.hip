@@ -2,6 +2,7 @@
 // each entry point replaces.
 #include "../../include/pioran_hip.h"
 #include "common.h"
+#include "route.h"
 
 // (celerite_predict.hip; declared here: the windowed prediction was added after the PMC profiles of common.h's kernels were taken)
 size_t pioran_predict_q_workspace_doubles(int64_t B, int64_t N, int32_t R);
@@ -432,12 +433,6 @@ int is_sorted(const double* t, int64_t N)
     return 1;
 }
 
-// May an entry (prediction, gradient, simulation) run on the windowed kernels (celerite_block.hip) with R rows of J terms?
-bool windowed_allowed(const ScanOptions& o, int32_t R, int32_t J)
-{
-    return !o.no_block && !o.force_fallback && !o.scan_config[0] && pioran_block_fits(R, J);
-}
-
 // A data set that lives for one call: the simulation's series of zeros on the caller's time stamps
 struct ScopedDataset {
     pioran_ds* ds = nullptr;
@@ -494,30 +489,37 @@ int set_rowmap(pioran_ds* ds, PrepState& s, const std::vector<int32_t>& rm)
 
 thread_local const char* g_last_kernel = "none";   // which kernel family the calling thread's last launch ran on (diagnostics)
 
-// Register-resident scan: small shared-table batches take the latency layout (celerite_wide.hip, one draw per
-// workgroup), everything else the throughput layouts (celerite_scan.hip).  PIORAN_SCAN_CONFIG=wide forces the former
-// for any batch size, any other value names a throughput configuration; PIORAN_NO_WIDE=1 disables the former.
-int scan_dispatch(const ScanParams& p, hipStream_t stream)
+// ---- the value path: which family takes a launch is route.hip's to say; here the family's table, workspace, second stream are acquired and it is launched ----
+// The prepared state whose shared table a launch reads, if it is one without per-draw terms.  What else a family needs of it is a second test at its
+// call: the windowed families (tile, block, split; the time-parallel family's repair pass) read the state's own step records (own_records); the
+// time-parallel family itself reads only the device copies of (c, d) — `s->dc && s->dd`, whatever the record stride.
+PrepState* plain_state(pioran_ds* ds, const ScanParams& p)
+{
+    PrepState* s = p.tab == ds->user.tab ? &ds->user : (p.tab == ds->host.tab ? &ds->host : nullptr);
+    return s && s->prepared && s->npd_terms == 0 ? s : nullptr;
+}
+bool own_records(const ScanParams& p, const PrepState& s) { return p.rec_stride == rec_stride_of(s.R); }
+
+// what the rules read of a launch (ds = nullptr: a launch with no prepared state to look at — mixed_core's combined table)
+RouteQuery route_query(pioran_ds* ds, const ScanParams& p)
 {
     static const ScanOptions kDefaults{};
-    const ScanOptions& o = p.opt ? *p.opt : kDefaults;
-    const char* cfg = o.scan_config[0] ? o.scan_config : nullptr;
-    const bool force_wide = cfg && !std::strcmp(cfg, "wide");
-    // (below 16 rows the per-step exchange of the latency layout costs more than the whole step of a throughput layout)
-    const bool auto_wide = !cfg && p.B <= pioran_wide_max_batch() && p.R >= 16 && !o.no_wide;
-    // 80..95 rows: the throughput layouts do not hold S in registers any more, the latency layout still does
-    // (exactly 80 rows with a shared table: the throughput layout holds them with y as a vector — large batches go there: 54 k
-    //  instead of 43 k evaluations per second at B = 1024 .. 4096, N = 1e4; at 512 draws the latency layout is still ahead,
-    //  39 k vs 27 k: tools/sweep_r80.py)
-    const bool y80 = p.R == pioran_scan_supported_rows_shared() && p.tab && p.npd_rows == 0 && !o.no_win2 && (p.B > 768 || o.no_wide);
-    const bool only_wide = p.R > pioran_scan_supported_rows() && !o.no_wide && !y80;
-    if (p.tab && p.R <= pioran_wide_supported_rows() && (force_wide || auto_wide || only_wide)) {
-        g_last_kernel = "wide";
-        return pioran_launch_scan_wide(p, stream);
+    RouteQuery q{p.R, p.J, p.B, p.N, p.tab != nullptr, p.npd_rows, p.Y != nullptr, 0, 0, false, false, p.opt ? *p.opt : kDefaults};
+    if (const PrepState* s = ds ? plain_state(ds, p) : nullptr) {
+        q.plain_state = true;
+        q.own_records = own_records(p, *s);
+        for (int j = 0; j < s->J; ++j) ++(s->real_host[j] ? q.n_one_row : q.n_two_row);
     }
-    if (p.R > pioran_scan_supported_rows() && !y80) return PIORAN_ERR_UNSUPPORTED;
-    g_last_kernel = "scan";
-    return pioran_launch_scan(p, stream);
+    return q;
+}
+
+int scan_dispatch(const ScanParams& p, hipStream_t stream)
+{
+    switch (scan_family(route_query(nullptr, p))) {
+        case ScanFamily::wide: g_last_kernel = "wide"; return pioran_launch_scan_wide(p, stream);
+        case ScanFamily::scan: g_last_kernel = "scan"; return pioran_launch_scan(p, stream);
+        default: return PIORAN_ERR_UNSUPPORTED;
+    }
 }
 
 // the windowed kernel's own table of a prepared (c, d): built on first use (PIORAN_ERR_UNSUPPORTED: too long a series / no memory)
@@ -577,46 +579,17 @@ int build_tables(pioran_ds* ds, const PrepState& s, bool per_draw, int64_t nb, c
     if (!rc && gtab) rc = pioran_launch_block_gtab_batch(ds->N, s.R, s.J, nb, s.rowmap, ds->t, m.C, m.D, ds->s2, gtab, tb.gstride, stream);
     return rc;
 }
-
-// Small shared-table batches without per-draw rows: the windowed kernel (celerite_block.hip), which needs its own table.
-// Returns PIORAN_ERR_UNSUPPORTED when the launch is not one of those (the caller goes on to the other kernels).
-int block_dispatch(pioran_ds* ds, const ScanParams& p)
+// The dispatchers of launch(): PIORAN_ERR_UNSUPPORTED when the launch is not the family's (the caller goes on to the next one).
+int block_dispatch(pioran_ds* ds, const ScanParams& p, const RouteQuery& q)
 {
-    pioran_ctx* ctx = ds->ctx;
-    const ScanOptions& o = ctx->opt;
-    const char* cfg = o.scan_config[0] ? o.scan_config : nullptr;
-    const bool force = cfg && !std::strcmp(cfg, "block");
-    // measured on N = 1e4 (tools/sweep_block.py, tools/sweep_midbatch.py, tools/sweep_block_emode.py): faster than both other kernels
-    // up to 512 draws from 6 rows on.  Late round 3: with the pair table read from global memory two workgroups share a CU at three
-    // block columns, which moves the crossover up — R = 32 .. 35: 768 draws 4.9 vs 5.4 ms; R = 36 .. 47: 1024 draws 5.3 .. 5.8 vs
-    // 5.7 .. 7.5 ms on the throughput shapes.  With four block columns (48 rows and more) the table stays in LDS and 512 draws is the
-    // limit (DRWCelerite-20 at 768 draws: 7.8 vs 7.1 ms on the throughput shape, which got faster this round).
-    // Round 4: five and six block columns (64 .. 95 rows; value only, one workgroup per CU: up to 256 draws).
-    // Late round 4 (tools/scalar_small_j.py, profiles/r04_few_rows.txt): five rows 1.84 -> 1.48 ms at N = 1e4; four and fewer rows stay on the
-    // throughput layout (1.42 against 1.47 ms) except for long series — its 20-double step records outgrow the L2 (N = 65536: 13.4 against
-    // 9.5 ms up to 256 draws, 11.2 at 512) — and for the scalar call, whose series arrive as per-draw (y, sigma2): N = 8192 1.36 -> 1.25 ms.
-    const bool few_rows = p.R < 5 && ((p.N >= 16384 && p.B <= 512) || (p.Y && p.B == 1 && p.N >= 2048));
-    const bool automatic = !cfg && !o.no_block &&
-                           (p.R < 5 ? few_rows
-                            : p.R > pioran_block_supported_rows()
-                                ? p.B <= 256
-                                : (p.B <= 512 || (p.B <= 768 && p.R >= 32 && p.R <= 47) || (p.B <= 1024 && p.R >= 36 && p.R <= 47)));
-    if (!(force || automatic) || !p.tab || p.npd_rows != 0 || !pioran_block_fits_value(p.R, p.J)) return PIORAN_ERR_UNSUPPORTED;
-    PrepState* s = p.tab == ds->user.tab ? &ds->user : (p.tab == ds->host.tab ? &ds->host : nullptr);
-    if (!s || !s->prepared || s->npd_terms != 0 || p.rec_stride != rec_stride_of(s->R)) return PIORAN_ERR_UNSUPPORTED;
+    if (!block_wanted(q)) return PIORAN_ERR_UNSUPPORTED;
+    PrepState* s = plain_state(ds, p);
     int rc = ensure_btab(ds, *s);
     if (rc) return rc;
     g_last_kernel = "block";
-    return pioran_launch_scan_block(p, s->btab, ctx->stream);
+    return pioran_launch_scan_block(p, s->btab, ds->ctx->stream);
 }
 
-// Batches that are not a whole number of passes (round 4).  A throughput launch is a sequence of PASSES — every SIMD of the chip holding as
-// many wavefronts as the kernel's registers allow (SHO-20: 2 x 1024 wavefronts x 2 draws = 4096 draws) — and a wavefront walks the whole
-// series whatever its pass carries: 4200 draws cost two passes' time less what the scheduler backfills (16.9 against 11.9 ms for 4096).
-// Small remainders are what the windowed kernel (celerite_block.hip) is fast at, and its workgroups fit BESIDE a resident scan wavefront
-// (205 + 250 registers per SIMD lane pair): so the remainder goes to that kernel on the context's second stream, launched first, while the
-// whole passes run on the main stream.  The two launches write disjoint slices of out / status; the main stream waits for the second
-// one's event, so the call is stream-ordered like any other.
 static ScanParams slice_draws(const ScanParams& p, int64_t off, int64_t n)
 {
     ScanParams q = p;
@@ -631,18 +604,15 @@ static ScanParams slice_draws(const ScanParams& p, int64_t off, int64_t n)
     if (p.only_if) q.only_if = p.only_if + off;     // (per draw: celerite_block_kernel)
     return q;
 }
-
-// A handful of draws of a long series: the time-parallel evaluation (celerite_tp.hip, round 5) — segments of the series on different CUs instead
-// of one serial chain per draw.  scan_config = "tp" forces it wherever it applies (shared (c, d), at most 64 state rows, at most 64 draws).
-int tp_dispatch(pioran_ds* ds, const ScanParams& p)
+int tp_dispatch(pioran_ds* ds, const ScanParams& p, const RouteQuery& rq)
 {
     pioran_ctx* ctx = ds->ctx;
     const ScanOptions& o = ctx->opt;
-    if (o.no_tp || (!o.force_tp && (o.scan_config[0] || o.force_tile)) || !p.tab || p.npd_rows != 0 || p.B > 64) return PIORAN_ERR_UNSUPPORTED;
-    PrepState* s = p.tab == ds->user.tab ? &ds->user : (p.tab == ds->host.tab ? &ds->host : nullptr);
-    if (!s || !s->prepared || s->npd_terms != 0 || !s->dc || !s->dd) return PIORAN_ERR_UNSUPPORTED;
-    // state rows: the two-row terms first (pairs on even / odd lanes), then the one-row terms, padded to an even count
-    const int J = s->J;
+    const TpPlan plan = tp_plan(rq);
+    PrepState* s = plan.take ? plain_state(ds, p) : nullptr;
+    if (!s || !s->dc || !s->dd) return PIORAN_ERR_UNSUPPORTED;
+    // state rows: the two-row terms first (pairs on even / odd lanes), then the one-row terms, padded to the plan's count
+    const int J = s->J, RP = plan.RP, nseg = plan.nseg;
     std::vector<int32_t> rows;
     rows.reserve(256);
     std::vector<int32_t> term, kind;
@@ -650,95 +620,7 @@ int tp_dispatch(pioran_ds* ds, const ScanParams& p)
         if (!s->real_host[j]) { term.push_back(j); kind.push_back(0); term.push_back(j); kind.push_back(1); }
     for (int j = 0; j < J; ++j)
         if (s->real_host[j]) { term.push_back(j); kind.push_back(2); }
-    if ((int)term.size() > pioran_tp_supported_rows() || p.N < 64) return PIORAN_ERR_UNSUPPORTED;
-    // The boundary phase as a scan over the segments' elements (tp_combine_kernel, round 6: ceil(log2 nseg) launches of one workgroup per (draw, target)
-    // instead of nseg - 1 dependent boundary steps) — up to two draws (nseg targets per draw and level want a CU each), 5 .. 64 state rows (padded to
-    // a multiple of 8 for it) — moves every crossover (tools/tp_scan_sweep.py, profiles/r06_time_parallel_scan.txt; one scalar call, PCIe included):
-    // 8 / 16 rows from 1024 steps on (N = 1024: 0.146 / 0.172 against 0.159 / 0.211 ms on the serial chain; N = 8192: 0.23 / 0.27 against 1.08 / 1.50),
-    // 24 rows from 1536 (0.254 against 0.306), 32 from 2048 (0.32 against 0.42), 40 / 48 from 3072 (0.50 / 0.58 against 0.60 / 0.76; N = 1e4:
-    // 0.64 / 0.76 against 1.87 / 2.40; N = 65536: 1.19 / 1.35 against 12.0 / 16.4).
-    const int nrows = (int)term.size();
-    // (three and four rows — the reference grid's j = 2 — padded to eight: N = 8192 0.19 ms against 0.28 on the one-thread boundary walk; from 2048 steps on)
-    const bool scan_rows = (nrows > 4 || (nrows > 2 && p.B <= 2 && (p.N >= 2048 || o.tp_scan > 0))) && nrows <= 64;
-    // Three to 32 draws (tools/tp_scan_batch_sweep.py, section 8 of the profile): the combinations of one level want a CU slot each — a CU holds kc = 4 / 2 / 1
-    // workgroups of tp_combine_kernel at up to 8 / up to 32 / more rows (its LDS) — so the segment count is the largest power of two with B nseg <= 256 kc
-    // (SHO-20, N = 1e4, 4 / 8 draws: 64 / 32 segments 0.76 / 1.06 ms against 1.50 / 1.53 on the walk and 1.85 on the serial chains; 128 segments 1.08 / 2.0).
-    const int RPs = (nrows + 7) & ~7, kc = RPs <= 8 ? 4 : (RPs <= 32 ? 2 : 1);
-    const bool scan_ok = o.tp_scan != 0 && scan_rows && (o.tp_scan > 0 || p.B <= 2 || (p.B <= 32 && 16 * p.B <= 256 * kc));      // the scan is possible
-    bool scan = scan_ok;                                                                                                                      // ... and chosen (below)
-    int scan_cap = 256;
-    if (scan_ok && p.B > 2) { scan_cap = 16; while (2 * scan_cap * p.B <= 256 * kc && scan_cap < 256) scan_cap *= 2; }
-    const int RPw = pioran_tp_padded_rows(nrows);        // rows as the boundary walk pads them (RPs: as the scan does)
-    // measured (tools/ab_tp.py sweep, profiles/r05_time_parallel_gpu.txt): with up to 8 draws it beats the serial-chain kernels from 1024 steps on at
-    // up to 4 state rows (N = 8192: one SHO term 0.17 against 1.16 ms, two 0.27 against 1.15; there also at 64 draws from 4096 steps on: 0.90
-    // against 1.16 ms), from 2048 steps at up to 8 rows (four terms, N = 8192: 0.47 against 1.21), from 4096 at up to 12, from 6144 at up to 16
-    // (eight terms: 0.96 against 1.47 ms); with more rows the boundary solves (R^3 each, one after the other) eat the gain (20 terms, N = 1e4:
-    // 2.6 against 1.83 ms).
-    if (!o.force_tp) {
-        const bool few = RPw <= 4 && ((p.B <= 8 && p.N >= 1024) || p.N >= 4096);
-        const bool mid = RPw > 4 && p.B <= 8 && p.N >= (RPw <= 8 ? 2048 : (RPw <= 12 ? 4096 : 6144)) && RPw <= 16;
-        // 17 .. 64 state rows: the boundary solves cost 14 .. 47 us each (four wavefronts, products and rank-4 updates on the matrix cores, four pivots per barrier), and
-        // the gain comes with the length of the series (its time grows like sqrt(N), the serial chain's like N): SHO-12 (24 rows) N = 8192 / 1e4 /
-        // 65536 0.84 / 0.93 / 2.4 against 1.45 / 1.77 / 11.6 ms; SHO-20 (40 rows) N = 8192 / 1e4 / 65536 1.39 / 1.54 / 3.9 against 1.50 / 1.83 / 11.9;
-        // SHO-24 (48 rows; three block columns on the serial chain) N = 1e4 1.80 against 2.47
-        // 49 .. 64 state rows: DRWCelerite-20 (60 rows; four block columns on the serial chain) N = 1e4 2.71 against 2.61 (not chosen), N = 16384 / 65536
-        // 3.5 / 7.0 against 4.3 / 19.1 ms; SHO-32 (64 rows; FIVE block columns on the serial chain) N = 8192 / 65536 2.45 / 7.0 against 3.7 / 34.4 ms
-        const int64_t nwide = p.R + 1 > 64 ? 6144 : 12288;
-        const int64_t nmin12 = RPw <= 24 ? 4096 : (RPw <= 32 ? 5120 : (RPw <= 40 ? 8192 : (RPw <= 48 ? 6144 : nwide)));
-        const int64_t nmin8 = RPw <= 24 ? 5120 : (RPw <= 32 ? 6144 : (RPw <= 40 ? 8192 : (RPw <= 48 ? 8192 : nwide)));
-        const bool many = RPw > 16 && ((p.B <= 2 && p.N >= nmin12) || (p.B <= 8 && p.N >= nmin8));
-        // (49 .. 64 rows, tp_combine_lean_kernel: 56 / 60 rows from 4096 steps on — 0.89 / 1.02 against 1.03 / 1.08 ms; N = 1e4: 1.10 / 1.21 against 2.46 / 2.58;
-        //  64 rows, five block columns on the serial chain, from 2048 — 0.89 against 0.98; N = 1e4: 1.21 against 4.6)
-        const bool scanned = scan_ok && p.N >= (nrows <= 4 ? 2048 : RPs <= 16 ? 1024 : (RPs <= 24 ? 1536 : (RPs <= 32 ? 2048 : (RPs <= 48 ? 3072 : (p.R + 1 > 64 ? 2048 : 4096)))));
-        // three and more draws on the scan: a model of its time (records + two phases of N / nseg steps + one combination per level and the check, in us)
-        // against the serial chain's time per step (measured at N = 1e4, resident inputs), taken when it promises 15 % off (up to 8 rows, where the model is
-        // optimistic at 32 draws: a quarter) — profiles/r06_time_parallel_scan.txt section 8 has the sweep this was held against at N = 2048 / 4096 / 1e4
-        bool scanned_b = false;
-        if (scan_ok && p.B > 2) {
-            const int RP = RPs;
-            const double tau = RP <= 16 ? 0.7 + RP / 8.0 : 1.0 + RP / 32.0, tc = 8.0 + (double)RP * RP / 50.0;
-            int lv = 0;
-            for (int c = scan_cap; c > 1; c >>= 1) ++lv;
-            // (17 .. 32 rows: two combinations and eight phase wavefronts share a CU at the cap — measured 1.5 x the steps' time there)
-            const double load = RP > 16 && RP <= 32 ? (double)p.B * scan_cap * 4.0 / 1024.0 : 1.0, rp = 1.0 + 0.5 * (load > 1.0 ? load - 1.0 : 0.0);
-            double t_scan = 35.0 + rp * tau * (double)p.N / scan_cap + (lv + 1) * tc;
-            const double s_chain = RP <= 8 ? 0.127 : (RP <= 24 ? 0.178 : (RP <= 40 ? 0.19 : (RP <= 48 ? 0.24 : (p.R + 1 > 64 ? 0.46 : 0.25))));
-            // ~2 % of the prior draws of the SHO models and ~7 % of the models with one-row terms (DRWCelerite) fail the check (profiles/r06_time_parallel_scan.txt
-            // section 11), and one failing draw sends the launch through the serial chain as well — its expected share
-            t_scan += (1.0 - std::pow(nrows != 2 * J ? 0.93 : 0.98, (double)p.B)) * s_chain * (double)p.N;
-            scanned_b = (int64_t)scan_cap * 16 <= p.N && t_scan < (RP <= 8 ? 0.75 : 0.85) * s_chain * (double)p.N;
-        }
-        // the scan where ITS rule says so (o.tp_scan > 0: wherever possible); else the boundary walk where its rules say so — a batch of 8 draws of SHO-20 that the
-        // walk's rule admits is better off there (1.53 ms) than on the scan with its expected repair (0.98 + 57 % x 1.86)
-        if (o.tp_scan < 0) scan = p.B <= 2 ? scanned : scanned_b;
-        if (!scan && !few && !mid && !many) return PIORAN_ERR_UNSUPPORTED;
-    }
-    const int RP = scan ? RPs : RPw;
     while ((int)term.size() < RP) { term.push_back(0); kind.push_back(3); }
-    // segments: phases 1 + 3 cost tau ~ 0.7 + R / 8 us per step with one wavefront per segment (up to 16 rows), ~ 1 + R / 32 with four; phase 2 t2 per
-    // boundary as below (measured at 2 .. 48 rows, tools/ab_tp.py): N / nseg tau + nseg t2 is least at sqrt(tau N / t2)
-    int nseg = o.tp_segments;
-    if (nseg <= 0 && scan) {
-        // N / nseg tau + ceil(log2 nseg) t_c, t_c = one combination (measured, tools/ab_tp.py: see profiles/r06_time_parallel_scan.txt): powers of two
-        const double tau = RP <= 16 ? 0.7 + RP / 8.0 : 1.0 + RP / 32.0, tc = 8.0 + (double)RP * RP / 50.0;
-        double best = 1e300;
-        for (int cand = 8, lv = 3; cand <= scan_cap; cand *= 2, ++lv) {
-            const double est = tau * (double)p.N / cand + lv * tc;
-            if (est < best && (int64_t)cand * 16 <= p.N) { best = est; nseg = cand; }
-        }
-        if (nseg <= 0) nseg = 1;
-    }
-    if (nseg <= 0) {
-        const double tau = RP <= 16 ? 0.7 + RP / 8.0 : 1.0 + RP / 32.0, t2 = RP == 2 ? 0.6 : (RP == 4 ? 2.0 : (RP <= 16 ? 1.3 + RP * RP / 21.0 : 5.0 + (double)RP * RP / 80.0));   // (2 / 4 rows: one thread per draw; up to 16: one wavefront, in registers;
-                                                                                 //  above: four wavefronts, products on the matrix cores, four pivots per barrier)
-        nseg = (int)std::lround(std::sqrt(tau * (double)p.N / t2));
-    }
-    if (nseg < 1) nseg = 1;
-    if (nseg > (scan ? 256 : 128)) nseg = scan ? 256 : 128;
-    if (scan && p.B > 2 && o.tp_segments <= 0) nseg = scan_cap;
-    if ((int64_t)nseg * 16 > p.N) nseg = (int)(p.N / 16);
-    const int64_t L = (p.N + nseg - 1) / nseg;
-    nseg = (int)((p.N + L - 1) / L);
     rows = term;
     rows.insert(rows.end(), kind.begin(), kind.end());
     int rc = upload(ctx, ctx->btprow, rows.data(), rows.size() * sizeof(int32_t));
@@ -752,25 +634,16 @@ int tp_dispatch(pioran_ds* ds, const ScanParams& p)
     q.C = s->dc; q.D = s->dd; q.J = J; q.opt = &ctx->opt;
     g_last_kernel = "tp";
     const int32_t* dr = (const int32_t*)ctx->btprow.p;
-    // A draw whose boundary states fail the filter's check (tp_filter_kernel: 1 .. 3 % of the prior draws of the SHO models, 6 .. 8 % of the DRWCelerite models; the scan
-    // or the walk ALONE is wrong by more than 1e-8 on a few per thousand of the latter — tools/tp_scan_accept.py, tp_walk_accuracy.py) is evaluated again by the
-    // serial-chain windowed kernel (celerite_block_kernel with ScanParams::only_if: its workgroups leave at once for every draw that passed).
-    bool repair = !o.tp_walk_repair && !o.tp_unchecked && !o.no_block && pioran_block_fits_value(p.R, p.J) &&
-                  p.rec_stride == rec_stride_of(s->R) && (p.Y == nullptr) == (p.S2 == nullptr);
+    // the repair pass (tp_repair_wanted) needs the windowed kernel's table
+    bool repair = tp_repair_wanted(rq) && (p.Y == nullptr) == (p.S2 == nullptr);
     if (repair) {
         rc = ensure_btab(ds, *s);
         if (rc == PIORAN_ERR_UNSUPPORTED) repair = false;
         else if (rc) return rc;
     }
-    // (no repair pass available — the windowed kernel's table does not fit, "no_block" — and the walk-repair mode not asked for: the boundary walk instead of the
-    //  scan; the walk-repair mode's own check, a state discrepancy relative to the state's largest entry, lets bad draws through: tools/tp_scan_metrics.py)
-    // Late round 6: the boundary WALK is checked and repaired the same way (mode 4) — a long segment's element is no better conditioned than a composite of the scan:
-    // on prior draws of DRWCelerite-10 the walk alone is off by up to 8e-7 where the serial chain holds 4e-10 (tools/tp_walk_accuracy.py).  Without a repair pass the
-    // family is not an AUTOMATIC choice any more; forced (scan_config "tp"; options tp_unchecked / tp_walk_repair: tools) it runs unchecked as in round 5.
-    if (!repair && !o.force_tp) return PIORAN_ERR_UNSUPPORTED;
-    const int mode = repair ? (scan ? 2 : 4) : (scan && o.tp_walk_repair ? 1 : 0);
-    if (scan && mode == 0 && nseg > 128) return PIORAN_ERR_UNSUPPORTED;      // (the segment count was chosen for the scan; the walk's kernels take up to 128)
-    rc = pioran_launch_tp(q, RP, nseg, L, dr, dr + RP, (double*)ctx->btp.p, ctx->stream, mode);
+    const int mode = tp_mode(plan, repair, o);
+    if (mode < 0) return PIORAN_ERR_UNSUPPORTED;
+    rc = pioran_launch_tp(q, RP, nseg, plan.L, dr, dr + RP, (double*)ctx->btp.p, ctx->stream, mode);
     if (rc || !repair) return rc;
     ScanParams qr = p;
     qr.only_if = pioran_tp_disc((const double*)ctx->btp.p, p.B, p.N, RP, nseg);
@@ -783,52 +656,11 @@ int tp_dispatch(pioran_ds* ds, const ScanParams& p)
     return rc;
 }
 
-// The automatic choice between the windowed form with one draw per wavefront ("tile", 1) and the rest (0: step-by-step throughput layouts / the
-// small-batch windowed kernel) for a shared-table batch of B draws with R active rows — a PURE function of its arguments, exported so that
-// tests/test_host.py can hold it against the committed sweep (profiles/r05_tile_batch_sweep.txt: the choice must be within 5 % of the faster
-// family on every measured line) and tools/retune_thresholds.py can print where it is not.  pass = draws per pass of the step-by-step
-// layout that would take the batch (pioran_scan_pass_draws; 0 = not known: -1 is returned where the ladder needs it).
-static int tile_choice(int32_t R, int64_t B, int64_t pass, int no_split)
-{
-    if (R >= 49) return B > (R > pioran_block_supported_rows() ? 256 : 512) ? 1 : 0;
-    if (R < 17 || B <= 512) return 0;
-    if (B <= 1024) return 1;
-    if (R < 33) return B <= 2048 ? 1 : 0;   // one round of this kernel's workgroups (2048 draws): SHO-12 1536 / 2048 draws 3.5 / 3.6 against 4.3 / 4.4 ms,
-                                          // SHO-16 level (5.3 / 5.4 against 5.4); beyond, the step-by-step layouts' pass (8192 / 4096 draws) is ahead
-    if (R >= 39 && R <= 47) return 1;   // three block columns cost the same for 33 .. 47 rows, the step-by-step layouts ~R^2: from 39 rows on this
-                                        // kernel is ahead on whole passes too (SHO-20, 4096 draws: 10.7 against 11.4 .. 12.0 ms)
-    if (pass <= 0) return -1;
-    const int64_t r = B % pass;
-    // a remainder of up to one round of the small-batch kernel rides beside the scan (split_dispatch) where that kernel takes these rows
-    const bool split = B > pass && r > 0 && r <= (R <= 47 ? 512 : 256) && !no_split;
-    return r > 0 && 4 * r <= 3 * pass && !split ? 1 : 0;
-}
-
-// Large shared-table batches: the windowed form with one draw per wavefront (celerite_tile.hip, round 5).  Same table as the windowed
-// kernel for small batches.  scan_config = "tile" forces it for any batch size.
-int tile_dispatch(pioran_ds* ds, const ScanParams& p)
+int tile_dispatch(pioran_ds* ds, const ScanParams& p, const RouteQuery& q)
 {
     pioran_ctx* ctx = ds->ctx;
-    const ScanOptions& o = ctx->opt;
-    const bool force = o.force_tile;
-    // measured on N = 1e4 (tools/ab_tile.py, profiles/r05_tile_batch_sweep.txt): from 49 rows on (four block columns and more) it beats the
-    // step-by-step layouts at every batch size above the small-batch windowed kernel's range — DRWCelerite-20 (60 rows) 1024 draws 6.3
-    // against 7.8 ms, 4096 draws 17.5 against 25.1 ms; SHO-40 (80 rows) 512 draws 10.0 against 13.1 ms, 4096 draws 41.3 against 75.3 ms.
-    // Up to 48 rows the throughput layouts (two draws per wavefront) are level with it (SHO-20: 11.2 against 11.4 ms) and stay the default.
-    // Up to 38 rows (and at 48) the throughput layouts (two and four draws per wavefront) are level with it or ahead on whole passes (SHO-24, 4096
-    // draws: 16.5 against 16.9 ms), well ahead of it below 33 rows (SHO-16, 4096 draws: 5.8 against 10.7 ms) — but their time is a staircase of passes
-    // (SHO-20: 4096 draws), and this kernel's steps are a quarter of that (1024 draws: one workgroup per CU): it takes what falls between
-    // (profiles/r05_tile_batch_sweep.txt: SHO-20 1024 draws 3.96 against 5.31 ms, 3072 draws 9.3 against 11.0, 5000 draws 14.8 against 16.7;
-    // SHO-12 / SHO-16 / SHO-24 at 1024 draws 2.9 / 3.9 / 6.2 against 4.2 / 5.6 / 8.2 ms).
-    bool automatic = !o.scan_config[0] && !o.no_tile && !o.no_block && p.tab && p.npd_rows == 0;
-    if (automatic) {
-        int choice = tile_choice(p.R, p.B, 0, o.no_split ? 1 : 0);
-        if (choice < 0) choice = tile_choice(p.R, p.B, pioran_scan_pass_draws(p, nullptr), o.no_split ? 1 : 0);   // (the occupancy query only where the ladder needs it)
-        automatic = choice == 1;
-    }
-    if (!(force || automatic) || !p.tab || p.npd_rows != 0 || !pioran_tile_fits(p.R, p.J)) return PIORAN_ERR_UNSUPPORTED;
-    PrepState* s = p.tab == ds->user.tab ? &ds->user : (p.tab == ds->host.tab ? &ds->host : nullptr);
-    if (!s || !s->prepared || s->npd_terms != 0 || p.rec_stride != rec_stride_of(s->R)) return PIORAN_ERR_UNSUPPORTED;
+    if (!tile_wanted(q, [&] { return pioran_scan_pass_draws(p, nullptr); })) return PIORAN_ERR_UNSUPPORTED;
+    PrepState* s = plain_state(ds, p);
     int rc = ensure_btab(ds, *s);
     if (rc) return rc;
     // workspace: 1 KB per draw and window (the windows' own covariance blocks); large batches in chunks of whole passes
@@ -848,34 +680,15 @@ int tile_dispatch(pioran_ds* ds, const ScanParams& p)
     return PIORAN_OK;
 }
 
-static int split_dispatch(pioran_ds* ds, const ScanParams& p)
+// The remainder of a multi-pass batch (split_plan) on the windowed kernel on the context's second stream, launched first, while the whole passes run
+// on the main stream.  The two launches write disjoint slices of out / status; the main stream waits for the second one's event, so the call is
+// stream-ordered like any other.
+int split_dispatch(pioran_ds* ds, const ScanParams& p, const RouteQuery& q)
 {
     pioran_ctx* ctx = ds->ctx;
-    const ScanOptions& o = ctx->opt;
-    if (o.no_split || o.scan_config[0] || o.no_block || o.force_fallback || !p.tab || p.npd_rows != 0 || p.R < 6 || p.R > 95 ||
-        !pioran_block_fits_value(p.R, p.J))
-        return PIORAN_ERR_UNSUPPORTED;
-    PrepState* s = p.tab == ds->user.tab ? &ds->user : (p.tab == ds->host.tab ? &ds->host : nullptr);
-    if (!s || !s->prepared || s->npd_terms != 0 || p.rec_stride != rec_stride_of(s->R)) return PIORAN_ERR_UNSUPPORTED;
-    int wps = 0;
-    const int64_t pass = pioran_scan_pass_draws(p, &wps);
-    if (pass < 1024) return PIORAN_ERR_UNSUPPORTED;
-    (void)wps;
-    // ONE round of the windowed kernel's workgroups: 512 draws (two workgroups per CU) up to three block columns, 256 with four
-    // (tools/sweep_batch_sizes.py, profiles/r04_batch_sizes.txt: SHO-20 4200 draws 16.8 -> 13.1 ms, 4608 16.8 -> 14.8; DRWCelerite-20 4200
-    // 32.5 -> 28.6.  A second round no longer hides behind the scan — SHO-20 5000 draws: 19.7 against 16.8 ms in one launch — and neither
-    // does sending what exceeds HALF a pass: 2500 draws 11.6 against 10.6 ms; both were measured and are not done.)
-    const int64_t rem_max = p.R <= 47 ? 512 : 256;   // (64 .. 95 rows, five / six block columns: a pass of the scan is 1024 .. 2048 draws there)
-    int64_t main_n = 0;
-    const int64_t k = p.B / pass, r = p.B - k * pass;
-    if (k >= 1 && r > 0 && r <= rem_max) main_n = k * pass;
-    if (main_n <= 0 || main_n >= p.B) return PIORAN_ERR_UNSUPPORTED;
-    // everything that can refuse is asked BEFORE the second stream gets work: the whole passes must be a launch the scan takes
-    {
-        const ScanParams probe = slice_draws(p, 0, main_n);
-        const bool y80 = probe.R == pioran_scan_supported_rows_shared() && !o.no_win2 && (probe.B > 768 || o.no_wide);
-        if (probe.R > pioran_scan_supported_rows() && !y80) return PIORAN_ERR_UNSUPPORTED;
-    }
+    const int64_t main_n = split_plan(q, [&] { return pioran_scan_pass_draws(p, nullptr); });
+    if (main_n <= 0) return PIORAN_ERR_UNSUPPORTED;
+    PrepState* s = plain_state(ds, p);
     int rc = ensure_btab(ds, *s);
     if (rc) return rc;
     if ((rc = ensure_aux(ctx))) return rc;
@@ -894,33 +707,26 @@ static int split_dispatch(pioran_ds* ds, const ScanParams& p)
     return PIORAN_OK;
 }
 
+int scan_or_wide_dispatch(pioran_ds* ds, const ScanParams& p, const RouteQuery&)
+{
+    return p.R <= pioran_wide_supported_rows() ? scan_dispatch(p, ds->ctx->stream) : PIORAN_ERR_UNSUPPORTED;
+}
+
 int launch(pioran_ds* ds, ScanParams& p)
 {
     pioran_ctx* ctx = ds->ctx;
     p.opt = &ctx->opt;
+    // the ladder: the first family that does not refuse (PIORAN_ERR_UNSUPPORTED) has the launch; what last_err says when its launch fails
+    // (split_dispatch names the failing kernel itself)
+    static constexpr struct { int (*dispatch)(pioran_ds*, const ScanParams&, const RouteQuery&); const char* failed; } kLadder[] = {
+        {tp_dispatch, "time-parallel kernel launch failed"}, {tile_dispatch, "tile kernel launch failed"}, {block_dispatch, "block kernel launch failed"},
+        {split_dispatch, nullptr}, {scan_or_wide_dispatch, "scan kernel launch failed"}};
     if (!ctx->opt.force_fallback) {
-        int rc = tp_dispatch(ds, p);
-        if (rc != PIORAN_ERR_UNSUPPORTED) {
-            if (rc == PIORAN_ERR_HIP) ctx->last_err = "time-parallel kernel launch failed";
-            return rc;
-        }
-        rc = tile_dispatch(ds, p);
-        if (rc != PIORAN_ERR_UNSUPPORTED) {
-            if (rc == PIORAN_ERR_HIP) ctx->last_err = "tile kernel launch failed";
-            return rc;
-        }
-        rc = block_dispatch(ds, p);
-        if (rc != PIORAN_ERR_UNSUPPORTED) {
-            if (rc == PIORAN_ERR_HIP) ctx->last_err = "block kernel launch failed";
-            return rc;
-        }
-        rc = split_dispatch(ds, p);
-        if (rc != PIORAN_ERR_UNSUPPORTED) return rc;
-    }
-    if (p.R <= pioran_wide_supported_rows() && !ctx->opt.force_fallback) {
-        int rc = scan_dispatch(p, ctx->stream);
-        if (rc != PIORAN_ERR_UNSUPPORTED) {
-            if (rc == PIORAN_ERR_HIP) ctx->last_err = "scan kernel launch failed";
+        const RouteQuery q = route_query(ds, p);
+        for (const auto& step : kLadder) {
+            const int rc = step.dispatch(ds, p, q);
+            if (rc == PIORAN_ERR_UNSUPPORTED) continue;
+            if (rc == PIORAN_ERR_HIP && step.failed) ctx->last_err = step.failed;
             return rc;
         }
     }
@@ -934,59 +740,10 @@ int launch(pioran_ds* ds, ScanParams& p)
     return rc;
 }
 
-}  // namespace
-
-int pioran_tile_choice(int32_t R, int64_t B, int64_t pass, int no_split) { return tile_choice(R, B, pass, no_split); }
-
-
-extern "C" {
-
-const char* pioran_strerror(int code)
+// `value` of option `key` into a set of options (pioran_ctx_set_option; the option string of pioran_value_route)
+int set_option(ScanOptions& o, const char* key, const char* value)
 {
-    switch (code) {
-        case PIORAN_OK: return "ok";
-        case PIORAN_ERR_ARG: return "invalid argument";
-        case PIORAN_ERR_HIP: return "HIP runtime error";
-        case PIORAN_ERR_ALLOC: return "allocation failed";
-        case PIORAN_ERR_UNSUPPORTED: return "unsupported size";
-        default: return "unknown error";
-    }
-}
-
-const char* pioran_last_hip_error(const pioran_ctx* ctx) { return ctx ? ctx->last_err.c_str() : ""; }
-
-int pioran_abi_version(void) { return 7; }
-
-// The FP64 FMA rate the device sustains now, at `waves_per_simd` (1 .. 8) wavefronts per SIMD on every SIMD: ~`ms` milliseconds of a pure
-// v_fma_f64 stream, event-timed on the context's stream (table.hip).  Diagnostics: bench.py's frac_of_measured_fma_ceiling.
-int pioran_ctx_fp64_probe(pioran_ctx* ctx, int waves_per_simd, double ms, double* tflops)
-{
-    if (!ctx || !tflops || waves_per_simd < 1 || waves_per_simd > 8 || !(ms > 0.0) || ms > 1000.0) return PIORAN_ERR_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int blocks = ctx->ncu * waves_per_simd;
-    int rc = ensure(ctx, ctx->bscratch, (size_t)blocks * 256 * sizeof(double));
-    if (rc) return rc;
-    // 64 FMAs per trip at ~4.6 issue cycles each and `waves_per_simd` wavefronts sharing the SIMD, ~2 GHz
-    int iters = (int)(ms * 1e-3 * 2.0e9 / (64.0 * 4.6 * waves_per_simd));
-    if (iters < 64) iters = 64;
-    double flop = 0.0;
-    if ((rc = pioran_launch_fma_stream(blocks, 64, (double*)ctx->bscratch.p, nullptr, ctx->stream))) return rc;   // warm
-    // (the context's internal event slots: 0 .. 11 are the caller's, pioran_ctx_event_record)
-    HIPCHK(ctx, hipEventRecord(ctx->ev[14], ctx->stream));
-    if ((rc = pioran_launch_fma_stream(blocks, iters, (double*)ctx->bscratch.p, &flop, ctx->stream))) return rc;
-    HIPCHK(ctx, hipEventRecord(ctx->ev[15], ctx->stream));
-    HIPCHK(ctx, hipEventSynchronize(ctx->ev[15]));
-    float t = 0.f;
-    HIPCHK(ctx, hipEventElapsedTime(&t, ctx->ev[14], ctx->ev[15]));
-    *tflops = t > 0.f ? flop / (t * 1e-3) / 1e12 : 0.0;
-    return PIORAN_OK;
-}
-
-int pioran_ctx_set_option(pioran_ctx* ctx, const char* key, const char* value)
-{
-    if (!ctx || !key) return PIORAN_ERR_ARG;
     const bool on = value && value[0] && std::strcmp(value, "0") != 0;
-    ScanOptions& o = ctx->opt;
     if (!std::strcmp(key, "scan_config")) {
         if (value && std::strlen(value) >= sizeof(o.scan_config)) return PIORAN_ERR_ARG;
         std::memset(o.scan_config, 0, sizeof(o.scan_config));
@@ -1037,6 +794,81 @@ int pioran_ctx_set_option(pioran_ctx* ctx, const char* key, const char* value)
     else if (!std::strcmp(key, "no_wide2")) o.no_wide2 = on;
     else return PIORAN_ERR_ARG;
     return PIORAN_OK;
+}
+
+}  // namespace
+
+int pioran_tile_choice(int32_t R, int64_t B, int64_t pass, int no_split) { return tile_choice(R, B, pass, no_split); }
+
+int pioran_value_route(int32_t R, int32_t J, int32_t n_one_row_terms, int64_t B, int64_t N, int per_draw_series, int64_t pass, const char* options,
+                       char* name, int name_len, int32_t* tp)
+{
+    if (J < 1 || n_one_row_terms < 0 || n_one_row_terms > J || R != 2 * J - n_one_row_terms || B < 1 || N < 1 || !name || name_len < 1) return PIORAN_ERR_ARG;
+    ScanOptions opt{};
+    for (const char* kv = options ? options : ""; *kv;) {
+        const char* end = std::strchr(kv, ';');
+        const std::string item = end ? std::string(kv, end) : std::string(kv);
+        kv = end ? end + 1 : kv + item.size();
+        if (item.empty()) continue;
+        const size_t eq = item.find('=');
+        if (eq == std::string::npos) return PIORAN_ERR_ARG;
+        if (const int rc = set_option(opt, item.substr(0, eq).c_str(), item.c_str() + eq + 1)) return rc;
+    }
+    // every resource granted: a plain prepared state behind the table, the launch on its own step records
+    const RouteQuery q{R, J, B, N, true, 0, per_draw_series != 0, J - n_one_row_terms, n_one_row_terms, true, true, opt};
+    TpPlan plan;
+    std::snprintf(name, (size_t)name_len, "%s", value_route(q, pass, &plan));
+    if (tp) { tp[0] = plan.scan; tp[1] = plan.RP; tp[2] = plan.nseg; tp[3] = (int32_t)plan.L; }
+    return PIORAN_OK;
+}
+
+
+extern "C" {
+
+const char* pioran_strerror(int code)
+{
+    switch (code) {
+        case PIORAN_OK: return "ok";
+        case PIORAN_ERR_ARG: return "invalid argument";
+        case PIORAN_ERR_HIP: return "HIP runtime error";
+        case PIORAN_ERR_ALLOC: return "allocation failed";
+        case PIORAN_ERR_UNSUPPORTED: return "unsupported size";
+        default: return "unknown error";
+    }
+}
+
+const char* pioran_last_hip_error(const pioran_ctx* ctx) { return ctx ? ctx->last_err.c_str() : ""; }
+
+int pioran_abi_version(void) { return 7; }
+
+// The FP64 FMA rate the device sustains now, at `waves_per_simd` (1 .. 8) wavefronts per SIMD on every SIMD: ~`ms` milliseconds of a pure
+// v_fma_f64 stream, event-timed on the context's stream (table.hip).  Diagnostics: bench.py's frac_of_measured_fma_ceiling.
+int pioran_ctx_fp64_probe(pioran_ctx* ctx, int waves_per_simd, double ms, double* tflops)
+{
+    if (!ctx || !tflops || waves_per_simd < 1 || waves_per_simd > 8 || !(ms > 0.0) || ms > 1000.0) return PIORAN_ERR_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int blocks = ctx->ncu * waves_per_simd;
+    int rc = ensure(ctx, ctx->bscratch, (size_t)blocks * 256 * sizeof(double));
+    if (rc) return rc;
+    // 64 FMAs per trip at ~4.6 issue cycles each and `waves_per_simd` wavefronts sharing the SIMD, ~2 GHz
+    int iters = (int)(ms * 1e-3 * 2.0e9 / (64.0 * 4.6 * waves_per_simd));
+    if (iters < 64) iters = 64;
+    double flop = 0.0;
+    if ((rc = pioran_launch_fma_stream(blocks, 64, (double*)ctx->bscratch.p, nullptr, ctx->stream))) return rc;   // warm
+    // (the context's internal event slots: 0 .. 11 are the caller's, pioran_ctx_event_record)
+    HIPCHK(ctx, hipEventRecord(ctx->ev[14], ctx->stream));
+    if ((rc = pioran_launch_fma_stream(blocks, iters, (double*)ctx->bscratch.p, &flop, ctx->stream))) return rc;
+    HIPCHK(ctx, hipEventRecord(ctx->ev[15], ctx->stream));
+    HIPCHK(ctx, hipEventSynchronize(ctx->ev[15]));
+    float t = 0.f;
+    HIPCHK(ctx, hipEventElapsedTime(&t, ctx->ev[14], ctx->ev[15]));
+    *tflops = t > 0.f ? flop / (t * 1e-3) / 1e12 : 0.0;
+    return PIORAN_OK;
+}
+
+int pioran_ctx_set_option(pioran_ctx* ctx, const char* key, const char* value)
+{
+    return ctx && key ? set_option(ctx->opt, key, value) : PIORAN_ERR_ARG;
 }
 
 static int ctx_create_impl(int device, void* stream, bool own, pioran_ctx** out)
@@ -1350,10 +1182,7 @@ int pioran_celerite_logl_batch_dev_cd(pioran_ds* ds, int64_t B, int64_t J, const
         // (window, draw) builds it: ~8 us per table at N = 1e4, J = 20) instead of evaluating 3 J transcendentals per step and draw inside
         // the throughput layout (14.7 ms per launch at N = 1e4, J = 20 whatever the batch): free Celerite / CARMA terms under a sampler
         // (src/CARMA.jl:98-143).  tools/bench_per_draw_small.py.
-        const ScanOptions& o = ctx->opt;
-        const bool automatic = !o.scan_config[0] && !o.no_block && B <= 768 && R >= 6;
-        const bool force = !std::strcmp(o.scan_config, "block");
-        if ((automatic || force) && !o.force_fallback && pioran_block_fits(R, (int32_t)J)) {
+        if (perdraw_tables_wanted(ctx->opt, B, R, (int32_t)J)) {
             const int64_t tdoubles = (int64_t)pioran_block_table_doubles(ds->N, R, (int32_t)J);
             int64_t chunk;
             if ((rc = size_tables(tdoubles, chunk))) return rc;
@@ -1977,7 +1806,7 @@ static int logl_grad_batch(pioran_ds* ds, bool per_draw, int64_t B, int64_t J, c
     // From 513 chains on (measured, SHO-20 / SHO-12 at N = 1e4: 512 chains 15.1 / 9.3 ms against the small-batch kernels' 11.0 / 9.2; 640 chains 15.2 /
     // 9.4 against 16.6 / 14.0; 2048 chains 27 / 16 against 44 / 36).
     const bool tilegrad = !per_draw && windowed && (grad.c != nullptr) == (grad.d != nullptr) && !grad.y && !grad.s2 && !shift &&
-                          s.R <= pioran_tile_grad_supported_rows() && (ctx->opt.force_tile || (!ctx->opt.no_tile && B > 512 && s.R >= 17));
+                          s.R <= pioran_tile_grad_supported_rows() && tile_grad_wanted(ctx->opt, B, s.R);
     // (48 .. 63 rows — DRWCelerite-20 is 60: three draws per workgroup there (two with d/d(c, d)); 4096 chains take 126 ms (163 with d/d(c, d)) against 166 (175)
     //  in 512-chain launches of the small-batch kernels: tools/ab_tile_grad_nb4.py, profiles/r06_tile_grad_four_block_columns.txt.  Until the reverse kernel
     //  stopped spilling at four block columns — T_k and the window's U operands loaded at the head of their own window instead of a window ahead — it was 177 (208).)

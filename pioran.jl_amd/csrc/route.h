@@ -1,0 +1,49 @@
+// Which kernel family evaluates a batch of log-likelihoods: the measured rules, as pure functions of a RouteQuery (route.hip).  Host code only: no
+// runtime call, no context, no data set.  capi.hip fills the query once per launch, asks the rules in the ladder's order (time-parallel, tile,
+// windowed, remainder split, scan / latency layout, fallback) and does the rest: tables, workspaces, streams, the launches.
+#pragma once
+#include "common.h"
+
+#include <functional>
+
+// What the rules read of a launch
+struct RouteQuery {
+    int32_t R, J;                   // active rows, terms
+    int64_t B, N;                   // draws, time stamps
+    bool shared;                    // the draws share a table (ScanParams::tab)
+    int32_t npd_rows;               // per-draw rows (mixed mode)
+    bool per_draw_series;           // (Y, S2) per draw
+    int32_t n_two_row, n_one_row;   // terms of the prepared state behind the table, by rows kept (0, 0: no such state)
+    bool plain_state;               // a prepared state without per-draw terms stands behind the table ...
+    bool own_records;               // ... and the launch's step records are that state's own (rec_stride)
+    const ScanOptions& opt;
+};
+
+// draws per pass of the step-by-step layout that would take the batch (an occupancy query: asked only where a rule needs it)
+using PassOf = std::function<int64_t()>;
+
+int tile_choice(int32_t R, int64_t B, int64_t pass, int no_split);
+bool tile_wanted(const RouteQuery& q, const PassOf& pass_of);
+bool block_wanted(const RouteQuery& q);
+enum class ScanFamily { none, wide, scan };
+ScanFamily scan_family(const RouteQuery& q);
+int64_t split_plan(const RouteQuery& q, const PassOf& pass_of);   // draws on whole passes of the scan (0: no split)
+
+// The time-parallel family's plan: taken or not; the boundary phase as a scan or as the walk; padded state rows, segments, steps per segment
+struct TpPlan {
+    bool take = false, scan = false;
+    int RP = 0, nseg = 0;
+    int64_t L = 0;
+    int scan_cap = 256;
+};
+TpPlan tp_plan(const RouteQuery& q);
+bool tp_repair_wanted(const RouteQuery& q);                           // may the serial-chain windowed kernel repair the draws that fail the check
+int tp_mode(const TpPlan& plan, bool repair, const ScanOptions& o);   // pioran_launch_tp's mode 0 / 1 / 2 / 4; -1: the family refuses the launch
+
+// the family the ladder takes when every resource is granted (pioran_value_route); *tp: the plan, where the family is "tp"
+const char* value_route(const RouteQuery& q, int64_t pass, TpPlan* tp);
+
+// the other entries' one-line rules
+bool windowed_allowed(const ScanOptions& o, int32_t R, int32_t J);
+bool perdraw_tables_wanted(const ScanOptions& o, int64_t B, int32_t R, int32_t J);
+bool tile_grad_wanted(const ScanOptions& o, int64_t B, int32_t R);

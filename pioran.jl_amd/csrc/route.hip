@@ -1,0 +1,295 @@
+// The routing rules of the value path (route.h): thresholds and time models, each with the measurements it was set from.  Pure host functions.
+#include "route.h"
+
+#include <cmath>
+#include <cstring>
+
+// The automatic choice between the windowed form with one draw per wavefront ("tile", 1) and the rest (0: step-by-step throughput layouts / the
+// small-batch windowed kernel) for a shared-table batch of B draws with R active rows — a PURE function of its arguments, exported so that
+// tests/test_host.py can hold it against the committed sweep (profiles/r05_tile_batch_sweep.txt: the choice must be within 5 % of the faster
+// family on every measured line) and tools/retune_thresholds.py can print where it is not.  pass = draws per pass of the step-by-step
+// layout that would take the batch (pioran_scan_pass_draws; 0 = not known: -1 is returned where the ladder needs it).
+int tile_choice(int32_t R, int64_t B, int64_t pass, int no_split)
+{
+    if (R >= 49) return B > (R > pioran_block_supported_rows() ? 256 : 512) ? 1 : 0;
+    if (R < 17 || B <= 512) return 0;
+    if (B <= 1024) return 1;
+    if (R < 33) return B <= 2048 ? 1 : 0;   // one round of this kernel's workgroups (2048 draws): SHO-12 1536 / 2048 draws 3.5 / 3.6 against 4.3 / 4.4 ms,
+                                          // SHO-16 level (5.3 / 5.4 against 5.4); beyond, the step-by-step layouts' pass (8192 / 4096 draws) is ahead
+    if (R >= 39 && R <= 47) return 1;   // three block columns cost the same for 33 .. 47 rows, the step-by-step layouts ~R^2: from 39 rows on this
+                                        // kernel is ahead on whole passes too (SHO-20, 4096 draws: 10.7 against 11.4 .. 12.0 ms)
+    if (pass <= 0) return -1;
+    const int64_t r = B % pass;
+    // a remainder of up to one round of the small-batch kernel rides beside the scan (split_plan) where that kernel takes these rows
+    const bool split = B > pass && r > 0 && r <= (R <= 47 ? 512 : 256) && !no_split;
+    return r > 0 && 4 * r <= 3 * pass && !split ? 1 : 0;
+}
+
+// Large shared-table batches: the windowed form with one draw per wavefront (celerite_tile.hip, round 5).  Same table as the windowed
+// kernel for small batches.  scan_config = "tile" forces it for any batch size.
+bool tile_wanted(const RouteQuery& q, const PassOf& pass_of)
+{
+    const ScanOptions& o = q.opt;
+    const bool force = o.force_tile;
+    // measured on N = 1e4 (tools/ab_tile.py, profiles/r05_tile_batch_sweep.txt): from 49 rows on (four block columns and more) it beats the
+    // step-by-step layouts at every batch size above the small-batch windowed kernel's range — DRWCelerite-20 (60 rows) 1024 draws 6.3
+    // against 7.8 ms, 4096 draws 17.5 against 25.1 ms; SHO-40 (80 rows) 512 draws 10.0 against 13.1 ms, 4096 draws 41.3 against 75.3 ms.
+    // Up to 48 rows the throughput layouts (two draws per wavefront) are level with it (SHO-20: 11.2 against 11.4 ms) and stay the default.
+    // Up to 38 rows (and at 48) the throughput layouts (two and four draws per wavefront) are level with it or ahead on whole passes (SHO-24, 4096
+    // draws: 16.5 against 16.9 ms), well ahead of it below 33 rows (SHO-16, 4096 draws: 5.8 against 10.7 ms) — but their time is a staircase of passes
+    // (SHO-20: 4096 draws), and this kernel's steps are a quarter of that (1024 draws: one workgroup per CU): it takes what falls between
+    // (profiles/r05_tile_batch_sweep.txt: SHO-20 1024 draws 3.96 against 5.31 ms, 3072 draws 9.3 against 11.0, 5000 draws 14.8 against 16.7;
+    // SHO-12 / SHO-16 / SHO-24 at 1024 draws 2.9 / 3.9 / 6.2 against 4.2 / 5.6 / 8.2 ms).
+    bool automatic = !o.scan_config[0] && !o.no_tile && !o.no_block && q.shared && q.npd_rows == 0;
+    if (automatic) {
+        int choice = tile_choice(q.R, q.B, 0, o.no_split ? 1 : 0);
+        if (choice < 0) choice = tile_choice(q.R, q.B, pass_of(), o.no_split ? 1 : 0);   // (the occupancy query only where the ladder needs it)
+        automatic = choice == 1;
+    }
+    return (force || automatic) && q.shared && q.npd_rows == 0 && pioran_tile_fits(q.R, q.J) && q.plain_state && q.own_records;
+}
+
+// Small shared-table batches without per-draw rows: the windowed kernel (celerite_block.hip), which needs its own table.
+bool block_wanted(const RouteQuery& q)
+{
+    const ScanOptions& o = q.opt;
+    const char* cfg = o.scan_config[0] ? o.scan_config : nullptr;
+    const bool force = cfg && !std::strcmp(cfg, "block");
+    // measured on N = 1e4 (tools/sweep_block.py, tools/sweep_midbatch.py, tools/sweep_block_emode.py): faster than both other kernels
+    // up to 512 draws from 6 rows on.  Late round 3: with the pair table read from global memory two workgroups share a CU at three
+    // block columns, which moves the crossover up — R = 32 .. 35: 768 draws 4.9 vs 5.4 ms; R = 36 .. 47: 1024 draws 5.3 .. 5.8 vs
+    // 5.7 .. 7.5 ms on the throughput shapes.  With four block columns (48 rows and more) the table stays in LDS and 512 draws is the
+    // limit (DRWCelerite-20 at 768 draws: 7.8 vs 7.1 ms on the throughput shape, which got faster this round).
+    // Round 4: five and six block columns (64 .. 95 rows; value only, one workgroup per CU: up to 256 draws).
+    // Late round 4 (tools/scalar_small_j.py, profiles/r04_few_rows.txt): five rows 1.84 -> 1.48 ms at N = 1e4; four and fewer rows stay on the
+    // throughput layout (1.42 against 1.47 ms) except for long series — its 20-double step records outgrow the L2 (N = 65536: 13.4 against
+    // 9.5 ms up to 256 draws, 11.2 at 512) — and for the scalar call, whose series arrive as per-draw (y, sigma2): N = 8192 1.36 -> 1.25 ms.
+    const bool few_rows = q.R < 5 && ((q.N >= 16384 && q.B <= 512) || (q.per_draw_series && q.B == 1 && q.N >= 2048));
+    const bool automatic = !cfg && !o.no_block &&
+                           (q.R < 5 ? few_rows
+                            : q.R > pioran_block_supported_rows()
+                                ? q.B <= 256
+                                : (q.B <= 512 || (q.B <= 768 && q.R >= 32 && q.R <= 47) || (q.B <= 1024 && q.R >= 36 && q.R <= 47)));
+    return (force || automatic) && q.shared && q.npd_rows == 0 && pioran_block_fits_value(q.R, q.J) && q.plain_state && q.own_records;
+}
+
+// Register-resident scan: small shared-table batches take the latency layout (celerite_wide.hip, one draw per
+// workgroup), everything else the throughput layouts (celerite_scan.hip).  PIORAN_SCAN_CONFIG=wide forces the former
+// for any batch size, any other value names a throughput configuration; PIORAN_NO_WIDE=1 disables the former.
+ScanFamily scan_family(const RouteQuery& q)
+{
+    const ScanOptions& o = q.opt;
+    const char* cfg = o.scan_config[0] ? o.scan_config : nullptr;
+    const bool force_wide = cfg && !std::strcmp(cfg, "wide");
+    // (below 16 rows the per-step exchange of the latency layout costs more than the whole step of a throughput layout)
+    const bool auto_wide = !cfg && q.B <= pioran_wide_max_batch() && q.R >= 16 && !o.no_wide;
+    // 80..95 rows: the throughput layouts do not hold S in registers any more, the latency layout still does
+    // (exactly 80 rows with a shared table: the throughput layout holds them with y as a vector — large batches go there: 54 k
+    //  instead of 43 k evaluations per second at B = 1024 .. 4096, N = 1e4; at 512 draws the latency layout is still ahead,
+    //  39 k vs 27 k: tools/sweep_r80.py)
+    const bool y80 = q.R == pioran_scan_supported_rows_shared() && q.shared && q.npd_rows == 0 && !o.no_win2 && (q.B > 768 || o.no_wide);
+    const bool only_wide = q.R > pioran_scan_supported_rows() && !o.no_wide && !y80;
+    if (q.shared && q.R <= pioran_wide_supported_rows() && (force_wide || auto_wide || only_wide)) return ScanFamily::wide;
+    if (q.R > pioran_scan_supported_rows() && !y80) return ScanFamily::none;
+    return ScanFamily::scan;
+}
+
+// Batches that are not a whole number of passes (round 4).  A throughput launch is a sequence of PASSES — every SIMD of the chip holding as
+// many wavefronts as the kernel's registers allow (SHO-20: 2 x 1024 wavefronts x 2 draws = 4096 draws) — and a wavefront walks the whole
+// series whatever its pass carries: 4200 draws cost two passes' time less what the scheduler backfills (16.9 against 11.9 ms for 4096).
+// Small remainders are what the windowed kernel (celerite_block.hip) is fast at, and its workgroups fit BESIDE a resident scan wavefront
+// (205 + 250 registers per SIMD lane pair): so the remainder goes to that kernel on the context's second stream, launched first, while the
+// whole passes run on the main stream (capi.hip split_dispatch).
+int64_t split_plan(const RouteQuery& q, const PassOf& pass_of)
+{
+    const ScanOptions& o = q.opt;
+    if (o.no_split || o.scan_config[0] || o.no_block || o.force_fallback || !q.shared || q.npd_rows != 0 || q.R < 6 || q.R > 95 ||
+        !pioran_block_fits_value(q.R, q.J))
+        return 0;
+    if (!q.plain_state || !q.own_records) return 0;
+    const int64_t pass = pass_of();
+    if (pass < 1024) return 0;
+    // ONE round of the windowed kernel's workgroups: 512 draws (two workgroups per CU) up to three block columns, 256 with four
+    // (tools/sweep_batch_sizes.py, profiles/r04_batch_sizes.txt: SHO-20 4200 draws 16.8 -> 13.1 ms, 4608 16.8 -> 14.8; DRWCelerite-20 4200
+    // 32.5 -> 28.6.  A second round no longer hides behind the scan — SHO-20 5000 draws: 19.7 against 16.8 ms in one launch — and neither
+    // does sending what exceeds HALF a pass: 2500 draws 11.6 against 10.6 ms; both were measured and are not done.)
+    const int64_t rem_max = q.R <= 47 ? 512 : 256;   // (64 .. 95 rows, five / six block columns: a pass of the scan is 1024 .. 2048 draws there)
+    int64_t main_n = 0;
+    const int64_t k = q.B / pass, r = q.B - k * pass;
+    if (k >= 1 && r > 0 && r <= rem_max) main_n = k * pass;
+    if (main_n <= 0 || main_n >= q.B) return 0;
+    // everything that can refuse is asked BEFORE the second stream gets work: the whole passes must be a launch the scan takes
+    RouteQuery whole = q;
+    whole.B = main_n;
+    return scan_family(whole) == ScanFamily::scan ? main_n : 0;
+}
+
+// The time model of the time-parallel family, us (measured at 2 .. 48 rows, tools/ab_tp.py; profiles/r06_time_parallel_scan.txt).
+// One step of phases 1 + 3: one wavefront per segment up to 16 rows, four above
+static double tp_step_us(int RP) { return RP <= 16 ? 0.7 + RP / 8.0 : 1.0 + RP / 32.0; }
+// one combination of the scan
+static double tp_combine_us(int RP) { return 8.0 + (double)RP * RP / 50.0; }
+// one boundary of the walk (2 / 4 rows: one thread per draw; up to 16: one wavefront, in registers; above: four wavefronts, products on the matrix
+// cores, four pivots per barrier)
+static double tp_boundary_us(int RP) { return RP == 2 ? 0.6 : (RP == 4 ? 2.0 : (RP <= 16 ? 1.3 + RP * RP / 21.0 : 5.0 + (double)RP * RP / 80.0)); }
+
+// A handful of draws of a long series: the time-parallel evaluation (celerite_tp.hip, round 5) — segments of the series on different CUs instead
+// of one serial chain per draw.  scan_config = "tp" forces it wherever it applies (shared (c, d), at most 64 state rows, at most 64 draws).
+TpPlan tp_plan(const RouteQuery& q)
+{
+    TpPlan plan;
+    const ScanOptions& o = q.opt;
+    if (o.no_tp || (!o.force_tp && (o.scan_config[0] || o.force_tile)) || !q.shared || q.npd_rows != 0 || q.B > 64) return plan;
+    if (!q.plain_state) return plan;
+    // state rows: the two-row terms first (pairs on even / odd lanes), then the one-row terms, padded to an even count
+    const int J = q.n_two_row + q.n_one_row;
+    const int nrows = 2 * q.n_two_row + q.n_one_row;
+    if (nrows > pioran_tp_supported_rows() || q.N < 64) return plan;
+    // The boundary phase as a scan over the segments' elements (tp_combine_kernel, round 6: ceil(log2 nseg) launches of one workgroup per (draw, target)
+    // instead of nseg - 1 dependent boundary steps) — up to two draws (nseg targets per draw and level want a CU each), 5 .. 64 state rows (padded to
+    // a multiple of 8 for it) — moves every crossover (tools/tp_scan_sweep.py, profiles/r06_time_parallel_scan.txt; one scalar call, PCIe included):
+    // 8 / 16 rows from 1024 steps on (N = 1024: 0.146 / 0.172 against 0.159 / 0.211 ms on the serial chain; N = 8192: 0.23 / 0.27 against 1.08 / 1.50),
+    // 24 rows from 1536 (0.254 against 0.306), 32 from 2048 (0.32 against 0.42), 40 / 48 from 3072 (0.50 / 0.58 against 0.60 / 0.76; N = 1e4:
+    // 0.64 / 0.76 against 1.87 / 2.40; N = 65536: 1.19 / 1.35 against 12.0 / 16.4).
+    // (three and four rows — the reference grid's j = 2 — padded to eight: N = 8192 0.19 ms against 0.28 on the one-thread boundary walk; from 2048 steps on)
+    const bool scan_rows = (nrows > 4 || (nrows > 2 && q.B <= 2 && (q.N >= 2048 || o.tp_scan > 0))) && nrows <= 64;
+    // Three to 32 draws (tools/tp_scan_batch_sweep.py, section 8 of the profile): the combinations of one level want a CU slot each — a CU holds kc = 4 / 2 / 1
+    // workgroups of tp_combine_kernel at up to 8 / up to 32 / more rows (its LDS) — so the segment count is the largest power of two with B nseg <= 256 kc
+    // (SHO-20, N = 1e4, 4 / 8 draws: 64 / 32 segments 0.76 / 1.06 ms against 1.50 / 1.53 on the walk and 1.85 on the serial chains; 128 segments 1.08 / 2.0).
+    const int RPs = (nrows + 7) & ~7, kc = RPs <= 8 ? 4 : (RPs <= 32 ? 2 : 1);
+    const bool scan_ok = o.tp_scan != 0 && scan_rows && (o.tp_scan > 0 || q.B <= 2 || (q.B <= 32 && 16 * q.B <= 256 * kc));      // the scan is possible
+    bool scan = scan_ok;                                                                                                                      // ... and chosen (below)
+    int scan_cap = 256;
+    if (scan_ok && q.B > 2) { scan_cap = 16; while (2 * scan_cap * q.B <= 256 * kc && scan_cap < 256) scan_cap *= 2; }
+    const int RPw = pioran_tp_padded_rows(nrows);        // rows as the boundary walk pads them (RPs: as the scan does)
+    // measured (tools/ab_tp.py sweep, profiles/r05_time_parallel_gpu.txt): with up to 8 draws it beats the serial-chain kernels from 1024 steps on at
+    // up to 4 state rows (N = 8192: one SHO term 0.17 against 1.16 ms, two 0.27 against 1.15; there also at 64 draws from 4096 steps on: 0.90
+    // against 1.16 ms), from 2048 steps at up to 8 rows (four terms, N = 8192: 0.47 against 1.21), from 4096 at up to 12, from 6144 at up to 16
+    // (eight terms: 0.96 against 1.47 ms); with more rows the boundary solves (R^3 each, one after the other) eat the gain (20 terms, N = 1e4:
+    // 2.6 against 1.83 ms).
+    if (!o.force_tp) {
+        const bool few = RPw <= 4 && ((q.B <= 8 && q.N >= 1024) || q.N >= 4096);
+        const bool mid = RPw > 4 && q.B <= 8 && q.N >= (RPw <= 8 ? 2048 : (RPw <= 12 ? 4096 : 6144)) && RPw <= 16;
+        // 17 .. 64 state rows: the boundary solves cost 14 .. 47 us each (four wavefronts, products and rank-4 updates on the matrix cores, four pivots per barrier), and
+        // the gain comes with the length of the series (its time grows like sqrt(N), the serial chain's like N): SHO-12 (24 rows) N = 8192 / 1e4 /
+        // 65536 0.84 / 0.93 / 2.4 against 1.45 / 1.77 / 11.6 ms; SHO-20 (40 rows) N = 8192 / 1e4 / 65536 1.39 / 1.54 / 3.9 against 1.50 / 1.83 / 11.9;
+        // SHO-24 (48 rows; three block columns on the serial chain) N = 1e4 1.80 against 2.47
+        // 49 .. 64 state rows: DRWCelerite-20 (60 rows; four block columns on the serial chain) N = 1e4 2.71 against 2.61 (not chosen), N = 16384 / 65536
+        // 3.5 / 7.0 against 4.3 / 19.1 ms; SHO-32 (64 rows; FIVE block columns on the serial chain) N = 8192 / 65536 2.45 / 7.0 against 3.7 / 34.4 ms
+        const int64_t nwide = q.R + 1 > 64 ? 6144 : 12288;
+        const int64_t nmin12 = RPw <= 24 ? 4096 : (RPw <= 32 ? 5120 : (RPw <= 40 ? 8192 : (RPw <= 48 ? 6144 : nwide)));
+        const int64_t nmin8 = RPw <= 24 ? 5120 : (RPw <= 32 ? 6144 : (RPw <= 40 ? 8192 : (RPw <= 48 ? 8192 : nwide)));
+        const bool many = RPw > 16 && ((q.B <= 2 && q.N >= nmin12) || (q.B <= 8 && q.N >= nmin8));
+        // (49 .. 64 rows, tp_combine_lean_kernel: 56 / 60 rows from 4096 steps on — 0.89 / 1.02 against 1.03 / 1.08 ms; N = 1e4: 1.10 / 1.21 against 2.46 / 2.58;
+        //  64 rows, five block columns on the serial chain, from 2048 — 0.89 against 0.98; N = 1e4: 1.21 against 4.6)
+        const bool scanned = scan_ok && q.N >= (nrows <= 4 ? 2048 : RPs <= 16 ? 1024 : (RPs <= 24 ? 1536 : (RPs <= 32 ? 2048 : (RPs <= 48 ? 3072 : (q.R + 1 > 64 ? 2048 : 4096)))));
+        // three and more draws on the scan: a model of its time (records + two phases of N / nseg steps + one combination per level and the check, in us)
+        // against the serial chain's time per step (measured at N = 1e4, resident inputs), taken when it promises 15 % off (up to 8 rows, where the model is
+        // optimistic at 32 draws: a quarter) — profiles/r06_time_parallel_scan.txt section 8 has the sweep this was held against at N = 2048 / 4096 / 1e4
+        bool scanned_b = false;
+        if (scan_ok && q.B > 2) {
+            const int RP = RPs;
+            const double tau = tp_step_us(RP), tc = tp_combine_us(RP);
+            int lv = 0;
+            for (int c = scan_cap; c > 1; c >>= 1) ++lv;
+            // (17 .. 32 rows: two combinations and eight phase wavefronts share a CU at the cap — measured 1.5 x the steps' time there)
+            const double load = RP > 16 && RP <= 32 ? (double)q.B * scan_cap * 4.0 / 1024.0 : 1.0, rp = 1.0 + 0.5 * (load > 1.0 ? load - 1.0 : 0.0);
+            double t_scan = 35.0 + rp * tau * (double)q.N / scan_cap + (lv + 1) * tc;
+            const double s_chain = RP <= 8 ? 0.127 : (RP <= 24 ? 0.178 : (RP <= 40 ? 0.19 : (RP <= 48 ? 0.24 : (q.R + 1 > 64 ? 0.46 : 0.25))));
+            // ~2 % of the prior draws of the SHO models and ~7 % of the models with one-row terms (DRWCelerite) fail the check (profiles/r06_time_parallel_scan.txt
+            // section 11), and one failing draw sends the launch through the serial chain as well — its expected share
+            t_scan += (1.0 - std::pow(nrows != 2 * J ? 0.93 : 0.98, (double)q.B)) * s_chain * (double)q.N;
+            scanned_b = (int64_t)scan_cap * 16 <= q.N && t_scan < (RP <= 8 ? 0.75 : 0.85) * s_chain * (double)q.N;
+        }
+        // the scan where ITS rule says so (o.tp_scan > 0: wherever possible); else the boundary walk where its rules say so — a batch of 8 draws of SHO-20 that the
+        // walk's rule admits is better off there (1.53 ms) than on the scan with its expected repair (0.98 + 57 % x 1.86)
+        if (o.tp_scan < 0) scan = q.B <= 2 ? scanned : scanned_b;
+        if (!scan && !few && !mid && !many) return plan;
+    }
+    const int RP = scan ? RPs : RPw;
+    // segments: phases 1 + 3 cost tau = tp_step_us per step; phase 2 t2 = tp_boundary_us per boundary: N / nseg tau + nseg t2 is least at sqrt(tau N / t2)
+    int nseg = o.tp_segments;
+    if (nseg <= 0 && scan) {
+        // N / nseg tau + ceil(log2 nseg) t_c, t_c = one combination: powers of two
+        const double tau = tp_step_us(RP), tc = tp_combine_us(RP);
+        double best = 1e300;
+        for (int cand = 8, lv = 3; cand <= scan_cap; cand *= 2, ++lv) {
+            const double est = tau * (double)q.N / cand + lv * tc;
+            if (est < best && (int64_t)cand * 16 <= q.N) { best = est; nseg = cand; }
+        }
+        if (nseg <= 0) nseg = 1;
+    }
+    if (nseg <= 0) {
+        const double tau = tp_step_us(RP), t2 = tp_boundary_us(RP);
+        nseg = (int)std::lround(std::sqrt(tau * (double)q.N / t2));
+    }
+    if (nseg < 1) nseg = 1;
+    if (nseg > (scan ? 256 : 128)) nseg = scan ? 256 : 128;
+    if (scan && q.B > 2 && o.tp_segments <= 0) nseg = scan_cap;
+    if ((int64_t)nseg * 16 > q.N) nseg = (int)(q.N / 16);
+    const int64_t L = (q.N + nseg - 1) / nseg;
+    nseg = (int)((q.N + L - 1) / L);
+    plan.take = true; plan.scan = scan; plan.RP = RP; plan.nseg = nseg; plan.L = L; plan.scan_cap = scan_cap;
+    return plan;
+}
+
+// A draw whose boundary states fail the filter's check (tp_filter_kernel: 1 .. 3 % of the prior draws of the SHO models, 6 .. 8 % of the DRWCelerite models; the scan
+// or the walk ALONE is wrong by more than 1e-8 on a few per thousand of the latter — tools/tp_scan_accept.py, tp_walk_accuracy.py) is evaluated again by the
+// serial-chain windowed kernel (celerite_block_kernel with ScanParams::only_if: its workgroups leave at once for every draw that passed).
+bool tp_repair_wanted(const RouteQuery& q)
+{
+    const ScanOptions& o = q.opt;
+    return !o.tp_walk_repair && !o.tp_unchecked && !o.no_block && pioran_block_fits_value(q.R, q.J) && q.own_records;
+}
+
+// (no repair pass available — the windowed kernel's table does not fit, "no_block" — and the walk-repair mode not asked for: the boundary walk instead of the
+//  scan; the walk-repair mode's own check, a state discrepancy relative to the state's largest entry, lets bad draws through: tools/tp_scan_metrics.py)
+// Late round 6: the boundary WALK is checked and repaired the same way (mode 4) — a long segment's element is no better conditioned than a composite of the scan:
+// on prior draws of DRWCelerite-10 the walk alone is off by up to 8e-7 where the serial chain holds 4e-10 (tools/tp_walk_accuracy.py).  Without a repair pass the
+// family is not an AUTOMATIC choice any more; forced (scan_config "tp"; options tp_unchecked / tp_walk_repair: tools) it runs unchecked as in round 5.
+int tp_mode(const TpPlan& plan, bool repair, const ScanOptions& o)
+{
+    if (!repair && !o.force_tp) return -1;
+    const int mode = repair ? (plan.scan ? 2 : 4) : (plan.scan && o.tp_walk_repair ? 1 : 0);
+    if (plan.scan && mode == 0 && plan.nseg > 128) return -1;      // (the segment count was chosen for the scan; the walk's kernels take up to 128)
+    return mode;
+}
+
+const char* value_route(const RouteQuery& q, int64_t pass, TpPlan* tp)
+{
+    const ScanOptions& o = q.opt;
+    const PassOf pass_of = [pass] { return pass; };
+    if (!o.force_fallback) {
+        const TpPlan plan = tp_plan(q);
+        if (plan.take && tp_mode(plan, tp_repair_wanted(q), o) >= 0) {
+            if (tp) *tp = plan;
+            return "tp";
+        }
+        if (tile_wanted(q, pass_of)) return "tile";
+        if (block_wanted(q)) return "block";
+        if (split_plan(q, pass_of) > 0) return "scan + block (remainder)";
+        const ScanFamily f = q.R <= pioran_wide_supported_rows() ? scan_family(q) : ScanFamily::none;
+        if (f != ScanFamily::none) return f == ScanFamily::wide ? "wide" : "scan";
+    }
+    return "fallback";
+}
+
+// May an entry (prediction, gradient, simulation) run on the windowed kernels (celerite_block.hip) with R rows of J terms?
+bool windowed_allowed(const ScanOptions& o, int32_t R, int32_t J)
+{
+    return !o.no_block && !o.force_fallback && !o.scan_config[0] && pioran_block_fits(R, J);
+}
+
+// (c, d) per draw, small batches, up to 63 rows: every draw gets its own table of the windowed kernel (pioran_celerite_logl_batch_dev_cd)
+bool perdraw_tables_wanted(const ScanOptions& o, int64_t B, int32_t R, int32_t J)
+{
+    const bool automatic = !o.scan_config[0] && !o.no_block && B <= 768 && R >= 6;
+    const bool force = !std::strcmp(o.scan_config, "block");
+    return (automatic || force) && !o.force_fallback && pioran_block_fits(R, J);
+}
+
+// value and gradient: the reverse mode with one draw per wavefront (celerite_tile.hip) above the windowed kernel's batch range
+bool tile_grad_wanted(const ScanOptions& o, int64_t B, int32_t R)
+{
+    return o.force_tile || (!o.no_tile && B > 512 && R >= 17);
+}

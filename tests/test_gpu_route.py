@@ -1,0 +1,48 @@
+"""GPU tests (-m gpu): capi.hip's launch() takes the family the routing rules name (csrc/route.hip, pioran_value_route) at every point of
+tools/route_grid.py — the smallest shapes that cross every batch rule (N = 256) and every time-parallel threshold (N up to 4416) — and
+the launch gives finite values with status 0.  That the plans are the ones the code made before the rules were separated is not a test
+here: docs/EXPERIMENTS.md section 22 has the listing against the parent's library."""
+import importlib.util
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+import pioran_jl_amd as pj  # noqa: E402
+
+ROOT = Path(__file__).resolve().parents[1]
+_spec = importlib.util.spec_from_file_location("route_grid", ROOT / "tools" / "route_grid.py")
+G = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(G)
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    return pj.Context(0)
+
+
+def check(ctx, pts):
+    seen = set()
+    for pt in pts:
+        want, plan = G.value_route(G.rows_of(pt), pt.J, pt.n_one, pt.B, pt.N, options=pt.options)
+        got, out, st = G.run_point(ctx, pt)
+        assert got == want, (pt, got, want, plan)
+        assert np.isfinite(out).all() and (st == 0).all(), (pt, got)
+        seen.add(got)
+    return seen
+
+
+def test_batch_rules(ctx):
+    seen = check(ctx, G.batch_points())
+    assert seen == {"tile", "block", "wide", "scan", "fallback"}
+
+
+def test_time_parallel_thresholds(ctx):
+    pts = G.tp_points()
+    seen = check(ctx, pts)
+    assert "tp" in seen and len(seen) > 1
+    for pt in pts:     # the table's side of the threshold is the rule's (tests/test_route.py) — and so the launch's
+        thr = G.TP_THRESHOLD[G.rows_of(pt)][G.TP_B.index(pt.B)]
+        assert (G.value_route(G.rows_of(pt), pt.J, pt.n_one, pt.B, pt.N)[0] == "tp") == (pt.N >= thr)
