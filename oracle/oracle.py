@@ -313,6 +313,38 @@ def predict_cov_numpy(a, b, c, d, tau, t, sigma2):
     return Kt - w.T @ w
 
 
+def predict_var_truth(a, b, c, d, tau, t, s2, dtype=np.longdouble):
+    """Truth for the posterior variance at the times tau: k(0) - k*' K^-1 k* evaluated densely in `dtype` (long double: LAPACK has none, so
+    the Cholesky is written out — a loop over the rows of K with vectorised inner products — and every evaluation time gets a triangular
+    solve of its own).  Shares no code with tools/predict_var_proto.py or the celerite recurrences.  Raises LinAlgError when K is not
+    positive definite in this arithmetic.  Returns (M,) in `dtype`.  tests/golden/predict_var_truth.npz (oracle/make_predict_var_truth.py)
+    holds this function's deviation from a 50-digit evaluation."""
+    if dtype is np.longdouble:
+        assert np.finfo(np.longdouble).eps < 1e-18, "long double is not the 80-bit format here"
+    a, b, c, d, tau, t, s2 = (np.asarray(v, dtype=np.float64).astype(dtype).reshape(-1) for v in (a, b, c, d, tau, t, s2))
+    def kern(dt):
+        dt = np.abs(dt)[..., None]
+        return (np.exp(-c * dt) * (a * np.cos(d * dt) + b * np.sin(d * dt))).sum(-1)
+    N = len(t)
+    K = kern(t[:, None] - t[None, :])
+    K[np.arange(N), np.arange(N)] = a.sum() + s2
+    L = np.zeros((N, N), dtype=dtype)
+    for n in range(N):
+        row = L[n, :n]
+        if n:
+            for j in range(n):          # forward substitution of row n against the rows above it
+                row[j] = (K[n, j] - row[:j] @ L[j, :j]) / L[j, j]
+        piv = K[n, n] - row @ row
+        if not piv > 0:
+            raise np.linalg.LinAlgError(f"not positive definite at row {n}")
+        L[n, n] = np.sqrt(piv)
+    Ks = kern(tau[:, None] - t[None, :])
+    w = np.zeros((len(tau), N), dtype=dtype)        # row m: L^-1 k*(tau_m), the evaluation times side by side
+    for n in range(N):
+        w[:, n] = (Ks[:, n] - w[:, :n] @ L[n, :n]) / L[n, n]
+    return a.sum() - (w * w).sum(axis=1)
+
+
 def dense_nll_numpy(a, b, c, d, t, y, sigma2):
     """src/direct_solver.jl:6-21 with numpy's LAPACK Cholesky (second implementation)."""
     a = np.asarray(a, float); b = np.asarray(b, float)

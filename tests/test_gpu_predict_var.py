@@ -6,9 +6,16 @@ The result is var = k(0) - q1 - q2, a difference of numbers of the size of k(0) 
               N = 400 (room for N five times longer and another summation order), a hundred times tighter than the project's 1e-8 bar.
   N = 1e4     against the prototype on the same inputs: 10 x the prototype's own deviation from the dense oracle at N = 4000 (computed here),
               never looser than 1e-8 k(0).
-Every figure is printed before it is asserted."""
+Every figure is printed before it is asserted.
+
+Below those (tests 7 - 10): the kernels against a truth that is neither them nor their prototype — oracle.predict_var_truth, dense in long
+double, and the 50-digit values of tests/golden/predict_var_truth.npz — at the shapes where predict_var_fwd_kernel<H> / predict_var_bwd_kernel<H>
+take another path and on ill-conditioned draws, with the bound max(20 x the prototype's deviation on the same draw, 256 eps) k(0) of
+tests/predict_var_cases.py (cases, checker and the reasoning behind the bound live there; the CPU suite shows that the cases catch seeded
+mistakes)."""
 import importlib.util
 import json
+import sys
 from pathlib import Path
 
 import numpy as np
@@ -21,6 +28,8 @@ from oracle import oracle as O  # noqa: E402
 
 ROOT = Path(__file__).resolve().parents[1]
 BOUND = 1e-10
+sys.path.insert(0, str(Path(__file__).resolve().parent))
+import predict_var_cases as PV  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -237,3 +246,101 @@ def test_limits_and_status(ctx):
     with pytest.raises(ValueError):
         ds.predict_var(A, Bc, C, Dd, np.array([0.0, np.nan]))
     ds.close()
+
+
+# ---- 7 --------------------------------------------------------------------------------------------------------------------------------
+def gpu_impl(ctx):
+    """Dataset.predict_var as an `impl` of predict_var_cases.check; (c, d) per draw goes draw by draw inside the entry"""
+    def impl(A, Bc, C, Dd, t, s2, nu, tau):
+        ds = pj.Dataset(t, np.zeros(len(t)), s2, ctx)
+        try:
+            v, st = ds.predict_var(A, Bc, C, Dd, tau, nu=nu, return_status=True)
+        finally:
+            ds.close()
+        assert pj._lib.lib().pioran_celerite_config_name(-1) == b"wide (step-by-step variance)"
+        return v, st
+    return impl
+
+
+@pytest.mark.parametrize("case", list(PV.edge_cases()), ids=lambda c: c[0])
+def test_edge_shapes_against_truth(ctx, case):
+    """Rows on both sides of every H = 16, 32, 48, 64, series around the VD = 4 prefetch depth, evaluation times all before / all after / on the
+    data / alone / forty in one gap; each with sigma2 as drawn and x 1e-6.  Three draws with their own nu, against the long-double truth."""
+    PV.check(gpu_impl(ctx), case)
+
+
+# ---- 8 --------------------------------------------------------------------------------------------------------------------------------
+def test_fuzz_slice_against_truth(ctx):
+    """40 seeded random shapes (R 1..64, N 1..120 with long gaps, M 1..60, 1..4 draws, sigma2 x 10^U(-7, 0)); shared (c, d): one launch,
+    (c, d) per draw: the entry's draw-by-draw route."""
+    worst, n = 0.0, 0
+    for case in PV.fuzz_cases(40):
+        worst = max(worst, PV.check(gpu_impl(ctx), case).max())
+        n += 1
+    print(f"fuzz: {n} cases, worst deviation {worst:.2e} k(0)")
+    assert n == 40
+
+
+# ---- 9 --------------------------------------------------------------------------------------------------------------------------------
+def test_ill_conditioned_draws_against_truth(ctx, proto, golden_dir):
+    """The nine draws of tests/golden/predict_var_truth.npz (SHO-20; ratio = nu min sigma2 / k(0) from 5.7e-11): N = 150 against the 50-digit
+    truth, N = 1000 against the long-double one.  Bound per draw: 20 x the prototype's deviation from the same truth, computed here, with the
+    floor of predict_var_cases.  Sorted and permuted evaluation times give the permuted result bit for bit."""
+    Q = np.load(golden_dir / "quad_truth.npz")
+    draws = PV.fixture_draws(golden_dir)
+    assert len(draws) == 9
+    F = np.load(golden_dir / "predict_var_truth.npz")
+    rng = np.random.default_rng(91)
+    for tag in ("n150", "n1000"):
+        idx, tau, t, yerr = F[f"{tag}_idx"], F[f"{tag}_tau"], Q[f"{tag}_t"], Q[f"{tag}_yerr"]
+        A, Bc, C, Dd, nu = Q[f"{tag}_A"][idx], Q[f"{tag}_Bc"][idx], Q[f"{tag}_C"], Q[f"{tag}_Dd"], Q[f"{tag}_nu"][idx]
+        ds = pj.Dataset(t, np.zeros(len(t)), yerr ** 2, ctx)
+        got, st = ds.predict_var(A, Bc, C, Dd, tau, nu=nu, return_status=True)
+        o = np.argsort(tau, kind="stable")
+        perm = rng.permutation(len(tau))
+        got_sorted = ds.predict_var(A, Bc, C, Dd, tau[o], nu=nu)
+        got_perm = ds.predict_var(A, Bc, C, Dd, tau[perm], nu=nu)
+        ds.close()
+        assert (st == 0).all(), st
+        fails = []
+        for k, (label, a, b, c, d, t_, s2, tau_, truth, ratio) in enumerate(x for x in draws if x[0].startswith(tag + " ")):
+            k0 = a.sum()
+            assert np.array_equal(a, A[k]) and np.array_equal(tau_, tau)
+            pdev = float(np.max(np.abs(proto.predict_var(a, b, c, d, t_, s2, tau_) - truth))) / k0
+            dev = float(np.max(np.abs(got[k] - truth))) / k0
+            bound = max(PV.MARGIN * pdev, PV.FLOOR)
+            print(f"{label}: ratio {ratio:.1e}   deviation {dev:.2e} k(0)   prototype {pdev:.2e}   bound {bound:.2e}   min var / k(0) {float(truth.min()) / k0:.2e}")
+            if not dev <= bound:
+                fails.append((label, dev, bound))
+        assert not fails, fails
+        assert np.array_equal(got[:, o], got_sorted)
+        assert np.array_equal(got[:, perm], got_perm)
+
+
+# ---- 10 -------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("rows", [(16, 32, 48, 64), (1, 17, 33, 49)], ids=["H_full", "H_one_live_lane_more"])
+def test_every_instantiation_runs(ctx, rows):
+    """Each of the four instantiations with every lane of H live and with one row (R = 1) or one row past the smaller H, on 70 draws: more
+    workgroups than one per SIMD of a CU, a multiple of nothing.  A draw that is not positive definite, first, in the middle and last:
+    status 2 and NaN for it, every other row bit-identical to the call without it; three of the good rows against the long-double truth."""
+    B, N = 70, 37
+    for R in rows:
+        rng = np.random.default_rng([20261020, R])
+        nreal = R % 2
+        t, s2, A, Bc, C, Dd, nu = PV._draws(rng, N, (R + nreal) // 2, B, np.arange(nreal))
+        tau = PV.make_tau("mixed", t, rng)
+        ds = pj.Dataset(t, np.zeros(N), s2, ctx)
+        good, st = ds.predict_var(A, Bc, C, Dd, tau, nu=nu, return_status=True)
+        assert pj._lib.lib().pioran_celerite_config_name(-1) == b"wide (step-by-step variance)"
+        assert (st == 0).all(), (R, st)
+        for bad in (0, B // 2, B - 1):
+            Ab = A.copy(); Ab[bad] = -A[bad]
+            v, st = ds.predict_var(Ab, Bc, C, Dd, tau, nu=nu, return_status=True)
+            want = np.zeros(B, dtype=st.dtype); want[bad] = 2
+            assert np.array_equal(st, want), (R, bad, st)
+            assert np.isnan(v[bad]).all(), (R, bad)
+            others = np.arange(B) != bad
+            assert np.array_equal(v[others], good[others]), (R, bad)
+        ds.close()
+        keep = [0, B // 2, B - 1]
+        PV.check(lambda *a: (good[keep], np.zeros(3, dtype=np.int32)), (f"R{R}-N{N}-B{B}-draws{keep}", t, s2, A[keep], Bc[keep], C, Dd, nu[keep], tau))

@@ -9,6 +9,7 @@ import ctypes
 import importlib.util
 import json
 import re
+import sys
 from pathlib import Path
 
 import numpy as np
@@ -19,6 +20,8 @@ from oracle import oracle as O
 
 ROOT = Path(__file__).resolve().parents[1]
 BOUND = 1e-11
+sys.path.insert(0, str(Path(__file__).resolve().parent))
+import predict_var_cases as PV  # noqa: E402
 
 
 def _proto():
@@ -114,3 +117,76 @@ def test_argument_validation_without_gpu():
     assert L.pioran_celerite_predict_var(fake, 1, 1, p, p, p, p, 1, None, 1, ctypes.cast(nan, ctypes.c_void_p), p, None) == -1
     with pytest.raises(ValueError):
         pj.std(None, None, solver="dense")
+
+
+# ---- the truth, the prototype against it, and the cases the kernels are held to -----------------------------------------------------
+def test_long_double_truth_against_50_digits(golden_dir):
+    """oracle.predict_var_truth in long double on the six N = 150 fixture draws against the stored mpmath values: within 4 x the deviation
+    recorded when the fixture was made (another libm), and that deviation at most 1/100 of the prototype's on the same draw, which is what
+    lets long double stand in as the truth everywhere else."""
+    F = np.load(golden_dir / "predict_var_truth.npz")
+    P = _proto()
+    draws = [d for d in PV.fixture_draws(golden_dir) if d[0].startswith("n150")]
+    assert len(draws) == 6 == len(F["ld_dev"])
+    for (label, a, b, c, d, t, s2, tau, truth, ratio), stored in zip(draws, F["ld_dev"]):
+        k0 = a.sum()
+        ld = float(np.max(np.abs(O.predict_var_truth(a, b, c, d, tau, t, s2) - truth))) / k0
+        pdev = float(np.max(np.abs(P.predict_var(a, b, c, d, t, s2, tau) - truth))) / k0
+        print(f"{label}: ratio {ratio:.1e}   long double {ld:.2e} k(0) (stored {stored:.2e})   prototype {pdev:.2e} k(0)")
+        assert ld <= 4 * stored, (label, ld, stored)
+        assert stored <= pdev / 100, (label, stored, pdev)
+
+
+def test_prototype_on_the_fixture(golden_dir):
+    """The prototype and the fp64 dense oracle on the nine ill-conditioned fixture draws (N = 150, N = 1000); the figures are printed (the
+    table of docs/EXPERIMENTS.md).  N = 150: the prototype within 20 x the 3.7e-14 k(0) measured on the worst of these draws.  N = 1000 is a
+    measurement (7e-12 k(0) on the lowest ratio: the recurrences' error grows with N on such a draw, the dense formula's does not); the GPU test
+    takes its bound from the figure computed on the same draw."""
+    P = _proto()
+    for label, a, b, c, d, t, s2, tau, truth, ratio in PV.fixture_draws(golden_dir):
+        k0 = a.sum()
+        pdev = float(np.max(np.abs(P.predict_var(a, b, c, d, t, s2, tau) - truth))) / k0
+        ddev = float(np.max(np.abs(np.diag(O.predict_cov_numpy(a, b, c, d, tau, t, s2)) - truth))) / k0
+        print(f"{label}: ratio {ratio:.1e}   prototype {pdev:.2e} k(0)   fp64 dense oracle {ddev:.2e} k(0)   min var / k(0) {float(truth.min()) / k0:.2e}")
+        assert np.isfinite(pdev) and (len(t) > 150 or pdev <= 20 * 3.7e-14), (label, pdev)
+
+
+@pytest.mark.parametrize("which", ["edge", "fuzz"])
+def test_prototype_on_the_cases(which):
+    """check(prototype) on every edge and fuzz case: every draw positive definite in the truth's own Cholesky (reference() raises otherwise),
+    the prototype within the floor of the bound where 20 x its own deviation is below it."""
+    cases = list(PV.edge_cases()) if which == "edge" else list(PV.fuzz_cases(40))
+    assert len(cases) == (2 * len(PV.edge_combinations()) if which == "edge" else 40)
+    worst = 0.0
+    for case in cases:
+        worst = max(worst, PV.check(PV.proto_impl(), case).max())
+    print(f"{which}: {len(cases)} cases, worst prototype deviation {worst:.2e} k(0)")
+
+
+def test_case_list_covers_what_it_promises():
+    combos = PV.edge_combinations()
+    assert len(set(combos)) == len(combos)
+    for R in PV.ROWS:
+        assert {(R, 3, "mixed"), (R, 9, "mixed")} <= set(combos)
+    for N in PV.LENGTHS:
+        assert {(3, N, "mixed"), (33, N, "mixed")} <= set(combos)
+    for pat in PV.PATTERNS:
+        assert {(17, 5, pat), (64, 33, pat)} <= set(combos)
+    for label, t, s2, A, Bc, C, Dd, nu, tau in PV.edge_cases():
+        R, N = int(label.split("-")[0][1:]), int(label.split("-")[1][1:])
+        assert len(t) == N and A.shape[0] == 3 and 2 * A.shape[1] - int(np.sum(Dd == 0.0)) == R, label
+    seen = {(c[0].split("-")[-2], c[0].split("-")[-1]) for c in PV.fuzz_cases(40)}
+    assert {k for _, k in seen} == {"shared", "perdraw"}
+
+
+@pytest.mark.parametrize("mistake", ["mask_last_row", "reuse_alpha", "phi_of_step", "n0_le_forward"])
+def test_the_cases_can_fail(mistake):
+    """Each seeded mistake of the prototype (tools/predict_var_proto.py, MISTAKES) fails check() on at least one edge case."""
+    caught = []
+    for case in PV.edge_cases():
+        try:
+            PV.check(PV.proto_impl(mistake=mistake), case)
+        except AssertionError:
+            caught.append(case[0])
+    print(f"{mistake}: caught by {len(caught)} edge cases, e.g. {caught[:4]}")
+    assert caught, mistake

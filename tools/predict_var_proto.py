@@ -12,6 +12,9 @@ alpha = e^{-c (tau - t_{n0-1})} U~(tau), beta = e^{-c (t_{n0} - tau)} V(tau):
     g = S+_{n0-1} alpha,  q1 = alpha'g;   e = beta - phi_{n0} o g,  q2 = e' B_{n0} e;   var = k(0) - q1 - q2.
 
 Importable: predict_var(a, b, c, d, t, sigma2, tau) -> (M,) (tests/test_predict_var_host.py holds it against the dense oracle).
+
+`mistake` seeds one of the slips a kernel of these recurrences can make (MISTAKES); tests/test_predict_var_host.py uses them to show that the
+case list of tests/predict_var_cases.py catches each of them.
 """
 from __future__ import annotations
 
@@ -34,7 +37,16 @@ def _uv(al, be, dr, ks, x):
     return al * v + be * np.where(ks, co, si), v
 
 
-def predict_var(a, b, c, d, t, sigma2, tau):
+MISTAKES = {
+    "mask_last_row": "row R - 1 left out of the two quadratic forms (a lane mask off by one)",
+    "reuse_alpha": "the second and later evaluation times of a step use the first one's alpha",
+    "phi_of_step": "e = beta - phi_{n0-1} o g: the phi of the step itself, not of the gap the evaluation time lies in",
+    "n0_le_forward": "the forward pass counts t_n <= tau, the backward pass t_n < tau",
+}
+
+
+def predict_var(a, b, c, d, t, sigma2, tau, mistake=None):
+    assert mistake is None or mistake in MISTAKES, mistake
     a, b, c, d, t, sigma2, tau = (np.asarray(v, dtype=np.float64).reshape(-1) for v in (a, b, c, d, t, sigma2, tau))
     N, M = len(t), len(tau)
     al, be, cr, dr, ks = _rows(a, b, c, d)
@@ -43,6 +55,10 @@ def predict_var(a, b, c, d, t, sigma2, tau):
     order = np.argsort(tau, kind="stable")
     ts = tau[order]
     n0 = np.searchsorted(t, ts, side="left")          # number of t_n < tau
+    n0f = np.searchsorted(t, ts, side="right") if mistake == "n0_le_forward" else n0
+    keep = np.ones(R)
+    if mistake == "mask_last_row":
+        keep[R - 1] = 0.0
     U = np.empty((N, R)); V = np.empty((N, R)); phi = np.zeros((N + 1, R))
     for n in range(N):
         U[n], V[n] = _uv(al, be, dr, ks, t[n])
@@ -53,9 +69,9 @@ def predict_var(a, b, c, d, t, sigma2, tau):
     q1 = np.zeros(M); E = np.zeros((M, R))
     Sp = np.zeros((R, R))                              # S+_{n-1}
     mp = 0
-    while mp < M and n0[mp] == 0:                      # before the first data point: g = 0, e = beta
+    while mp < M and n0f[mp] == 0:                     # before the first data point: g = 0, e = beta
         _, vt = _uv(al, be, dr, ks, ts[mp])
-        E[mp] = np.exp(-cr * (t[0] - ts[mp])) * vt
+        E[mp] = keep * np.exp(-cr * (t[0] - ts[mp])) * vt
         mp += 1
     for n in range(N):
         S = np.outer(phi[n], phi[n]) * Sp
@@ -63,13 +79,17 @@ def predict_var(a, b, c, d, t, sigma2, tau):
         D[n] = k0 + sigma2[n] - U[n] @ Su
         W[n] = (V[n] - Su) / D[n]
         Sp = S + D[n] * np.outer(W[n], W[n])
-        while mp < M and n0[mp] == n + 1:
+        first = None
+        while mp < M and n0f[mp] == n + 1:
             ut, vt = _uv(al, be, dr, ks, ts[mp])
-            alpha = np.exp(-cr * (ts[mp] - t[n])) * ut
+            alpha = keep * np.exp(-cr * (ts[mp] - t[n])) * ut
+            if mistake == "reuse_alpha":
+                first = alpha if first is None else first
+                alpha = first
             g = Sp @ alpha
             q1[mp] = alpha @ g
             if n + 1 < N:
-                E[mp] = np.exp(-cr * (t[n + 1] - ts[mp])) * vt - phi[n + 1] * g
+                E[mp] = keep * (np.exp(-cr * (t[n + 1] - ts[mp])) * vt - phi[n if mistake == "phi_of_step" else n + 1] * g)
             mp += 1
     # backward pass
     out = np.empty(M)
