@@ -313,36 +313,89 @@ def predict_cov_numpy(a, b, c, d, tau, t, sigma2):
     return Kt - w.T @ w
 
 
-def predict_var_truth(a, b, c, d, tau, t, s2, dtype=np.longdouble):
-    """Truth for the posterior variance at the times tau: k(0) - k*' K^-1 k* evaluated densely in `dtype` (long double: LAPACK has none, so
-    the Cholesky is written out — a loop over the rows of K with vectorised inner products — and every evaluation time gets a triangular
-    solve of its own).  Shares no code with tools/predict_var_proto.py or the celerite recurrences.  Raises LinAlgError when K is not
-    positive definite in this arithmetic.  Returns (M,) in `dtype`.  tests/golden/predict_var_truth.npz (oracle/make_predict_var_truth.py)
-    holds this function's deviation from a 50-digit evaluation."""
+def _truth_inputs(dtype, *arrays):
     if dtype is np.longdouble:
         assert np.finfo(np.longdouble).eps < 1e-18, "long double is not the 80-bit format here"
-    a, b, c, d, tau, t, s2 = (np.asarray(v, dtype=np.float64).astype(dtype).reshape(-1) for v in (a, b, c, d, tau, t, s2))
+    return tuple(np.asarray(v, dtype=np.float64).astype(dtype).reshape(-1) for v in arrays)
+
+
+def _truth_kernel(a, b, c, d):
     def kern(dt):
         dt = np.abs(dt)[..., None]
         return (np.exp(-c * dt) * (a * np.cos(d * dt) + b * np.sin(d * dt))).sum(-1)
+    return kern
+
+
+_truth_factors = {}       # the last factors by their inputs' bytes: the cases of one shape differ in tau alone and share theirs
+
+
+def _truth_cholesky(a, b, c, d, t, s2, dtype):
+    """The lower Cholesky factor (positive diagonal) of K = k(|t_i - t_j|) + diag(s2) in `dtype`, written out (LAPACK has no long double): column
+    j is the pivot, then every row below it at once, each entry the same left-to-right inner product over the columns before j that a
+    row-by-row forward substitution forms.  Only the lower triangle of K is evaluated.  Raises LinAlgError when K is not positive definite
+    in this arithmetic.  The result is read-only."""
+    key = (np.dtype(dtype).str,) + tuple(v.astype(np.float64).tobytes() for v in (a, b, c, d, t, s2))   # (the inputs are fp64 values)
+    if key in _truth_factors:
+        return _truth_factors[key]
     N = len(t)
-    K = kern(t[:, None] - t[None, :])
+    i, j = np.tril_indices(N, -1)
+    K = np.zeros((N, N), dtype=dtype)
+    K[i, j] = _truth_kernel(a, b, c, d)(t[i] - t[j])
     K[np.arange(N), np.arange(N)] = a.sum() + s2
     L = np.zeros((N, N), dtype=dtype)
-    for n in range(N):
-        row = L[n, :n]
-        if n:
-            for j in range(n):          # forward substitution of row n against the rows above it
-                row[j] = (K[n, j] - row[:j] @ L[j, :j]) / L[j, j]
-        piv = K[n, n] - row @ row
+    for j in range(N):
+        piv = K[j, j] - L[j, :j] @ L[j, :j]
         if not piv > 0:
-            raise np.linalg.LinAlgError(f"not positive definite at row {n}")
-        L[n, n] = np.sqrt(piv)
+            raise np.linalg.LinAlgError(f"not positive definite at row {j}")
+        L[j, j] = np.sqrt(piv)
+        if j + 1 < N:
+            L[j + 1:, j] = (K[j + 1:, j] - L[j + 1:, :j] @ L[j, :j]) / L[j, j]
+    L.setflags(write=False)
+    while len(_truth_factors) >= 24:
+        _truth_factors.pop(next(iter(_truth_factors)))
+    _truth_factors[key] = L
+    return L
+
+
+def predict_var_truth(a, b, c, d, tau, t, s2, dtype=np.longdouble):
+    """Truth for the posterior variance at the times tau: k(0) - k*' K^-1 k* evaluated densely in `dtype` (long double: the Cholesky is
+    _truth_cholesky above, and every evaluation time gets a triangular solve of its own).  Shares no code with tools/predict_var_proto.py or
+    the celerite recurrences.  Raises LinAlgError when K is not positive definite in this arithmetic.  Returns (M,) in `dtype`.
+    tests/golden/predict_var_truth.npz (oracle/make_predict_var_truth.py) holds this function's deviation from a 50-digit evaluation."""
+    a, b, c, d, tau, t, s2 = _truth_inputs(dtype, a, b, c, d, tau, t, s2)
+    kern = _truth_kernel(a, b, c, d)
+    N = len(t)
+    L = _truth_cholesky(a, b, c, d, t, s2, dtype)
     Ks = kern(tau[:, None] - t[None, :])
     w = np.zeros((len(tau), N), dtype=dtype)        # row m: L^-1 k*(tau_m), the evaluation times side by side
     for n in range(N):
         w[:, n] = (Ks[:, n] - w[:, :n] @ L[n, :n]) / L[n, n]
     return a.sum() - (w * w).sum(axis=1)
+
+
+def predict_mean_truth(a, b, c, d, tau, t, y, s2, dtype=np.longdouble):
+    """Truth for the posterior mean of the zero-mean GP at the times tau: K* K^-1 y evaluated densely in `dtype`, K = L L' by _truth_cholesky,
+    two triangular solves for K^-1 y, then the dense product with k(|tau_m - t_n|).  Shares no code with the celerite recurrences or
+    tools/predict_mean_proto.py.  Raises LinAlgError when K is not positive definite.  Returns (M,) in `dtype`."""
+    a, b, c, d, tau, t, y, s2 = _truth_inputs(dtype, a, b, c, d, tau, t, y, s2)
+    kern = _truth_kernel(a, b, c, d)
+    N = len(t)
+    L = _truth_cholesky(a, b, c, d, t, s2, dtype)
+    z = np.zeros(N, dtype=dtype)
+    for n in range(N):                              # L w = y
+        z[n] = (y[n] - L[n, :n] @ z[:n]) / L[n, n]
+    for n in range(N - 1, -1, -1):                  # L' z = w
+        z[n] = (z[n] - L[n + 1:, n] @ z[n + 1:]) / L[n, n]
+    return kern(tau[:, None] - t[None, :]) @ z
+
+
+def sim_truth(a, b, c, d, t, s2, q, dtype=np.longdouble):
+    """Truth for a realisation from the normals q: C q with C the Cholesky factor (positive diagonal) of K = k(|t_i - t_j|) + diag(s2), dense
+    in `dtype` (_truth_cholesky).  C = L D^1/2 of the celerite factorisation K = L D L', so this is what `sim` (src/celerite_solver.jl:515-549)
+    returns.  s2 may be zero.  Raises LinAlgError when K is not positive definite.  Returns (N,) in `dtype`."""
+    a, b, c, d, t, s2, q = _truth_inputs(dtype, a, b, c, d, t, s2, q)
+    L = _truth_cholesky(a, b, c, d, t, s2, dtype)
+    return L @ q
 
 
 def dense_nll_numpy(a, b, c, d, t, y, sigma2):

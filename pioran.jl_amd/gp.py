@@ -100,7 +100,11 @@ class Context:
 
     def simulate(self, A, Bc, C, Dd, t, sigma2, q):
         """GP realisations from standard-normal draws q (B, N): sim of src/celerite_solver.jl:515-549 for B coefficient
-        sets (A, Bc: (B, J)) sharing (C, Dd: (J,)).  Returns (B, N)."""
+        sets (A, Bc: (B, J)) sharing (C, Dd: (J,)) or with (C, Dd: (B, J)) of their own.  sigma2 may be zero (pj.rand at new times).
+        Error, measured against a long-double dense truth C q, C the Cholesky factor of K (docs/EXPERIMENTS.md section 24), in units of
+        max |y|: <= 8.0e-15 at every edge shape (R 1..143, N 1..257, sigma2 as given, x 1e-6 and 0) on the windowed and the step-by-step
+        kernels alike, 1.4e-13 on the worst of 40 random shapes (N = 256, sigma2 / k(0) down to 1.5e-8) where the fp64 references deviate by the same
+        1.4e-13.  Returns (B, N)."""
         A, Bc, C, Dd, t, sigma2, q = map(_f64, (A, Bc, C, Dd, t, sigma2, q))
         if A.ndim != 2 or A.shape != Bc.shape or C.shape not in ((A.shape[1],), A.shape) or Dd.shape != C.shape:
             raise ValueError("A, Bc must be (B, J) and C, Dd (J,) or (B, J)")
@@ -282,8 +286,11 @@ class Dataset:
         return (out, st) if return_status else out
 
     def predict(self, A, Bc, C, Dd, tau, mu=None, nu=None, return_status=False):
-        """Posterior mean at the times tau (M,) for B coefficient sets sharing (C, Dd): pred of
-        src/celerite_solver.jl:363-483 (+ the constant mean mu_b).  Returns (B, M)."""
+        """Posterior mean at the times tau (M,), any order, for B coefficient sets sharing (C, Dd: (J,)) or with (C, Dd: (B, J)) of their own:
+        pred of src/celerite_solver.jl:363-483 (+ the constant mean mu_b).  Error, measured against a long-double dense truth K* K^-1 (y - mu)
+        (docs/EXPERIMENTS.md section 24), in units of max |y - mu|: <= 6.2e-15 at every edge shape (R 1..143, N 1..257, M 1..257, sigma2 as
+        given and x 1e-6) on the fused, the two-pass, the per-draw-table and the step-by-step route alike, 1.4e-14 on the worst of 40 random
+        shapes; the fp64 references deviate by 1.2e-14 resp. 4.9e-14 on the same draws.  Returns (B, M)."""
         A, Bc, C, Dd, tau = map(_f64, (A, Bc, C, Dd, tau))
         if A.ndim != 2 or A.shape != Bc.shape or C.shape not in ((A.shape[1],), A.shape) or Dd.shape != C.shape or tau.ndim != 1:
             raise ValueError("A, Bc must be (B, J), C, Dd (J,) or (B, J) and tau (M,)")
