@@ -106,12 +106,11 @@ int pioran_ctx_trim(pioran_ctx* ctx);
  *                     same way; "tp_unchecked" = "1" (with "scan_config" = "tp"): the family's own arithmetic, no check, no repair (tests, tools); "tp_walk_repair" = "1": by the family's own
  *                     boundary walk instead; "tp_scan_lean" = "1", "tp_scan_waves" = "4": the forms of the combination kernel that are the default only at
  *                     49 .. 64 rows / up to 16 rows (tests, tools)
- *   "dense_old_chain" 0 one launch per block column (default), 1 the panel / update chain of rounds 1-3 (2 .. 8: timing experiments, only in
- *                     builds with -DPIORAN_EXPERIMENTS; PIORAN_ERR_ARG otherwise);
+ *   "dense_old_chain" 0 one launch per block column (default), 1 the panel / update chain of rounds 1-3 (any other value: PIORAN_ERR_ARG);
  *                     "dense_no_pairs", "dense_no_halves", "dense_pair_tiles", "dense_half_tile_limit", "dense_quad_threshold", "dense_batch_pair_threshold", "dense_streams": schedule knobs
- *   "block_emode", "gsum", "exp"   tuning / experiment selectors of single kernels (tools/ only; "exp" can make results meaningless)
+ *   "block_emode", "exp"   tuning / experiment selectors of single kernels (tools/ only; "exp" can make results meaningless)
  * Initial values come from the environment variables PIORAN_SCAN_CONFIG, PIORAN_NO_WIDE, PIORAN_NO_BLOCK, PIORAN_NO_TILE, PIORAN_NO_TP, PIORAN_NO_PAIRED,
- * PIORAN_NO_MIXED, PIORAN_FORCE_FALLBACK, PIORAN_WIN2, PIORAN_NO_WIN2, PIORAN_GSUM, PIORAN_WIDE2, read once when the context is created. */
+ * PIORAN_NO_MIXED, PIORAN_FORCE_FALLBACK, PIORAN_WIN2, PIORAN_NO_WIN2, PIORAN_WIDE2, PIORAN_NO_WIDE2, read once when the context is created. */
 int pioran_ctx_set_option(pioran_ctx* ctx, const char* key, const char* value);
 /* hipEvent-based timing on the ctx stream: record slot i (0..11), elapsed between two slots. */
 int pioran_ctx_event_record(pioran_ctx* ctx, int slot);

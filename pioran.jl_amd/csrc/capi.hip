@@ -777,16 +777,13 @@ int set_option(ScanOptions& o, const char* key, const char* value)
     else if (!std::strcmp(key, "dense_batch_pair_threshold")) o.dense.batch_pair_threshold = (value && value[0]) ? std::atoi(value) : -1;
     else if (!std::strcmp(key, "dense_old_chain")) {
         const int v = (value && value[0]) ? std::atoi(value) : 0;
-#ifndef PIORAN_EXPERIMENTS
-        if (v < 0 || v > 1) return PIORAN_ERR_ARG;     // 2 .. 8 (timing experiments, garbage results) exist in experiment builds only
-#endif
+        if (v < 0 || v > 1) return PIORAN_ERR_ARG;
         o.dense.old_chain = v;
     }
     else if (!std::strcmp(key, "dense_no_pairs")) o.dense.no_pairs = on ? 1 : 0;
     else if (!std::strcmp(key, "dense_no_halves")) o.dense.no_halves = on ? 1 : 0;
     else if (!std::strcmp(key, "workspace_limit_mb")) o.workspace_limit_mb = (value && value[0]) ? std::atoll(value) : 0;
     else if (!std::strcmp(key, "dense_streams")) o.dense_streams = (value && value[0]) ? std::atoi(value) : 0;
-    else if (!std::strcmp(key, "gsum")) o.gsum = (value && value[0]) ? std::atoi(value) : -1;
     else if (!std::strcmp(key, "exp")) o.exp = (value && value[0]) ? std::atoi(value) : 0;
     else if (!std::strcmp(key, "ls_tile")) o.ls_tile = (value && value[0]) ? std::atoi(value) : 0;
     else if (!std::strcmp(key, "ls_only")) o.ls_only = (value && value[0]) ? std::atoi(value) : 0;
@@ -891,11 +888,7 @@ static int ctx_create_impl(int device, void* stream, bool own, pioran_ctx** out)
     pioran_ctx_set_option(ctx, "no_tp", std::getenv("PIORAN_NO_TP"));
     pioran_ctx_set_option(ctx, "win2", std::getenv("PIORAN_WIN2"));
     pioran_ctx_set_option(ctx, "no_win2", std::getenv("PIORAN_NO_WIN2"));
-    pioran_ctx_set_option(ctx, "gsum", std::getenv("PIORAN_GSUM"));
     pioran_ctx_set_option(ctx, "wide2", std::getenv("PIORAN_WIDE2"));
-#ifdef PIORAN_EXPERIMENTS
-    pioran_ctx_set_option(ctx, "exp", std::getenv("PIORAN_EXP"));     // experiment builds only: the product library never reads it
-#endif
     pioran_ctx_set_option(ctx, "no_wide2", std::getenv("PIORAN_NO_WIDE2"));
     if (hipSetDevice(device) != hipSuccess) { delete ctx; return PIORAN_ERR_HIP; }
     if (hipDeviceGetAttribute(&ctx->ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || ctx->ncu < 1) { delete ctx; return PIORAN_ERR_HIP; }

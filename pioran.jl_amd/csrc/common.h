@@ -22,8 +22,7 @@ struct DenseOptions {
     int pair_tiles = -1;            // dense_step_kernel: tiles of the trailing matrix above which the bulk goes in pairs of panels (-1: the measured default)
     int half_tile_limit = -1;       // dense_step_kernel: tiles per launch up to which a tile is split over two wavefronts (-1: default)
     int batch_pair_threshold = -1;  // ... in pairs
-    int old_chain = 0;              // 1: one matrix on the panel / update chain of rounds 1-3 (A/B and cross-check of dense_step_kernel);
-                                    // 2 / 3 / 4: timing experiments of dense_step_kernel's roles (tools/dense_roles.py)
+    int old_chain = 0;              // 1: one matrix on the panel / update chain of rounds 1-3 (A/B and cross-check of dense_step_kernel)
     int no_halves = 0;              // 1: dense_step_kernel's bulk never splits a tile over two wavefronts
     int no_pairs = 0;               // 1: dense_step_kernel's bulk one panel per launch from the start (no paired phase)
 };
@@ -47,7 +46,6 @@ struct ScanOptions {
     int dense_streams = 0;   // pioran_dense_nll_batch: factorisations per batched launch (0 = default 32; at most 64)
     DenseOptions dense;
     long long workspace_limit_mb = 0;   // absolute cap on a call's NEW chunked workspace, MiB (0 = default 16384; capi.hip ws_allow)
-    int gsum = -1;        // throughput layouts, two-step form: row sums with fewer exchange rounds (group_sum's GS); -1 = automatic
     int block_emode = -1; // windowed kernel, diagnostics: where the pair table E lives (0 one LDS buffer, 1 two, 2 global memory); -1 automatic
     bool btab_reference;  // windowed kernel: build its table with the entry-per-thread kernel of round 2 (cross-check of the windowed table kernel)
     int exp;              // diagnostics: experiment selector of the kernel under study (0 in the product; tools/ only)
@@ -253,7 +251,7 @@ int pioran_launch_approx(int64_t B, int model, int P, int J, int basis, int inte
 int pioran_launch_fma_stream(int blocks, int iters, double* scratch, double* flop, hipStream_t stream);
 // dense.hip
 // doubles behind a slab: 1024 (the four 16 x 16 inverses of the current diagonal block) + 4 x 4096 (dense_step_kernel's tile snapshots)
-#define PIORAN_DENSE_WS (1024 + 4 * 4096 + 1024)   // inverse copies | tile snapshots | flags of the persistent-chain prototype
+#define PIORAN_DENSE_WS (1024 + 4 * 4096)   // inverse copies | tile snapshots
 void pioran_dense_dims(int64_t N, int64_t* Mp, int64_t* ld);
 int pioran_dense_nll_device(int64_t N, int32_t J, const double* a, const double* b, const double* c,
                             const double* d, const double* t, const double* y, const double* s2,

@@ -1086,7 +1086,7 @@ __device__ __forceinline__ void step_solve_role(double* __restrict__ A, int64_t 
     double* C = A + i0 + 16 * wave + lr + q0 * ld;
     double cv[4][4];
     if constexpr (CRIT) {                               // the diagonal tile: its load overlaps the exchange (issued any earlier it delays
-                                                        // the solve's own operands: 16.5 instead of 15.5 us per step, tools/dense_roles.py)
+                                                        // the solve's own operands: 16.5 instead of 15.5 us per step, profiles/r04_dense_roles.txt)
 #pragma unroll
         for (int jb = 0; jb < 4; ++jb)
 #pragma unroll
@@ -1135,35 +1135,6 @@ __device__ __forceinline__ void step_solve_role(double* __restrict__ A, int64_t 
     }
 }
 
-// ---- prototype (round 4, DenseOptions::old_chain == 5): the chain without kernel boundaries -------------------------------------------
-// One persistent workgroup (dense_crit_chain_kernel, on a second stream) runs the CRIT role of every step; the step launches carry DIAG2,
-// the strips and the bulk only.  Hand-offs through flags in device memory (release: fence + atomic add; acquire: atomic load + fence):
-//   factored[k]  posted by CRIT(k-1) once block k is factored and its inverses are parked — DIAG2 and the strips of launch k wait for it;
-//   ready[k]     posted by STRIP(row k+1) and DIAG2 of launch k-1 (they leave tile (k+1, k) and the diagonal tile (k+1, k+1) one panel
-//                short) — CRIT(k) waits for both.
-// Only the bulk-side consumers wait on the chain's flag; the chain waits for two workgroups that started a whole step earlier.  Every wait
-// is bounded (kFlagSpinLimit polls): on expiry the workgroup reports info = -7 and leaves, so a lost hand-off cannot hang the device.
-constexpr int kFlagSpinLimit = 1 << 19;
-constexpr int FLG_FACTORED = 0, FLG_READY = 128;
-__device__ __forceinline__ bool flag_wait(int* f, int need, int32_t* info, int* sh_ok, int tid, bool fence = true)
-{
-    if (tid == 0) {
-        int it = 0;
-        while (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need && ++it < kFlagSpinLimit) __builtin_amdgcn_s_sleep(1);
-        *sh_ok = it < kFlagSpinLimit;
-        if (it >= kFlagSpinLimit) *info = -7;
-    }
-    __syncthreads();
-    if (fence) __threadfence();                          // acquire (every wavefront: its own view of L1 / L2)
-    return *sh_ok != 0;
-}
-__device__ __forceinline__ void flag_post(int* f, int tid, bool fence = true)
-{
-    if (fence) __threadfence();                          // release: this workgroup's stores are visible device-wide before the flag is
-    __syncthreads();
-    if (tid == 0) __hip_atomic_fetch_add(f, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // What the bulk role of one launch does: panels pcb .. pcb + kp - 1 (block columns; all final) onto the tiles (ti >= tj) of the trailing matrix
 // whose origin is block column org, tiles in COLUMN order (id -> (tj, ti)), ids id0 .. id0 + cnt - 1 (id 0 = tile (0, 0): DIAG2's, never listed).
 constexpr int kStepBulkBuffers = 6;   // operand k-steps in flight in dense_step_kernel's bulk tiles (mostly one wavefront per SIMD there)
@@ -1173,13 +1144,12 @@ struct StepBulk {
 };
 template <int KP>   // depth of the bulk role's update in panels (one instantiation per depth: both tile bodies in one kernel cost 14 spilled registers)
 __global__ void __launch_bounds__(256, 2) dense_step_kernel(double* __restrict__ A, int64_t ld, int64_t Mp, int k,
-                                                            int32_t* __restrict__ info, int bx0, int nprev, StepBulk bulk, int* flg)
+                                                            int32_t* __restrict__ info, int nprev, StepBulk bulk)
 {
     __shared__ double Sh[NB * LP + 4 * 16 * 64];
     double* Ls = Sh;                     // the diagonal tile being factored (CRIT)
     double* Xq = Sh + NB * LP;           // the solved rows of the operand tile: [piece of 16 rows][s * 4 + g][lane]
     __shared__ int flag;
-    __shared__ int sh_ok;
     const int nb = (int)(Mp / NB);
     const int tid = threadIdx.x;
     const int nstrip = nb - k - 1;                      // row tiles k+2 .. nb
@@ -1187,8 +1157,8 @@ __global__ void __launch_bounds__(256, 2) dense_step_kernel(double* __restrict__
     // CU again, i.e. beside workgroup 0 — the chain, whose sweeps then share their SIMDs' DP pipe with a neighbour's matrix instructions
     // (15.5 -> 20.7 us per step in the launches of 257 .. 512 workgroups).  The blank exits at once and the chain keeps its CU to itself
     // unless the launch has more than 512 workgroups (where the bulk bounds the step anyway).
-    if (bx0 == 0 && blockIdx.x == 256) return;
-    const int bx = (int)blockIdx.x - (bx0 == 0 && blockIdx.x > 256 ? 1 : 0) + bx0;   // (bx0 != 0: timing experiments, tools/dense_roles.py)
+    if (blockIdx.x == 256) return;
+    const int bx = (int)blockIdx.x - (blockIdx.x > 256 ? 1 : 0);
     // nprev: finished panels a tile of block column k+1 (k+2 for DIAG2) still lacks when this launch starts (the bulk role lags: 1 in the
     // one-panel schedule, 1 or 2 in the paired one)
     if (bx == 0) {
@@ -1197,13 +1167,9 @@ __global__ void __launch_bounds__(256, 2) dense_step_kernel(double* __restrict__
         __builtin_amdgcn_s_setprio(3);
         step_solve_role<true>(A, ld, Mp, k, k + 1, k + 1, true, 0, Ls, Xq, &flag, info, tid);
     } else if (bx == 1) {
-        if (flg && k >= 1 && !flag_wait(flg + FLG_FACTORED + k, 1, info, &sh_ok, tid)) return;
         if (k + 2 < nb) step_solve_role<false>(A, ld, Mp, k, k + 2, k + 2, false, nprev, Ls, Xq, &flag, info, tid);
-        if (flg) flag_post(flg + FLG_READY + k + 1, tid);
     } else if (bx < 2 + nstrip) {
-        if (flg && k >= 1 && !flag_wait(flg + FLG_FACTORED + k, 1, info, &sh_ok, tid)) return;
         step_solve_role<false>(A, ld, Mp, k, k + bx, k + 1, true, nprev, Ls, Xq, &flag, info, tid);
-        if (flg && bx == 2) flag_post(flg + FLG_READY + k + 1, tid);
     } else {
         // ---- BULK: one tile per wavefront (schedule: dense_nll_impl) -----------------------------------------------------------------------
         // Measured alternatives to this role, none kept (profiles/r04_dense_steps_wg_tiles.txt, r04_dense_roles.txt): one tile per WORKGROUP
@@ -1222,31 +1188,6 @@ __global__ void __launch_bounds__(256, 2) dense_step_kernel(double* __restrict__
         else syrk_tile<KP, kStepBulkBuffers>(A, ld, (int64_t)bulk.pcb * NB, j0, ti, tj, lane & 15, lane >> 4);
     }
 }
-
-#ifdef PIORAN_EXPERIMENTS
-// The persistent chain of the prototype: CRIT(0 .. nb-1) in one workgroup.  Measured slower than the launched chain (1.55 against 1.24 ms,
-// docs/EXPERIMENTS.md section 11.7): compiled only into experiment builds (-DPIORAN_EXPERIMENTS), never into the product library.
-// (launched with kChainPadLds bytes of dynamic LDS it never touches: no workgroup of a step launch then fits beside it, and the chain keeps
-//  its CU's DP pipes to itself — what the blank workgroup 256 achieves for the launched chain)
-constexpr int kChainPadLds = 56 * 1024;
-__global__ void __launch_bounds__(256, 1) dense_crit_chain_kernel(double* __restrict__ A, int64_t ld, int64_t Mp, int32_t* __restrict__ info, int* flg, int mode)
-{
-    __shared__ double Sh[NB * LP + 4 * 16 * 64];
-    double* Ls = Sh;
-    double* Xq = Sh + NB * LP;
-    __shared__ int flag;
-    __shared__ int sh_ok;
-    const int nb = (int)(Mp / NB);
-    const int tid = threadIdx.x;
-    __builtin_amdgcn_s_setprio(3);
-    for (int k = 0; k < nb; ++k) {
-        // mode (timing experiments; results may then be stale): bit 0 no release fence here, bit 1 no acquire fence here
-        if (k >= 1 && !flag_wait(flg + FLG_READY + k, 2, info, &sh_ok, tid, !(mode & 2))) return;
-        step_solve_role<true>(A, ld, Mp, k, k + 1, k + 1, true, 0, Ls, Xq, &flag, info, tid);
-        flag_post(flg + FLG_FACTORED + k + 1, tid, !(mode & 1));
-    }
-}
-#endif
 
 __global__ void __launch_bounds__(256) dense_finish_kernel(const double* __restrict__ A, int64_t ld, int64_t N,
                                                            int64_t Mp, double* __restrict__ out,
@@ -1388,33 +1329,6 @@ static int dense_nll_impl(unsigned nbatch, DenseBatch bt, int64_t N, int32_t J, 
         const int kHalfTileLimit = dop.half_tile_limit >= 0 ? dop.half_tile_limit : 1024;      // tiles per launch up to which every tile is split over two wavefronts
         int ks = 2;
         if (!dop.no_pairs) while (ks + 2 < nb && tiles_of(ks + 2) > kPairTiles) ks += 2;
-        // prototype: the chain as one persistent workgroup on a second stream (see flag_wait above); the step launches start at DIAG2
-#ifndef PIORAN_EXPERIMENTS
-        if (dop.old_chain > 1) return PIORAN_ERR_ARG;     // timing experiments exist in experiment builds only
-        int* const flg = nullptr;
-#else
-        const bool persist = dop.old_chain >= 5 && dop.old_chain <= 8;
-        int* flg = persist ? reinterpret_cast<int*>(ws + WS_DOUBLES + 4 * SNAP_TILE) : nullptr;
-        static thread_local hipStream_t chain_stream = nullptr;     // (experiment builds drive one device from one thread)
-        static thread_local hipEvent_t chain_ev[2] = {nullptr, nullptr};
-        if (persist) {
-            if (!chain_stream) {
-                if (hipStreamCreateWithFlags(&chain_stream, hipStreamNonBlocking) != hipSuccess) return PIORAN_ERR_HIP;
-                for (auto& e : chain_ev)
-                    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return PIORAN_ERR_HIP;
-            }
-            if (hipMemsetAsync(flg, 0, 1024 * sizeof(int), stream) != hipSuccess) return PIORAN_ERR_HIP;
-            (void)hipEventRecord(chain_ev[0], stream);
-            (void)hipStreamWaitEvent(chain_stream, chain_ev[0], 0);
-            static thread_local bool chain_attr = false;
-            if (!chain_attr) {
-                if (hipFuncSetAttribute((const void*)dense_crit_chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kChainPadLds) != hipSuccess) return PIORAN_ERR_HIP;
-                chain_attr = true;
-            }
-            hipLaunchKernelGGL(dense_crit_chain_kernel, dim3(1), dim3(256), kChainPadLds, chain_stream, K, ld, Mp, info, flg, dop.old_chain - 5);
-            (void)hipEventRecord(chain_ev[1], chain_stream);
-        }
-#endif
         for (int k = 0; k < nb; ++k) {
             const int nstrip = nb - k - 1;
             StepBulk bk{0, 1, 0, 0, 0, 0};
@@ -1440,21 +1354,10 @@ static int dense_nll_impl(unsigned nbatch, DenseBatch bt, int64_t N, int32_t J, 
             // half tiles (two wavefronts per tile) once whole tiles would leave SIMDs idle: the launch then lasts as long as its slowest wavefront
             if (!dop.no_halves && bk.cnt > 0 && bk.cnt <= kHalfTileLimit) { bk.halves = 1; bk.cnt *= 2; }
             unsigned grid = (unsigned)(2 + nstrip + (bk.cnt + 3) / 4);
-            int bx0 = 0;
-#ifdef PIORAN_EXPERIMENTS
-            // timing experiments only (results are garbage): 2 = the critical workgroup alone, 3 = DIAG2 + the strips alone, 4 = the bulk alone
-            if (dop.old_chain == 2) grid = 1;
-            else if (dop.old_chain == 3) { grid = (unsigned)(1 + nstrip); bx0 = 1; }
-            else if (dop.old_chain == 4) { if (grid <= (unsigned)(2 + nstrip)) continue; grid -= (unsigned)(2 + nstrip); bx0 = 2 + nstrip; }
-            if (persist) { grid -= 1; bx0 = 1; }
-#endif
-            if (bx0 == 0 && grid > 256) ++grid;                  // the blank workgroup (see the kernel)
-            if (bk.kp == 2) hipLaunchKernelGGL(dense_step_kernel<2>, dim3(grid), dim3(256), 0, stream, K, ld, Mp, k, info, bx0, nprev, bk, flg);
-            else hipLaunchKernelGGL(dense_step_kernel<1>, dim3(grid), dim3(256), 0, stream, K, ld, Mp, k, info, bx0, nprev, bk, flg);
+            if (grid > 256) ++grid;                              // the blank workgroup (see the kernel)
+            if (bk.kp == 2) hipLaunchKernelGGL(dense_step_kernel<2>, dim3(grid), dim3(256), 0, stream, K, ld, Mp, k, info, nprev, bk);
+            else hipLaunchKernelGGL(dense_step_kernel<1>, dim3(grid), dim3(256), 0, stream, K, ld, Mp, k, info, nprev, bk);
         }
-#ifdef PIORAN_EXPERIMENTS
-        if (persist) (void)hipStreamWaitEvent(stream, chain_ev[1], 0);
-#endif
         if (phase_ev) (void)hipEventRecord(phase_ev[1], stream);
         hipLaunchKernelGGL(dense_finish_kernel, dim3(1, 1, 1), dim3(256), 0, stream, K, ld, N, Mp, out, info, bt);
         if (phase_ev) (void)hipEventRecord(phase_ev[2], stream);

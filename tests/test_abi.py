@@ -103,7 +103,7 @@ def test_shipped_library_is_what_build_py_makes(tmp_path):
     fresh = tmp_path / "fresh.o"
     subprocess.run([b.hipcc(), *b.FLAGS, "-c", str(b.CSRC / small), "-o", str(fresh)], check=True)
     assert fresh.stat().st_size == (b.OBJ / "celerite_fallback.o").stat().st_size
-    # no experiment code in the product: the persistent dense chain and the two-wavefront scan shape need -DPIORAN_EXPERIMENTS
+    # no experiment code in the product: neither the persistent dense chain nor the two-wavefront scan shape
     data = b.LIB.read_bytes()
     assert b"dense_crit_chain_kernel" not in data and b"rpl5_cbr4_nsrc2_w2" not in data
 

@@ -432,12 +432,10 @@ def test_fewer_than_six_rows_long_series_and_scalar_call(ctx, J, nreal):
 @pytest.mark.parametrize("J,nreal,N,B", [(40, 0, 61, 300), (40, 0, 90, 5), (33, 0, 130, 290), (36, 0, 47, 301), (39, 0, 1, 280), (39, 0, 2, 280),
                                           (40, 0, 3, 7), (40, 0, 4, 7), (40, 0, 5, 7), (40, 0, 6, 7), (40, 0, 7, 7), (40, 0, 8, 7), (40, 0, 9, 7),
                                           (45, 20, 75, 300), (50, 22, 64, 258), (42, 4, 333, 259), (44, 12, 51, 3)])
-def test_rows_65_to_80_one_draw_over_two_wavefronts(ctx, J, nreal, N, B):
+def test_rows_65_to_80_throughput_shapes(ctx, J, nreal, N, B):
     """65 .. 80 active rows, shared table (SHO-33 .. 40 — the dense configuration's model is SHO-40 —, DRWCelerite-22 .. 26 and other mixes
-    of two-row and one-row terms): the throughput layout that spreads one draw's column blocks over a PAIR of wavefronts (round 4,
-    rpl5_cbr4_nsrc2_w2_y[p], selected by name: two-step form with 50 entries of the state per lane, per-step inputs through an LDS ring,
-    one LDS exchange per pair of steps).  Against the oracle, the one-wavefront 80-row shapes (the default) and the lean latency kernel;
-    series of odd and even length and of every remainder of the ring's three slots, N = 1 and 2, per-draw series."""
+    of two-row and one-row terms): the throughput shapes with five rows per lane (rpl5_cbr4_nsrc4 and its paired / y-as-a-vector forms).
+    Against the oracle and the lean latency kernel; series of odd and even length, N = 1 and 2, per-draw series."""
     rng = np.random.default_rng(8000 + J + N)
     t, y, s2, A, Bc, C, Dd, mu, nu = _random_case(rng, N, J, B)
     if nreal:      # one-row terms (b = d = 0: Exp / DRW): rows = 2 J - nreal
@@ -448,20 +446,15 @@ def test_rows_65_to_80_one_draw_over_two_wavefronts(ctx, J, nreal, N, B):
     ref, rst = O.logl_batch(A, Bc, C, Dd, t, y, s2, mu, nu, nthreads=8, return_status=True)
     try:
         ctx.set_option("no_wide", True); ctx.set_option("no_block", True)   # (batches up to 256 draws would take the windowed / the latency kernel)
-        one = ds.logl_batch(A, Bc, C, Dd, mu=mu, nu=nu)
-        assert pj._lib.lib().pioran_celerite_config_name(-1).decode() == "scan" and "w2" not in pj._lib.lib().pioran_celerite_config_name(0).decode()
-        # the two-wavefront shape is compiled into experiment builds only (-DPIORAN_EXPERIMENTS, round 5): where the library has it, it is
-        # checked; in the product library the one-wavefront shape stands in for the rest of the test
-        ctx.set_option("scan_config", "rpl5_cbr4_nsrc2_w2_yp" if nreal == 0 else "rpl5_cbr4_nsrc2_w2_y")
         got, st = ds.logl_batch(A, Bc, C, Dd, mu=mu, nu=nu, return_status=True)
-        cfg = pj._lib.lib().pioran_celerite_config_name(0).decode()     # (a name the library does not know leaves the choice automatic)
-        assert pj._lib.lib().pioran_celerite_config_name(-1).decode() == "scan" and ("_w2_y" in cfg or cfg.startswith("rpl5_cbr4_nsrc4")), cfg
+        cfg = pj._lib.lib().pioran_celerite_config_name(0).decode()
+        assert pj._lib.lib().pioran_celerite_config_name(-1).decode() == "scan" and cfg.startswith("rpl5_cbr4_nsrc4"), cfg
         Y = rng.standard_normal((B, N)); S2 = rng.uniform(0.01, 0.1, (B, N))
         got2 = ds.logl_batch(A, Bc, C, Dd, mu=mu, nu=nu, Y=Y, S2=S2)
     finally:
-        ctx.set_option("scan_config", None); ctx.set_option("no_wide", False); ctx.set_option("no_block", False)
+        ctx.set_option("no_wide", False); ctx.set_option("no_block", False)
     assert np.array_equal(st, rst)
-    assert relerr(got, ref) < 1e-11 and relerr(one, ref) < 1e-11
+    assert relerr(got, ref) < 1e-11
     ref2 = np.array([O.logl(A[i], Bc[i], C, Dd, t, Y[i] - mu[i], nu[i] * S2[i]) for i in range(min(B, 40))])
     assert relerr(got2[:len(ref2)], ref2) < 1e-11
     try:
@@ -1088,8 +1081,7 @@ def test_dense_one_launch_per_block_column_equals_the_panel_update_chain(ctx, N)
         ctx.set_option("dense_no_pairs", False); ctx.set_option("dense_no_halves", True)
         whole, i3 = ctx.dense_nll(a, b, c, d, t, y, s2, return_info=True)
         ctx.set_option("dense_no_halves", False)
-        # the timing experiments of round 4 (2 .. 4: single roles, garbage results; 5 .. 8: the persistent-chain prototype, measured slower)
-        # are not in the product library (-DPIORAN_EXPERIMENTS builds only): the option refuses them
+        # the option has two values: anything else (the numbers once taken by the timing experiments of round 4 among them) is refused
         for v in (2, 5, 8):
             with pytest.raises(pj._lib.PioranHipError):
                 ctx.set_option("dense_old_chain", v)

@@ -184,3 +184,13 @@ def test_argument_validation():
     assert L.pioran_value_route(40, 20, 0, 8, 100, 0, 0, b"no_such_option=1", name, 8, None) == -1
     assert L.pioran_value_route(40, 20, 0, 8, 100, 0, 0, b"no_block", name, 8, None) == -1
     assert L.pioran_value_route(40, 20, 0, 8, 100, 0, 0, None, None, 8, None) == -1
+
+
+def test_removed_experiment_options_are_unknown():
+    """The row-sum variants ("gsum") and the dense timing experiments (dense_old_chain above 1) are gone from the library: their option
+    strings are refused like any unknown key or value, the options that stay are accepted."""
+    import ctypes
+    L = pj._lib.lib()
+    name = ctypes.create_string_buffer(32)
+    for options, rc in ((b"gsum=1", -1), (b"dense_old_chain=2", -1), (b"dense_old_chain=1", 0), (b"no_win2=1", 0)):
+        assert L.pioran_value_route(40, 20, 0, 8, 100, 0, 0, options, name, 32, None) == rc, options

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """GPU: randomized comparison of the dense factorisation's schedules — one launch per block column (default), the panel / update chain of
-rounds 1-3 (dense_old_chain = 1), single-panel / whole-tile variants and the persistent-chain prototype — on random sizes (129 .. 5200, any
+rounds 1-3 (dense_old_chain = 1), single-panel / whole-tile variants — on random sizes (129 .. 5200, any
 remainder mod 64), term counts and amplitudes, plus matrices that stop being positive definite at a random pivot (same LAPACK-style info)."""
 import os, sys, time
 import numpy as np
@@ -20,7 +20,7 @@ for idx in range(ncase):
     bad = int(rng.integers(0, N)) if idx % 5 == 0 else -1
     if bad >= 0: s2 = s2.copy(); s2[bad] = -50.0
     res = {}
-    for name, opts in (("steps", {}), ("old", {"dense_old_chain": 1}), ("single", {"dense_no_pairs": True}), ("whole", {"dense_no_halves": True}), ("persistent", {"dense_old_chain": 5})):
+    for name, opts in (("steps", {}), ("old", {"dense_old_chain": 1}), ("single", {"dense_no_pairs": True}), ("whole", {"dense_no_halves": True})):
         for k, v in opts.items(): ctx.set_option(k, v)
         res[name] = ctx.dense_nll(a, b, c, d, t, y, s2, return_info=True)
         for k in opts: ctx.set_option(k, 0 if k == "dense_old_chain" else False)
