@@ -287,6 +287,27 @@ int pioran_celerite_logl_grad_shift(pioran_ds* ds, int64_t B, int64_t J, const d
 int pioran_celerite_simulate(pioran_ctx* ctx, int64_t N, int64_t B, int64_t J, const double* A, const double* Bc,
                              const double* C, const double* Dd, int cd_shared, const double* t, const double* sigma2,
                              const double* q, double* y_out);
+/* Posterior draws at new times in O((N + M) R^2) by Matheron's rule (rand(fp, t_pred, 1) of src/scalable_GP.jl:106-112 behind
+ * get_ppc_timeseries, src/plots_diagnostics.jl:640-671, without the dense mean and covariance on all N + M points): with f~ a draw of the
+ * zero-mean prior on the merged grid T = sort(unique(t, tau)) (times are merged only where they compare equal) and eta_n = sqrt(nu_b sigma2_n) eps_n,
+ *     out[b][m] = mu_b + f~_b(tau_m) + k*(tau_m)' K_b^-1 ((y - mu_b) - f~_b(t) - eta_b),   K_b = kernel_b + diag(nu_b sigma2)
+ * is a draw of N(mean(fp, tau), cov(fp, tau)), jointly over all of tau: a tau equal to a data time or to another tau gets the same latent value
+ * (where the dense covariance is singular).  The chain composes the simulation on T (sigma2 = 0) and the posterior mean on the per-draw series
+ * y - f~_b(t) - eta_b, with three streaming kernels between them (celerite_predict.hip); nothing but the normals and the draws crosses the bus.
+ * q_data [B][N], q_new [B][M], eps [B][N]: standard normals supplied by the caller (as pioran_celerite_simulate takes its q): of the latent
+ * process at the data times, at the new times, and of the measurement noise.  The normal of a tau that coincides with a data time or an earlier tau
+ * is not used.  tau: M >= 1 times in any order, out [B][M] in the same order; a non-finite tau: PIORAN_ERR_ARG.
+ * mu, nu, shift [B], status [B] may be NULL.  shift: the shifted log-flux models — the data set holds raw flux and yerr^2, draw b conditions on
+ * log(y - shift_b) with variances sigma2 / (y - shift_b)^2 (as pioran_celerite_logl_batch_shift) and out is in the transformed scale.
+ * status: 0, or 2 with NaN in the draw's row — a non-positive D_n in either factorisation, or y - shift_b <= 0; other draws are unaffected.
+ * Routing as predict / simulate: up to 63 rows both on the windowed kernels, to 143 step by step, beyond: PIORAN_ERR_UNSUPPORTED before any upload or
+ * allocation.  C, Dd: [J] (cd_shared != 0) or [B][J] (each draw then its own one-draw batch).  Draws go in chunks of at most 256 sized to the free
+ * memory.  NULL ds / A .. Dd / tau / q_data / q_new / eps / out, B < 1, J < 1, M < 1: PIORAN_ERR_ARG before any GPU call.  Host pointers, blocking.
+ * pioran_celerite_config_name(-1) afterwards: "block (windowed posterior draw)" or "wide (step-by-step posterior draw)". */
+int pioran_celerite_rand_posterior(pioran_ds* ds, int64_t B, int64_t J, const double* A, const double* Bc, const double* C,
+                                   const double* Dd, int cd_shared, const double* mu, const double* nu, const double* shift,
+                                   int64_t M, const double* tau, const double* q_data, const double* q_new, const double* eps,
+                                   double* out, int32_t* status);
 /* ---- batched Lomb-Scargle periodogram (the per-draw loop of plot_lsp_ppc, src/plots_diagnostics.jl:514-571) --------------------------
  * The generalised Lomb-Scargle periodogram (Zechmeister & Kuerster 2009, time-shift-free form) of B series on one sampling, at F frequencies —
  * what LombScargle.jl evaluates with its defaults fit_mean = true, center_data = true, normalization = :standard:

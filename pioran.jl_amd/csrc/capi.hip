@@ -56,6 +56,10 @@ struct pioran_ctx {
     };
     Buf bA, bB, bC, bD, bmu, bnu, bY, bS2, bout, bst, bscratch, bK, bwork, bshift, bgtab, bq, bpair, btp, btprow;
     Buf blstab, blsaux;   // periodogram: the cos/sin table of a frequency chunk | weights and per-draw scalars
+    // posterior draws (rand_posterior_batch): what the chain holds BESIDE the prediction's buffers, which keep their roles there —
+    // the caller's normals q_data | q_new | eps, the normals on the merged grid, the simulation's stores | xi | realisations | log L | status,
+    // the index maps, the residual series Y | S2, the shifts, a chunk's draws | their status
+    Buf brqd, brqn, breps, brqT, brstores, brxi, brf, brsout, brsst, brmaps, brY, brS2, brshift, brres, brst;
     // scalar entry point: the last series' time stamps stay resident (samplers call logl with the same t)
     pioran_ds* scalar_ds = nullptr;
     std::vector<double> scalar_t;
@@ -787,6 +791,7 @@ int set_option(ScanOptions& o, const char* key, const char* value)
     else if (!std::strcmp(key, "exp")) o.exp = (value && value[0]) ? std::atoi(value) : 0;
     else if (!std::strcmp(key, "ls_tile")) o.ls_tile = (value && value[0]) ? std::atoi(value) : 0;
     else if (!std::strcmp(key, "ls_only")) o.ls_only = (value && value[0]) ? std::atoi(value) : 0;
+    else if (!std::strcmp(key, "rp_events")) o.rp_events = on ? 1 : 0;
     else if (!std::strcmp(key, "wide2")) o.wide2 = on;
     else if (!std::strcmp(key, "no_wide2")) o.no_wide2 = on;
     else return PIORAN_ERR_ARG;
@@ -919,7 +924,8 @@ int pioran_ctx_destroy(pioran_ctx* ctx)
     if (ctx->scalar_ds) pioran_dataset_destroy(ctx->scalar_ds);
     ctx->scalar_ds = nullptr;
     pioran_ctx::Buf* bufs[] = {&ctx->bA, &ctx->bB, &ctx->bC, &ctx->bD, &ctx->bmu, &ctx->bnu, &ctx->bY,
-                               &ctx->bS2, &ctx->bout, &ctx->bst, &ctx->bscratch, &ctx->bK, &ctx->bwork, &ctx->bshift, &ctx->bgtab, &ctx->bq, &ctx->bpair, &ctx->btp, &ctx->btprow};
+                               &ctx->bS2, &ctx->bout, &ctx->bst, &ctx->bscratch, &ctx->bK, &ctx->bwork, &ctx->bshift, &ctx->bgtab, &ctx->bq, &ctx->bpair, &ctx->btp, &ctx->btprow, &ctx->brqd, &ctx->brqn, &ctx->breps, &ctx->brqT, &ctx->brstores, &ctx->brxi, &ctx->brf, &ctx->brsout, &ctx->brsst, &ctx->brmaps,
+                               &ctx->brY, &ctx->brS2, &ctx->brshift, &ctx->brres, &ctx->brst};
     for (auto* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto& e : ctx->ev)
@@ -944,7 +950,8 @@ int pioran_ctx_trim(pioran_ctx* ctx)
     SYNC(ctx);
     pioran_ctx::Buf* bufs[] = {&ctx->bA, &ctx->bB, &ctx->bC, &ctx->bD, &ctx->bmu, &ctx->bnu, &ctx->bY,
                                &ctx->bS2, &ctx->bout, &ctx->bst, &ctx->bscratch, &ctx->bK, &ctx->bwork, &ctx->bshift, &ctx->bgtab, &ctx->bq, &ctx->bpair, &ctx->btp, &ctx->btprow,
-                               &ctx->blstab, &ctx->blsaux};
+                               &ctx->blstab, &ctx->blsaux, &ctx->brqd, &ctx->brqn, &ctx->breps, &ctx->brqT, &ctx->brstores, &ctx->brxi, &ctx->brf, &ctx->brsout, &ctx->brsst, &ctx->brmaps,
+                               &ctx->brY, &ctx->brS2, &ctx->brshift, &ctx->brres, &ctx->brst};
     for (auto* b : bufs) {
         if (b->p) (void)hipFree(b->p);
         b->p = nullptr;
@@ -2020,6 +2027,207 @@ int pioran_celerite_simulate(pioran_ctx* ctx, int64_t N, int64_t B, int64_t J, c
     const int rc = simulate_batch(ctx, true, N, B, J, in, t, sigma2, q, y_out);
     if (rc != PIORAN_ERR_UNSUPPORTED) return rc;
     return each_draw(B, [&](int64_t b) { return simulate_batch(ctx, false, N, 1, J, in.from_draw(b, J, 0), t, sigma2, q + b * N, y_out + b * N); });
+}
+
+// ---- posterior draws at new times by Matheron's rule ("(f)-4d posterior draws") ----------------------------------
+//   out(tau) = mu + f~(tau) + k*(tau)' K^-1 ((y - mu) - f~(t) - eta),   eta_n = sqrt(nu sigma2_n) eps_n
+// with f~ a realisation of the zero-mean prior on the merged grid T = sort(unique(t, tau)): the simulation (sigma2 = 0 on T) followed by the
+// prediction on the per-draw series Y_b = y - f~_b(t) - eta_b.  Nothing between the caller's normals and the draws goes to the host.
+
+// The merged grid of a call and its index maps (built once, on the host).  Times are merged only where they compare equal; among equal times the
+// first in (t, tau) order gives the normal: a tau on a data time, or on an earlier tau, shares that one's latent value.
+struct MergedGrid {
+    std::vector<double> T;          // [P] ascending, distinct
+    std::vector<int32_t> maps;      // origin [P] (index into (t | tau) of the first occurrence) | it [N] | itau [M] (merged indices)
+    int64_t P = 0;
+    void build(int64_t N, const double* t, int64_t M, const double* tau)
+    {
+        const int64_t n = N + M;
+        auto at_ = [&](int64_t i) { return i < N ? t[i] : tau[i - N]; };
+        std::vector<int64_t> idx((size_t)n);
+        for (int64_t i = 0; i < n; ++i) idx[(size_t)i] = i;
+        std::stable_sort(idx.begin(), idx.end(), [&](int64_t x, int64_t y) { return at_(x) < at_(y); });
+        maps.assign((size_t)(2 * n), 0);
+        T.clear();
+        std::vector<int32_t> origin, where((size_t)n);
+        for (int64_t k = 0; k < n; ++k) {
+            const int64_t i = idx[(size_t)k];
+            if (T.empty() || at_(i) != T.back()) { T.push_back(at_(i)); origin.push_back((int32_t)i); }
+            where[(size_t)i] = (int32_t)(T.size() - 1);
+        }
+        P = (int64_t)T.size();
+        maps.resize((size_t)(P + n));
+        std::copy(origin.begin(), origin.end(), maps.begin());
+        std::copy(where.begin(), where.end(), maps.begin() + P);
+    }
+};
+
+// B draws at M times on shared (c, d); chunks of at most 256 draws.  `simds`: the scratch data set on grid.T with y = 0, sigma2 = 0.
+static int rand_posterior_batch(pioran_ds* ds, pioran_ds* simds, int64_t B, int64_t J, const DrawChunk& in, const double* shift, const MergedGrid& grid,
+                                int64_t M, const double* tau, const double* q_data, const double* q_new, const double* eps, double* out, int32_t* status)
+{
+    pioran_ctx* ctx = ds->ctx;
+    PrepState &s = ds->host, &ss = simds->host;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    PendingGuard pending_guard(ctx);
+    int rc;
+    if ((rc = prepare_shared(ds, B, J, in.Bc, in.C, in.D))) return rc;
+    if ((rc = prepare_shared(simds, B, J, in.Bc, in.C, in.D))) return rc;
+    if (s.R > std::min(pioran_predict_supported_rows(), pioran_wide_supported_rows_modes()) || s.npd_terms) return PIORAN_ERR_UNSUPPORTED;   // before any upload / workspace
+    const int64_t N = ds->N, P = grid.P;
+    // Buffer roles.  The simulation's side and everything the chain adds live in buffers of their own (pioran_ctx::br*); the prediction's side keeps the
+    // roles it has in predict_batch.  Alive together within a chunk, none shared between two roles:
+    //   the caller's normals: q_data | q_new | eps                              brqd | brqn | breps
+    //   the normals on the merged grid [nb][P]                                  brqT
+    //   simulation: per-window stores | xi | f~ [nb][P] | log L | status        brstores | brxi | brf | brsout | brsst
+    //   index maps origin [P] | it [N] | itau [M]                               brmaps
+    //   residual series Y | S2 [nb][N], the shifts [nb]                         brY | brS2 | brshift
+    //   prediction: per-window stores (step by step: the factor) | reverse table | -z and the Q recurrences | tau-only factors | means [nb][M] | tau
+    //                                                                           bwork | bgtab | bq | bK | bY | bshift   (log L, status: bout, bst)
+    //   the draws [nb][M] | their status                                        brres | brst
+    //   (A, Bc, mu, nu of the chunk: bA, bB, bmu, bnu — one role, read by both sides)
+    pioran_ctx::Buf &qd = ctx->brqd, &qn = ctx->brqn, &ep = ctx->breps, &qT = ctx->brqT, &sstores = ctx->brstores, &xi = ctx->brxi, &fsim = ctx->brf,
+                    &sout = ctx->brsout, &sst = ctx->brsst, &maps = ctx->brmaps, &Yb = ctx->brY, &S2b = ctx->brS2, &shifts = ctx->brshift,
+                    &stores = ctx->bwork, &gtabs = ctx->bgtab, &qws = ctx->bq, &tauws = ctx->bK, &mean = ctx->bY, &taus = ctx->bshift, &res = ctx->brres,
+                    &rst = ctx->brst;
+    bool windowed = windowed_allowed(ctx->opt, s.R, s.J) && s.R <= 63;
+    if ((rc = windowed_ready(ds, s, false, windowed))) return rc;
+    if ((rc = windowed_ready(simds, ss, false, windowed))) return rc;
+    const size_t gt = windowed ? pioran_block_gtab_doubles(N, s.R) : 0;
+    auto work_doubles = [&](int64_t nb) {   // the two kernel families' workspaces
+        return windowed ? pioran_block_store_workspace_doubles(nb, P, s.R, 3) + pioran_block_store_workspace_doubles(nb, N, s.R, 2) +
+                              pioran_predict_q_workspace_doubles(nb, N, s.R)
+                        : pioran_predict_workspace_doubles(nb, N, s.R);
+    };
+    auto need = [&](int64_t nb) { return (work_doubles(nb) + (size_t)nb * (size_t)(3 * P + 4 * N + 3 * M)) * sizeof(double); };
+    auto grow = [&](int64_t nb) {
+        const size_t bn = (size_t)nb * (size_t)N * sizeof(double), bm = (size_t)nb * (size_t)M * sizeof(double), bp = (size_t)nb * (size_t)P * sizeof(double);
+        return ensure_each(ctx, {{&qd, bn}, {&qn, bm}, {&ep, bn}, {&qT, bp}, {&fsim, bp}, {&Yb, bn}, {&S2b, bn}, {&mean, bm}, {&res, bm},
+                                 {&sstores, windowed ? pioran_block_store_workspace_doubles(nb, P, s.R, 3) * sizeof(double) : 0},
+                                 {&xi, windowed ? bp : 0},
+                                 {&stores, (windowed ? pioran_block_store_workspace_doubles(nb, N, s.R, 2) : pioran_predict_workspace_doubles(nb, N, s.R)) * sizeof(double)},
+                                 {&qws, windowed ? pioran_predict_q_workspace_doubles(nb, N, s.R) * sizeof(double) : 0},
+                                 {&sout, nb * sizeof(double)}, {&sst, nb * sizeof(int32_t)}, {&rst, nb * sizeof(int32_t)}, {&shifts, nb * sizeof(double)}});
+    };
+    int64_t chunk = B < 256 ? B : 256;
+    if ((rc = size_chunk(ctx, chunk, {&qd, &qn, &ep, &qT, &fsim, &Yb, &S2b, &mean, &res, &sstores, &xi, &stores, &qws}, need, grow))) return rc;
+    if (windowed && (rc = ensure_each(ctx, {{&gtabs, gt * sizeof(double)}, {&tauws, pioran_predict_tau_workspace_doubles(M, s.R, 1) * sizeof(double)}}))) return rc;
+    if ((rc = upload(ctx, taus, tau, (size_t)M * sizeof(double)))) return rc;
+    if ((rc = upload(ctx, maps, grid.maps.data(), grid.maps.size() * sizeof(int32_t)))) return rc;
+    if ((rc = ensure_results(ctx, chunk))) return rc;
+    const int32_t *origin = (const int32_t*)maps.p, *it = origin + P, *itau = it + N;
+    const int tau_sorted = is_sorted(tau, M);
+    const bool timed = ctx->opt.rp_events != 0;
+    auto mark = [&](int slot) { return timed ? hipEventRecord(ctx->ev[slot], ctx->stream) : hipSuccess; };
+    ChunkTables tb, stb;
+    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+        const int64_t nb = std::min(B - b0, chunk);
+        DrawChunk m;
+        if ((rc = upload_draws(ctx, J, b0, nb, in.A, in.Bc, nullptr, nullptr, in.mu, in.nu, m))) return rc;
+        if ((rc = upload(ctx, qd, q_data + b0 * N, (size_t)nb * N * sizeof(double)))) return rc;
+        if ((rc = upload(ctx, qn, q_new + b0 * M, (size_t)nb * M * sizeof(double)))) return rc;
+        if ((rc = upload(ctx, ep, eps + b0 * N, (size_t)nb * N * sizeof(double)))) return rc;
+        if (shift && (rc = upload(ctx, shifts, shift + b0, (size_t)nb * sizeof(double)))) return rc;
+        if (windowed && b0 == 0) {
+            // (shared (c, d): the states' own forward tables; the buffer of per-draw tables is not touched)
+            if ((rc = build_tables(ds, s, false, nb, m, ctx->bscratch, &gtabs, tb))) return rc;
+            if ((rc = build_tables(simds, ss, false, nb, m, ctx->bscratch, nullptr, stb))) return rc;
+        }
+        if (b0 == 0) HIPCHK(ctx, mark(4));
+        // 1. the normals on the merged grid
+        if ((rc = pioran_launch_rp_gather(nb, N, M, P, origin, (const double*)qd.p, (const double*)qn.p, (double*)qT.p, ctx->stream))) return rc;
+        if (b0 == 0) HIPCHK(ctx, mark(5));
+        // 2. f~ on the merged grid (no mu, no nu: the zero-mean latent process)
+        DrawChunk msim = m;
+        msim.mu = msim.nu = nullptr;
+        ScanParams ps = shared_params(simds, ss, nb, msim);
+        ps.out = (double*)sout.p; ps.status = (int32_t*)sst.p;
+        ps.noise = (const double*)qT.p; ps.ysim = (double*)fsim.p;
+        if (windowed) {
+            ps.gw = (double*)sstores.p;
+            rc = pioran_launch_block_sim(ps, stb.btab, (double*)xi.p, ctx->stream);
+        } else {
+            rc = pioran_launch_scan_wide_sim(ps, ctx->stream);
+        }
+        if (rc) { ctx->last_err = "posterior draw: simulation launch failed"; return rc; }
+        if (b0 == 0) HIPCHK(ctx, mark(6));
+        // 3. the series the correction is predicted from
+        if ((rc = pioran_launch_rp_residual(nb, N, P, it, ds->y, ds->s2, m.nu, shift ? (const double*)shifts.p : nullptr, (const double*)fsim.p,
+                                            (const double*)ep.p, (double*)Yb.p, (double*)S2b.p, ctx->stream)))
+            return rc;
+        if (b0 == 0) HIPCHK(ctx, mark(7));
+        // 4. mu + k*' K^-1 (Y - mu)
+        m.Y = (const double*)Yb.p; m.S2 = (const double*)S2b.p;
+        ScanParams p = shared_params(ds, s, nb, m);
+        p.out = (double*)ctx->bout.p; p.status = (int32_t*)ctx->bst.p;
+        if (windowed) {
+            p.gw = (double*)stores.p;
+            g_last_kernel = "block (windowed posterior draw)";
+            rc = pioran_launch_block_solve(p, tb.btab, tb.gtab, (double*)qws.p, ctx->stream);
+            if (!rc) rc = pioran_launch_predict_from_gy(p, (double*)qws.p, (double*)tauws.p, ds->t, M, (const double*)taus.p, (double*)mean.p, ctx->stream, 0,
+                                                        tau_sorted);
+        } else {
+            g_last_kernel = "wide (step-by-step posterior draw)";
+            rc = pioran_launch_predict(p, (double*)stores.p, ds->t, M, (const double*)taus.p, (double*)mean.p, ctx->stream);
+        }
+        if (rc) { ctx->last_err = "posterior draw: prediction launch failed"; return rc; }
+        if (b0 == 0) HIPCHK(ctx, mark(8));
+        // 5. the draws, in the caller's order of tau
+        if ((rc = pioran_launch_rp_combine(nb, M, P, itau, (const double*)mean.p, (const double*)fsim.p, (const int32_t*)sst.p, (const int32_t*)ctx->bst.p,
+                                           (double*)res.p, (int32_t*)rst.p, ctx->stream)))
+            return rc;
+        if (b0 == 0) HIPCHK(ctx, mark(9));
+        // 6. download
+        if ((rc = download(ctx, out + b0 * M, res.p, (size_t)nb * M * sizeof(double)))) return rc;
+        if (status && (rc = download(ctx, status + b0, rst.p, nb * sizeof(int32_t)))) return rc;
+        SYNC(ctx);
+    }
+    return PIORAN_OK;
+}
+
+int pioran_celerite_rand_posterior(pioran_ds* ds, int64_t B, int64_t J, const double* A, const double* Bc, const double* C, const double* Dd,
+                                   int cd_shared, const double* mu, const double* nu, const double* shift, int64_t M, const double* tau,
+                                   const double* q_data, const double* q_new, const double* eps, double* out, int32_t* status)
+{
+    if (!ds || B < 1 || J < 1 || M < 1 || !A || !Bc || !C || !Dd || !tau || !q_data || !q_new || !eps || !out) return PIORAN_ERR_ARG;
+    for (int64_t m = 0; m < M; ++m)
+        if (!std::isfinite(tau[m])) return PIORAN_ERR_ARG;
+    pioran_ctx* ctx = ds->ctx;
+    const int64_t N = ds->N;
+    if (N + M > 0x7fffffff) return PIORAN_ERR_UNSUPPORTED;
+    // rows past the step-by-step kernels: refused before any upload or allocation (the row count prepare_shared arrives at: a term with d = 0 and
+    // b = 0 in every draw of the batch keeps one row)
+    auto rows_of = [&](int64_t nb, const double* bc, const double* dd) {
+        int64_t R = 0;
+        for (int64_t j = 0; j < J; ++j) {
+            bool one_row = dd[j] == 0.0;
+            for (int64_t b = 0; b < nb && one_row; ++b) one_row = bc[b * J + j] == 0.0;
+            R += one_row ? 1 : 2;
+        }
+        return R;
+    };
+    const int64_t max_rows = std::min(pioran_predict_supported_rows(), pioran_wide_supported_rows_modes());
+    const bool one_batch = cd_shared || B == 1;
+    for (int64_t b = 0; b < (one_batch ? 1 : B); ++b)
+        if (rows_of(one_batch ? B : 1, Bc + b * J, Dd + b * J) > max_rows) return PIORAN_ERR_UNSUPPORTED;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // the merged grid and its index maps, once per call: the data times come back from the data set
+    std::vector<double> t((size_t)N);
+    HIPCHK(ctx, hipMemcpyAsync(t.data(), ds->t, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SYNC(ctx);
+    MergedGrid grid;
+    grid.build(N, t.data(), M, tau);
+    ScopedDataset series;
+    std::vector<double> zero_s2((size_t)grid.P, 0.0);
+    int rc = series.create_zeros(ctx, grid.P, grid.T.data(), zero_s2.data());
+    if (rc) return rc;
+    const DrawChunk in{A, Bc, C, Dd, mu, nu, nullptr, nullptr};
+    if (one_batch) return rand_posterior_batch(ds, series.ds, B, J, in, shift, grid, M, tau, q_data, q_new, eps, out, status);
+    // (c, d) per draw: every draw is its own one-draw batch with its own tables, on the same merged grid
+    return each_draw(B, [&](int64_t b) {
+        return rand_posterior_batch(ds, series.ds, 1, J, in.from_draw(b, J, 0), at(shift, b), grid, M, tau, q_data + b * N, q_new + b * M, eps + b * N,
+                                    out + b * M, at(status, b));
+    });
 }
 
 // ---- batched Lomb-Scargle periodogram (periodogram.hip) --------------------------------------------------------------------------

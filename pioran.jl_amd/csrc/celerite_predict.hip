@@ -896,3 +896,95 @@ int pioran_launch_predict_var(ScanParams p, double* work, double* tau_work, cons
     }
     return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;
 }
+
+// ---- posterior draws at new times by Matheron's rule ("(f)-4d posterior draws") --------------------------------
+//   out(tau) = mu + f~(tau) + k*(tau)' K^-1 ((y - mu) - f~(t) - eta),   f~ a prior draw on the merged grid T of (t, tau), eta_n = sqrt(nu sigma2_n) eps_n
+// The simulation gives f~ and the prediction the correction; the three kernels below are what lies between them.  Each is a streaming kernel:
+// blockIdx.y strides over the draws, blockIdx.x / threadIdx.x over the time index (grid-stride, neighbouring lanes on neighbouring times — the
+// index maps are ascending along the merged grid, so the indexed reads stay near-contiguous), no atomics.
+namespace {
+
+// The normals of the merged grid: qT[b][p] = origin[p] < N ? q_data[b][origin[p]] : q_new[b][origin[p] - N]
+__global__ void __launch_bounds__(256) rp_gather_kernel(int64_t nb, int64_t N, int64_t M, int64_t P, const int32_t* __restrict__ origin,
+                                                        const double* __restrict__ q_data, const double* __restrict__ q_new,
+                                                        double* __restrict__ qT)
+{
+    for (int64_t b = blockIdx.y; b < nb; b += gridDim.y)
+        for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < P; p += (int64_t)gridDim.x * 256) {
+            const int64_t o = origin[p];
+            qT[b * P + p] = o < N ? q_data[b * N + o] : q_new[b * M + (o - N)];
+        }
+}
+
+// The series the correction is predicted from: Y[b][n] = y_n - f~[b][it[n]] - sqrt(nu_b S2[b][n]) eps[b][n], S2[b][n] = sigma2_n; with a shift
+// c_b, on the transformed series of table.hip's shift_transform_kernel: y_n -> log(y_n - c_b), sigma2_n -> sigma2_n / (y_n - c_b)^2.
+// y_n - c_b <= 0: NaN in Y, which the factorisation that follows reports as status 2.
+__global__ void __launch_bounds__(256) rp_residual_kernel(int64_t nb, int64_t N, int64_t P, const int32_t* __restrict__ it,
+                                                          const double* __restrict__ y, const double* __restrict__ s2,
+                                                          const double* __restrict__ nu, const double* __restrict__ shift,
+                                                          const double* __restrict__ fsim, const double* __restrict__ eps,
+                                                          double* __restrict__ Y, double* __restrict__ S2)
+{
+    for (int64_t b = blockIdx.y; b < nb; b += gridDim.y) {
+        const double nub = nu ? nu[b] : 1.0;
+        for (int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x; n < N; n += (int64_t)gridDim.x * 256) {
+            double yn = y[n], s2n = s2[n];
+            if (shift) {
+                const double v = yn - shift[b];
+                yn = v > 0.0 ? log(v) : __builtin_nan("");
+                s2n = s2n / (v * v);
+            }
+            Y[b * N + n] = yn - fsim[b * P + it[n]] - sqrt(nub * s2n) * eps[b * N + n];
+            S2[b * N + n] = s2n;
+        }
+    }
+}
+
+// out[b][m] = mean[b][m] + f~[b][itau[m]] in the caller's order of tau; a draw whose simulation or prediction reported a status: 2 and a NaN row
+__global__ void __launch_bounds__(256) rp_combine_kernel(int64_t nb, int64_t M, int64_t P, const int32_t* __restrict__ itau,
+                                                         const double* __restrict__ mean, const double* __restrict__ fsim,
+                                                         const int32_t* __restrict__ st_sim, const int32_t* __restrict__ st_pred,
+                                                         double* __restrict__ out, int32_t* __restrict__ status)
+{
+    for (int64_t b = blockIdx.y; b < nb; b += gridDim.y) {
+        const bool bad = st_sim[b] != 0 || st_pred[b] != 0;
+        if (blockIdx.x == 0 && threadIdx.x == 0) status[b] = bad ? 2 : 0;
+        for (int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x; m < M; m += (int64_t)gridDim.x * 256)
+            out[b * M + m] = bad ? __builtin_nan("") : mean[b * M + m] + fsim[b * P + itau[m]];
+    }
+}
+
+dim3 rp_grid(int64_t n, int64_t nb)
+{
+    const int64_t gx = (n + 255) / 256;
+    return dim3((unsigned)(gx < 1 ? 1 : (gx > 4096 ? 4096 : gx)), (unsigned)(nb > 65535 ? 65535 : nb));
+}
+
+}  // namespace
+
+// origin: device [P] (index into q_data | q_new of the first occurrence of merged time p); q_data [nb][N], q_new [nb][M], qT [nb][P]: device
+int pioran_launch_rp_gather(int64_t nb, int64_t N, int64_t M, int64_t P, const int32_t* origin, const double* q_data, const double* q_new, double* qT,
+                            hipStream_t stream)
+{
+    if (nb < 1 || N < 1 || M < 1 || P < 1 || P > N + M || !origin || !q_data || !q_new || !qT) return PIORAN_ERR_ARG;
+    hipLaunchKernelGGL(rp_gather_kernel, rp_grid(P, nb), dim3(256), 0, stream, nb, N, M, P, origin, q_data, q_new, qT);
+    return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;
+}
+
+// it: device [N] (merged index of data time n, < P); y, s2: device [N]; nu, shift: device [nb] or nullptr; fsim [nb][P], eps, Y, S2 [nb][N]: device
+int pioran_launch_rp_residual(int64_t nb, int64_t N, int64_t P, const int32_t* it, const double* y, const double* s2, const double* nu,
+                              const double* shift, const double* fsim, const double* eps, double* Y, double* S2, hipStream_t stream)
+{
+    if (nb < 1 || N < 1 || P < 1 || !it || !y || !s2 || !fsim || !eps || !Y || !S2) return PIORAN_ERR_ARG;
+    hipLaunchKernelGGL(rp_residual_kernel, rp_grid(N, nb), dim3(256), 0, stream, nb, N, P, it, y, s2, nu, shift, fsim, eps, Y, S2);
+    return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;
+}
+
+// itau: device [M] (merged index of tau_m, < P); mean, out [nb][M], fsim [nb][P]; st_sim, st_pred, status: device [nb]
+int pioran_launch_rp_combine(int64_t nb, int64_t M, int64_t P, const int32_t* itau, const double* mean, const double* fsim, const int32_t* st_sim,
+                             const int32_t* st_pred, double* out, int32_t* status, hipStream_t stream)
+{
+    if (nb < 1 || M < 1 || P < 1 || !itau || !mean || !fsim || !st_sim || !st_pred || !out || !status) return PIORAN_ERR_ARG;
+    hipLaunchKernelGGL(rp_combine_kernel, rp_grid(M, nb), dim3(256), 0, stream, nb, M, P, itau, mean, fsim, st_sim, st_pred, out, status);
+    return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;
+}

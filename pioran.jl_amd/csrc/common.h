@@ -53,6 +53,8 @@ struct ScanOptions {
     int ls_tile = 0;      // periodogram.hip: output tile of the product per workgroup, 64 or 128 (0 = automatic; tools)
     int ls_only = 0;      // periodogram.hip, timing tools ONLY: run only these phases (1 weights + table, 2 series, 4 product; 0 = all) on the workspace the previous
                           // call left — the powers of such a call are not a result (stale or undefined)
+    int rp_events = 0;    // posterior draws (capi.hip rand_posterior_batch), timing tools ONLY: 1 = the steps of a call's first chunk record the context's event
+                          // slots 4 .. 9 (before the gather | after it | after the simulation | the residual | the prediction | the combination)
 };
 
 struct ScanParams {
@@ -207,6 +209,13 @@ size_t pioran_predict_tau_workspace_doubles(int64_t M, int32_t R, int64_t ntab);
 size_t pioran_predict_var_workspace_doubles(int64_t B, int64_t N, int32_t R, int64_t M);
 int pioran_launch_predict_var(ScanParams p, double* work, double* tau_work, const double* t, int64_t M, const double* tau, double* var_out,
                               int32_t* status, hipStream_t stream);
+// ... posterior draws at new times by Matheron's rule: the streaming kernels between the simulation and the prediction (capi.hip rand_posterior_batch)
+int pioran_launch_rp_gather(int64_t nb, int64_t N, int64_t M, int64_t P, const int32_t* origin, const double* q_data, const double* q_new, double* qT,
+                            hipStream_t stream);
+int pioran_launch_rp_residual(int64_t nb, int64_t N, int64_t P, const int32_t* it, const double* y, const double* s2, const double* nu,
+                              const double* shift, const double* fsim, const double* eps, double* Y, double* S2, hipStream_t stream);
+int pioran_launch_rp_combine(int64_t nb, int64_t M, int64_t P, const int32_t* itau, const double* mean, const double* fsim, const int32_t* st_sim,
+                             const int32_t* st_pred, double* out, int32_t* status, hipStream_t stream);
 // celerite_fallback.hip
 int pioran_launch_scan_fallback(const ScanParams& p, hipStream_t stream);
 size_t pioran_fallback_scratch_doubles(int R);

@@ -323,6 +323,36 @@ class Dataset:
                                                           len(tau), _ptr(tau), _ptr(out), _ptr(st)), self.ctx._h)
         return (out, st) if return_status else out
 
+    def rand_posterior(self, A, Bc, C, Dd, tau, q_data, q_new, eps, mu=None, nu=None, shift=None, return_status=False):
+        """Draws of the posterior at the times tau (M,), any order, for B coefficient sets, in O((N + M) R^2) by Matheron's rule
+        (pioran_celerite_rand_posterior): a prior draw on the merged grid of (t, tau) from the normals q_data (B, N) and q_new (B, M), corrected
+        by the posterior mean of y - f~(t) - sqrt(nu sigma2) eps with eps (B, N).  Jointly N(mean(fp, tau), cov(fp, tau)), also where tau repeats
+        or meets a data time (the normal of such a tau is not used).  shift (B,): the data set holds raw flux and yerr**2, draw b conditions on
+        log(y - shift_b) and the result is in that scale.  Error, measured against a long-double dense truth (docs/EXPERIMENTS.md section 26),
+        in units of max(max |y - mu|, max |f~|): <= 5.7e-14 at every edge shape (R 1..143, N 1..257, tau outside / on the data, tied, crowded;
+        sigma2 as given and x 1e-6) on the windowed and the step-by-step route alike, where the fp64 references deviate by up to 7.6e-14.
+        Returns (B, M) [, status (B,)]: status 2 and a NaN row for a draw whose matrix is not positive definite — which the zero-noise prior
+        draw on the merged grid is, numerically, when a tau lies very close to a data time and the process is smooth — or whose y - shift is
+        not positive."""
+        A, Bc, C, Dd, tau, q_data, q_new, eps = map(_f64, (A, Bc, C, Dd, tau, q_data, q_new, eps))
+        if A.ndim != 2 or A.shape != Bc.shape or C.shape not in ((A.shape[1],), A.shape) or Dd.shape != C.shape or tau.ndim != 1:
+            raise ValueError("A, Bc must be (B, J), C, Dd (J,) or (B, J) and tau (M,)")
+        if not np.isfinite(tau).all():
+            raise ValueError("tau must be finite")
+        B, J = A.shape
+        M = len(tau)
+        if q_data.shape != (B, self.N) or eps.shape != (B, self.N) or q_new.shape != (B, M):
+            raise ValueError("q_data, eps must be (B, N) and q_new (B, M)")
+        mu = None if mu is None else _f64(np.broadcast_to(mu, (B,)))
+        nu = None if nu is None else _f64(np.broadcast_to(nu, (B,)))
+        shift = None if shift is None else _f64(np.broadcast_to(shift, (B,)))
+        out = np.empty((B, M))
+        st = np.zeros(B, dtype=np.int32)
+        _lib.check(_lib.lib().pioran_celerite_rand_posterior(self._h, B, J, _ptr(A), _ptr(Bc), _ptr(C), _ptr(Dd), int(C.ndim == 1), _ptr(mu),
+                                                             _ptr(nu), _ptr(shift), M, _ptr(tau), _ptr(q_data), _ptr(q_new), _ptr(eps),
+                                                             _ptr(out), _ptr(st)), self.ctx._h)
+        return (out, st) if return_status else out
+
     def logl_grad(self, A, Bc, C, Dd, mu=None, nu=None, series_grad=False, shift=None, cd_grad=True):
         """log L and its gradient for B draws: returns a dict with logl (B,), status, grad_a, grad_b, grad_c, grad_d (B, J),
         grad_mu, grad_nu (B,) and, with series_grad, grad_y, grad_sigma2 (B, N).  C, Dd: (J,) shared by the draws or
@@ -617,9 +647,26 @@ def std(fp: PosteriorGP, tau=None, ctx: Context | None = None, solver=None):
     return np.sqrt(np.diag(cov(fp, tau, ctx=ctx)))
 
 
-def rand_posterior(rng, fp: PosteriorGP, tau=None, n: int = 1, ctx: Context | None = None):
-    """rand(rng, fp[, tau], N): draws from MvNormal(mean, cov)   src/scalable_GP.jl:106-129.  Returns (len(tau), n)."""
+def rand_posterior(rng, fp: PosteriorGP, tau=None, n: int = 1, ctx: Context | None = None, solver=None):
+    """rand(rng, fp[, tau], N): draws from MvNormal(mean, cov)   src/scalable_GP.jl:106-129.  Returns (len(tau), n).
+    solver=None: the reference's dense route (mean, dense covariance, Cholesky on the host).  solver="celerite": Matheron's rule through the
+    celerite factorisation in O(N + M) per draw (Dataset.rand_posterior), exact also where tau repeats or meets a data time; `rng` then supplies
+    standard_normal((n, N)), ((n, M)), ((n, N)) in this order: the latent normals at the data times, at tau, and the noise normals."""
     tau = fp.f.x if tau is None else _f64(tau).reshape(-1)
+    if solver is not None:
+        if str(solver).lstrip(":") != "celerite":
+            raise ValueError(f"solver {solver} not recognised, use None (dense) or 'celerite'")
+        x, N, M = fp.f.x, len(fp.f.x), len(tau)
+        a, b, c, d = (np.real(np.atleast_1d(v)) for v in fp.f.f.kernel.celerite_coefs())
+        q_data, q_new, eps = rng.standard_normal((n, N)), rng.standard_normal((n, M)), rng.standard_normal((n, N))
+        ds = Dataset(x, fp.y - _mean_vector(fp.f.f.mean, x), fp.f.sigma2, ctx)
+        try:
+            out, st = ds.rand_posterior(np.tile(a, (n, 1)), np.tile(b, (n, 1)), c, d, tau, q_data, q_new, eps, return_status=True)
+        finally:
+            ds.close()
+        if (st != 0).any():
+            raise np.linalg.LinAlgError("matrix is not positive definite; the celerite factorisation met a non-positive pivot")
+        return (out + _mean_vector(fp.f.f.mean, tau)[None, :]).T
     m, K = mean(fp, tau, ctx=ctx), cov(fp, tau, ctx=ctx)
     L = np.linalg.cholesky(K + 1e-14 * np.trace(K) / len(tau) * np.eye(len(tau)))
     return m[:, None] + L @ rng.standard_normal((len(tau), n))
@@ -741,3 +788,33 @@ def lsp_ppc(rng, t, yerr, A, Bc, C, Dd, mu=None, nu=None, frequencies=None, S_lo
         Y = Y + _f64(mu).reshape(-1)[:, None]
     P = ctx.lombscargle(t, Y, yerr, freq)
     return freq, P, np.quantile(P, np.asarray(quantiles, dtype=np.float64), axis=0)
+
+
+def ppc_t_pred(t, t_pred=None):
+    """The prediction grid of get_ppc_timeseries (src/plots_diagnostics.jl:643-647): range(t[1], t[end], 2 N) unless given, merged with t:
+    sort(unique(vcat(t, t_pred)))."""
+    t = _f64(t).reshape(-1)
+    t_pred = np.linspace(t[0], t[-1], 2 * len(t)) if t_pred is None else _f64(t_pred).reshape(-1)
+    return np.unique(np.concatenate([t, t_pred]))
+
+
+def ppc_timeseries(rng, t, y, yerr, A, Bc, C, Dd, mu=None, nu=None, shift=None, t_pred=None, ctx: Context | None = None):
+    """get_ppc_timeseries (src/plots_diagnostics.jl:640-671) for B posterior samples (A, Bc: (B, J); C, Dd: (J,) or (B, J); mu, nu, shift: (B,)
+    or None) in one device call: one realisation of the posterior at t_pred per row of A (Dataset.rand_posterior on the data set
+    (t, y, yerr**2)).  t_pred defaults to the reference's grid and is merged with t either way (ppc_t_pred).  shift: the samples of the
+    log-transform's constant c; sample b conditions on log(y - c_b) and its realisation is transformed back as the reference writes it,
+    exp(realisation + c_b).  rng: numpy Generator; it supplies standard_normal((B, N)), ((B, M)), ((B, N)) in this order.
+    Returns (ts_array (len(t_pred), B), t_pred)."""
+    t, y, yerr, A = _f64(t).reshape(-1), _f64(y).reshape(-1), _f64(yerr).reshape(-1), _f64(A)
+    B, N = A.shape[0], len(t)
+    t_pred = ppc_t_pred(t, t_pred)
+    M = len(t_pred)
+    q_data, q_new, eps = rng.standard_normal((B, N)), rng.standard_normal((B, M)), rng.standard_normal((B, N))
+    ds = Dataset(t, y, yerr ** 2, ctx)
+    try:
+        out = ds.rand_posterior(A, Bc, C, Dd, t_pred, q_data, q_new, eps, mu=mu, nu=nu, shift=shift)
+    finally:
+        ds.close()
+    if shift is not None:
+        out = np.exp(out + _f64(np.broadcast_to(shift, (B,)))[:, None])
+    return out.T, t_pred

@@ -354,6 +354,35 @@ function predict_var(ds::Dataset, A::Matrix{Float64}, B::Matrix{Float64}, c::Vec
     return out, status
 end
 
+"""
+    rand_posterior(ds, A, B, c, d, τ, q_data, q_new, ϵ; μ = nothing, ν = nothing, shift = nothing)
+
+Posterior draws at the times `τ` (any order) for every column of `A`, `B`, in O(N + M) per draw by Matheron's rule
+(`pioran_celerite_rand_posterior`): what `rand(posterior(fx, y), τ, 1)` (src/scalable_GP.jl:106-112) draws from the dense mean and covariance,
+also where `τ` repeats or meets a data time.  `q_data` (`N × nbatch`), `q_new` (`length(τ) × nbatch`), `ϵ` (`N × nbatch`): standard normals of the
+latent process at the data times, at `τ`, and of the measurement noise.  `shift`: the shifted log-flux models (the data set holds raw flux and
+`yerr.^2`; the draws are in the transformed scale).  Returns the `length(τ) × nbatch` matrix and the status vector (2 and NaN where a draw's
+factorisation is not positive definite or `y .- shift` is not positive).
+"""
+function rand_posterior(ds::Dataset, A::Matrix{Float64}, B::Matrix{Float64}, c::VecOrMat{Float64}, d::VecOrMat{Float64},
+                        τ::Vector{Float64}, q_data::Matrix{Float64}, q_new::Matrix{Float64}, ϵ::Matrix{Float64};
+                        μ::Union{Nothing, Vector{Float64}} = nothing, ν::Union{Nothing, Vector{Float64}} = nothing,
+                        shift::Union{Nothing, Vector{Float64}} = nothing)
+    J, nb = size(A)
+    size(q_new) == (length(τ), nb) || error("q_new must be length(τ) × nbatch")
+    size(q_data) == size(ϵ) && size(q_data, 2) == nb || error("q_data and ϵ must be N × nbatch")
+    out = Matrix{Float64}(undef, length(τ), nb)      # column-major = the ABI's [B][M]
+    status = zeros(Int32, nb)
+    p(x) = x === nothing ? Ptr{Cdouble}(C_NULL) : pointer(x)
+    GC.@preserve A B c d μ ν shift τ q_data q_new ϵ out status begin
+        check(ccall((:pioran_celerite_rand_posterior, LIB), Cint,
+                    (Ptr{Cvoid}, Int64, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}),
+                    ds.h, nb, J, A, B, c, d, c isa Vector ? 1 : 0, p(μ), p(ν), p(shift), length(τ), τ, q_data, q_new, ϵ, out, status))
+    end
+    return out, status
+end
+
 # Float64 drop-in for Pioran.pred (predict(cov, τ, t, y, σ²) reaches it for every covariance type, :348-361)
 function pred_hip(a::Vector{Float64}, b::Vector{Float64}, c::Vector{Float64}, d::Vector{Float64}, τ::Vector{Float64},
                   t::Vector{Float64}, y::Vector{Float64}, σ²::Vector{Float64}; ctx = default_context())
