@@ -364,6 +364,18 @@ int pioran_tile_choice(int32_t R, int64_t B, int64_t pass, int no_split);
  * The rules are csrc/route.hip; tests/test_route.py holds them, tests/test_gpu_route.py holds the launches to them. */
 int pioran_value_route(int32_t R, int32_t J, int32_t n_one_row_terms, int64_t B, int64_t N, int per_draw_series, int64_t pass,
                        const char* options, char* name, int name_len, int32_t* tp);
+/* Diagnostics (no GPU needed): the same for draws that bring (c, d) of their own in n_per_draw_terms (>= 1) of the terms — what
+ * pioran_celerite_logl_batch (cd_shared = 0) does with a batch whose other terms are n_two_row_terms with both rows and n_one_row_terms with one
+ * (b = d = 0 in every draw), or, must_run != 0, pioran_logpdf_batch_theta with n_per_draw_terms QPO features on such a continuum; every resource
+ * granted.  In the host entry's order: mixed mode where its plan takes the batch (csrc/route.hip mixed_plan: "block+pd", the windowed kernel with
+ * per-draw rows, or "scan" / "wide" on a combined table, the last chunk's), else every term per draw (perdraw_form: "block (per-draw tables)",
+ * "wide (per-draw tables)", or without tables "scan" / "fallback").  One draw (B = 1) is the shared case to the host entry and not asked here
+ * unless must_run.  mixed_chunk, where not NULL: the draws per combined table of mixed mode (also where the windowed kernel is the plan: what the
+ * call falls to when that kernel's table cannot be had), 0 where mixed mode is not taken.  PIORAN_ERR_UNSUPPORTED (name ""): must_run and mixed
+ * mode refuses the rows.  Under force_fallback mixed mode only loses the windowed kernel: a batch it takes still runs on the scan.  options,
+ * name, PIORAN_ERR_ARG: as above; also N above 2^48.  tests/test_route.py, tests/test_gpu_route.py. */
+int pioran_value_route_cd(int32_t n_two_row_terms, int32_t n_one_row_terms, int32_t n_per_draw_terms, int64_t B, int64_t N, int per_draw_series,
+                          int must_run, const char* options, char* name, int name_len, int64_t* mixed_chunk);
 /* Diagnostics: the FP64 FMA rate (TFLOP/s) the device sustains right now with `waves_per_simd` (1 .. 8) wavefronts on every SIMD — about
  * `ms` milliseconds of a pure stream of independent v_fma_f64, event-timed on the context's stream.  The measured ceiling of any FP64
  * vector kernel on this box at that occupancy (the 78.6 TFLOP/s vendor figure assumes one FMA per SIMD every 4 cycles at 2.4 GHz).

@@ -4,24 +4,10 @@
 #include "common.h"
 #include "route.h"
 
-// (celerite_predict.hip; declared here: the windowed prediction was added after the PMC profiles of common.h's kernels were taken)
-size_t pioran_predict_q_workspace_doubles(int64_t B, int64_t N, int32_t R);
-int pioran_dense_nll_device_batch(int64_t nbatch, int64_t N, int32_t J, const double* a, const double* b, const double* c, const double* d,
-                                  int64_t cd_stride, const double* t, const double* y, const double* s2, double* K, int64_t slab,
-                                  const double* mu, const double* nu, double* out, int32_t* info, int sorted, hipStream_t stream,
-                                  const DenseOptions* dopt);   // dense.hip
-int pioran_launch_block_sim(const ScanParams& p, const double* btab, double* xi, hipStream_t stream);   // celerite_block.hip
-int pioran_launch_block_solve(const ScanParams& p, const double* btab, const double* gtab, double* gy, hipStream_t stream);   // celerite_block.hip
-size_t pioran_predict_tau_workspace_doubles(int64_t M, int32_t R, int64_t ntab);
-int pioran_launch_predict_from_gy(ScanParams p, double* work, double* tau_work, const double* t, int64_t M, const double* tau, double* mean_out,
-                                  hipStream_t stream, int cd_per_draw, int tau_sorted);
-
-
 #include <cmath>
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
-#include <functional>
 #include <new>
 #include <string>
 #include <thread>
@@ -245,9 +231,6 @@ int download(pioran_ctx* ctx, void* host, const void* dev, size_t bytes)
 }
 
 // ---- what the batched entries share: launch descriptions, one chunk of draws up and down, the size of a chunk ------------------------------------
-// doubles of one step record of the shared table (table.hip): (v, x, phi) of R + 2 rows, then (y_n, sigma2_n)
-constexpr int64_t rec_stride_of(int64_t R) { return 3 * (int64_t)(R + 2) + 2; }
-
 // element i of an array that may be absent
 template <class T>
 T* at(T* p, int64_t i) { return p ? p + i : nullptr; }
@@ -802,11 +785,9 @@ int set_option(ScanOptions& o, const char* key, const char* value)
 
 int pioran_tile_choice(int32_t R, int64_t B, int64_t pass, int no_split) { return tile_choice(R, B, pass, no_split); }
 
-int pioran_value_route(int32_t R, int32_t J, int32_t n_one_row_terms, int64_t B, int64_t N, int per_draw_series, int64_t pass, const char* options,
-                       char* name, int name_len, int32_t* tp)
+// "key=value;key=value" into a set of options
+static int parse_options(const char* options, ScanOptions& opt)
 {
-    if (J < 1 || n_one_row_terms < 0 || n_one_row_terms > J || R != 2 * J - n_one_row_terms || B < 1 || N < 1 || !name || name_len < 1) return PIORAN_ERR_ARG;
-    ScanOptions opt{};
     for (const char* kv = options ? options : ""; *kv;) {
         const char* end = std::strchr(kv, ';');
         const std::string item = end ? std::string(kv, end) : std::string(kv);
@@ -816,6 +797,15 @@ int pioran_value_route(int32_t R, int32_t J, int32_t n_one_row_terms, int64_t B,
         if (eq == std::string::npos) return PIORAN_ERR_ARG;
         if (const int rc = set_option(opt, item.substr(0, eq).c_str(), item.c_str() + eq + 1)) return rc;
     }
+    return PIORAN_OK;
+}
+
+int pioran_value_route(int32_t R, int32_t J, int32_t n_one_row_terms, int64_t B, int64_t N, int per_draw_series, int64_t pass, const char* options,
+                       char* name, int name_len, int32_t* tp)
+{
+    if (J < 1 || n_one_row_terms < 0 || n_one_row_terms > J || R != 2 * J - n_one_row_terms || B < 1 || N < 1 || !name || name_len < 1) return PIORAN_ERR_ARG;
+    ScanOptions opt{};
+    if (const int rc = parse_options(options, opt)) return rc;
     // every resource granted: a plain prepared state behind the table, the launch on its own step records
     const RouteQuery q{R, J, B, N, true, 0, per_draw_series != 0, J - n_one_row_terms, n_one_row_terms, true, true, opt};
     TpPlan plan;
@@ -824,6 +814,19 @@ int pioran_value_route(int32_t R, int32_t J, int32_t n_one_row_terms, int64_t B,
     return PIORAN_OK;
 }
 
+int pioran_value_route_cd(int32_t n_two_row_terms, int32_t n_one_row_terms, int32_t n_per_draw_terms, int64_t B, int64_t N, int per_draw_series,
+                          int must_run, const char* options, char* name, int name_len, int64_t* mixed_chunk)
+{
+    if (n_two_row_terms < 0 || n_one_row_terms < 0 || n_per_draw_terms < 1 || B < 1 || N < 1 || !name || name_len < 1) return PIORAN_ERR_ARG;
+    if ((int64_t)n_two_row_terms + n_one_row_terms + n_per_draw_terms > 0xfffff || N > ((int64_t)1 << 48)) return PIORAN_ERR_ARG;
+    ScanOptions opt{};
+    if (const int rc = parse_options(options, opt)) return rc;
+    int64_t chunk = 0;
+    const char* fam = value_route_cd(opt, n_two_row_terms, n_one_row_terms, n_per_draw_terms, B, N, per_draw_series != 0, must_run != 0, &chunk);
+    std::snprintf(name, (size_t)name_len, "%s", fam ? fam : "");
+    if (mixed_chunk) *mixed_chunk = chunk;
+    return fam ? PIORAN_OK : PIORAN_ERR_UNSUPPORTED;
+}
 
 extern "C" {
 
@@ -1142,80 +1145,62 @@ int pioran_celerite_logl_batch_dev_cd(pioran_ds* ds, int64_t B, int64_t J, const
     HIPCHK(ctx, hipMemcpyAsync(drm, rm.data(), rm.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     SYNC(ctx);
     const int32_t R = (int32_t)rm.size();
+    const DrawChunk in{dA, dBc, dC, dDd, dmu, dnu, dY, dS2};
     // draws [b0, b0 + nb) of the caller's device arrays, on per-draw tables tab_stride doubles apart (0: no tables)
     auto draws = [&](int64_t b0, int64_t nb, int64_t tab_stride) {
-        const DrawChunk m{dA + b0 * J, dBc + b0 * J, dC + b0 * J, dDd + b0 * J, dmu ? dmu + b0 : nullptr, dnu ? dnu + b0 : nullptr,
-                          dY ? dY + b0 * ds->N : nullptr, dS2 ? dS2 + b0 * ds->N : nullptr};
-        ScanParams q = perdraw_params(ds, (int32_t)J, R, drm, nb, m, tab_stride, 0);
-        q.out = dout + b0; q.status = dstatus ? dstatus + b0 : nullptr;
+        ScanParams q = perdraw_params(ds, (int32_t)J, R, drm, nb, in.from_draw(b0, J, ds->N), tab_stride, 0);
+        q.out = dout + b0; q.status = at(dstatus, b0);
         return q;
     };
-    // a chunk of at most 256 per-draw tables of tdoubles doubles each in bscratch
-    auto size_tables = [&](int64_t tdoubles, int64_t& chunk) {
-        chunk = B < 256 ? B : 256;
-        auto bytes = [&](int64_t nb) { return (size_t)nb * (size_t)tdoubles * sizeof(double); };
-        return size_chunk(ctx, chunk, {&ctx->bscratch}, bytes, [&](int64_t nb) { return ensure(ctx, ctx->bscratch, bytes(nb)); });
-    };
-    if (R > pioran_scan_supported_rows() && R <= pioran_wide_supported_rows() && !ctx->opt.force_fallback) {
-        // More rows than the throughput layouts hold (which evaluate per-draw transcendentals in the kernel): every draw gets its
-        // OWN table, built for a chunk of draws at a time, and the lean latency kernel walks it (one draw per workgroup) — the
-        // reference benchmark's j = 64 with the reference's call pattern (one random (a, b, c, d) per call,
-        // benchmark/benchmarks.jl:74-91): 16 k instead of 0.8 k evaluations per second (any-rank kernel, S in HBM).
-        const int64_t tdoubles = (int64_t)pioran_table_doubles(ds->N, R);
-        int64_t chunk;
-        if ((rc = size_tables(tdoubles, chunk))) return rc;
-        for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-            const int64_t nb = std::min(B - b0, chunk);
-            ScanParams q = draws(b0, nb, tdoubles);
-            q.tab = (const double*)ctx->bscratch.p;
-            rc = pioran_launch_table_batch(ds->N, R, (int32_t)J, nb, drm, ds->t, q.C, q.D, ds->y, ds->s2, (double*)ctx->bscratch.p, q.rec_stride, tdoubles,
-                                           ctx->stream);
-            if (rc) return rc;
-            g_last_kernel = "wide (per-draw tables)";
-            rc = pioran_launch_scan_wide(q, ctx->stream);
-            if (rc) { if (rc == PIORAN_ERR_HIP) ctx->last_err = "per-draw-table latency kernel launch failed"; return rc; }
-        }
-        return PIORAN_OK;
+    const PerDrawForm form = perdraw_form(ctx->opt, B, R, (int32_t)J);
+    if (form == PerDrawForm::no_table) {
+        ScanParams p = draws(0, B, 0);
+        p.rec_stride = 0;   // no table at all: the kernels evaluate the per-draw transcendentals themselves
+        return launch(ds, p);
     }
-    {
-        // Small batches, up to 63 rows: every draw gets its own table of the WINDOWED kernel (celerite_block.hip; one workgroup per
-        // (window, draw) builds it: ~8 us per table at N = 1e4, J = 20) instead of evaluating 3 J transcendentals per step and draw inside
-        // the throughput layout (14.7 ms per launch at N = 1e4, J = 20 whatever the batch): free Celerite / CARMA terms under a sampler
-        // (src/CARMA.jl:98-143).  tools/bench_per_draw_small.py.
-        if (perdraw_tables_wanted(ctx->opt, B, R, (int32_t)J)) {
-            const int64_t tdoubles = (int64_t)pioran_block_table_doubles(ds->N, R, (int32_t)J);
-            int64_t chunk;
-            if ((rc = size_tables(tdoubles, chunk))) return rc;
-            for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-                const int64_t nb = std::min(B - b0, chunk);
-                const ScanParams q = draws(b0, nb, tdoubles);
-                rc = pioran_launch_block_table_batch(ds->N, R, (int32_t)J, nb, drm, ds->t, q.C, q.D, ds->y, ds->s2, (double*)ctx->bscratch.p, tdoubles,
-                                                     ctx->stream);
-                if (rc) return rc;
-                g_last_kernel = "block (per-draw tables)";
-                rc = pioran_launch_scan_block(q, (const double*)ctx->bscratch.p, ctx->stream);
-                if (rc) { if (rc == PIORAN_ERR_HIP) ctx->last_err = "windowed kernel (per-draw tables) launch failed"; return rc; }
-            }
-            return PIORAN_OK;
-        }
+    // every draw its own table — the step records the latency kernel walks, or the windowed kernel's: a chunk of at most 256 tables in bscratch
+    const bool wide = form == PerDrawForm::wide_tables;
+    const int64_t tdoubles = wide ? (int64_t)pioran_table_doubles(ds->N, R) : (int64_t)pioran_block_table_doubles(ds->N, R, (int32_t)J);
+    int64_t chunk = B < 256 ? B : 256;
+    auto bytes = [&](int64_t nb) { return (size_t)nb * (size_t)tdoubles * sizeof(double); };
+    if ((rc = size_chunk(ctx, chunk, {&ctx->bscratch}, bytes, [&](int64_t nb) { return ensure(ctx, ctx->bscratch, bytes(nb)); }))) return rc;
+    double* const tabs = (double*)ctx->bscratch.p;
+    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+        const int64_t nb = std::min(B - b0, chunk);
+        ScanParams q = draws(b0, nb, tdoubles);
+        if (wide) q.tab = tabs;
+        rc = wide ? pioran_launch_table_batch(ds->N, R, (int32_t)J, nb, drm, ds->t, q.C, q.D, ds->y, ds->s2, tabs, q.rec_stride, tdoubles, ctx->stream)
+                  : pioran_launch_block_table_batch(ds->N, R, (int32_t)J, nb, drm, ds->t, q.C, q.D, ds->y, ds->s2, tabs, tdoubles, ctx->stream);
+        if (rc) return rc;
+        g_last_kernel = wide ? "wide (per-draw tables)" : "block (per-draw tables)";
+        rc = wide ? pioran_launch_scan_wide(q, ctx->stream) : pioran_launch_scan_block(q, tabs, ctx->stream);
+        if (rc == PIORAN_ERR_HIP) ctx->last_err = wide ? "per-draw-table latency kernel launch failed" : "windowed kernel (per-draw tables) launch failed";
+        if (rc) return rc;
     }
-    ScanParams p = draws(0, B, 0);
-    p.rec_stride = 0;   // no table at all: the kernels evaluate the per-draw transcendentals themselves
-    return launch(ds, p);
+    return PIORAN_OK;
 }
 
-// Shared (c, d): terms whose sin row is identically zero for the whole batch (d_j = 0 and b_j = 0 for all draws) keep
-// only their cos row; builds (or reuses) the shared table.
-static int prepare_shared(pioran_ds* ds, int64_t B, int64_t J, const double* Bc, const double* C, const double* Dd)
+// kind[j] of a batch's terms (build_rowmap): 2 where (c, d) differ between the draws (per_draw: C, Dd are [B][J]; else [J]); 1 where the sin row is
+// identically zero for the whole batch (d_j = 0 and b_j = 0 in every draw): the term keeps only its cos row; 0 otherwise
+static std::vector<int32_t> classify_terms(int64_t B, int64_t J, const double* Bc, const double* C, const double* Dd, bool per_draw)
 {
-    std::vector<int32_t> real(J, 0);
+    std::vector<int32_t> kind(J, 0);
     for (int64_t j = 0; j < J; ++j) {
+        bool shared = true;
+        for (int64_t b = 1; per_draw && b < B && shared; ++b) shared = C[b * J + j] == C[j] && Dd[b * J + j] == Dd[j];
+        if (!shared) { kind[j] = 2; continue; }
         if (Dd[j] != 0.0) continue;
         bool allzero = true;
-        for (int64_t b = 0; b < B && allzero; ++b) allzero = (Bc[b * J + j] == 0.0);
-        real[j] = allzero;
+        for (int64_t b = 0; b < B && allzero; ++b) allzero = Bc[b * J + j] == 0.0;
+        kind[j] = allzero;
     }
-    return prepare_state(ds, ds->host, J, C, Dd, real.data());
+    return kind;
+}
+
+// Shared (c, d): builds (or reuses) the shared table, one-row terms with their cos row only.
+static int prepare_shared(pioran_ds* ds, int64_t B, int64_t J, const double* Bc, const double* C, const double* Dd)
+{
+    return prepare_state(ds, ds->host, J, C, Dd, classify_terms(B, J, Bc, C, Dd, false).data());
 }
 
 // The host state of an entry that serves both forms.  per_draw — (C, Dd) [B][J], every term's of its own in every draw: the row map with both rows of
@@ -1225,94 +1210,78 @@ static int prepare_draws(pioran_ds* ds, bool per_draw, int64_t B, int64_t J, con
     return per_draw ? prepare_state(ds, ds->host, J, C, Dd, nullptr) : prepare_shared(ds, B, J, Bc, C, Dd);
 }
 
-// Mixed mode (host-pointer entry, cd_shared == 0): when only a few terms really differ between draws (QPO features on
-// top of an approx continuum, src/psd.jl:254-261), the shared terms keep using the shared table and only the per-draw
-// terms get a per-draw table, built by a pre-pass kernel for chunks of draws (32-bit buffer offsets).
-// Returns 1 if it handled the batch, 0 if the caller should take the generic per-draw path, < 0 on error.
-// Mixed-mode core: kind[J] (0 shared two-row, 1 shared real, 2 per-draw) and the shared values (C0, D0: [J], entries of
-// per-draw terms ignored) declare the layout; `fetch(b0, nb, ptrs)` hands the DEVICE pointers of one chunk of draws
-// (A, Bc, C, D as [nb][J]; mu, nu [nb] or nullptr; Y, S2 [nb][N] or nullptr).  Results go to the caller's host arrays.
-// Returns 1 if it handled the batch, 0 if this layout is not worth / not able to run mixed (caller takes the generic path).
-static int mixed_core(pioran_ds* ds, int64_t B, int64_t J, const std::vector<int32_t>& kind, const double* C0, const double* D0,
-                      const std::function<int(int64_t, int64_t, DrawChunk&)>& fetch, double* out, int32_t* status,
-                      bool must_run = false)
+// Where mixed_core's draws are: `draws` holds the whole batch on the device, or the caller's host arrays, which go up a chunk at a time — their
+// per-draw series too, unless the context's bY / bS2 have the whole batch's already (series_on_device: shift transform)
+struct MixedSource { DrawChunk draws; bool on_device, series_on_device; };
+
+// draws [b0, b0 + nb) of `src` on the device
+static int mixed_chunk(pioran_ds* ds, int64_t J, const MixedSource& src, int64_t b0, int64_t nb, DrawChunk& m)
+{
+    pioran_ctx* ctx = ds->ctx;
+    const DrawChunk& h = src.draws;
+    if (src.on_device) { m = h.from_draw(b0, J, ds->N); return PIORAN_OK; }
+    int rc;
+    if ((rc = upload_draws(ctx, J, b0, nb, h.A, h.Bc, h.C, h.D, h.mu, h.nu, m))) return rc;
+    if (h.Y) {
+        const size_t bn = (size_t)nb * (size_t)ds->N * sizeof(double);
+        if ((rc = upload(ctx, ctx->bY, h.Y + b0 * ds->N, bn))) return rc;
+        if ((rc = upload(ctx, ctx->bS2, h.S2 + b0 * ds->N, bn))) return rc;
+        m.Y = (const double*)ctx->bY.p; m.S2 = (const double*)ctx->bS2.p;
+    } else if (src.series_on_device) {
+        m.Y = (const double*)ctx->bY.p + b0 * ds->N; m.S2 = (const double*)ctx->bS2.p + b0 * ds->N;
+    }
+    return PIORAN_OK;
+}
+
+// Mixed mode (route.hip mixed_plan): kind[J] (0 shared two-row, 1 shared real, 2 per-draw) and the shared values (C0, D0: [J], entries of per-draw
+// terms ignored) declare the layout; the shared terms keep the shared table, the per-draw terms get per-draw rows, built by a pre-pass kernel for
+// chunks of draws.  Results go to the caller's host arrays.  Returns 1 if it handled the batch, 0 if the caller should take the generic per-draw
+// path (must_run: if no kernel can take the rows), < 0 on error.
+static int mixed_core(pioran_ds* ds, int64_t B, int64_t J, const std::vector<int32_t>& kind, const double* C0, const double* D0, const MixedSource& src,
+                      double* out, int32_t* status, bool must_run = false)
 {
     pioran_ctx* ctx = ds->ctx;
     PrepState& s = ds->host;
-    int64_t npd = 0, rows = 0;
+    int32_t npd = 0, rows = 0;
     for (int64_t j = 0; j < J; ++j) { npd += kind[j] == 2; rows += kind[j] == 1 ? 1 : 2; }
-    // all shared is handled by the caller; many per-draw terms: the generic per-draw path is as good.  must_run: the caller has
-    // no generic path to fall back to (theta entry: the continuum's (c, d) exist only as a shared table), so the two
-    // "not worth it" cuts — a performance heuristic, not a kernel constraint — are skipped
-    // (the windowed kernel takes small batches with one or two per-draw terms whatever the share of per-draw terms: see below)
-    bool blk_ok = false;
-    {
-        const ScanOptions& o = ctx->opt;
-        const char* cfg = o.scan_config[0] ? o.scan_config : nullptr;
-        const bool force = cfg && !std::strcmp(cfg, "block");
-        // (fewer than six rows, late round 4, tools/per_draw_few_rows.py: the generic per-draw path took 7.5 ms for 16 draws of ONE term at N = 1e4 —
-        //  1.7 ms here; 768 draws 8.2 -> 4.2 ms)
-        const bool automatic = !cfg && !o.no_block && (rows >= 6 ? B <= 512 : B <= 768);
-        blk_ok = (force || automatic) && !o.force_fallback && npd >= 1 && pioran_block_fits_pd((int32_t)rows, (int32_t)J, (int32_t)npd);
-    }
-    if (npd == 0 || npd > 8 || (!must_run && !blk_ok && npd * 2 > J)) return 0;
-    if (rows > pioran_scan_supported_rows()) return 0;
-    const int64_t rs_shared = rec_stride_of(rows);              // shared part of a step record (doubles)
-    // combined table: (N+1) records of rs_shared + chunk * 2 npd * 3 doubles, addressed with 32-bit byte offsets
-    int64_t chunk = ((int64_t)0x7fff0000 / ((ds->N + 1) * 8) - rs_shared) / (6 * npd);
-    chunk = chunk > B ? B : (chunk >= 16 ? chunk & ~(int64_t)15 : chunk);
-    if (chunk < 1 || (!must_run && !blk_ok && chunk < 16)) return 0;
+    const MixedPlan plan = mixed_plan(ctx->opt, B, ds->N, (int32_t)J, rows, npd, must_run);
+    if (!plan.take) return 0;
     int rc;
     if ((rc = prepare_state(ds, s, J, C0, D0, kind.data()))) return rc;
-    // Small batches with one or two per-draw terms (a QPO feature on an approx continuum at a few hundred live points,
-    // src/psd.jl:254-261): the windowed kernel with per-draw rows (celerite_block.hip; round 3) — same automatic range as for shared
-    // batches (block_dispatch).  Needs the kernel's own table of the shared rows and the per-draw (cos, sin)(d t_n).
-    {
-        if (blk_ok && (rc = ensure_btab(ds, s)) != PIORAN_ERR_UNSUPPORTED) {
-            if (rc) return rc;
-            const int64_t cb = B < 4096 ? B : 4096;
-            const size_t trig_bytes = pioran_block_pd_trig_doubles(ds->N, cb, s.npd_terms) * sizeof(double);
-            if ((rc = ensure(ctx, ctx->bscratch, trig_bytes))) return rc;
-            if ((rc = ensure_results(ctx, cb))) return rc;
-            for (int64_t b0 = 0; b0 < B; b0 += cb) {
-                const int64_t nb = std::min(B - b0, cb);
-                DrawChunk m{};
-                if ((rc = fetch(b0, nb, m))) return rc;
-                if ((rc = pioran_launch_block_pd_trig(ds->N, nb, (int32_t)J, s.npd_terms, s.dpd_terms, ds->t, m.D, (double*)ctx->bscratch.p, ctx->stream)))
-                    return rc;
-                ScanParams p = shared_params(ds, s, nb, m);
-                p.out = (double*)ctx->bout.p; p.status = (int32_t*)ctx->bst.p;
-                p.npd_rows = 2 * s.npd_terms;
-                p.pd_C = m.C; p.pd_trig = (const double*)ctx->bscratch.p; p.pd_npad = (ds->N + 15) / 16 * 16;
-                g_last_kernel = "block+pd";
-                rc = pioran_launch_scan_block(p, s.btab, ctx->stream);
-                if (rc) { ctx->last_err = "windowed kernel (per-draw rows) launch failed"; return rc; }
-                if ((rc = download_results(ctx, out, status, b0, nb))) return rc;
-                SYNC(ctx);
-            }
-            return 1;
-        }
+    // The windowed kernel with per-draw rows needs its own table of the shared rows and the per-draw (cos, sin)(d t_n); where that table cannot be
+    // had, the scan takes the batch on a combined table — the shared records widened by a chunk's per-draw rows, chunk * 2 npd * 3 doubles
+    bool windowed = plan.windowed;
+    if (windowed && (rc = ensure_btab(ds, s))) {
+        if (rc != PIORAN_ERR_UNSUPPORTED) return rc;
+        windowed = false;
     }
-    const int64_t rec_stride = rs_shared + chunk * 6 * npd;
-    if ((rc = ensure(ctx, ctx->bscratch, (size_t)(ds->N + 1) * (size_t)rec_stride * sizeof(double)))) return rc;
-    double* ctab = (double*)ctx->bscratch.p;
+    const int64_t chunk = windowed ? std::min<int64_t>(B, 4096) : plan.chunk;
+    const int64_t rs_shared = rec_stride_of(rows), rec_stride = rs_shared + chunk * 6 * npd;
+    const size_t wdoubles = windowed ? pioran_block_pd_trig_doubles(ds->N, chunk, s.npd_terms) : (size_t)(ds->N + 1) * (size_t)rec_stride;
+    if ((rc = ensure(ctx, ctx->bscratch, wdoubles * sizeof(double)))) return rc;
+    double* const work = (double*)ctx->bscratch.p;
     // shared rows into the combined layout (same kernel as the plain table, wider record stride)
-    if ((rc = pioran_launch_table(ds->N, s.R, s.rowmap, ds->t, s.dc, s.dd, ds->y, ds->s2, ctab, rec_stride, ctx->stream)))
-        return rc;
+    if (!windowed && (rc = pioran_launch_table(ds->N, s.R, s.rowmap, ds->t, s.dc, s.dd, ds->y, ds->s2, work, rec_stride, ctx->stream))) return rc;
     if ((rc = ensure_results(ctx, chunk))) return rc;
     for (int64_t b0 = 0; b0 < B; b0 += chunk) {
         const int64_t nb = std::min(B - b0, chunk);
         DrawChunk m{};
-        if ((rc = fetch(b0, nb, m))) return rc;
-        rc = pioran_launch_pd_table(ds->N, nb, (int32_t)J, s.npd_terms, s.dpd_terms, ds->t, m.C, m.D, ctab, rec_stride, rs_shared,
-                                    ctx->stream);
+        if ((rc = mixed_chunk(ds, J, src, b0, nb, m))) return rc;
+        rc = windowed ? pioran_launch_block_pd_trig(ds->N, nb, (int32_t)J, s.npd_terms, s.dpd_terms, ds->t, m.D, work, ctx->stream)
+                      : pioran_launch_pd_table(ds->N, nb, (int32_t)J, s.npd_terms, s.dpd_terms, ds->t, m.C, m.D, work, rec_stride, rs_shared, ctx->stream);
         if (rc) return rc;
         ScanParams p = shared_params(ds, s, nb, m);
-        p.tab = ctab; p.rec_stride = rec_stride;   // the combined table: the shared records widened by the chunk's per-draw rows
         p.out = (double*)ctx->bout.p; p.status = (int32_t*)ctx->bst.p;
         p.npd_rows = 2 * s.npd_terms;
-        rc = scan_dispatch(p, ctx->stream);
-        if (rc) { ctx->last_err = "mixed-mode scan launch failed"; return rc; }
+        if (windowed) {
+            p.pd_C = m.C; p.pd_trig = work; p.pd_npad = (ds->N + 15) / 16 * 16;
+            g_last_kernel = "block+pd";
+            rc = pioran_launch_scan_block(p, s.btab, ctx->stream);
+        } else {
+            p.tab = work; p.rec_stride = rec_stride;
+            rc = scan_dispatch(p, ctx->stream);
+        }
+        if (rc) { ctx->last_err = windowed ? "windowed kernel (per-draw rows) launch failed" : "mixed-mode scan launch failed"; return rc; }
         if ((rc = download_results(ctx, out, status, b0, nb))) return rc;
         SYNC(ctx);
     }
@@ -1323,33 +1292,9 @@ static int batch_host_mixed(pioran_ds* ds, int64_t B, int64_t J, const double* A
                             const double* Dd, const double* mu, const double* nu, const double* Y, const double* S2,
                             bool series_on_device, double* out, int32_t* status)
 {
-    pioran_ctx* ctx = ds->ctx;
-    if (ctx->opt.no_mixed) return 0;
-    std::vector<int32_t> kind(J, 0);
-    for (int64_t j = 0; j < J; ++j) {
-        bool shared = true;
-        for (int64_t b = 1; b < B && shared; ++b) shared = C[b * J + j] == C[j] && Dd[b * J + j] == Dd[j];
-        if (!shared) { kind[j] = 2; continue; }
-        if (Dd[j] == 0.0) {
-            bool allzero = true;
-            for (int64_t b = 0; b < B && allzero; ++b) allzero = Bc[b * J + j] == 0.0;
-            kind[j] = allzero ? 1 : 0;
-        }
-    }
-    auto fetch = [&](int64_t b0, int64_t nb, DrawChunk& m) -> int {
-        int rc;
-        if ((rc = upload_draws(ctx, J, b0, nb, A, Bc, C, Dd, mu, nu, m))) return rc;
-        if (Y) {
-            const size_t bn = (size_t)nb * (size_t)ds->N * sizeof(double);
-            if ((rc = upload(ctx, ctx->bY, Y + b0 * ds->N, bn))) return rc;
-            if ((rc = upload(ctx, ctx->bS2, S2 + b0 * ds->N, bn))) return rc;
-            m.Y = (const double*)ctx->bY.p; m.S2 = (const double*)ctx->bS2.p;
-        } else if (series_on_device) {
-            m.Y = (const double*)ctx->bY.p + b0 * ds->N; m.S2 = (const double*)ctx->bS2.p + b0 * ds->N;
-        }
-        return PIORAN_OK;
-    };
-    return mixed_core(ds, B, J, kind, C, Dd, fetch, out, status);   // row 0 of C, Dd: the shared values
+    if (ds->ctx->opt.no_mixed) return 0;   // (mixed_plan says so too: this saves classify_terms' pass over the batch)
+    const MixedSource src{{A, Bc, C, Dd, mu, nu, Y, S2}, false, series_on_device};
+    return mixed_core(ds, B, J, classify_terms(B, J, Bc, C, Dd, true), C, Dd, src, out, status);   // row 0 of C, Dd: the shared values
 }
 
 // host-pointer batch; series_on_device: ctx->bY / ctx->bS2 already hold the per-draw series (shift transform)
@@ -1553,15 +1498,10 @@ int pioran_logpdf_batch_theta(pioran_ds* ds, int64_t B, int model, int64_t n_com
         std::vector<double> c0((size_t)Jt, 0.0), d0((size_t)Jt, 0.0);
         for (int64_t j = 0; j < Jc; ++j) { kind[j] = real[j] ? 1 : 0; c0[j] = c[j]; d0[j] = d[j]; }
         for (int64_t q = 0; q < n_qpo; ++q) kind[Jc + q] = 2;
-        auto fetch = [&](int64_t b0, int64_t nb, DrawChunk& m) -> int {
-            (void)nb;
-            m.A = (const double*)ctx->bA.p + b0 * Jt; m.Bc = (const double*)ctx->bB.p + b0 * Jt;
-            m.C = dCq + b0 * Jt; m.D = dDq + b0 * Jt;
-            m.mu = dmu ? dmu + b0 : nullptr; m.nu = dnu ? dnu + b0 : nullptr;
-            if (shift) { m.Y = (const double*)ctx->bY.p + b0 * ds->N; m.S2 = (const double*)ctx->bS2.p + b0 * ds->N; }
-            return PIORAN_OK;
-        };
-        rc = mixed_core(ds, B, Jt, kind, c0.data(), d0.data(), fetch, out, status, /*must_run=*/true);
+        const bool series = shift != nullptr;   // (the transformed series of the whole batch: the chunks read their slices)
+        const MixedSource src{{(const double*)ctx->bA.p, (const double*)ctx->bB.p, dCq, dDq, dmu, dnu, series ? (const double*)ctx->bY.p : nullptr,
+                               series ? (const double*)ctx->bS2.p : nullptr}, true, false};
+        rc = mixed_core(ds, B, Jt, kind, c0.data(), d0.data(), src, out, status, /*must_run=*/true);
         if (rc < 0) return rc;
         if (rc == 0) return PIORAN_ERR_UNSUPPORTED;   // too many rows for the register-resident kernels
     } else {

@@ -166,6 +166,8 @@ int pioran_launch_block_table(int64_t N, int32_t R, int32_t J, const int32_t* ro
 int pioran_launch_scan_block(const ScanParams& p, const double* btab, hipStream_t stream);   // p.tab_draw_stride: doubles between per-draw tables (0: one shared table)
 int pioran_launch_block_table_batch(int64_t N, int32_t R, int32_t J, int64_t nb, const int32_t* rowmap, const double* t, const double* C /*[nb][J]*/,
                                     const double* D, const double* y, const double* s2, double* btab, int64_t draw_stride, hipStream_t stream);
+int pioran_launch_block_sim(const ScanParams& p, const double* btab, double* xi, hipStream_t stream);
+int pioran_launch_block_solve(const ScanParams& p, const double* btab, const double* gtab, double* gy, hipStream_t stream);
 // windowed reverse mode (gradient w.r.t. a, b, mu, nu): forward pass with stores + adjoint kernel
 size_t pioran_block_grad_workspace_doubles(int64_t B, int64_t N, int32_t R);
 size_t pioran_block_store_workspace_doubles(int64_t B, int64_t N, int32_t R, int what);   // prediction (what = 2) / simulation (3): packed stores
@@ -204,6 +206,9 @@ int pioran_launch_block_table_reference(int64_t N, int32_t R, int32_t J, const i
 size_t pioran_predict_workspace_doubles(int64_t B, int64_t N, int32_t R);
 int pioran_launch_predict(ScanParams p, double* work, const double* t, int64_t M, const double* tau, double* mean_out,
                           hipStream_t stream);
+size_t pioran_predict_q_workspace_doubles(int64_t B, int64_t N, int32_t R);
+int pioran_launch_predict_from_gy(ScanParams p, double* work, double* tau_work, const double* t, int64_t M, const double* tau, double* mean_out,
+                                  hipStream_t stream, int cd_per_draw, int tau_sorted);
 // ... posterior variance at new times through the stored factor (at most 64 rows; tau ascending)
 size_t pioran_predict_tau_workspace_doubles(int64_t M, int32_t R, int64_t ntab);
 size_t pioran_predict_var_workspace_doubles(int64_t B, int64_t N, int32_t R, int64_t M);
@@ -273,3 +278,7 @@ int pioran_dense_predict_cov_device(int64_t N, int64_t M, int32_t J, const doubl
 int pioran_dense_build_device(int64_t N, int32_t J, const double* a, const double* b, const double* c,
                               const double* d, const double* t, const double* y, const double* s2,
                               double* K, int sorted, hipStream_t stream);
+int pioran_dense_nll_device_batch(int64_t nbatch, int64_t N, int32_t J, const double* a, const double* b, const double* c, const double* d,
+                                  int64_t cd_stride, const double* t, const double* y, const double* s2, double* K, int64_t slab,
+                                  const double* mu, const double* nu, double* out, int32_t* info, int sorted, hipStream_t stream,
+                                  const DenseOptions* dopt);

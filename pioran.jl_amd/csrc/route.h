@@ -1,10 +1,14 @@
 // Which kernel family evaluates a batch of log-likelihoods: the measured rules, as pure functions of a RouteQuery (route.hip).  Host code only: no
 // runtime call, no context, no data set.  capi.hip fills the query once per launch, asks the rules in the ladder's order (time-parallel, tile,
-// windowed, remainder split, scan / latency layout, fallback) and does the rest: tables, workspaces, streams, the launches.
+// windowed, remainder split, scan / latency layout, fallback) and does the rest: tables, workspaces, streams, the launches.  Draws with (c, d) of
+// their own are planned before the ladder: mixed_plan where only a few terms differ between the draws, perdraw_form where the caller says all do.
 #pragma once
 #include "common.h"
 
 #include <functional>
+
+// doubles of one step record of the shared table (table.hip): (v, x, phi) of R + 2 rows, then (y_n, sigma2_n)
+constexpr int64_t rec_stride_of(int64_t R) { return 3 * (int64_t)(R + 2) + 2; }
 
 // What the rules read of a launch
 struct RouteQuery {
@@ -43,7 +47,25 @@ int tp_mode(const TpPlan& plan, bool repair, const ScanOptions& o);   // pioran_
 // the family the ladder takes when every resource is granted (pioran_value_route); *tp: the plan, where the family is "tp"
 const char* value_route(const RouteQuery& q, int64_t pass, TpPlan* tp);
 
+// Draws that bring (c, d) of their own.  Every term per draw (pioran_celerite_logl_batch_dev_cd, R = 2 J rows): a table per draw for the latency
+// kernel, for the windowed kernel, or none — the kernels evaluate the transcendentals themselves, on the ladder above with shared = false
+enum class PerDrawForm { no_table, wide_tables, block_tables };
+PerDrawForm perdraw_form(const ScanOptions& o, int64_t B, int32_t R, int32_t J);
+
+// A few terms per draw (mixed mode, capi.hip mixed_core): npd of the J terms, `rows` rows in all.  take: mixed mode has the batch (else the caller's
+// generic path); windowed: the windowed kernel with per-draw rows is wanted; chunk: the draws per combined table of the scan's leg — also where the
+// windowed leg is wanted, for the call whose windowed table cannot be had.  must_run: the caller has no generic path.
+struct MixedPlan {
+    bool take = false, windowed = false;
+    int64_t chunk = 0;
+};
+MixedPlan mixed_plan(const ScanOptions& o, int64_t B, int64_t N, int32_t J, int32_t rows, int32_t npd, bool must_run);
+
+// what pioran_celerite_config_name(-1) reports after a host call with per-draw (c, d) in npd of the terms, every resource granted
+// (pioran_value_route_cd); nullptr: must_run, and mixed mode refuses.  *chunk: the mixed plan's (0: not taken)
+const char* value_route_cd(const ScanOptions& o, int32_t n_two_row, int32_t n_one_row, int32_t npd, int64_t B, int64_t N, bool per_draw_series,
+                           bool must_run, int64_t* chunk);
+
 // the other entries' one-line rules
 bool windowed_allowed(const ScanOptions& o, int32_t R, int32_t J);
-bool perdraw_tables_wanted(const ScanOptions& o, int64_t B, int32_t R, int32_t J);
 bool tile_grad_wanted(const ScanOptions& o, int64_t B, int32_t R);

@@ -280,12 +280,78 @@ bool windowed_allowed(const ScanOptions& o, int32_t R, int32_t J)
     return !o.no_block && !o.force_fallback && !o.scan_config[0] && pioran_block_fits(R, J);
 }
 
-// (c, d) per draw, small batches, up to 63 rows: every draw gets its own table of the windowed kernel (pioran_celerite_logl_batch_dev_cd)
-bool perdraw_tables_wanted(const ScanOptions& o, int64_t B, int32_t R, int32_t J)
+// Every term with (c, d) of its own in every draw (pioran_celerite_logl_batch_dev_cd: R = 2 J rows, no shared table)
+PerDrawForm perdraw_form(const ScanOptions& o, int64_t B, int32_t R, int32_t J)
 {
+    if (o.force_fallback) return PerDrawForm::no_table;
+    // More rows than the throughput layouts hold (which evaluate per-draw transcendentals in the kernel): every draw gets its
+    // OWN table, built for a chunk of draws at a time, and the lean latency kernel walks it (one draw per workgroup) — the
+    // reference benchmark's j = 64 with the reference's call pattern (one random (a, b, c, d) per call,
+    // benchmark/benchmarks.jl:74-91): 16 k instead of 0.8 k evaluations per second (any-rank kernel, S in HBM).
+    if (R > pioran_scan_supported_rows() && R <= pioran_wide_supported_rows()) return PerDrawForm::wide_tables;
+    // Small batches, up to 63 rows: every draw gets its own table of the WINDOWED kernel (celerite_block.hip; one workgroup per
+    // (window, draw) builds it: ~8 us per table at N = 1e4, J = 20) instead of evaluating 3 J transcendentals per step and draw inside
+    // the throughput layout (14.7 ms per launch at N = 1e4, J = 20 whatever the batch): free Celerite / CARMA terms under a sampler
+    // (src/CARMA.jl:98-143).  tools/bench_per_draw_small.py.
     const bool automatic = !o.scan_config[0] && !o.no_block && B <= 768 && R >= 6;
     const bool force = !std::strcmp(o.scan_config, "block");
-    return (automatic || force) && !o.force_fallback && pioran_block_fits(R, J);
+    return (automatic || force) && pioran_block_fits(R, J) ? PerDrawForm::block_tables : PerDrawForm::no_table;
+}
+
+// Mixed mode: when only a few terms really differ between draws (QPO features on top of an approx continuum, src/psd.jl:254-261), the shared
+// terms keep using the shared table and only the per-draw terms get per-draw rows.
+MixedPlan mixed_plan(const ScanOptions& o, int64_t B, int64_t N, int32_t J, int32_t rows, int32_t npd, bool must_run)
+{
+    MixedPlan plan;
+    if (o.no_mixed && !must_run) return plan;
+    // Small batches with one or two per-draw terms (a QPO feature on an approx continuum at a few hundred live points): the windowed kernel with
+    // per-draw rows (celerite_block.hip; round 3) — same automatic range as for shared batches (block_wanted), whatever the share of per-draw terms
+    const char* cfg = o.scan_config[0] ? o.scan_config : nullptr;
+    const bool force = cfg && !std::strcmp(cfg, "block");
+    // (fewer than six rows, late round 4, tools/per_draw_few_rows.py: the generic per-draw path took 7.5 ms for 16 draws of ONE term at N = 1e4 —
+    //  1.7 ms here; 768 draws 8.2 -> 4.2 ms)
+    const bool automatic = !cfg && !o.no_block && (rows >= 6 ? B <= 512 : B <= 768);
+    // (force_fallback takes this leg away and nothing else: a batch the plan takes still runs its combined table on the scan)
+    const bool windowed = (force || automatic) && !o.force_fallback && npd >= 1 && pioran_block_fits_pd(rows, J, npd);
+    // all shared is handled by the caller; many per-draw terms: the generic per-draw path is as good.  must_run: the caller has no generic path
+    // to fall back to (theta entry: the continuum's (c, d) exist only as a shared table), so the two "not worth it" cuts — a performance
+    // heuristic, not a kernel constraint — are skipped
+    const bool any_size = must_run || windowed;
+    if (npd == 0 || npd > 8 || (!any_size && npd * 2 > J)) return plan;
+    if (rows > pioran_scan_supported_rows()) return plan;
+    // combined table: (N + 1) records of the shared rows' doubles + chunk * 2 npd * 3 doubles, addressed with 32-bit byte offsets
+    const int64_t rs_shared = rec_stride_of(rows);
+    int64_t chunk = ((int64_t)0x7fff0000 / ((N + 1) * 8) - rs_shared) / (6 * (int64_t)npd);
+    chunk = chunk > B ? B : (chunk >= 16 ? chunk & ~(int64_t)15 : chunk);
+    if (chunk < 1 || (!any_size && chunk < 16)) return plan;   // (fewer than 16 draws per table: not worth it)
+    plan.take = true; plan.windowed = windowed; plan.chunk = chunk;
+    return plan;
+}
+
+const char* value_route_cd(const ScanOptions& o, int32_t n_two_row, int32_t n_one_row, int32_t npd, int64_t B, int64_t N, bool per_draw_series,
+                           bool must_run, int64_t* chunk)
+{
+    const int32_t J = n_two_row + n_one_row + npd;
+    *chunk = 0;
+    if (must_run || B > 1) {   // (one draw is the shared case to the host entry)
+        const int32_t rows = 2 * n_two_row + n_one_row + 2 * npd;
+        const MixedPlan plan = mixed_plan(o, B, N, J, rows, npd, must_run);
+        if (plan.take) {
+            *chunk = plan.chunk;
+            if (plan.windowed) return "block+pd";
+            // the combined table on the scan, chunk by chunk: the name is the last chunk's
+            const RouteQuery last{rows, J, B - (B - 1) / plan.chunk * plan.chunk, N, true, 2 * npd, per_draw_series, 0, 0, false, false, o};
+            return scan_family(last) == ScanFamily::wide ? "wide" : "scan";
+        }
+        if (must_run) return nullptr;
+    }
+    switch (perdraw_form(o, B, 2 * J, J)) {
+        case PerDrawForm::wide_tables: return "wide (per-draw tables)";
+        case PerDrawForm::block_tables: return "block (per-draw tables)";
+        default: break;
+    }
+    const RouteQuery q{2 * J, J, B, N, false, 0, per_draw_series, 0, 0, false, false, o};
+    return value_route(q, 0, nullptr);
 }
 
 // value and gradient: the reverse mode with one draw per wavefront (celerite_tile.hip) above the windowed kernel's batch range

@@ -194,3 +194,176 @@ def test_removed_experiment_options_are_unknown():
     name = ctypes.create_string_buffer(32)
     for options, rc in ((b"gsum=1", -1), (b"dense_old_chain=2", -1), (b"dense_old_chain=1", 0), (b"no_win2=1", 0)):
         assert L.pioran_value_route(40, 20, 0, 8, 100, 0, 0, options, name, 32, None) == rc, options
+
+
+# ---- draws that bring (c, d) of their own: pioran_value_route_cd (route.hip mixed_plan, perdraw_form) ---------------------------------------------
+def route_cd(n_two, n_one, npd, B, N, options="", series=False, must_run=False):
+    return G.value_route_cd(n_two, n_one, npd, B, N, series, must_run, options)
+
+
+EDGE_J = ((3, 1, 0), (7, 2, 1), (15, 1, 0), (16, 2, 3), (23, 1, 0), (24, 2, 0), (30, 2, 0), (31, 1, 0))      # test_block_kernel_per_draw_rows_edges: J < 32
+# (two-row, one-row, per-draw terms, B, N, options, must_run) -> family; a tuple: one of these; "~block": a name without "block".  Each from an
+# assertion on pioran_celerite_config_name(-1) in the suite, but for the names no test there asserts on these paths — those are points of
+# tools/route_grid.py, which tests/test_gpu_route.py holds to the launch and profiles/value_route_cd_listing.txt to the library before the rules moved
+PINNED_CD = [
+    ((0, 0, 2, 19, 130, "", False), "block+pd"),                                      # test_gpu_parity.py:186 (J = 2; layout "block")
+    ((0, 0, 7, 19, 130, "", False), "block (per-draw tables)"),                       # test_gpu_parity.py:186 (J = 7)
+    ((0, 0, 20, 19, 130, "", False), "block (per-draw tables)"),                      # test_gpu_parity.py:186 (J = 20)
+    ((0, 0, 30, 19, 130, "", False), "block (per-draw tables)"),                      # test_gpu_parity.py:186 (J = 30)
+    ((0, 0, 2, 19, 130, "scan_config=tile", False), "block+pd"),                      # test_gpu_parity.py:186 (layout "tile": takes no per-draw (c, d))
+    ((0, 0, 20, 19, 130, "scan_config=tile", False), "block (per-draw tables)"),      # test_gpu_parity.py:186
+    ((0, 0, 2, 19, 130, "no_block=1;no_wide=1", False), ("scan", "wide")),            # test_gpu_parity.py:188 (layout "throughput")
+    ((0, 0, 30, 19, 130, "no_block=1;no_wide=1;no_win2=1", False), ("scan", "wide")), # test_gpu_parity.py:188 ("throughput_steps")
+    ((0, 0, 7, 19, 130, "no_block=1", False), ("scan", "wide")),                      # test_gpu_parity.py:188 ("latency")
+    ((0, 0, 20, 19, 130, "no_block=1;wide2=1;scan_config=wide", False), ("scan", "wide")),   # test_gpu_parity.py:188 ("latency_lean")
+    ((0, 0, 1, 16, 300, "", False), "block+pd"),                                      # test_gpu_parity.py:381
+    ((0, 0, 2, 70, 129, "", False), "block+pd"),                                      # test_gpu_parity.py:381
+    ((0, 0, 2, 300, 1000, "", False), "block+pd"),                                    # test_gpu_parity.py:381
+    ((0, 0, 1, 700, 77, "", False), "block+pd"),                                      # test_gpu_parity.py:381
+    ((0, 0, 2, 2, 40, "", False), "block+pd"),                                        # test_gpu_parity.py:381
+    ((0, 0, 1, 16, 300, "no_block=1", False), "~block"),                              # test_gpu_parity.py:385
+    ((0, 0, 2, 300, 1000, "no_block=1", False), "~block"),                            # test_gpu_parity.py:385
+    ((0, 0, 1, 700, 77, "no_block=1", False), "~block"),                              # test_gpu_parity.py:385
+    ((20, 0, 1, 37, 140, "", False), "block+pd"),                                     # test_gpu_parity.py:1472 (J = 21, one per draw)
+    ((10, 0, 2, 37, 140, "", False), "block+pd"),                                     # test_gpu_parity.py:1472 (J = 12, two)
+    ((6, 2, 1, 37, 140, "", False), "block+pd"),                                      # test_gpu_parity.py:1472 (J = 9, two one-row terms)
+    ((1, 2, 2, 37, 140, "", False), "block+pd"),                                      # test_gpu_parity.py:1472 (J = 5)
+    *[((J - npd - nreal, nreal, npd, B, N, "", False), "block+pd")                    # test_gpu_parity.py:1506 (J < 32)
+      for J, npd, nreal in EDGE_J for N, B in ((1, 3), (17, 9), (100, 300))],
+    *[((J - npd - nreal, nreal, npd, B, N, "no_block=1", False), ("wide", "scan"))    # test_gpu_parity.py:1516
+      for J, npd, nreal in EDGE_J for N, B in ((17, 9), (100, 300))],
+    ((20, 0, 1, 24, 10000, "", False), "block+pd"),                                   # test_gpu_parity.py:1539 (approx continuum + one QPO term, 24 draws)
+    ((0, 0, 10, 23, 300, "", False), "block (per-draw tables)"),                      # test_gpu_chunking.py:229
+    ((0, 0, 40, 8, 130, "", False), "wide (per-draw tables)"),                        # tools/route_grid.py (80 rows)
+    ((0, 0, 40, 300, 24, "", False), "wide (per-draw tables)"),                       # tools/route_grid.py (two chunks of tables)
+    ((0, 0, 32, 8, 130, "", False), "scan"),                                          # tools/route_grid.py (64 rows: past the windowed tables)
+    ((0, 0, 72, 8, 130, "", False), "fallback"),                                      # tools/route_grid.py (144 rows)
+    ((5, 0, 3, 37, 130, "", False), "wide"),                                          # tools/route_grid.py (three per draw: the combined table, 16 rows)
+    ((5, 0, 3, 8, 130, "", True), "wide"),                                            # tools/route_grid.py theta_points (n_qpo = 3: must run below 16 draws)
+    ((5, 0, 1, 8, 130, "", True), "block+pd"),                                        # tools/route_grid.py theta_points (n_qpo = 1)
+]
+CD_NAMES = ("block+pd", "block (per-draw tables)", "wide (per-draw tables)", "scan", "wide", "fallback")
+
+
+@pytest.mark.parametrize("query,family", PINNED_CD)
+def test_per_draw_routes_the_suite_already_asserts(query, family):
+    n_two, n_one, npd, B, N, options, must_run = query
+    got, _ = route_cd(n_two, n_one, npd, B, N, options, must_run=must_run)
+    assert got in CD_NAMES
+    if family == "~block":
+        assert "block" not in got, got
+    else:
+        assert got in ((family,) if isinstance(family, str) else family), got
+
+
+def test_every_per_draw_name_is_pinned():
+    names = [f for _, f in PINNED_CD]
+    for fam in CD_NAMES:
+        assert fam in names, fam
+
+
+MIXED_LIMIT = 0x7fff0000      # the combined table is addressed with 32-bit byte offsets
+
+
+def cd_grid():
+    """rows 1 .. 150 with 1, 2, 3, 8, 9 or all terms per draw, the other rows as two-row terms and at most one one-row term."""
+    for rows in range(1, 151):
+        for npd in (1, 2, 3, 8, 9, "all"):
+            if npd == "all":
+                if rows % 2:
+                    continue
+                npd = rows // 2
+            rest = rows - 2 * npd
+            if rest < 0:
+                continue
+            yield rows, rest // 2, rest % 2, npd
+
+
+def check_cd(query, fam, chunk, options=""):
+    rows, n_two, n_one, npd, B, N, must_run = query
+    J, R = n_two + n_one + npd, 2 * (n_two + n_one + npd)
+    forced = "scan_config=block" in options
+    assert fam in CD_NAMES or (must_run and fam is None), (query, options, fam)
+    if fam == "block+pd":
+        assert npd <= 2 and chunk >= 1, (query, options)
+        if not forced:
+            assert B <= (512 if rows >= 6 else 768), (query, options)
+    if fam == "block (per-draw tables)":
+        assert 6 <= R <= 63 and B <= 768 or forced, (query, options)
+        assert R <= 63
+    if fam == "wide (per-draw tables)":
+        assert 80 <= R <= 143, (query, options)
+    if chunk:        # mixed mode has the batch: the combined table of a chunk stays addressable
+        assert fam in ("block+pd", "scan", "wide") and 1 <= chunk <= B and npd <= 8, (query, options, fam, chunk)
+        assert (N + 1) * 8 * (3 * (rows + 2) + 2 + 6 * npd * chunk) <= MIXED_LIMIT, (query, options, chunk)
+        if not must_run and fam != "block+pd":
+            assert chunk >= 16 and (chunk % 16 == 0 or chunk == B), (query, options, chunk)
+    elif fam is not None:
+        assert fam != "block+pd" and fam != "wide"
+
+
+def test_per_draw_properties_over_the_grid():
+    """Default options over (rows, per-draw terms) x B x N with and without must_run.  B = 1 without must_run is the shared case to the host
+    entry: the rule answers for the device entry there."""
+    n = 0
+    for (rows, n_two, n_one, npd), B, N in itertools.product(cd_grid(), GRID_B, GRID_N):
+        for must_run in (False, True):
+            fam, chunk = route_cd(n_two, n_one, npd, B, N, must_run=must_run)
+            check_cd((rows, n_two, n_one, npd, B, N, must_run), fam, chunk)
+            n += 1
+    assert n == 2 * 127008
+
+
+def test_per_draw_options_over_the_grid():
+    """The options that forbid or force a family, over the whole grid.  scan_config=block lifts the batch limits and nothing else: the windowed
+    kernel with per-draw rows has a batch of any size exactly where it has two draws of the same terms and series length by default (two draws
+    are within every batch limit; what remains is what the kernel fits and mixed mode's own cuts), and so have the windowed per-draw tables
+    where mixed mode does not take the batch.
+    force_fallback takes the windowed kernels away and nothing else of mixed mode: a batch mixed mode takes runs its combined table on the scan
+    with the option set (16 858 "scan" and 11 898 "wide" of the 127 008 queries — the library did so before the rules were written down, and
+    tools/route_grid.py holds one such launch against it); every other query ends on the fallback kernel."""
+    small = {}
+    on_scan = 0
+    for (rows, n_two, n_one, npd), B, N in itertools.product(cd_grid(), GRID_B, GRID_N):
+        q = (rows, n_two, n_one, npd, B, N, False)
+        for options in ("no_block=1", "no_block=1;no_wide=1"):
+            fam, chunk = route_cd(n_two, n_one, npd, B, N, options)
+            check_cd(q, fam, chunk, options)
+            assert "block" not in fam, (q, options, fam)
+        nb_chunk = chunk
+        fam, chunk = route_cd(n_two, n_one, npd, B, N, "no_mixed=1")
+        check_cd(q, fam, chunk, "no_mixed=1")
+        assert fam != "block+pd" and chunk == 0, (q, fam)
+        fam, chunk = route_cd(n_two, n_one, npd, B, N, "scan_config=block")
+        check_cd(q, fam, chunk, "scan_config=block")
+        key = (n_two, n_one, npd, N)
+        if key not in small:
+            small[key] = route_cd(n_two, n_one, npd, 2, N)[0]
+        if B > 1:
+            assert (fam == "block+pd") == (small[key] == "block+pd"), (q, fam, small[key])
+            if small[key] == "block (per-draw tables)" and not chunk:      # (unless mixed mode has the larger batch on its combined table)
+                assert fam == small[key], (q, fam)
+        fam, chunk = route_cd(n_two, n_one, npd, B, N, "force_fallback=1")
+        assert chunk == nb_chunk, (q, chunk, nb_chunk)      # mixed mode takes what it takes without the windowed kernel
+        assert fam in ("scan", "wide") if chunk else fam == "fallback", (q, fam, chunk)
+        on_scan += chunk != 0
+    assert on_scan == 28756
+
+
+def test_per_draw_argument_validation():
+    import ctypes
+    L = pj._lib.lib()
+    name = ctypes.create_string_buffer(8)
+    chunk = ctypes.c_int64(-1)
+    assert L.pioran_value_route_cd(20, 0, 1, 24, 10000, 0, 0, None, name, 8, ctypes.byref(chunk)) == 0 and name.value == b"block+p"   # cut to the buffer
+    assert chunk.value == 24
+    assert L.pioran_value_route_cd(20, 0, 0, 24, 100, 0, 0, None, name, 8, None) == -1           # no per-draw term: pioran_value_route's business
+    assert L.pioran_value_route_cd(-1, 0, 1, 24, 100, 0, 0, None, name, 8, None) == -1
+    assert L.pioran_value_route_cd(20, 0, 1, 0, 100, 0, 0, None, name, 8, None) == -1
+    assert L.pioran_value_route_cd(20, 0, 1, 24, 100, 0, 0, b"no_such_option=1", name, 8, None) == -1
+    assert L.pioran_value_route_cd(20, 0, 1, 24, 100, 0, 0, None, None, 8, None) == -1
+    assert L.pioran_value_route_cd(20, 0, 1, 24, 2 ** 48, 0, 0, None, name, 8, None) == 0            # the longest series the entry answers for
+    assert L.pioran_value_route_cd(20, 0, 1, 24, 2 ** 48 + 1, 0, 0, None, name, 8, None) == -1
+    # the theta entry with more rows than the scan holds: refused (PIORAN_ERR_UNSUPPORTED), where the host entry goes on to the generic path
+    assert L.pioran_value_route_cd(40, 0, 1, 24, 100, 0, 1, None, name, 8, ctypes.byref(chunk)) == -4 and name.value == b"" and chunk.value == 0
+    assert L.pioran_value_route_cd(40, 0, 1, 24, 100, 0, 0, None, name, 8, None) == 0 and name.value == b"wide (p"
