@@ -246,6 +246,10 @@ int pioran_celerite_predict_var(pioran_ds* ds, int64_t B, int64_t J, const doubl
  *   grad_a, grad_b [B][J] = dlogL/da_j, dlogL/db_j;
  *   grad_c, grad_d [B][J] (may be NULL) = dlogL/dc_j, dlogL/dd_j — what QPO features (src/psd.jl:15-27), CARMA kernels
  *       (src/CARMA.jl:98-143) and free Celerite terms need; per draw also when (c, d) are shared (sum over b for a common parameter);
+ *       grad_b_j and grad_d_j of a one-row term (b_j = d_j = 0: no sine row, no phase) are structurally zero, and every reverse mode writes exactly
+ *       0.0 there — never the caller's memory left as it was, a stale value of an earlier chunk or a NaN: every kernel family stores all J entries
+ *       of each array asked for, and what it adds up for such a term is zero (the step-by-step kernels add nothing for a row without a phase).
+ *       tests/test_gpu_grad_truth.py asserts it with == on every family;
  *   grad_nu, grad_mu [B] (may be NULL);
  *   grad_y, grad_sigma2 [B][N] (may be NULL) = dlogL/dy_n and dlogL/dsigma2_n of the series in the data set — what a
  *       model that transforms the data per draw (the sampled shift of docs/src/ultranest.md:199-205) chains through.

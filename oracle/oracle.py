@@ -398,6 +398,64 @@ def sim_truth(a, b, c, d, t, s2, q, dtype=np.longdouble):
     return L @ q
 
 
+def logl_grad_truth(a, b, c, d, t, y, s2, mu=0.0, nu=1.0, shift=None, dtype=np.longdouble):
+    """Truth for log L and its gradient (pioran_celerite_logl_grad, pioran_celerite_logl_grad_shift) of one draw, dense in `dtype` and in
+    the entry's conventions: (y, s2) are the data set's, the draw is evaluated on yc = y - mu with the variances nu s2 (both formed in fp64, as
+    every caller of the fp64 references forms them), or — shift given, the data set then holds raw flux — on log(y - shift) - mu with
+    nu s2 / (y - shift)^2, the transform of table.hip carried out in `dtype` and differentiated through; no Jacobian term: the entry returns
+    the likelihood of the transformed series.  With K = k(|t_i - t_j|) + diag(nu s2) = L L' (_truth_cholesky), K^-1 from N triangular solves,
+    z = K^-1 yc and G = (z z' - K^-1) / 2 = dlogL/dK:
+        logl          -yc'z / 2 - sum log L_nn - N log(2 pi) / 2
+        grad_a_j      sum_mn G_mn e^(-c_j D) cos(d_j D)          D = |t_m - t_n|, the diagonal included
+        grad_b_j      sum_mn G_mn e^(-c_j D) sin(d_j D)
+        grad_c_j      sum_mn G_mn (-D) e^(-c_j D) (a_j cos + b_j sin)
+        grad_d_j      sum_mn G_mn D e^(-c_j D) (-a_j sin + b_j cos)          (grad_b_j = grad_d_j = 0 exactly where b_j = d_j = 0)
+        grad_y        -z                       grad_sigma2   nu G_nn          (of the data set's series; without shift)
+        grad_mu       sum z_n                  grad_nu       sum S_n G_nn     (S = s2, or s2 / (y - shift)^2)
+        grad_shift    sum z_n / v_n + 2 nu G_nn s2_n / v_n^3                  (v = y - shift)
+    and, as the scale of the three sums, the sum of the absolute values of their terms: scale_mu, scale_nu, scale_shift.  Shares no code with
+    the celerite recurrences or their adjoints.  Raises LinAlgError when K is not positive definite.  Returns a dict of `dtype` values;
+    tests/golden/grad_truth.npz (oracle/make_grad_truth.py) holds this function's deviation from a 50-digit evaluation."""
+    a, b, c, d, t = _truth_inputs(dtype, a, b, c, d, t)
+    y64, s64 = (np.asarray(v, dtype=np.float64).reshape(-1) for v in (y, s2))
+    if shift is None:
+        yc, S = (y64 - float(mu)).astype(dtype), s64.astype(dtype)
+        sk = (float(nu) * s64).astype(dtype)
+    else:
+        v = y64.astype(dtype) - dtype(shift)
+        if not (v > 0).all():
+            raise ValueError("y - shift must be positive")
+        yc, S = np.log(v) - dtype(mu), s64.astype(dtype) / (v * v)
+        sk = dtype(nu) * S
+    N = len(t)
+    L = _truth_cholesky(a, b, c, d, t, sk, dtype)
+    W = np.zeros((N, N), dtype=dtype)                  # L^-1, row by row
+    for n in range(N):
+        W[n, :n] = -(L[n, :n] @ W[:n, :n]) / L[n, n]
+        W[n, n] = 1 / L[n, n]
+    Kinv = W.T @ W
+    z = W.T @ (W @ yc)
+    G = (np.outer(z, z) - Kinv) / 2
+    pi = 4 * np.arctan(dtype(1))
+    out = {"logl": -(yc @ z) / 2 - np.log(np.diag(L)).sum() - N * np.log(2 * pi) / 2}
+    D = np.abs(t[:, None] - t[None, :])
+    ga, gb, gc, gd = (np.zeros(len(a), dtype=dtype) for _ in range(4))
+    for j in range(len(a)):
+        E = np.exp(-c[j] * D)
+        GEc, GEs = G * E * np.cos(d[j] * D), G * E * np.sin(d[j] * D)
+        ga[j], gb[j] = GEc.sum(), GEs.sum()
+        gc[j] = -(D * (a[j] * GEc + b[j] * GEs)).sum()
+        gd[j] = (D * (b[j] * GEc - a[j] * GEs)).sum()
+    g = np.diag(G)
+    out.update(grad_a=ga, grad_b=gb, grad_c=gc, grad_d=gd, grad_y=-z, grad_sigma2=dtype(nu) * g,
+               grad_mu=z.sum(), scale_mu=np.abs(z).sum(), grad_nu=(S * g).sum(), scale_nu=np.abs(S * g).sum())
+    if shift is not None:
+        terms = np.concatenate([z / v, 2 * dtype(nu) * g * s64.astype(dtype) / (v * v * v)])
+        out.update(grad_shift=terms.sum(), scale_shift=np.abs(terms).sum())
+        out["grad_y"] = out["grad_sigma2"] = None      # (the entry does not return them for the transformed series)
+    return out
+
+
 def dense_nll_numpy(a, b, c, d, t, y, sigma2):
     """src/direct_solver.jl:6-21 with numpy's LAPACK Cholesky (second implementation)."""
     a = np.asarray(a, float); b = np.asarray(b, float)
