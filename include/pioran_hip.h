@@ -345,12 +345,61 @@ int pioran_lombscargle_batch(pioran_ctx* ctx, int64_t N, int64_t B, int64_t F, c
 int pioran_lombscargle_batch_dev(pioran_ctx* ctx, int64_t N, int64_t B, int64_t F, const double* dt, const double* dY,
                                  const double* dyerr, const double* dfreq, int fit_mean, int center_data, double* dpower,
                                  int32_t* dstatus);
+/* ---- quantiles and means over the draw axis (what every posterior predictive check of the reference ends in: plot_ppc_timeseries,
+ * src/plots_diagnostics.jl:805-816; plot_lsp_ppc :547-559; plot_psd_ppc :417-447) --------------------------------------------------------
+ * X [B][ldx] holds one draw per row (the layout pioran_celerite_rand_posterior and pioran_lombscargle_batch produce).  Every output column m is
+ * reduced over the rows with status 0 (status NULL: all rows) to Q quantiles and a mean.  The value of draw b in column m is formed while loading:
+ *     v = X[b][cols ? cols[m] : m];   shift given: v = exp(v + shift[b])  (src/plots_diagnostics.jl:663);
+ *     ref, scale given: v = (ref[m] - v) / scale[m]  (the standardised residual of :812).
+ * The quantile is Statistics.quantile with its defaults (type 7).  For the K kept values of a column sorted ascending, v[1..K]:
+ *     aleph = K p + (1 - p),  j = clamp(trunc(aleph), 1, K - 1),  gamma = clamp(aleph - j, 0, 1),  a = v[j], b = v[j+1]  (K = 1: a = b = v[1]),
+ *     q = a + gamma (b - a) where a, b are finite and |a - b| <= 2^-26 max(|a|, |b|), else q = (1 - gamma) a + gamma b,
+ * every operation rounded on its own in fp64: the result has the bits of the numpy twin tools/quantiles_proto.py, which is the definition.
+ * (The condition on |a - b| is this library's: with it p = 0 and p = 1 return the minimum and the maximum exactly, which the first form alone
+ * does not once b - a rounds.)
+ * A NaN among the kept values of a column gives NaN in its quantiles and its mean; +-inf sort to the ends and take the second form; K = 0 gives
+ * NaN everywhere.  The mean is summed in an order that depends on B and the sorted position only, so neither Mc, cols nor a split of the columns
+ * over several calls changes a bit of any output.
+ *   X [B][ldx], status [B] or NULL, shift [B] or NULL, cols [Mc] int32 or NULL (any order, repeats allowed; NULL: all M columns, Mc is not read),
+ *   ref, scale [Mc] or both NULL, probs [Q] in [0, 1], quant [Q][Mc], mean [Mc] or NULL, kept: one int32 (K) or NULL.
+ * A column is sorted inside one workgroup's LDS: B > 4096 is PIORAN_ERR_UNSUPPORTED, before any GPU call.
+ * PIORAN_ERR_ARG, before any GPU call: NULL ctx / X / probs / quant; B, M, Q < 1; ldx < M; Mc < 1 with cols; exactly one of ref and scale; a
+ * prob outside [0, 1] or NaN; and in the host form a cols entry outside [0, M) or a scale that is zero or not finite (the device form cannot
+ * look at its arrays: a column index outside [0, M) reads as NaN there).
+ * The host form stages X [B][ldx] in a resident buffer of the context (PIORAN_ERR_ALLOC where it does not fit what the context may take,
+ * "workspace_limit_mb"; pioran_ctx_trim releases it) and blocks; the device form takes device pointers for everything but probs, which is
+ * on the host and copied, and is asynchronous on the context's stream.  pioran_celerite_config_name(-1) afterwards:
+ * "quantiles (sort over draws)". */
+int pioran_quantiles_batch(pioran_ctx* ctx, int64_t B, int64_t M, int64_t ldx, const double* X, const int32_t* status,
+                           const double* shift, int64_t Mc, const int32_t* cols, const double* ref, const double* scale, int64_t Q,
+                           const double* probs, double* quant, double* mean, int32_t* kept);
+int pioran_quantiles_batch_dev(pioran_ctx* ctx, int64_t B, int64_t M, int64_t ldx, const double* dX, const int32_t* dstatus,
+                               const double* dshift, int64_t Mc, const int32_t* dcols, const double* dref, const double* dscale,
+                               int64_t Q, const double* probs, double* dquant, double* dmean, int32_t* dkept);
+/* pioran_celerite_rand_posterior with its sink changed: the B draws at tau stay on the device ([B][M] and their status, in buffers of the context
+ * that count against "workspace_limit_mb" and are released by pioran_ctx_trim; PIORAN_ERR_ALLOC before any draw is computed where they do not
+ * fit), and what comes back are their summaries over the draws with status 0 — the arrays plot_ppc_timeseries draws (src/plots_diagnostics.jl:805-816):
+ *   ts_quant [Q][M], ts_mean [M] or NULL: quantiles and mean of the draws at every tau;
+ *   Nres > 0: res_quant [Q][Nres], res_mean [Nres] or NULL of (res_ref[k] - draw[res_cols[k]]) / res_scale[k] — with res_cols the positions of the
+ *   data times in tau, res_ref = y and res_scale = yerr the standardised residuals of :812 (res_cols NULL: Nres must be M, columns in order);
+ *   Nres == 0: no residual summary, the res_* arguments are not read;
+ *   status [B] or NULL as pioran_celerite_rand_posterior gives it; kept: the number of draws with status 0, or NULL.
+ * backtransform != 0 (needs shift): the summaries are of exp(draw + shift_b), as the reference plots the log-flux models (:663).
+ * The draws are the bits pioran_celerite_rand_posterior returns for the same arguments; the reduction is pioran_quantiles_batch's.
+ * PIORAN_ERR_ARG / PIORAN_ERR_UNSUPPORTED as the two entries have them, all before any GPU call; Nres < 0 and backtransform without shift
+ * are PIORAN_ERR_ARG. */
+int pioran_celerite_rand_posterior_summary(pioran_ds* ds, int64_t B, int64_t J, const double* A, const double* Bc, const double* C,
+                                           const double* Dd, int cd_shared, const double* mu, const double* nu, const double* shift,
+                                           int64_t M, const double* tau, const double* q_data, const double* q_new, const double* eps,
+                                           int backtransform, int64_t Q, const double* probs, double* ts_quant, double* ts_mean,
+                                           int64_t Nres, const int32_t* res_cols, const double* res_ref, const double* res_scale,
+                                           double* res_quant, double* res_mean, int32_t* status, int32_t* kept);
 /* Name of the kernel configuration a large batch with R active rows (all terms with both rows when R is even) runs on;
  * R == 0: the configuration the calling thread's last throughput-layout launch actually ran on; R < 0: the kernel FAMILY of the
  * calling thread's last launch — "tile" (windowed form, one draw per wavefront: large batches from 49 rows on and batch sizes between the
  * passes of the throughput layouts), "block" (windowed kernel), "block+pd" (with per-draw rows), "block (per-draw tables)", "wide"
  * (latency layout), "scan" (throughput layouts), "fallback", "block (windowed gradient[, per-draw tables])",
- * "wide (step-by-step gradient)", "wide (step-by-step variance)" (diagnostics). */
+ * "wide (step-by-step gradient)", "wide (step-by-step variance)", "periodogram (fp64 matrix product)", "quantiles (sort over draws)" (diagnostics). */
 const char* pioran_celerite_config_name(int64_t R);
 /* Diagnostics (no GPU needed): the automatic choice between the windowed form with one draw per wavefront (1, "tile") and the other families (0)
  * for a shared-table batch of B draws with R active rows; `pass` = draws per pass of the step-by-step layout of these rows (0 = unknown:

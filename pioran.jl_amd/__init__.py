@@ -4,8 +4,8 @@ Directory name has a dot, so import it through the repo-root shim: `import piora
 """
 from . import _lib, farm  # noqa: F401
 from .gp import (Context, CustomMean, Dataset, Farm, FiniteScalableGP, PosteriorGP, ScalableGP, cov, default_context,
-                 log_likelihood, log_likelihood_direct, logl, logpdf, logpdf_batch, lombscargle, lsp_ppc, lsp_ppc_frequencies, mean, posterior, ppc_t_pred, ppc_timeseries, predict, predict_cov, predict_direct,
-                 predict_var, rand, rand_posterior, simulate, std, var)
+                 log_likelihood, log_likelihood_direct, logl, logpdf, logpdf_batch, lombscargle, lsp_ppc, lsp_ppc_frequencies, mean, posterior, ppc_t_pred, ppc_timeseries, ppc_timeseries_summary, predict, predict_cov, predict_direct,
+                 predict_var, quantiles, rand, rand_posterior, simulate, std, var)
 from .kernels import (CARMA, Celerite, Exp, ScaledKernel, SemiSeparable, SHO, SumOfCelerite, SumOfSemiSeparable,
                       SumOfTerms, celerite_coefs)
 from .psd import (QPO, DoubleBendingPowerLaw, SingleBendingPowerLaw, approx, approx_batch, approx_batch_vjp, build_approx,

@@ -57,6 +57,10 @@ SIGNATURES = {
     "pioran_celerite_simulate": (ctypes.c_int, [c_void_p, i64, i64, i64] + [c_void_p] * 4 + [ctypes.c_int] + [c_void_p] * 4),
     "pioran_lombscargle_batch": (ctypes.c_int, [c_void_p, i64, i64, i64] + [c_void_p] * 4 + [ctypes.c_int, ctypes.c_int, c_void_p, c_void_p]),
     "pioran_lombscargle_batch_dev": (ctypes.c_int, [c_void_p, i64, i64, i64] + [c_void_p] * 4 + [ctypes.c_int, ctypes.c_int, c_void_p, c_void_p]),
+    "pioran_quantiles_batch": (ctypes.c_int, [c_void_p, i64, i64, i64] + [c_void_p] * 3 + [i64] + [c_void_p] * 3 + [i64] + [c_void_p] * 4),
+    "pioran_quantiles_batch_dev": (ctypes.c_int, [c_void_p, i64, i64, i64] + [c_void_p] * 3 + [i64] + [c_void_p] * 3 + [i64] + [c_void_p] * 4),
+    "pioran_celerite_rand_posterior_summary": (ctypes.c_int, [c_void_p, i64, i64] + [c_void_p] * 4 + [ctypes.c_int] + [c_void_p] * 3 + [i64] + [c_void_p] * 4 +
+                                               [ctypes.c_int, i64] + [c_void_p] * 3 + [i64] + [c_void_p] * 7),
     "pioran_celerite_config_name": (ctypes.c_char_p, [i64]),
     "pioran_ctx_fp64_probe": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_double, ctypes.POINTER(ctypes.c_double)]),
     "pioran_tile_choice": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),

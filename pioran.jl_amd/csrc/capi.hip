@@ -46,6 +46,9 @@ struct pioran_ctx {
     // the caller's normals q_data | q_new | eps, the normals on the merged grid, the simulation's stores | xi | realisations | log L | status,
     // the index maps, the residual series Y | S2, the shifts, a chunk's draws | their status
     Buf brqd, brqn, breps, brqT, brstores, brxi, brf, brsout, brsst, brmaps, brY, brS2, brshift, brres, brst;
+    // quantiles over draws (quantiles.hip): the resident draws [B][M] | their status [B] (the summary entry's sink; the host form's staged X and
+    // status), the small inputs probs | shift | ref | scale, the indices cols | kept, the results quant | mean
+    Buf bqX, bqst, bqin, bqidx, bqout;
     // scalar entry point: the last series' time stamps stay resident (samplers call logl with the same t)
     pioran_ds* scalar_ds = nullptr;
     std::vector<double> scalar_t;
@@ -928,7 +931,7 @@ int pioran_ctx_destroy(pioran_ctx* ctx)
     ctx->scalar_ds = nullptr;
     pioran_ctx::Buf* bufs[] = {&ctx->bA, &ctx->bB, &ctx->bC, &ctx->bD, &ctx->bmu, &ctx->bnu, &ctx->bY,
                                &ctx->bS2, &ctx->bout, &ctx->bst, &ctx->bscratch, &ctx->bK, &ctx->bwork, &ctx->bshift, &ctx->bgtab, &ctx->bq, &ctx->bpair, &ctx->btp, &ctx->btprow, &ctx->brqd, &ctx->brqn, &ctx->breps, &ctx->brqT, &ctx->brstores, &ctx->brxi, &ctx->brf, &ctx->brsout, &ctx->brsst, &ctx->brmaps,
-                               &ctx->brY, &ctx->brS2, &ctx->brshift, &ctx->brres, &ctx->brst};
+                               &ctx->brY, &ctx->brS2, &ctx->brshift, &ctx->brres, &ctx->brst, &ctx->bqX, &ctx->bqst, &ctx->bqin, &ctx->bqidx, &ctx->bqout};
     for (auto* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto& e : ctx->ev)
@@ -954,7 +957,7 @@ int pioran_ctx_trim(pioran_ctx* ctx)
     pioran_ctx::Buf* bufs[] = {&ctx->bA, &ctx->bB, &ctx->bC, &ctx->bD, &ctx->bmu, &ctx->bnu, &ctx->bY,
                                &ctx->bS2, &ctx->bout, &ctx->bst, &ctx->bscratch, &ctx->bK, &ctx->bwork, &ctx->bshift, &ctx->bgtab, &ctx->bq, &ctx->bpair, &ctx->btp, &ctx->btprow,
                                &ctx->blstab, &ctx->blsaux, &ctx->brqd, &ctx->brqn, &ctx->breps, &ctx->brqT, &ctx->brstores, &ctx->brxi, &ctx->brf, &ctx->brsout, &ctx->brsst, &ctx->brmaps,
-                               &ctx->brY, &ctx->brS2, &ctx->brshift, &ctx->brres, &ctx->brst};
+                               &ctx->brY, &ctx->brS2, &ctx->brshift, &ctx->brres, &ctx->brst, &ctx->bqX, &ctx->bqst, &ctx->bqin, &ctx->bqidx, &ctx->bqout};
     for (auto* b : bufs) {
         if (b->p) (void)hipFree(b->p);
         b->p = nullptr;
@@ -2002,9 +2005,19 @@ struct MergedGrid {
     }
 };
 
+// Where the draws of a call go: the caller's host arrays out [B][M] | status [B] (nullptr: not wanted), or — the summary entry — device arrays
+// dev_out [.][M] | dev_status [.] that stay resident for the reduction over the draws.  from_draw: the sink of the draws from b0 on.
+struct DrawSink {
+    double* out = nullptr;
+    int32_t* status = nullptr;
+    double* dev_out = nullptr;
+    int32_t* dev_status = nullptr;
+    DrawSink from_draw(int64_t b0, int64_t M) const { return {at(out, b0 * M), at(status, b0), at(dev_out, b0 * M), at(dev_status, b0)}; }
+};
+
 // B draws at M times on shared (c, d); chunks of at most 256 draws.  `simds`: the scratch data set on grid.T with y = 0, sigma2 = 0.
 static int rand_posterior_batch(pioran_ds* ds, pioran_ds* simds, int64_t B, int64_t J, const DrawChunk& in, const double* shift, const MergedGrid& grid,
-                                int64_t M, const double* tau, const double* q_data, const double* q_new, const double* eps, double* out, int32_t* status)
+                                int64_t M, const double* tau, const double* q_data, const double* q_new, const double* eps, const DrawSink& sink)
 {
     pioran_ctx* ctx = ds->ctx;
     PrepState &s = ds->host, &ss = simds->host;
@@ -2112,27 +2125,28 @@ static int rand_posterior_batch(pioran_ds* ds, pioran_ds* simds, int64_t B, int6
         }
         if (rc) { ctx->last_err = "posterior draw: prediction launch failed"; return rc; }
         if (b0 == 0) HIPCHK(ctx, mark(8));
-        // 5. the draws, in the caller's order of tau
+        // 5. the draws, in the caller's order of tau: into the chunk's buffer, or straight to their rows of a device sink
+        const DrawSink to = sink.from_draw(b0, M);
         if ((rc = pioran_launch_rp_combine(nb, M, P, itau, (const double*)mean.p, (const double*)fsim.p, (const int32_t*)sst.p, (const int32_t*)ctx->bst.p,
-                                           (double*)res.p, (int32_t*)rst.p, ctx->stream)))
+                                           to.dev_out ? to.dev_out : (double*)res.p, to.dev_out ? to.dev_status : (int32_t*)rst.p, ctx->stream)))
             return rc;
         if (b0 == 0) HIPCHK(ctx, mark(9));
         // 6. download
-        if ((rc = download(ctx, out + b0 * M, res.p, (size_t)nb * M * sizeof(double)))) return rc;
-        if (status && (rc = download(ctx, status + b0, rst.p, nb * sizeof(int32_t)))) return rc;
+        if (to.out && (rc = download(ctx, to.out, res.p, (size_t)nb * M * sizeof(double)))) return rc;
+        if (to.out && to.status && (rc = download(ctx, to.status, rst.p, nb * sizeof(int32_t)))) return rc;
         SYNC(ctx);
     }
     return PIORAN_OK;
 }
 
-int pioran_celerite_rand_posterior(pioran_ds* ds, int64_t B, int64_t J, const double* A, const double* Bc, const double* C, const double* Dd,
-                                   int cd_shared, const double* mu, const double* nu, const double* shift, int64_t M, const double* tau,
-                                   const double* q_data, const double* q_new, const double* eps, double* out, int32_t* status)
+// What pioran_celerite_rand_posterior and its summary form share: the checks that need no GPU (rand_posterior_refuse), then the merged grid
+// and the draws into `sink` (rand_posterior_into).
+static int rand_posterior_refuse(pioran_ds* ds, int64_t B, int64_t J, const double* A, const double* Bc, const double* C, const double* Dd, int cd_shared,
+                                 int64_t M, const double* tau, const double* q_data, const double* q_new, const double* eps)
 {
-    if (!ds || B < 1 || J < 1 || M < 1 || !A || !Bc || !C || !Dd || !tau || !q_data || !q_new || !eps || !out) return PIORAN_ERR_ARG;
+    if (!ds || B < 1 || J < 1 || M < 1 || !A || !Bc || !C || !Dd || !tau || !q_data || !q_new || !eps) return PIORAN_ERR_ARG;
     for (int64_t m = 0; m < M; ++m)
         if (!std::isfinite(tau[m])) return PIORAN_ERR_ARG;
-    pioran_ctx* ctx = ds->ctx;
     const int64_t N = ds->N;
     if (N + M > 0x7fffffff) return PIORAN_ERR_UNSUPPORTED;
     // rows past the step-by-step kernels: refused before any upload or allocation (the row count prepare_shared arrives at: a term with d = 0 and
@@ -2150,6 +2164,16 @@ int pioran_celerite_rand_posterior(pioran_ds* ds, int64_t B, int64_t J, const do
     const bool one_batch = cd_shared || B == 1;
     for (int64_t b = 0; b < (one_batch ? 1 : B); ++b)
         if (rows_of(one_batch ? B : 1, Bc + b * J, Dd + b * J) > max_rows) return PIORAN_ERR_UNSUPPORTED;
+    return PIORAN_OK;
+}
+
+static int rand_posterior_into(pioran_ds* ds, int64_t B, int64_t J, const double* A, const double* Bc, const double* C, const double* Dd, int cd_shared,
+                               const double* mu, const double* nu, const double* shift, int64_t M, const double* tau, const double* q_data,
+                               const double* q_new, const double* eps, const DrawSink& sink)
+{
+    pioran_ctx* ctx = ds->ctx;
+    const int64_t N = ds->N;
+    const bool one_batch = cd_shared || B == 1;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     // the merged grid and its index maps, once per call: the data times come back from the data set
     std::vector<double> t((size_t)N);
@@ -2162,12 +2186,164 @@ int pioran_celerite_rand_posterior(pioran_ds* ds, int64_t B, int64_t J, const do
     int rc = series.create_zeros(ctx, grid.P, grid.T.data(), zero_s2.data());
     if (rc) return rc;
     const DrawChunk in{A, Bc, C, Dd, mu, nu, nullptr, nullptr};
-    if (one_batch) return rand_posterior_batch(ds, series.ds, B, J, in, shift, grid, M, tau, q_data, q_new, eps, out, status);
+    if (one_batch) return rand_posterior_batch(ds, series.ds, B, J, in, shift, grid, M, tau, q_data, q_new, eps, sink);
     // (c, d) per draw: every draw is its own one-draw batch with its own tables, on the same merged grid
     return each_draw(B, [&](int64_t b) {
         return rand_posterior_batch(ds, series.ds, 1, J, in.from_draw(b, J, 0), at(shift, b), grid, M, tau, q_data + b * N, q_new + b * M, eps + b * N,
-                                    out + b * M, at(status, b));
+                                    sink.from_draw(b, M));
     });
+}
+
+int pioran_celerite_rand_posterior(pioran_ds* ds, int64_t B, int64_t J, const double* A, const double* Bc, const double* C, const double* Dd,
+                                   int cd_shared, const double* mu, const double* nu, const double* shift, int64_t M, const double* tau,
+                                   const double* q_data, const double* q_new, const double* eps, double* out, int32_t* status)
+{
+    if (!out) return PIORAN_ERR_ARG;
+    if (const int rc = rand_posterior_refuse(ds, B, J, A, Bc, C, Dd, cd_shared, M, tau, q_data, q_new, eps)) return rc;
+    DrawSink sink;
+    sink.out = out;
+    sink.status = status;
+    return rand_posterior_into(ds, B, J, A, Bc, C, Dd, cd_shared, mu, nu, shift, M, tau, q_data, q_new, eps, sink);
+}
+
+// ---- quantiles and means over the draw axis (quantiles.hip) ------------------------------------------------------------------------------
+// what both forms can see without looking at a device array
+static int quantiles_refuse(const void* ctx, int64_t B, int64_t M, int64_t ldx, const void* X, int64_t Mc, const int32_t* cols, const double* ref,
+                            const double* scale, int64_t Q, const double* probs, const double* quant)
+{
+    if (!ctx || !X || !probs || !quant || B < 1 || M < 1 || Q < 1 || ldx < M) return PIORAN_ERR_ARG;
+    if (cols && Mc < 1) return PIORAN_ERR_ARG;
+    if ((ref != nullptr) != (scale != nullptr)) return PIORAN_ERR_ARG;
+    for (int64_t q = 0; q < Q; ++q)
+        if (!(probs[q] >= 0.0 && probs[q] <= 1.0)) return PIORAN_ERR_ARG;   // NaN included
+    return B > pioran_quantiles_max_draws() ? PIORAN_ERR_UNSUPPORTED : PIORAN_OK;
+}
+
+// ... and what only a host array shows
+static int quantiles_refuse_host(int64_t M, int64_t Mc, const int32_t* cols, const double* scale)
+{
+    for (int64_t m = 0; cols && m < Mc; ++m)
+        if (cols[m] < 0 || cols[m] >= M) return PIORAN_ERR_ARG;
+    for (int64_t m = 0; scale && m < Mc; ++m)
+        if (!std::isfinite(scale[m]) || scale[m] == 0.0) return PIORAN_ERR_ARG;
+    return PIORAN_OK;
+}
+
+int pioran_quantiles_batch_dev(pioran_ctx* ctx, int64_t B, int64_t M, int64_t ldx, const double* dX, const int32_t* dstatus, const double* dshift,
+                               int64_t Mc, const int32_t* dcols, const double* dref, const double* dscale, int64_t Q, const double* probs,
+                               double* dquant, double* dmean, int32_t* dkept)
+{
+    if (const int rc = quantiles_refuse(ctx, B, M, ldx, dX, Mc, dcols, dref, dscale, Q, probs, dquant)) return rc;
+    if (!dcols) Mc = M;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (const int rc = upload(ctx, ctx->bqin, probs, (size_t)Q * sizeof(double))) return rc;
+    g_last_kernel = "quantiles (sort over draws)";
+    return pioran_launch_quantiles(B, M, ldx, dX, dstatus, dshift, Mc, dcols, dref, dscale, Q, (const double*)ctx->bqin.p, dquant, dmean, dkept,
+                                   ctx->stream);
+}
+
+// The small inputs of a reduction on the device — probs [Q] | shift [B] | ref [Mc] | scale [Mc] in bqin, cols [Mc] | kept [1] in bqidx — and
+// the reduction of the resident dX [B][ldx] | dstatus into bqout = quant [Q][Mc] | mean [Mc], which go to the caller's arrays (delivered by the
+// next synchronisation).  shift, cols, ref / scale, mean, kept: nullptr = not part of the call.
+static int quantiles_reduce(pioran_ctx* ctx, int64_t B, int64_t M, int64_t ldx, const double* dX, const int32_t* dstatus, const double* shift, int64_t Mc,
+                            const int32_t* cols, const double* ref, const double* scale, int64_t Q, const double* probs, double* quant, double* mean,
+                            int32_t* kept)
+{
+    int rc;
+    std::vector<double> in(probs, probs + Q);
+    const size_t o_shift = in.size();
+    if (shift) in.insert(in.end(), shift, shift + B);
+    const size_t o_ref = in.size();
+    if (ref) { in.insert(in.end(), ref, ref + Mc); in.insert(in.end(), scale, scale + Mc); }
+    // the two calls of the summary entry follow each other on the stream without a synchronisation: the second must not move the buffers the first reads
+    if ((rc = upload(ctx, ctx->bqin, in.data(), in.size() * sizeof(double)))) return rc;
+    if ((rc = ensure(ctx, ctx->bqidx, (size_t)(Mc + 1) * sizeof(int32_t)))) return rc;
+    if (cols) HIPCHK(ctx, hipMemcpyAsync(ctx->bqidx.p, cols, (size_t)Mc * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = ensure(ctx, ctx->bqout, (size_t)(Q + 1) * (size_t)Mc * sizeof(double)))) return rc;
+    const double* din = (const double*)ctx->bqin.p;
+    int32_t* didx = (int32_t*)ctx->bqidx.p;
+    double* dq = (double*)ctx->bqout.p;
+    g_last_kernel = "quantiles (sort over draws)";
+    if ((rc = pioran_launch_quantiles(B, M, ldx, dX, dstatus, shift ? din + o_shift : nullptr, Mc, cols ? didx : nullptr, ref ? din + o_ref : nullptr,
+                                      ref ? din + o_ref + Mc : nullptr, Q, din, dq, mean ? dq + Q * Mc : nullptr, kept ? didx + Mc : nullptr, ctx->stream))) {
+        if (rc == PIORAN_ERR_HIP && ctx->last_err.empty()) ctx->last_err = "quantile launch failed";
+        return rc;
+    }
+    if ((rc = download(ctx, quant, dq, (size_t)Q * (size_t)Mc * sizeof(double)))) return rc;
+    if (mean && (rc = download(ctx, mean, dq + Q * Mc, (size_t)Mc * sizeof(double)))) return rc;
+    if (kept && (rc = download(ctx, kept, didx + Mc, sizeof(int32_t)))) return rc;
+    return PIORAN_OK;
+}
+
+// the resident draws [B][ld] and their status: refused with the out-of-memory code where they do not fit what the context may take
+static int quantiles_resident(pioran_ctx* ctx, int64_t B, int64_t ld)
+{
+    const size_t bytes = (size_t)B * (size_t)ld * sizeof(double);
+    if (!ws_fits(ctx, ctx->bqX, bytes)) { ctx->last_err = "the draws do not fit the context's workspace budget"; return PIORAN_ERR_ALLOC; }
+    if (const int rc = ensure(ctx, ctx->bqX, bytes)) return rc;
+    return ensure(ctx, ctx->bqst, (size_t)B * sizeof(int32_t));
+}
+
+int pioran_quantiles_batch(pioran_ctx* ctx, int64_t B, int64_t M, int64_t ldx, const double* X, const int32_t* status, const double* shift, int64_t Mc,
+                           const int32_t* cols, const double* ref, const double* scale, int64_t Q, const double* probs, double* quant, double* mean,
+                           int32_t* kept)
+{
+    if (const int rc = quantiles_refuse(ctx, B, M, ldx, X, Mc, cols, ref, scale, Q, probs, quant)) return rc;
+    if (!cols) Mc = M;
+    if (const int rc = quantiles_refuse_host(M, Mc, cols, scale)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    PendingGuard guard(ctx);
+    int rc;
+    if ((rc = quantiles_resident(ctx, B, ldx))) return rc;
+    // (the last row is read up to column M only: the caller's array may end there)
+    HIPCHK(ctx, hipMemcpyAsync(ctx->bqX.p, X, ((size_t)(B - 1) * (size_t)ldx + (size_t)M) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (status) HIPCHK(ctx, hipMemcpyAsync(ctx->bqst.p, status, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = quantiles_reduce(ctx, B, M, ldx, (const double*)ctx->bqX.p, status ? (const int32_t*)ctx->bqst.p : nullptr, shift, Mc, cols, ref, scale, Q,
+                               probs, quant, mean, kept)))
+        return rc;
+    SYNC(ctx);
+    return PIORAN_OK;
+}
+
+int pioran_celerite_rand_posterior_summary(pioran_ds* ds, int64_t B, int64_t J, const double* A, const double* Bc, const double* C, const double* Dd,
+                                           int cd_shared, const double* mu, const double* nu, const double* shift, int64_t M, const double* tau,
+                                           const double* q_data, const double* q_new, const double* eps, int backtransform, int64_t Q,
+                                           const double* probs, double* ts_quant, double* ts_mean, int64_t Nres, const int32_t* res_cols,
+                                           const double* res_ref, const double* res_scale, double* res_quant, double* res_mean, int32_t* status,
+                                           int32_t* kept)
+{
+    // every bad argument first, then what is not supported; nothing here touches the GPU
+    const int rdraw = rand_posterior_refuse(ds, B, J, A, Bc, C, Dd, cd_shared, M, tau, q_data, q_new, eps);
+    if (rdraw == PIORAN_ERR_ARG) return rdraw;
+    if (Nres < 0 || (backtransform && !shift)) return PIORAN_ERR_ARG;
+    const bool with_res = Nres > 0;
+    if (with_res && (!res_ref || !res_scale || !res_quant || (!res_cols && Nres != M))) return PIORAN_ERR_ARG;
+    const int rquant = quantiles_refuse(ds, B, M, M, tau, Nres, with_res ? res_cols : nullptr, with_res ? res_ref : nullptr,
+                                        with_res ? res_scale : nullptr, Q, probs, ts_quant);
+    if (rquant == PIORAN_ERR_ARG) return rquant;
+    if (with_res)
+        if (const int rc = quantiles_refuse_host(M, Nres, res_cols, res_scale)) return rc;
+    if (rdraw) return rdraw;
+    if (rquant) return rquant;
+    pioran_ctx* ctx = ds->ctx;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = quantiles_resident(ctx, B, M))) return rc;   // before any draw is computed
+    DrawSink sink;
+    sink.dev_out = (double*)ctx->bqX.p;
+    sink.dev_status = (int32_t*)ctx->bqst.p;
+    if ((rc = rand_posterior_into(ds, B, J, A, Bc, C, Dd, cd_shared, mu, nu, shift, M, tau, q_data, q_new, eps, sink))) return rc;
+    PendingGuard guard(ctx);
+    const double* bt = backtransform ? shift : nullptr;
+    if ((rc = quantiles_reduce(ctx, B, M, M, sink.dev_out, sink.dev_status, bt, M, nullptr, nullptr, nullptr, Q, probs, ts_quant, ts_mean, kept))) return rc;
+    SYNC(ctx);   // bqin / bqidx / bqout are the second reduction's as well
+    if (with_res) {
+        if ((rc = quantiles_reduce(ctx, B, M, M, sink.dev_out, sink.dev_status, bt, Nres, res_cols, res_ref, res_scale, Q, probs, res_quant, res_mean, kept)))
+            return rc;
+    }
+    if (status && (rc = download(ctx, status, sink.dev_status, (size_t)B * sizeof(int32_t)))) return rc;
+    SYNC(ctx);
+    return PIORAN_OK;
 }
 
 // ---- batched Lomb-Scargle periodogram (periodogram.hip) --------------------------------------------------------------------------

@@ -250,6 +250,13 @@ int pioran_launch_ls_table(int64_t N, int64_t Fc, const double* t, const double*
                            hipStream_t stream);
 int pioran_launch_ls_product(int64_t N, int64_t B, int64_t Fc, const double* Y, const double* work, const double* dr, double* power,
                              int64_t ldp, int tile /*0: automatic; 64, 128*/, hipStream_t stream);
+// quantiles.hip: quantiles (Statistics.quantile's default, type 7) and mean of every column over the rows with status 0 (sort in LDS)
+int64_t pioran_quantiles_max_draws();                     // most rows of one call: a column sorts inside one workgroup's LDS
+int pioran_launch_quantiles(int64_t B, int64_t M, int64_t ldx, const double* X, const int32_t* status /*nullptr: every row*/,
+                            const double* shift /*nullptr, or [B]: v = exp(v + shift_b)*/, int64_t Mc, const int32_t* cols /*nullptr: Mc = M in order*/,
+                            const double* ref /*nullptr, or with scale [Mc]: v = (ref - v) / scale*/, const double* scale, int64_t Q,
+                            const double* probs, double* quant /*[Q][Mc]*/, double* mean /*[Mc] or nullptr*/, int32_t* kept /*[1] or nullptr*/,
+                            hipStream_t stream);
 // approx.hip
 #ifdef __cplusplus
 #include <vector>

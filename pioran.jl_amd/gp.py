@@ -19,6 +19,7 @@ from . import _lib
 from .kernels import SemiSeparable, SumOfCelerite
 
 _SOLVERS = ("celerite", "celerite_matrix")
+PPC_QUANTILES = (0.025, 0.16, 0.5, 0.84, 0.975)   # what the reference's predictive checks plot (src/plots_diagnostics.jl:805-816)
 
 
 def _f64(x):
@@ -140,6 +141,48 @@ class Context:
         v = ctypes.c_void_p
         _lib.check(_lib.lib().pioran_lombscargle_batch_dev(self._h, int(N), int(B), int(F), v(dt), v(dY), v(dyerr or None), v(dfreq),
                                                            int(bool(fit_mean)), int(bool(center_data)), v(dpower), v(dstatus or None)), self._h)
+
+    # -- quantiles and means over the draw axis ------------------------------------------------
+    def quantiles(self, X, probs, status=None, shift=None, cols=None, ref=None, scale=None):
+        """Quantiles (Statistics.quantile's default, type 7; the definition is tools/quantiles_proto.py) and mean of every column of X (B, M)
+        over its rows, one draw per row: pioran_quantiles_batch.  status (B,) int32: rows with a non-zero entry are left out; shift (B,): the
+        values are exp(X + shift_b); cols (Mc,) int: the columns to reduce, any order, repeats allowed; ref, scale (Mc,): the values are
+        (ref - v) / scale.  Returns (quant (Q, Mc), mean (Mc,), kept): kept = the number of rows that entered.  At most 4096 rows."""
+        probs = _f64(probs).reshape(-1)
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim != 2:
+            raise ValueError("X must be (B, M): one draw per row")
+        B, M = X.shape
+        # a view of the leading columns of a wider row-major array goes as it is (ldx = its row stride), anything else as a contiguous copy
+        if not (B > 0 and M > 0 and X.strides[1] == 8 and X.strides[0] % 8 == 0 and X.strides[0] >= 8 * M):
+            X = np.ascontiguousarray(X)
+        ldx = X.strides[0] // 8 if B > 0 and M > 0 else M
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
+        shift = None if shift is None else _f64(np.broadcast_to(shift, (B,)))
+        cols = None if cols is None else np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        Mc = M if cols is None else len(cols)
+        if (ref is None) != (scale is None):
+            raise ValueError("ref and scale come together")
+        ref, scale = (None, None) if ref is None else (_f64(ref).reshape(-1), _f64(scale).reshape(-1))
+        if (status is not None and status.shape != (B,)) or (ref is not None and (ref.shape != (Mc,) or scale.shape != (Mc,))):
+            raise ValueError("status must be (B,) and ref, scale (Mc,)")
+        quant = np.empty((len(probs), Mc))
+        mean = np.empty(Mc)
+        kept = ctypes.c_int32(-1)
+        _lib.check(_lib.lib().pioran_quantiles_batch(self._h, B, M, ldx, _ptr(X), _ptr(status), _ptr(shift), Mc, _ptr(cols), _ptr(ref), _ptr(scale),
+                                                     len(probs), _ptr(probs), _ptr(quant), _ptr(mean), ctypes.cast(ctypes.byref(kept), ctypes.c_void_p)),
+                   self._h)
+        return quant, mean, kept.value
+
+    def quantiles_dev(self, B, M, ldx, dX, probs, dstatus=0, dshift=0, Mc=0, dcols=0, dref=0, dscale=0, dquant=0, dmean=0, dkept=0):
+        """Device-pointer (int addresses) asynchronous variant: dX (B, ldx) with the draws in its first M columns, dstatus (B,) int32, dshift (B,),
+        dcols (Mc,) int32, dref, dscale (Mc,), dquant (Q, Mc), dmean (Mc,), dkept one int32 in HBM; probs on the host (copied); enqueues on the
+        context's stream (pioran_quantiles_batch_dev).  dstatus, dshift, dcols (then all M columns), dref / dscale, dmean, dkept may be 0."""
+        v = ctypes.c_void_p
+        probs = _f64(probs).reshape(-1)
+        _lib.check(_lib.lib().pioran_quantiles_batch_dev(self._h, int(B), int(M), int(ldx), v(dX), v(dstatus or None), v(dshift or None), int(Mc),
+                                                         v(dcols or None), v(dref or None), v(dscale or None), len(probs), _ptr(probs), v(dquant),
+                                                         v(dmean or None), v(dkept or None)), self._h)
 
     def dense_nll(self, a, b, c, d, t, y, sigma2, return_info=False):
         a, b, c, d, t, y, sigma2 = map(_f64, (a, b, c, d, t, y, sigma2))
@@ -352,6 +395,48 @@ class Dataset:
                                                              _ptr(nu), _ptr(shift), M, _ptr(tau), _ptr(q_data), _ptr(q_new), _ptr(eps),
                                                              _ptr(out), _ptr(st)), self.ctx._h)
         return (out, st) if return_status else out
+
+    def rand_posterior_summary(self, A, Bc, C, Dd, tau, q_data, q_new, eps, probs=PPC_QUANTILES, mu=None, nu=None, shift=None, backtransform=False,
+                               res_cols=None, res_ref=None, res_scale=None):
+        """rand_posterior with the draws left on the device and reduced there (pioran_celerite_rand_posterior_summary): the quantiles `probs`
+        and the mean over the draws with status 0 at every tau and, with res_cols (Nres,) indices into tau, res_ref, res_scale (Nres,), of the
+        residuals (res_ref - draw[res_cols]) / res_scale.  backtransform (needs shift): the summaries are of exp(draw + shift_b).  The draws are
+        rand_posterior's for the same arguments, the reduction is Context.quantiles'.  Returns a dict: ts_quantiles (Q, M), ts_mean (M,),
+        res_quantiles (Q, Nres), res_mean (Nres,) (None without res_cols), status (B,), kept."""
+        A, Bc, C, Dd, tau, q_data, q_new, eps = map(_f64, (A, Bc, C, Dd, tau, q_data, q_new, eps))
+        probs = _f64(probs).reshape(-1)
+        if A.ndim != 2 or A.shape != Bc.shape or C.shape not in ((A.shape[1],), A.shape) or Dd.shape != C.shape or tau.ndim != 1:
+            raise ValueError("A, Bc must be (B, J), C, Dd (J,) or (B, J) and tau (M,)")
+        if not np.isfinite(tau).all():
+            raise ValueError("tau must be finite")
+        B, J = A.shape
+        M = len(tau)
+        if q_data.shape != (B, self.N) or eps.shape != (B, self.N) or q_new.shape != (B, M):
+            raise ValueError("q_data, eps must be (B, N) and q_new (B, M)")
+        mu = None if mu is None else _f64(np.broadcast_to(mu, (B,)))
+        nu = None if nu is None else _f64(np.broadcast_to(nu, (B,)))
+        shift = None if shift is None else _f64(np.broadcast_to(shift, (B,)))
+        Q, Nres = len(probs), 0
+        res_q = res_m = None
+        if res_cols is not None:
+            res_cols = np.ascontiguousarray(res_cols, dtype=np.int32).reshape(-1)
+            Nres = len(res_cols)
+            if res_ref is None or res_scale is None:
+                raise ValueError("res_cols needs res_ref and res_scale")
+            res_ref, res_scale = _f64(res_ref).reshape(-1), _f64(res_scale).reshape(-1)
+            if res_ref.shape != (Nres,) or res_scale.shape != (Nres,):
+                raise ValueError("res_ref, res_scale must be (Nres,)")
+            res_q, res_m = np.empty((Q, Nres)), np.empty(Nres)
+        else:
+            res_ref = res_scale = None
+        ts_q, ts_m = np.empty((Q, M)), np.empty(M)
+        st = np.zeros(B, dtype=np.int32)
+        kept = ctypes.c_int32(-1)
+        _lib.check(_lib.lib().pioran_celerite_rand_posterior_summary(
+            self._h, B, J, _ptr(A), _ptr(Bc), _ptr(C), _ptr(Dd), int(C.ndim == 1), _ptr(mu), _ptr(nu), _ptr(shift), M, _ptr(tau), _ptr(q_data),
+            _ptr(q_new), _ptr(eps), int(bool(backtransform)), Q, _ptr(probs), _ptr(ts_q), _ptr(ts_m), Nres, _ptr(res_cols), _ptr(res_ref),
+            _ptr(res_scale), _ptr(res_q), _ptr(res_m), _ptr(st), ctypes.cast(ctypes.byref(kept), ctypes.c_void_p)), self.ctx._h)
+        return dict(ts_quantiles=ts_q, ts_mean=ts_m, res_quantiles=res_q, res_mean=res_m, status=st, kept=kept.value)
 
     def logl_grad(self, A, Bc, C, Dd, mu=None, nu=None, series_grad=False, shift=None, cd_grad=True):
         """log L and its gradient for B draws: returns a dict with logl (B,), status, grad_a, grad_b, grad_c, grad_d (B, J),
@@ -818,3 +903,35 @@ def ppc_timeseries(rng, t, y, yerr, A, Bc, C, Dd, mu=None, nu=None, shift=None, 
     if shift is not None:
         out = np.exp(out + _f64(np.broadcast_to(shift, (B,)))[:, None])
     return out.T, t_pred
+
+
+def quantiles(X, probs=PPC_QUANTILES, status=None, shift=None, cols=None, ref=None, scale=None, ctx: Context | None = None):
+    """quantile(k, p) for k in eachrow(array), p in probs, and mean(array, dims = 2) of the reference's predictive checks
+    (src/plots_diagnostics.jl:805-816, :547-559, :417-447) on the device, for an array that holds one draw per ROW: X (B, M), as
+    Dataset.rand_posterior and pj.lombscargle return them (the reference's ts_array is the transpose).  The other arguments as
+    Context.quantiles.  Returns (quant (Q, Mc), mean (Mc,), kept)."""
+    return (ctx or default_context()).quantiles(X, probs, status=status, shift=shift, cols=cols, ref=ref, scale=scale)
+
+
+def ppc_timeseries_summary(rng, t, y, yerr, A, Bc, C, Dd, mu=None, nu=None, shift=None, t_pred=None, quantiles=PPC_QUANTILES,
+                           ctx: Context | None = None):
+    """What plot_ppc_timeseries draws (src/plots_diagnostics.jl:805-816) without the (M, B) array of pj.ppc_timeseries leaving the device: the
+    realisations of get_ppc_timeseries for the B posterior samples (arguments and use of the generator exactly as pj.ppc_timeseries:
+    standard_normal((B, N)), ((B, M)), ((B, N))), back-transformed with shift as exp(realisation + c_b), reduced over the samples to
+    ts_quantiles (Q, M); and the standardised residuals at the data times, (y - ts[indexes]) / yerr with indexes the positions of t in t_pred
+    (:807), reduced to res_quantiles (Q, N) and mean_res (N,).  Samples whose draw failed (status 2) are left out of every reduction.
+    Returns a dict with t_pred, ts_quantiles, res_quantiles, mean_res, status (B,) and kept."""
+    t, y, yerr, A = _f64(t).reshape(-1), _f64(y).reshape(-1), _f64(yerr).reshape(-1), _f64(A)
+    B, N = A.shape[0], len(t)
+    t_pred = ppc_t_pred(t, t_pred)
+    M = len(t_pred)
+    q_data, q_new, eps = rng.standard_normal((B, N)), rng.standard_normal((B, M)), rng.standard_normal((B, N))
+    indexes = np.searchsorted(t_pred, t)      # t_pred is sorted, distinct and holds every t
+    ds = Dataset(t, y, yerr ** 2, ctx)
+    try:
+        r = ds.rand_posterior_summary(A, Bc, C, Dd, t_pred, q_data, q_new, eps, probs=quantiles, mu=mu, nu=nu, shift=shift,
+                                      backtransform=shift is not None, res_cols=indexes, res_ref=y, res_scale=yerr)
+    finally:
+        ds.close()
+    return dict(t_pred=t_pred, ts_quantiles=r["ts_quantiles"], res_quantiles=r["res_quantiles"], mean_res=r["res_mean"], status=r["status"],
+                kept=r["kept"])

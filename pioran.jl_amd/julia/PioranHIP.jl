@@ -441,6 +441,90 @@ function lombscargle_batch(t::Vector{Float64}, Y::Matrix{Float64}, yerr::Union{N
     return power, status
 end
 
+const PPC_QUANTILES = [0.025, 0.16, 0.5, 0.84, 0.975]
+
+"""
+    quantiles_batch(X, probs = PPC_QUANTILES; status, shift, cols, ref, scale)
+
+`[quantile(k, p) for k in eachrow(X), p in probs]` and `mean(X, dims = 2)` of the predictive checks (src/plots_diagnostics.jl:805-816) on the
+device: `X` is `M × nbatch`, one draw per column (the reference's `ts_array`).  `status` (`nbatch`): draws with a non-zero entry are left out;
+`shift` (`nbatch`): the values are `exp.(X .+ shift')`; `cols` (1-based row indices of `X`, any order): the rows to reduce; `ref`, `scale`
+(`length(cols)`): the values are `(ref .- v) ./ scale`.  Returns `(quant, mean, kept)`: `quant` is `Mc × length(probs)`.
+"""
+function quantiles_batch(X::Matrix{Float64}, probs::Vector{Float64} = PPC_QUANTILES; status::Union{Nothing, Vector{Int32}} = nothing,
+                         shift::Union{Nothing, Vector{Float64}} = nothing, cols::Union{Nothing, Vector{<:Integer}} = nothing,
+                         ref::Union{Nothing, Vector{Float64}} = nothing, scale::Union{Nothing, Vector{Float64}} = nothing, ctx = default_context())
+    M, nb = size(X)
+    cols0 = cols === nothing ? nothing : Int32.(cols .- 1)
+    Mc = cols0 === nothing ? M : length(cols0)
+    quant = Matrix{Float64}(undef, Mc, length(probs))      # column-major = the ABI's [Q][Mc]
+    mean = Vector{Float64}(undef, Mc)
+    kept = Ref{Int32}(-1)
+    p(x) = x === nothing ? Ptr{Cdouble}(C_NULL) : pointer(x)
+    pint(x) = x === nothing ? Ptr{Int32}(C_NULL) : pointer(x)
+    GC.@preserve X probs status shift cols0 ref scale quant mean begin
+        check(ccall((:pioran_quantiles_batch, LIB), Cint,
+                    (Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Cdouble}, Ptr{Int32}, Ptr{Cdouble}, Int64, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Int32}),
+                    ctx.h, nb, M, M, X, pint(status), p(shift), Mc, pint(cols0), p(ref), p(scale), length(probs), probs, quant, mean, kept))
+    end
+    return quant, mean, Int(kept[])
+end
+
+"""
+    quantiles_batch_dev(ctx, B, M, ldx, dX, probs; dstatus, dshift, Mc, dcols, dref, dscale, dquant, dmean, dkept)
+
+The same on arrays already in device memory (`Ptr`s into HBM; `probs` on the host), asynchronous on the context's stream.
+"""
+function quantiles_batch_dev(ctx, B::Integer, M::Integer, ldx::Integer, dX::Ptr{Cdouble}, probs::Vector{Float64}; dstatus = Ptr{Int32}(C_NULL),
+                             dshift = Ptr{Cdouble}(C_NULL), Mc::Integer = 0, dcols = Ptr{Int32}(C_NULL), dref = Ptr{Cdouble}(C_NULL),
+                             dscale = Ptr{Cdouble}(C_NULL), dquant::Ptr{Cdouble}, dmean = Ptr{Cdouble}(C_NULL), dkept = Ptr{Int32}(C_NULL))
+    GC.@preserve probs begin
+        check(ccall((:pioran_quantiles_batch_dev, LIB), Cint,
+                    (Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Cdouble}, Ptr{Int32}, Ptr{Cdouble}, Int64, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}),
+                    ctx.h, B, M, ldx, dX, dstatus, dshift, Mc, dcols, dref, dscale, length(probs), probs, dquant, dmean, dkept))
+    end
+    return nothing
+end
+
+"""
+    rand_posterior_summary(ds, A, B, c, d, τ, q_data, q_new, ϵ, probs = PPC_QUANTILES; μ, ν, shift, backtransform, res_cols, res_ref, res_scale)
+
+`rand_posterior_batch` with the draws left on the device and reduced there: quantiles and mean over the draws with status 0 at every `τ`
+(`length(τ) × length(probs)`), and, with `res_cols` (1-based indices into `τ`), `res_ref`, `res_scale`, of the residuals
+`(res_ref .- draw[res_cols]) ./ res_scale` — the arrays `plot_ppc_timeseries` draws (src/plots_diagnostics.jl:805-816).  `backtransform`
+(needs `shift`): summaries of `exp.(draw .+ shift_b)` (:663).  Returns `(ts_quant, ts_mean, res_quant, res_mean, status, kept)`.
+"""
+function rand_posterior_summary(ds::Dataset, A::Matrix{Float64}, B::Matrix{Float64}, c::VecOrMat{Float64}, d::VecOrMat{Float64},
+                                τ::Vector{Float64}, q_data::Matrix{Float64}, q_new::Matrix{Float64}, ϵ::Matrix{Float64},
+                                probs::Vector{Float64} = PPC_QUANTILES; μ::Union{Nothing, Vector{Float64}} = nothing,
+                                ν::Union{Nothing, Vector{Float64}} = nothing, shift::Union{Nothing, Vector{Float64}} = nothing,
+                                backtransform::Bool = false, res_cols::Union{Nothing, Vector{<:Integer}} = nothing,
+                                res_ref::Union{Nothing, Vector{Float64}} = nothing, res_scale::Union{Nothing, Vector{Float64}} = nothing)
+    J, nb = size(A)
+    M, Q = length(τ), length(probs)
+    size(q_new) == (M, nb) || error("q_new must be length(τ) × nbatch")
+    size(q_data) == size(ϵ) && size(q_data, 2) == nb || error("q_data and ϵ must be N × nbatch")
+    cols0 = res_cols === nothing ? nothing : Int32.(res_cols .- 1)
+    Nres = cols0 === nothing ? 0 : length(cols0)
+    ts_quant = Matrix{Float64}(undef, M, Q); ts_mean = Vector{Float64}(undef, M)
+    res_quant = Matrix{Float64}(undef, Nres, Q); res_mean = Vector{Float64}(undef, Nres)
+    status = zeros(Int32, nb)
+    kept = Ref{Int32}(-1)
+    p(x) = x === nothing ? Ptr{Cdouble}(C_NULL) : pointer(x)
+    pint(x) = x === nothing ? Ptr{Int32}(C_NULL) : pointer(x)
+    GC.@preserve A B c d μ ν shift τ q_data q_new ϵ probs cols0 res_ref res_scale ts_quant ts_mean res_quant res_mean status begin
+        check(ccall((:pioran_celerite_rand_posterior_summary, LIB), Cint,
+                    (Ptr{Cvoid}, Int64, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Int64, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Int64, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ref{Int32}),
+                    ds.h, nb, J, A, B, c, d, c isa Vector ? 1 : 0, p(μ), p(ν), p(shift), M, τ, q_data, q_new, ϵ, backtransform ? 1 : 0, Q, probs,
+                    ts_quant, ts_mean, Nres, pint(cols0), p(res_ref), p(res_scale), res_quant, res_mean, status, kept))
+    end
+    return ts_quant, ts_mean, res_quant, res_mean, status, Int(kept[])
+end
+
 # ---- value and gradient (reverse mode through the recurrence on the GPU) --------------------------------------------------
 """
     logpdf_grad_batch(ds, A, B, c, d; μ, ν, series = false, cd = true)
