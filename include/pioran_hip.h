@@ -284,6 +284,34 @@ int pioran_celerite_logl_grad_shift(pioran_ds* ds, int64_t B, int64_t J, const d
                                     const double* Dd, int cd_shared, const double* mu, const double* nu, const double* shift,
                                     double* out, int32_t* status, double* grad_a, double* grad_b, double* grad_c,
                                     double* grad_d, double* grad_nu, double* grad_mu, double* grad_shift);
+/* log L and its gradient with respect to the SAMPLED parameters in one call: pioran_logpdf_batch_theta's arguments (continuum models 0 and 1, both
+ * bases, both normalisations), and out of it
+ *   grad_theta [B][P] = dlogL/dtheta_k,  grad_norm [B] = dlogL/dnorm,
+ *   grad_nu, grad_mu, grad_shift [B]: each NULL exactly when its input (nu, mu, shift) is NULL,
+ *   grad_a, grad_b [B][J] (both or neither; may be NULL): the intermediate dlogL/da_j, dlogL/db_j, for checking.
+ * Per chunk of chains approx runs on the device into the buffers the reverse mode reads, the reverse mode is pioran_celerite_logl_grad[_shift]'s for the
+ * same (a, b) with the grid's shared (c, d) and grad_c = grad_d = NULL — same kernels, same routing, same out and status —, and the reverse mode of
+ * approx (approx_vjp_kernel, csrc/approx.hip) chains its grad_a, grad_b on the device: [B][P + 4] doubles go in and come out instead of [B][2 J] each
+ * way and P + 1 host evaluations of approx.  For a draw whose status is not 0 grad_theta / grad_norm chain whatever the reverse mode left in its rows.
+ * The chain rule, with p_j = P(f_j) / P(f_0), x = B^-1 p, I = w'x (w_j: the bracket of integral_sho / integral_drwcelerite between f_min and f_max,
+ * or f_j pi / sqrt2, 2 pi f_j / 3 for the variance form) and kappa_j = f_j pi / sqrt2 (SHO), f_j pi / 3 (DRWCelerite):
+ *   h_j = kappa_j (ga_j + gb_j)   |   kappa_j (ga_j + ga_{J+j} + sqrt3 gb_j),      grad_norm = h'x / I,
+ *   xbar = (norm / I) h - (norm / I^2) (h'x) w,   pbar = B^-T xbar (transposed solve on the same LU),
+ *   grad_theta_k = sum_j pbar_j p_j (dlog P(f_j)/dtheta_k - dlog P(f_0)/dtheta_k).
+ * PSD features (QPO) are out of scope: there is no mixed shared / per-draw reverse mode to chain through, and n_qpo is not a parameter here.
+ * NULL ds / theta / norm / out / grad_theta / grad_norm, model outside 0 .. 1, basis outside 0 .. 1: PIORAN_ERR_ARG before any GPU call.
+ * Host pointers, blocking. */
+int pioran_logpdf_batch_theta_grad(pioran_ds* ds, int64_t B, int model, int64_t n_components, int basis, int is_integrated_power,
+                                   double f_min, double f_max, double S_low, double S_high, const double* theta, const double* norm,
+                                   const double* mu, const double* nu, const double* shift, double* out, int32_t* status,
+                                   double* grad_theta, double* grad_norm, double* grad_nu, double* grad_mu, double* grad_shift,
+                                   double* grad_a, double* grad_b);
+/* The reverse mode of approx alone (what an rrule for `approx` calls; no data set): grad_a, grad_b [B][J] (J = n_components for basis 0,
+ * 2 n_components for basis 1) -> grad_theta [B][P], grad_norm [B], by the formulas above.  2 <= n_components <= 256.  NULL ctx or pointer, model or
+ * basis out of range: PIORAN_ERR_ARG before any GPU call.  Host pointers, blocking. */
+int pioran_approx_vjp_batch(pioran_ctx* ctx, int64_t B, int model, int64_t n_components, int basis, int is_integrated_power,
+                            double f_min, double f_max, double S_low, double S_high, const double* theta, const double* norm,
+                            const double* grad_a, const double* grad_b, double* grad_theta, double* grad_norm);
 /* simulate (src/celerite_solver.jl:497-513 -> sim :515-549; rand(f(t, sigma2)) of src/scalable_GP.jl:137-146):
  * realisations y_b = L_b D_b^(1/2) q_b of the GP with kernel (a_b, b_b, c, d) + diag(sigma2) at the times t, from
  * caller-supplied standard-normal draws q [B][N] (the reference draws them with its rng, :528).  y_out [B][N].

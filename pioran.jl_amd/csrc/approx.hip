@@ -131,6 +131,115 @@ __global__ void __launch_bounds__(64) approx_kernel(int64_t B, int model, int P,
     }
 }
 
+// P(f) of psd_model and its logarithmic derivatives dl[k] = d log P(f) / d theta_k, from the pow values the value needs and one log per bend:
+//   x = f / f1, u = x^(a2 - a1), q = u / (1 + u):   d/da1 = -log x / (1 + u),  d/df1 = (a1 + q (a2 - a1)) / f1,  d/da2 = -q log x
+//   y = f / f2, v = y^(a3 - a2), r = v / (1 + v):   d/da2 += r log y,  d/df2 = r (a3 - a2) / f2,  d/da3 = -r log y
+// (q, r -> 1 where the pow overflows: P is 0 there, the derivative of its logarithm is not)
+__device__ __forceinline__ double psd_model_dlog(int model, const double* th, double f, double dl[5])
+{
+    const double x = f / th[1], lx = log(x);
+    const double u = pow(x, th[2] - th[0]);
+    const double q = isinf(u) ? 1.0 : u / (1.0 + u);
+    double v = pow(x, -th[0]) / (1.0 + u);
+    dl[0] = -lx * (1.0 - q);
+    dl[1] = (th[0] + q * (th[2] - th[0])) / th[1];
+    dl[2] = -q * lx;
+    dl[3] = dl[4] = 0.0;
+    if (model == 1) {
+        const double ly = log(f / th[3]);
+        const double w = pow(f / th[3], th[4] - th[2]);
+        const double r = isinf(w) ? 1.0 : w / (1.0 + w);
+        v /= 1.0 + w;
+        dl[2] += r * ly;
+        dl[3] = r * (th[4] - th[2]) / th[3];
+        dl[4] = -r * ly;
+    }
+    return v;
+}
+
+// Reverse mode of approx_kernel for the continuum models: (grad_a, grad_b) [B][Jt] -> grad_theta [B][P], grad_norm [B].  With x = B^-1 p the
+// amplitudes, I = w'x the normalising integral (w: pioran_approx_weights_host) and kappa_j x_j norm / I the coefficients, sum(ga a + gb b) is
+// (norm / I) h'x with h_j = kappa_j (ga_j + gb_j) (SHO) or kappa_j (ga_j + ga_{J+j} + sqrt3 gb_j) (DRWCelerite; the b of its second half is
+// structurally 0), so
+//   grad_norm = h'x / I,    xbar = (norm / I) h - (norm / I^2) (h'x) w,    pbar = B^-T xbar,
+//   grad_theta_k = sum_j pbar_j p_j (dlog P(f_j)/dtheta_k - dlog P(f_0)/dtheta_k).
+// The forward quantities are recomputed (nothing is kept between approx_kernel and this one).  One thread per draw as in approx_kernel: the LU
+// entries are uniform over a wavefront (scalar loads), each draw's x and xbar sit in `scratch` [2 J][B] so that a wavefront's accesses to one
+// entry are one coalesced line.  No operation mixes draws: a draw's result does not depend on its place in the batch.
+__global__ void __launch_bounds__(64) approx_vjp_kernel(int64_t B, int model, int P, int J, int basis, int64_t Jt,
+                                                        const double* __restrict__ sp, const double* __restrict__ w,
+                                                        const double* __restrict__ LU, const int32_t* __restrict__ piv,
+                                                        const double* __restrict__ theta, const double* __restrict__ norm,
+                                                        const double* __restrict__ ga, const double* __restrict__ gb,
+                                                        double* __restrict__ scratch, double* __restrict__ gtheta, double* __restrict__ gnorm)
+{
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double* x = scratch + b;                         // x[j * B]
+    double* xb = scratch + (int64_t)J * B + b;       // xbar[j * B]
+    const double* th = theta + b * P;
+    double d0[5], dj[5];
+    const double p0 = psd_model_dlog(model, th, sp[0], d0);
+    for (int j = 0; j < J; ++j) x[(int64_t)j * B] = psd_model(model, th, sp[j]) / p0;
+    // forward: row interchanges, L y = P p, U x = y (as approx_kernel)
+    for (int j = 0; j < J; ++j) {
+        const int pj = piv[j];
+        if (pj != j) { const double tmp = x[(int64_t)j * B]; x[(int64_t)j * B] = x[(int64_t)pj * B]; x[(int64_t)pj * B] = tmp; }
+    }
+    for (int i = 1; i < J; ++i) {
+        double acc = x[(int64_t)i * B];
+        for (int k = 0; k < i; ++k) acc = fma(-LU[i * J + k], x[(int64_t)k * B], acc);
+        x[(int64_t)i * B] = acc;
+    }
+    for (int i = J - 1; i >= 0; --i) {
+        double acc = x[(int64_t)i * B];
+        for (int k = i + 1; k < J; ++k) acc = fma(-LU[i * J + k], x[(int64_t)k * B], acc);
+        x[(int64_t)i * B] = acc / LU[i * J + i];
+    }
+    // h, I = w'x, h'x
+    const double* gar = ga + b * Jt;
+    const double* gbr = gb + b * Jt;
+    const double kap = basis == 0 ? M_PI / 1.4142135623730951 : M_PI / 3.0;
+    double integ = 0.0, hx = 0.0;
+    for (int j = 0; j < J; ++j) {
+        const double g = basis == 0 ? gar[j] + gbr[j] : gar[j] + gar[J + j] + 1.7320508075688772 * gbr[j];
+        const double h = kap * sp[j] * g, xj = x[(int64_t)j * B];
+        integ = fma(w[j], xj, integ);
+        hx = fma(h, xj, hx);
+        xb[(int64_t)j * B] = h;
+    }
+    const double s = norm[b] / integ, cw = s * hx / integ;
+    gnorm[b] = hx / integ;
+    for (int j = 0; j < J; ++j) xb[(int64_t)j * B] = s * xb[(int64_t)j * B] - cw * w[j];
+    // pbar = B^-T xbar with P B = L U:  U' y = xbar (forward), L' z = y (backward, unit diagonal), pbar = P' z
+    for (int i = 0; i < J; ++i) {
+        double acc = xb[(int64_t)i * B];
+        for (int k = 0; k < i; ++k) acc = fma(-LU[k * J + i], xb[(int64_t)k * B], acc);
+        xb[(int64_t)i * B] = acc / LU[i * J + i];
+    }
+    for (int i = J - 2; i >= 0; --i) {
+        double acc = xb[(int64_t)i * B];
+        for (int k = i + 1; k < J; ++k) acc = fma(-LU[k * J + i], xb[(int64_t)k * B], acc);
+        xb[(int64_t)i * B] = acc;
+    }
+    // the row interchanges undone in reverse order.  The sparse grids have none; dense ones do (f_max / f_min = 1e3, S_low = S_high = 20: SHO from
+    // J = 48 on, DRWCelerite from J = 72 on — tools/approx_vjp_proto.py interchanges(); the tests run both)
+    for (int j = J - 1; j >= 0; --j) {
+        const int pj = piv[j];
+        if (pj != j) { const double tmp = xb[(int64_t)j * B]; xb[(int64_t)j * B] = xb[(int64_t)pj * B]; xb[(int64_t)pj * B] = tmp; }
+    }
+    double g[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int j = 0; j < J; ++j) {
+        const double pj = psd_model_dlog(model, th, sp[j], dj) / p0;
+        const double t = xb[(int64_t)j * B] * pj;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) g[k] = fma(t, dj[k] - d0[k], g[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+        if (k < P) gtheta[b * P + k] = g[k];
+}
+
 }  // namespace
 
 // Host side: the spectral grid, its LU factorisation and the (c, d) that go with it.
@@ -187,5 +296,38 @@ int pioran_launch_approx(int64_t B, int model, int P, int J, int basis, int inte
     if (n_qpo > 0 && (!qpo || !Cq || !Dq)) return PIORAN_ERR_ARG;
     hipLaunchKernelGGL(approx_kernel, dim3((unsigned)blocks), dim3(64), 0, stream, B, model, P, J, basis, integrated, f_min,
                        f_max, sp, LU, piv, theta, norm, n_qpo, qpo, A, Bc, Cq, Dq);
+    return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;
+}
+
+// w_j of the normalising integral I = sum_j w_j x_j over the amplitudes x (get_norm_psd, src/psd.jl:375-395; the terms approx_kernel adds up):
+// the bracket of integral_sho / integral_drwcelerite between f_min and f_max per unit amplitude, or the variance form's f_j pi / sqrt2, 2 pi f_j / 3.
+// They depend on the grid alone: once per call on the host, like the LU factors.
+void pioran_approx_weights_host(int basis, int integrated, double f_min, double f_max, const std::vector<double>& sp, std::vector<double>& w)
+{
+    const double s2 = std::sqrt(2.0), s3 = std::sqrt(3.0);
+    w.resize(sp.size());
+    for (size_t j = 0; j < sp.size(); ++j) {
+        const double c = sp[j];
+        if (!integrated) { w[j] = basis == 0 ? c * M_PI / s2 : c * 2.0 * M_PI / 3.0; continue; }
+        auto sho = [&](double f) {
+            const double ph = (f * f + s2 * c * f + c * c) / (f * f - s2 * c * f + c * c);
+            return c / (4.0 * s2) * (std::log(ph) + 2.0 * std::atan2(c * s2 * f, c * c - f * f));
+        };
+        auto drw = [&](double f) {
+            const double ph = (f * f + s3 * c * f + c * c) / (f * f - s3 * c * f + c * c);
+            return c / 3.0 * (std::atan(f / c) + 0.5 * std::atan2(f * f - c * c, c * f) + s3 / 4.0 * std::log(ph));
+        };
+        w[j] = basis == 0 ? sho(f_max) - sho(f_min) : drw(f_max) - drw(f_min);
+    }
+}
+
+int pioran_launch_approx_vjp(int64_t B, int model, int P, int J, int basis, const double* sp, const double* w, const double* LU,
+                             const int32_t* piv, const double* theta, const double* norm, const double* ga, const double* gb,
+                             double* scratch, double* gtheta, double* gnorm, hipStream_t stream)
+{
+    const int64_t blocks = (B + 63) / 64;
+    if (blocks <= 0 || blocks > 0x7fffffffLL || J < 2 || J > 256 || model < 0 || model > 1 || P != (model == 0 ? 3 : 5)) return PIORAN_ERR_ARG;
+    hipLaunchKernelGGL(approx_vjp_kernel, dim3((unsigned)blocks), dim3(64), 0, stream, B, model, P, J, basis, (int64_t)(basis == 0 ? J : 2 * J),
+                       sp, w, LU, piv, theta, norm, ga, gb, scratch, gtheta, gnorm);
     return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;
 }

@@ -49,6 +49,9 @@ struct pioran_ctx {
     // quantiles over draws (quantiles.hip): the resident draws [B][M] | their status [B] (the summary entry's sink; the host form's staged X and
     // status), the small inputs probs | shift | ref | scale, the indices cols | kept, the results quant | mean
     Buf bqX, bqst, bqin, bqidx, bqout;
+    // approx and its reverse mode as the two ends of the gradient (ThetaDraws): the grid's sp | w | LU | piv and the batch's theta | norm, a chunk's
+    // grad_theta | grad_norm | the kernel's scratch
+    Buf bthin, bthout;
     // scalar entry point: the last series' time stamps stay resident (samplers call logl with the same t)
     pioran_ds* scalar_ds = nullptr;
     std::vector<double> scalar_t;
@@ -208,17 +211,22 @@ void* pin_reserve(pioran_ctx* ctx, size_t bytes)
     return p;
 }
 
-int upload(pioran_ctx* ctx, pioran_ctx::Buf& b, const void* host, size_t bytes)
+// caller -> device memory `dev`: through pinned staging where it fits (the caller's memory is then free again), else directly
+int upload_to(pioran_ctx* ctx, void* dev, const void* host, size_t bytes)
 {
-    int rc = ensure(ctx, b, bytes);
-    if (rc) return rc;
     const void* src = host;
     if (void* st = pin_reserve(ctx, bytes)) {
         std::memcpy(st, host, bytes);
         src = st;
     }
-    HIPCHK(ctx, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(dev, src, bytes, hipMemcpyHostToDevice, ctx->stream));
     return PIORAN_OK;
+}
+
+int upload(pioran_ctx* ctx, pioran_ctx::Buf& b, const void* host, size_t bytes)
+{
+    const int rc = ensure(ctx, b, bytes);
+    return rc ? rc : upload_to(ctx, b.p, host, bytes);
 }
 
 // device -> caller: through pinned staging (delivered by the next ctx_sync) where it fits, else directly
@@ -320,6 +328,80 @@ int upload_draws(pioran_ctx* ctx, int64_t J, int64_t b0, int64_t nb, const doubl
     return PIORAN_OK;
 }
 
+// approx on the device as the source of a batch's draws, and its reverse mode as the sink of their gradients (approx.hip): the sampled parameters of the
+// whole batch and the grid's constants on the device (bthin), a chunk's results (bthout), the caller's arrays, and what the grid says of the terms
+struct ThetaDraws {
+    int model = 0, P = 0, J = 0, basis = 0, integrated = 0;
+    double f_min = 0.0, f_max = 0.0;
+    const double *sp = nullptr, *w = nullptr, *LU = nullptr, *theta = nullptr, *norm = nullptr;
+    const int32_t* piv = nullptr;
+    double *grad_theta = nullptr, *grad_norm = nullptr;          // the caller's: [B][P], [B]
+    std::vector<double> grid, c, d;                              // host: sp | w | LU | piv (what `sp` .. `piv` hold), the shared (c, d) of the celerite terms
+    std::vector<int32_t> real;                                   // ... and which of them keep their cos row only
+    int64_t terms() const { return basis == 0 ? J : 2 * (int64_t)J; }
+};
+
+// The grid of approx and the batch's theta [B][P], norm [B] onto the device.  `td` keeps the host copies until the call's last synchronisation.
+int stage_theta(pioran_ctx* ctx, int64_t B, int model, int64_t J, int basis, int integrated, double f_min, double f_max, double S_low, double S_high,
+                const double* theta, const double* norm, ThetaDraws& td)
+{
+    std::vector<double> sp, w, LU;
+    std::vector<int32_t> piv;
+    int rc = pioran_approx_setup_host(J, basis, f_min, f_max, S_low, S_high, sp, LU, piv, td.c, td.d, td.real);
+    if (rc) return rc;
+    pioran_approx_weights_host(basis, integrated, f_min, f_max, sp, w);
+    td.model = model; td.P = model == 0 ? 3 : 5; td.J = (int)J; td.basis = basis; td.integrated = integrated; td.f_min = f_min; td.f_max = f_max;
+    const size_t nJ = (size_t)J, npiv = (nJ + 1) / 2, ngrid = 2 * nJ + nJ * nJ + npiv, nth = (size_t)B * td.P;
+    td.grid.assign(ngrid, 0.0);
+    std::memcpy(td.grid.data(), sp.data(), nJ * sizeof(double));
+    std::memcpy(td.grid.data() + nJ, w.data(), nJ * sizeof(double));
+    std::memcpy(td.grid.data() + 2 * nJ, LU.data(), nJ * nJ * sizeof(double));
+    std::memcpy(td.grid.data() + 2 * nJ + nJ * nJ, piv.data(), nJ * sizeof(int32_t));
+    if ((rc = ensure(ctx, ctx->bthin, (ngrid + nth + (size_t)B) * sizeof(double)))) return rc;
+    double* dev = (double*)ctx->bthin.p;
+    if ((rc = upload_to(ctx, dev, td.grid.data(), ngrid * sizeof(double)))) return rc;
+    if ((rc = upload_to(ctx, dev + ngrid, theta, nth * sizeof(double)))) return rc;
+    if ((rc = upload_to(ctx, dev + ngrid + nth, norm, (size_t)B * sizeof(double)))) return rc;
+    td.sp = dev; td.w = dev + nJ; td.LU = dev + 2 * nJ; td.piv = (const int32_t*)(dev + 2 * nJ + nJ * nJ);
+    td.theta = dev + ngrid; td.norm = dev + ngrid + nth;
+    return PIORAN_OK;
+}
+
+// a chunk's grad_theta [nb][P] | grad_norm [nb] | the reverse kernel's scratch [2 J][nb] in bthout
+int ensure_theta_grads(pioran_ctx* ctx, const ThetaDraws& td, int64_t nb)
+{
+    return ensure(ctx, ctx->bthout, (size_t)nb * (size_t)(td.P + 1 + 2 * td.J) * sizeof(double));
+}
+
+// (ga, gb) [nb][terms] of draws [b0, b0 + nb), on the device, through the reverse mode of approx to the caller's grad_theta, grad_norm
+int theta_grads(pioran_ctx* ctx, const ThetaDraws& td, int64_t b0, int64_t nb, const double* ga, const double* gb)
+{
+    double* gth = (double*)ctx->bthout.p; double* gn = gth + (size_t)nb * td.P;
+    int rc = pioran_launch_approx_vjp(nb, td.model, td.P, td.J, td.basis, td.sp, td.w, td.LU, td.piv, td.theta + b0 * td.P, td.norm + b0, ga, gb, gn + nb,
+                                      gth, gn, ctx->stream);
+    if (rc) return rc;
+    if ((rc = download(ctx, td.grad_theta + b0 * td.P, gth, (size_t)nb * td.P * sizeof(double)))) return rc;
+    return download(ctx, td.grad_norm + b0, gn, (size_t)nb * sizeof(double));
+}
+
+// Where a chunk's draws come from: draws [b0, b0 + nb) of the caller's host arrays `in` (upload_draws; per_draw: with their (c, d)), or, `td`,
+// approx_kernel's coefficients of the sampled parameters, written into the staging buffers upload_draws would have filled (mu, nu: the caller's, `in`'s)
+int stage_draws(pioran_ctx* ctx, int64_t J, int64_t b0, int64_t nb, const DrawChunk& in, bool per_draw, const ThetaDraws* td, DrawChunk& m)
+{
+    if (!td) return upload_draws(ctx, J, b0, nb, in.A, in.Bc, per_draw ? in.C : nullptr, in.D, in.mu, in.nu, m);
+    int rc;
+    const size_t bj = (size_t)nb * (size_t)J * sizeof(double);
+    if ((rc = ensure(ctx, ctx->bA, bj))) return rc;
+    if ((rc = ensure(ctx, ctx->bB, bj))) return rc;
+    if (in.mu && (rc = upload(ctx, ctx->bmu, in.mu + b0, nb * sizeof(double)))) return rc;
+    if (in.nu && (rc = upload(ctx, ctx->bnu, in.nu + b0, nb * sizeof(double)))) return rc;
+    m = DrawChunk{};
+    m.A = (const double*)ctx->bA.p; m.Bc = (const double*)ctx->bB.p;
+    m.mu = in.mu ? (const double*)ctx->bmu.p : nullptr; m.nu = in.nu ? (const double*)ctx->bnu.p : nullptr;
+    return pioran_launch_approx(nb, td->model, td->P, td->J, td->basis, td->integrated, td->f_min, td->f_max, td->sp, td->LU, td->piv,
+                                td->theta + b0 * td->P, td->norm + b0, 0, nullptr, (double*)ctx->bA.p, (double*)ctx->bB.p, nullptr, nullptr, ctx->stream);
+}
+
 // log L and status of n draws land in bout / bst ...
 int ensure_results(pioran_ctx* ctx, int64_t n)
 {
@@ -337,12 +419,12 @@ int download_results(pioran_ctx* ctx, double* out, int32_t* status, int64_t b0, 
 }
 
 // Gradient arrays, the caller's or a chunk's on the device: a, b, c, d [.][J]; nu, mu [.]; y, s2 [.][N].  In the caller's set everything but
-// a and b may be nullptr (not wanted).
+// a and b may be nullptr (not wanted); a and b too where the call chains them on (ThetaDraws).
 struct GradPtrs {
     double *a, *b, *c, *d, *nu, *mu, *y, *s2;
     GradPtrs from_draw(int64_t b0, int64_t J, int64_t N) const
     {
-        return {a + b0 * J, b + b0 * J, at(c, b0 * J), at(d, b0 * J), at(nu, b0), at(mu, b0), at(y, b0 * N), at(s2, b0 * N)};
+        return {at(a, b0 * J), at(b, b0 * J), at(c, b0 * J), at(d, b0 * J), at(nu, b0), at(mu, b0), at(y, b0 * N), at(s2, b0 * N)};
     }
 };
 
@@ -360,8 +442,8 @@ int download_grads(pioran_ctx* ctx, const GradPtrs& host, const GradPtrs& dev, i
 {
     int rc;
     const size_t nbj = (size_t)nb * J * sizeof(double), nbn = (size_t)nb * N * sizeof(double);
-    if ((rc = download(ctx, host.a, dev.a, nbj))) return rc;
-    if ((rc = download(ctx, host.b, dev.b, nbj))) return rc;
+    if (host.a && (rc = download(ctx, host.a, dev.a, nbj))) return rc;
+    if (host.b && (rc = download(ctx, host.b, dev.b, nbj))) return rc;
     if (host.c && (rc = download(ctx, host.c, dev.c, nbj))) return rc;
     if (host.d && (rc = download(ctx, host.d, dev.d, nbj))) return rc;
     if (host.nu && (rc = download(ctx, host.nu, dev.nu, nb * sizeof(double)))) return rc;
@@ -778,6 +860,7 @@ int set_option(ScanOptions& o, const char* key, const char* value)
     else if (!std::strcmp(key, "ls_tile")) o.ls_tile = (value && value[0]) ? std::atoi(value) : 0;
     else if (!std::strcmp(key, "ls_only")) o.ls_only = (value && value[0]) ? std::atoi(value) : 0;
     else if (!std::strcmp(key, "rp_events")) o.rp_events = on ? 1 : 0;
+    else if (!std::strcmp(key, "theta_events")) o.theta_events = on ? 1 : 0;
     else if (!std::strcmp(key, "wide2")) o.wide2 = on;
     else if (!std::strcmp(key, "no_wide2")) o.no_wide2 = on;
     else return PIORAN_ERR_ARG;
@@ -931,7 +1014,8 @@ int pioran_ctx_destroy(pioran_ctx* ctx)
     ctx->scalar_ds = nullptr;
     pioran_ctx::Buf* bufs[] = {&ctx->bA, &ctx->bB, &ctx->bC, &ctx->bD, &ctx->bmu, &ctx->bnu, &ctx->bY,
                                &ctx->bS2, &ctx->bout, &ctx->bst, &ctx->bscratch, &ctx->bK, &ctx->bwork, &ctx->bshift, &ctx->bgtab, &ctx->bq, &ctx->bpair, &ctx->btp, &ctx->btprow, &ctx->brqd, &ctx->brqn, &ctx->breps, &ctx->brqT, &ctx->brstores, &ctx->brxi, &ctx->brf, &ctx->brsout, &ctx->brsst, &ctx->brmaps,
-                               &ctx->brY, &ctx->brS2, &ctx->brshift, &ctx->brres, &ctx->brst, &ctx->bqX, &ctx->bqst, &ctx->bqin, &ctx->bqidx, &ctx->bqout};
+                               &ctx->brY, &ctx->brS2, &ctx->brshift, &ctx->brres, &ctx->brst, &ctx->bqX, &ctx->bqst, &ctx->bqin, &ctx->bqidx, &ctx->bqout,
+                               &ctx->bthin, &ctx->bthout};
     for (auto* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto& e : ctx->ev)
@@ -957,7 +1041,8 @@ int pioran_ctx_trim(pioran_ctx* ctx)
     pioran_ctx::Buf* bufs[] = {&ctx->bA, &ctx->bB, &ctx->bC, &ctx->bD, &ctx->bmu, &ctx->bnu, &ctx->bY,
                                &ctx->bS2, &ctx->bout, &ctx->bst, &ctx->bscratch, &ctx->bK, &ctx->bwork, &ctx->bshift, &ctx->bgtab, &ctx->bq, &ctx->bpair, &ctx->btp, &ctx->btprow,
                                &ctx->blstab, &ctx->blsaux, &ctx->brqd, &ctx->brqn, &ctx->breps, &ctx->brqT, &ctx->brstores, &ctx->brxi, &ctx->brf, &ctx->brsout, &ctx->brsst, &ctx->brmaps,
-                               &ctx->brY, &ctx->brS2, &ctx->brshift, &ctx->brres, &ctx->brst, &ctx->bqX, &ctx->bqst, &ctx->bqin, &ctx->bqidx, &ctx->bqout};
+                               &ctx->brY, &ctx->brS2, &ctx->brshift, &ctx->brres, &ctx->brst, &ctx->bqX, &ctx->bqst, &ctx->bqin, &ctx->bqidx, &ctx->bqout,
+                               &ctx->bthin, &ctx->bthout};
     for (auto* b : bufs) {
         if (b->p) (void)hipFree(b->p);
         b->p = nullptr;
@@ -1722,8 +1807,10 @@ int pioran_celerite_predict_var(pioran_ds* ds, int64_t B, int64_t J, const doubl
 // shift / grad_shift != nullptr: the shifted log-flux models (the data set holds raw flux and yerr^2); grad_y / grad_sigma2 then refer to the
 // TRANSFORMED series of each draw.  per_draw (CARMA kernels, QPO features, free Celerite sums under NUTS): the windowed reverse mode with one pair of
 // tables per draw, all chains of a chunk in one launch — 16 chains in the time of one instead of 16 one-draw calls; it has no shifted form.
+// td != nullptr (shared (c, d) only): the draws are approx of the sampled parameters — `in` holds mu, nu alone, a chunk's (a, b) are made on the device
+// (stage_draws), its grad_a, grad_b go through the reverse mode of approx there (theta_grads), and (c, d), with the terms that keep one row, are the grid's.
 static int logl_grad_batch(pioran_ds* ds, bool per_draw, int64_t B, int64_t J, const DrawChunk& in, const double* shift, double* out, int32_t* status,
-                           const GradPtrs& grad, double* grad_shift)
+                           const GradPtrs& grad, double* grad_shift, const ThetaDraws* td = nullptr)
 {
     pioran_ctx* ctx = ds->ctx;
     PrepState& s = ds->host;
@@ -1731,7 +1818,7 @@ static int logl_grad_batch(pioran_ds* ds, bool per_draw, int64_t B, int64_t J, c
     HIPCHK(ctx, hipSetDevice(ctx->device));
     PendingGuard pending_guard(ctx);
     int rc;
-    if ((rc = prepare_draws(ds, per_draw, B, J, in.Bc, in.C, in.D))) return rc;
+    if ((rc = td ? prepare_state(ds, s, J, td->c.data(), td->d.data(), td->real.data()) : prepare_draws(ds, per_draw, B, J, in.Bc, in.C, in.D))) return rc;
     if (s.R > pioran_wide_supported_rows_grad() || s.npd_terms) return PIORAN_ERR_UNSUPPORTED;
     const int64_t N = ds->N;
     // buffer roles: the reverse mode's workspace | a chunk's forward tables (per_draw) or its transformed series Y | S2 (shift): never both | the reverse
@@ -1794,13 +1881,18 @@ static int logl_grad_batch(pioran_ds* ds, bool per_draw, int64_t B, int64_t J, c
     if (shift && (rc = ensure(ctx, shifted, 2 * cn))) return rc;
     if (shift && (rc = ensure(ctx, shifts, 2 * chunk * sizeof(double)))) return rc;
     if ((rc = ensure_results(ctx, chunk))) return rc;
+    if (td && (rc = ensure_theta_grads(ctx, *td, chunk))) return rc;
+    const bool timed = td && ctx->opt.theta_events != 0;
+    auto mark = [&](int slot) { return timed ? hipEventRecord(ctx->ev[slot], ctx->stream) : hipSuccess; };
     if (!per_draw && (rc = ensure_aux(ctx))) return rc;   // (the step-by-step reverse pass's; the shared form creates it whichever kernel it takes)
     const GradPtrs dev = grad_chunk(ctx, terms, scalars, chunk, J);
     ChunkTables tb;
     for (int64_t b0 = 0; b0 < B; b0 += chunk) {
         const int64_t nb = std::min(B - b0, chunk);
         DrawChunk m;
-        if ((rc = upload_draws(ctx, J, b0, nb, in.A, in.Bc, per_draw ? in.C : nullptr, in.D, in.mu, in.nu, m))) return rc;
+        if (b0 == 0) HIPCHK(ctx, mark(4));
+        if ((rc = stage_draws(ctx, J, b0, nb, in, per_draw, td, m))) return rc;
+        if (b0 == 0) HIPCHK(ctx, mark(5));
         if (windowed && (per_draw || b0 == 0) && (rc = build_tables(ds, s, per_draw, nb, m, btabs, &gtabs, tb))) return rc;
         ScanParams p = chunk_params(ds, s, per_draw, nb, m, tb);
         p.out = (double*)ctx->bout.p; p.status = (int32_t*)ctx->bst.p;
@@ -1834,6 +1926,11 @@ static int logl_grad_batch(pioran_ds* ds, bool per_draw, int64_t B, int64_t J, c
         }
         if ((rc = download_results(ctx, out, status, b0, nb))) return rc;
         if ((rc = download_grads(ctx, grad.from_draw(b0, J, N), dev, nb, J, N))) return rc;
+        if (td) {
+            if (b0 == 0) HIPCHK(ctx, mark(6));
+            if ((rc = theta_grads(ctx, *td, b0, nb, dev.a, dev.b))) return rc;
+            if (b0 == 0) HIPCHK(ctx, mark(7));
+        }
         // Chunks follow each other on the stream without a host synchronisation in between (round 4): every transfer is stream-ordered
         // and staged through pinned memory, which drains itself when it fills (pin_reserve); only the large series gradients, which go
         // straight to the caller's pageable memory, are waited for per chunk.  (No change in time: 4096 chains are 16 launches of 7.5 ms, 122 ms.)
@@ -1878,6 +1975,51 @@ int pioran_celerite_logl_grad_shift(pioran_ds* ds, int64_t B, int64_t J, const d
     if (!shift || !grad_shift) return PIORAN_ERR_ARG;
     return logl_grad_impl(ds, B, J, A, Bc, C, Dd, cd_shared, mu, nu, shift, out, status,
                           {grad_a, grad_b, grad_c, grad_d, grad_nu, grad_mu, nullptr, nullptr}, grad_shift);
+}
+
+int pioran_logpdf_batch_theta_grad(pioran_ds* ds, int64_t B, int model, int64_t n_components, int basis, int is_integrated_power, double f_min,
+                                   double f_max, double S_low, double S_high, const double* theta, const double* norm, const double* mu, const double* nu,
+                                   const double* shift, double* out, int32_t* status, double* grad_theta, double* grad_norm, double* grad_nu,
+                                   double* grad_mu, double* grad_shift, double* grad_a, double* grad_b)
+{
+    if (!ds || B < 1 || !theta || !norm || !out || !grad_theta || !grad_norm || model < 0 || model > 1 || basis < 0 || basis > 1) return PIORAN_ERR_ARG;
+    if ((nu == nullptr) != (grad_nu == nullptr) || (mu == nullptr) != (grad_mu == nullptr) || (shift == nullptr) != (grad_shift == nullptr) ||
+        (grad_a == nullptr) != (grad_b == nullptr))
+        return PIORAN_ERR_ARG;
+    pioran_ctx* ctx = ds->ctx;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    PendingGuard pending_guard(ctx);
+    ThetaDraws td;
+    int rc = stage_theta(ctx, B, model, n_components, basis, is_integrated_power, f_min, f_max, S_low, S_high, theta, norm, td);
+    if (rc) return rc;
+    td.grad_theta = grad_theta; td.grad_norm = grad_norm;
+    const DrawChunk in{nullptr, nullptr, nullptr, nullptr, mu, nu, nullptr, nullptr};
+    return logl_grad_batch(ds, false, B, td.terms(), in, shift, out, status, {grad_a, grad_b, nullptr, nullptr, grad_nu, grad_mu, nullptr, nullptr},
+                           grad_shift, &td);
+}
+
+int pioran_approx_vjp_batch(pioran_ctx* ctx, int64_t B, int model, int64_t n_components, int basis, int is_integrated_power, double f_min, double f_max,
+                            double S_low, double S_high, const double* theta, const double* norm, const double* grad_a, const double* grad_b,
+                            double* grad_theta, double* grad_norm)
+{
+    if (!ctx || B < 1 || !theta || !norm || !grad_a || !grad_b || !grad_theta || !grad_norm || model < 0 || model > 1 || basis < 0 || basis > 1)
+        return PIORAN_ERR_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    PendingGuard pending_guard(ctx);
+    ThetaDraws td;
+    int rc = stage_theta(ctx, B, model, n_components, basis, is_integrated_power, f_min, f_max, S_low, S_high, theta, norm, td);
+    if (rc) return rc;
+    td.grad_theta = grad_theta; td.grad_norm = grad_norm;
+    // grad_a | grad_b of the batch where the gradient entries keep a chunk's (grad_chunk)
+    const size_t bj = (size_t)B * (size_t)td.terms();
+    if ((rc = ensure(ctx, ctx->bK, 2 * bj * sizeof(double)))) return rc;
+    double* dga = (double*)ctx->bK.p;
+    if ((rc = upload_to(ctx, dga, grad_a, bj * sizeof(double)))) return rc;
+    if ((rc = upload_to(ctx, dga + bj, grad_b, bj * sizeof(double)))) return rc;
+    if ((rc = ensure_theta_grads(ctx, td, B))) return rc;
+    if ((rc = theta_grads(ctx, td, 0, B, dga, dga + bj))) return rc;
+    SYNC(ctx);
+    return PIORAN_OK;
 }
 
 // ---- simulation ----------------------------------------------------------------------------------------------------------------------

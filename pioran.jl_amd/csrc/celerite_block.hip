@@ -1360,19 +1360,24 @@ __global__ void __launch_bounds__(256, 1) celerite_block_adjoint_kernel(const Sc
     PIORAN_ASTAMP_FLUSH
     // ---- reductions: rows -> terms ------------------------------------------------------------------------------------------------
     __syncthreads();
-    if (owner) {
-        const int row = 16 * w + c16;
-        if (row < R) {
-            const int rm = p.rowmap[row];
-            const int term = rm & 0xfffff;
-            atomicAdd(&sh.ra[term], acc_al);
-            atomicAdd(&sh.rb[term], ((rm >> 30) & 1) ? -acc_be : acc_be);
-            if constexpr (CD) {
-                atomicAdd(&sh.rc[term], acc_c);
-                atomicAdd(&sh.rd[term], ((rm >> 30) & 1) ? acc_d : -acc_d);
+    // One wavefront after the other, the pair threads (a term's are in one wavefront) last: a term's sum gets its addends in the same order in every
+    // launch, so the same draw gives the same bits whatever else runs (with all wavefronts adding at once the order was the one they arrived in)
+    for (int ww = 0; ww < NB; ++ww) {
+        if (w == ww) {
+            const int row = 16 * w + c16;
+            if (row < R) {
+                const int rm = p.rowmap[row];
+                const int term = rm & 0xfffff;
+                atomicAdd(&sh.ra[term], acc_al);
+                atomicAdd(&sh.rb[term], ((rm >> 30) & 1) ? -acc_be : acc_be);
+                if constexpr (CD) {
+                    atomicAdd(&sh.rc[term], acc_c);
+                    atomicAdd(&sh.rd[term], ((rm >> 30) & 1) ? acc_d : -acc_d);
+                }
             }
+            if (ycol) atomicAdd(&sh.rs[0], acc_mu);
         }
-        if (ycol) atomicAdd(&sh.rs[0], acc_mu);
+        __syncthreads();
     }
     if (chain) { atomicAdd(&sh.rs[1], acc_sa); atomicAdd(&sh.rs[2], acc_nu); }
     if (ethread) {

@@ -55,6 +55,8 @@ struct ScanOptions {
                           // call left — the powers of such a call are not a result (stale or undefined)
     int rp_events = 0;    // posterior draws (capi.hip rand_posterior_batch), timing tools ONLY: 1 = the steps of a call's first chunk record the context's event
                           // slots 4 .. 9 (before the gather | after it | after the simulation | the residual | the prediction | the combination)
+    int theta_events = 0; // theta gradient (capi.hip logl_grad_batch fed by approx), timing tools ONLY: 1 = a call's first chunk records the context's event slots
+                          // 4 .. 7 (before approx_kernel | after it | before approx_vjp_kernel | after it)
 };
 
 struct ScanParams {
@@ -263,11 +265,16 @@ int pioran_launch_quantiles(int64_t B, int64_t M, int64_t ldx, const double* X, 
 int pioran_approx_setup_host(int64_t J, int basis, double f_min, double f_max, double S_low, double S_high,
                              std::vector<double>& sp, std::vector<double>& LU, std::vector<int32_t>& piv,
                              std::vector<double>& c, std::vector<double>& d, std::vector<int32_t>& real_term);
+void pioran_approx_weights_host(int basis, int integrated, double f_min, double f_max, const std::vector<double>& sp, std::vector<double>& w);
 #endif
 int pioran_launch_approx(int64_t B, int model, int P, int J, int basis, int integrated, double f_min, double f_max,
                          const double* sp, const double* LU, const int32_t* piv, const double* theta, const double* norm,
                          int n_qpo, const double* qpo /*[B][n_qpo][3]: S0, f0, Q*/, double* A, double* Bc,
                          double* Cq /*[B][Jt]: per-draw c of the feature terms*/, double* Dq, hipStream_t stream);
+// reverse mode of approx for the continuum models: ga, gb [B][Jt] (Jt = J for basis 0, 2 J for basis 1) -> gtheta [B][P], gnorm [B]; scratch: 2 J B doubles
+int pioran_launch_approx_vjp(int64_t B, int model, int P, int J, int basis, const double* sp, const double* w /*pioran_approx_weights_host*/,
+                             const double* LU, const int32_t* piv, const double* theta, const double* norm, const double* ga, const double* gb,
+                             double* scratch, double* gtheta, double* gnorm, hipStream_t stream);
 // table.hip (diagnostics)
 int pioran_launch_fma_stream(int blocks, int iters, double* scratch, double* flop, hipStream_t stream);
 // dense.hip

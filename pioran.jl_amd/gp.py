@@ -30,6 +30,20 @@ def _ptr(x):
     return None if x is None else ctypes.c_void_p(x.ctypes.data)
 
 
+def _theta_args(model, theta, norm, basis_function):
+    """(model id, basis id, theta (B, P), norm (B,)) of the entries that run `approx` on the device."""
+    from .psd import DoubleBendingPowerLaw, SingleBendingPowerLaw
+    mid = {SingleBendingPowerLaw: 0, DoubleBendingPowerLaw: 1}.get(model)
+    if mid is None:
+        raise ValueError("model must be SingleBendingPowerLaw or DoubleBendingPowerLaw")
+    if basis_function not in ("SHO", "DRWCelerite"):
+        raise ValueError("Basis function" + basis_function + "not implemented")
+    theta = _f64(np.atleast_2d(theta))
+    if theta.shape[1] != (3 if mid == 0 else 5):
+        raise ValueError("theta has the wrong number of columns for this model")
+    return mid, 0 if basis_function == "SHO" else 1, theta, _f64(np.broadcast_to(norm, (theta.shape[0],)))
+
+
 class Context:
     """One GPU + one HIP stream (pioran_ctx).  One per host thread / rank."""
 
@@ -117,6 +131,21 @@ class Context:
         _lib.check(_lib.lib().pioran_celerite_simulate(self._h, N, B, J, _ptr(A), _ptr(Bc), _ptr(C), _ptr(Dd), int(C.ndim == 1), _ptr(t),
                                                        _ptr(sigma2), _ptr(q), _ptr(out)), self._h)
         return out
+
+    def approx_vjp(self, model, theta, norm, grad_a, grad_b, f_min, f_max, n_components=20, S_low=20.0, S_high=20.0, *,
+                   is_integrated_power=True, basis_function="SHO"):
+        """Chain rule through `approx` on the device (pioran_approx_vjp_batch): dL/da, dL/db (B, J) -> dL/dtheta (B, P), dL/dnorm (B,).
+        model, theta, norm and the keywords as in Dataset.logpdf_theta; J = n_components ("SHO") or 2 n_components ("DRWCelerite")."""
+        mid, basis, theta, norm = _theta_args(model, theta, norm, basis_function)
+        B, P = theta.shape
+        grad_a, grad_b = _f64(grad_a), _f64(grad_b)
+        if grad_a.shape != (B, n_components * (1 + basis)) or grad_b.shape != grad_a.shape:
+            raise ValueError("grad_a, grad_b must be (B, J)")
+        gth, gnorm = np.empty((B, P)), np.empty(B)
+        _lib.check(_lib.lib().pioran_approx_vjp_batch(self._h, B, mid, int(n_components), basis, int(bool(is_integrated_power)), float(f_min),
+                                                      float(f_max), float(S_low), float(S_high), _ptr(theta), _ptr(norm), _ptr(grad_a),
+                                                      _ptr(grad_b), _ptr(gth), _ptr(gnorm)), self._h)
+        return gth, gnorm
 
     # -- batched Lomb-Scargle periodogram ------------------------------------------------------
     def lombscargle(self, t, Y, yerr, freq, fit_mean=True, center_data=True, return_status=False):
@@ -475,11 +504,19 @@ class Dataset:
                 "grad_y": gy, "grad_sigma2": gs}
 
     def logpdf_theta_grad(self, model, theta, norm, f_min, f_max, n_components=20, S_low=20.0, S_high=20.0, *,
-                          is_integrated_power=True, basis_function="SHO", mu=None, nu=None, shift=None):
+                          is_integrated_power=True, basis_function="SHO", mu=None, nu=None, shift=None, approx_on="host",
+                          return_coef_grads=False):
         """log L and its gradient with respect to the SAMPLED parameters of the reference's models
         (README.md:38-71: theta = PSD parameters, norm = variance, nu, mu): the device gradient w.r.t. (a, b, nu, mu)
-        chained through `approx` on the host (approx_batch_vjp).  Returns a dict: logl, status, grad_theta (B, P),
-        grad_norm, grad_nu, grad_mu (B,)."""
+        chained through `approx` on the host (approx_batch_vjp) or, approx_on="device", in one device call
+        (pioran_logpdf_batch_theta_grad: approx and its reverse mode run either side of the same reverse-mode kernels).
+        Returns a dict: logl, status, grad_theta (B, P), grad_norm, grad_nu, grad_mu (B,) and, with return_coef_grads,
+        the intermediate grad_a, grad_b (B, J)."""
+        if approx_on == "device":
+            return self._logpdf_theta_grad_device(model, theta, norm, f_min, f_max, n_components, S_low, S_high, is_integrated_power,
+                                                  basis_function, mu, nu, shift, return_coef_grads)
+        if approx_on != "host":
+            raise ValueError('approx_on must be "host" or "device"')
         from .psd import approx_batch, approx_batch_vjp
         theta = np.atleast_2d(_f64(theta))
         A, Bc, C, Dd = approx_batch(model, theta, f_min, f_max, n_components, norm, S_low, S_high,
@@ -487,9 +524,32 @@ class Dataset:
         g = self.logl_grad(A, Bc, C, Dd, mu=mu, nu=nu, shift=shift, cd_grad=False)   # (c, d) are fixed by the spectral grid: windowed reverse mode
         gth, gnorm = approx_batch_vjp(model, theta, f_min, f_max, n_components, norm, g["grad_a"], g["grad_b"], S_low, S_high,
                                       is_integrated_power=is_integrated_power, basis_function=basis_function)
-        return {"logl": g["logl"], "status": g["status"], "grad_theta": gth, "grad_norm": gnorm,
-                "grad_nu": g["grad_nu"] if nu is not None else None, "grad_mu": g["grad_mu"] if mu is not None else None,
-                "grad_shift": g.get("grad_shift")}
+        res = {"logl": g["logl"], "status": g["status"], "grad_theta": gth, "grad_norm": gnorm,
+               "grad_nu": g["grad_nu"] if nu is not None else None, "grad_mu": g["grad_mu"] if mu is not None else None,
+               "grad_shift": g.get("grad_shift")}
+        if return_coef_grads:
+            res["grad_a"], res["grad_b"] = g["grad_a"], g["grad_b"]
+        return res
+
+    def _logpdf_theta_grad_device(self, model, theta, norm, f_min, f_max, n_components, S_low, S_high, is_integrated_power, basis_function,
+                                  mu, nu, shift, return_coef_grads):
+        mid, basis, theta, norm = _theta_args(model, theta, norm, basis_function)
+        B, P = theta.shape
+        mu, nu, shift = (None if v is None else _f64(np.broadcast_to(v, (B,))) for v in (mu, nu, shift))
+        out, st = np.empty(B), np.zeros(B, dtype=np.int32)
+        gth, gnorm = np.empty((B, P)), np.empty(B)
+        gnu, gmu, gsh = (None if v is None else np.empty(B) for v in (nu, mu, shift))
+        Jt = n_components * (1 + basis)
+        ga = np.empty((B, Jt)) if return_coef_grads else None
+        gb = np.empty((B, Jt)) if return_coef_grads else None
+        _lib.check(_lib.lib().pioran_logpdf_batch_theta_grad(
+            self._h, B, mid, int(n_components), basis, int(bool(is_integrated_power)), float(f_min), float(f_max), float(S_low), float(S_high),
+            _ptr(theta), _ptr(norm), _ptr(mu), _ptr(nu), _ptr(shift), _ptr(out), _ptr(st), _ptr(gth), _ptr(gnorm), _ptr(gnu), _ptr(gmu),
+            _ptr(gsh), _ptr(ga), _ptr(gb)), self.ctx._h)
+        res = {"logl": out, "status": st, "grad_theta": gth, "grad_norm": gnorm, "grad_nu": gnu, "grad_mu": gmu, "grad_shift": gsh}
+        if return_coef_grads:
+            res["grad_a"], res["grad_b"] = ga, gb
+        return res
 
     def logl_batch_dev(self, B, dA, dBc, dmu=0, dnu=0, dY=0, dS2=0, dout=0, dstatus=0):
         """Device-pointer (int addresses) asynchronous variant; (c, d) from prepare()."""

@@ -260,6 +260,66 @@ function logpdf_batch_theta(ds::Dataset, model::Symbol, θ::Matrix{Float64}, nor
     return out, status
 end
 
+"""
+    logpdf_theta_grad_batch(ds, model, θ, norm, f_min, f_max, n_components; basis, μ, ν, shift, coef_grads, ...)
+
+Value and gradient with respect to the sampled parameters in one device call: `approx`, the reverse mode of the likelihood and the
+reverse mode of `approx` all run on the GPU; `θ` (`P × nbatch`), `norm`, `μ`, `ν`, `shift` go in and `grad_θ` (`P × nbatch`),
+`grad_norm`, `grad_ν`, `grad_μ`, `grad_shift` (each `nothing` when its input is) come out.  Continuum models only (no QPO features).
+`coef_grads = true` also returns the intermediate `grad_a`, `grad_b` (`J × nbatch`).
+"""
+function logpdf_theta_grad_batch(ds::Dataset, model::Symbol, θ::Matrix{Float64}, norm::Vector{Float64}, f_min::Real, f_max::Real,
+                                 n_components::Integer; basis::String = "SHO", is_integrated_power::Bool = true,
+                                 S_low::Real = 20.0, S_high::Real = 20.0, μ::Union{Nothing, Vector{Float64}} = nothing,
+                                 ν::Union{Nothing, Vector{Float64}} = nothing, shift::Union{Nothing, Vector{Float64}} = nothing,
+                                 coef_grads::Bool = false)
+    m = model === :SingleBendingPowerLaw ? 0 : model === :DoubleBendingPowerLaw ? 1 : error("model $model not supported on the device")
+    bs = basis == "SHO" ? 0 : basis == "DRWCelerite" ? 1 : error("basis $basis not supported on the device")
+    size(θ, 1) == (m == 0 ? 3 : 5) || error("θ must be $(m == 0 ? 3 : 5) × nbatch")
+    nb = size(θ, 2)
+    J = bs == 0 ? n_components : 2 * n_components
+    out = Vector{Float64}(undef, nb); status = zeros(Int32, nb)
+    gθ = Matrix{Float64}(undef, size(θ, 1), nb); gn = Vector{Float64}(undef, nb)
+    like(x) = x === nothing ? nothing : Vector{Float64}(undef, nb)
+    gν = like(ν); gμ = like(μ); gs = like(shift)
+    ga = coef_grads ? Matrix{Float64}(undef, J, nb) : nothing; gb = coef_grads ? Matrix{Float64}(undef, J, nb) : nothing
+    p(x) = x === nothing ? Ptr{Cdouble}(C_NULL) : pointer(x)
+    GC.@preserve θ norm μ ν shift out status gθ gn gν gμ gs ga gb begin
+        check(ccall((:pioran_logpdf_batch_theta_grad, LIB), Cint,
+                    (Ptr{Cvoid}, Int64, Cint, Int64, Cint, Cint, Cdouble, Cdouble, Cdouble, Cdouble, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    ds.h, nb, m, n_components, bs, is_integrated_power ? 1 : 0, f_min, f_max, S_low, S_high, θ, norm,
+                    p(μ), p(ν), p(shift), out, status, gθ, gn, p(gν), p(gμ), p(gs), p(ga), p(gb)))
+    end
+    return (logl = out, status = status, grad_θ = gθ, grad_norm = gn, grad_ν = gν, grad_μ = gμ, grad_shift = gs, grad_a = ga, grad_b = gb)
+end
+
+"""
+    approx_vjp_batch(model, θ, norm, grad_a, grad_b, f_min, f_max, n_components; basis, ctx, ...)
+
+The reverse mode of `approx` alone, on the GPU — what an `rrule` for `approx` returns for the cotangents `grad_a`, `grad_b`
+(`J × nbatch`) of the celerite coefficients: `(grad_θ, grad_norm)`.
+"""
+function approx_vjp_batch(model::Symbol, θ::Matrix{Float64}, norm::Vector{Float64}, grad_a::Matrix{Float64}, grad_b::Matrix{Float64},
+                          f_min::Real, f_max::Real, n_components::Integer; basis::String = "SHO", is_integrated_power::Bool = true,
+                          S_low::Real = 20.0, S_high::Real = 20.0, ctx = default_context())
+    m = model === :SingleBendingPowerLaw ? 0 : model === :DoubleBendingPowerLaw ? 1 : error("model $model not supported on the device")
+    bs = basis == "SHO" ? 0 : basis == "DRWCelerite" ? 1 : error("basis $basis not supported on the device")
+    size(θ, 1) == (m == 0 ? 3 : 5) || error("θ must be $(m == 0 ? 3 : 5) × nbatch")
+    nb = size(θ, 2)
+    size(grad_a) == size(grad_b) == ((bs == 0 ? 1 : 2) * n_components, nb) || error("grad_a, grad_b must be J × nbatch")
+    gθ = Matrix{Float64}(undef, size(θ, 1), nb); gn = Vector{Float64}(undef, nb)
+    GC.@preserve θ norm grad_a grad_b gθ gn begin
+        check(ccall((:pioran_approx_vjp_batch, LIB), Cint,
+                    (Ptr{Cvoid}, Int64, Cint, Int64, Cint, Cint, Cdouble, Cdouble, Cdouble, Cdouble, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    ctx.h, nb, m, n_components, bs, is_integrated_power ? 1 : 0, f_min, f_max, S_low, S_high, θ, norm,
+                    grad_a, grad_b, gθ, gn))
+    end
+    return gθ, gn
+end
+
 # ---- in-process farm: ONE Julia process driving several GPUs (no Distributed/MPI launcher needed) ----------------------
 mutable struct Farm
     h::Ptr{Cvoid}
