@@ -457,6 +457,21 @@ int pioran_value_route(int32_t R, int32_t J, int32_t n_one_row_terms, int64_t B,
  * name, PIORAN_ERR_ARG: as above; also N above 2^48.  tests/test_route.py, tests/test_gpu_route.py. */
 int pioran_value_route_cd(int32_t n_two_row_terms, int32_t n_one_row_terms, int32_t n_per_draw_terms, int64_t B, int64_t N, int per_draw_series,
                           int must_run, const char* options, char* name, int name_len, int64_t* mixed_chunk);
+/* Diagnostics (no GPU needed): the plan of the other batched entries — entry = "predict" (pioran_celerite_predict), "predict_var"
+ * (pioran_celerite_predict_var), "grad" (pioran_celerite_logl_grad[_shift], pioran_logpdf_batch_theta_grad), "simulate" (pioran_celerite_simulate),
+ * "rand_posterior" (pioran_celerite_rand_posterior[_summary]) — for B draws of J terms, n_one_row_terms of them with one row (R = 2 J -
+ * n_one_row_terms active rows), every resource granted.  per_draw != 0: (c, d) per draw (cd_shared = 0); gradient only: shift != 0 the shifted
+ * log-flux form, want_c / want_d: grad_c / grad_d asked for, series_grads: grad_y or grad_sigma2 asked for.  `name` receives the string
+ * pioran_celerite_config_name(-1) reports after the call: "block (windowed ...)", "block (windowed ..., per-draw tables)", "tile (windowed gradient,
+ * one draw per wavefront)" or "wide (step-by-step ...)" with ... = prediction, variance, gradient, simulation, posterior draw; for a call with
+ * (c, d) per draw whose batch form refuses (more than 63 rows, an option that forbids the windowed kernels, the shifted gradient, an entry without
+ * such a form) the name of the one-draw shared calls the entry falls back to.  chunk_cap, where not NULL: the draws per chunk before any memory
+ * budget; shrink, where not NULL: 1 where a call short of memory halves its chunk, 0 where it leaves the windowed kernels for the step-by-step ones
+ * (shared prediction and simulation).  PIORAN_ERR_UNSUPPORTED (name ""): the entry refuses the rows (143; variance: 64).  options, name,
+ * PIORAN_ERR_ARG: as for pioran_value_route; also an unknown entry.  The rule is csrc/route.hip entry_plan; tests/test_route.py holds it,
+ * tests/test_gpu_entry_route.py holds the calls to it. */
+int pioran_entry_route(const char* entry, int32_t R, int32_t J, int32_t n_one_row_terms, int64_t B, int per_draw, int shift, int want_c, int want_d,
+                       int series_grads, const char* options, char* name, int name_len, int64_t* chunk_cap, int* shrink);
 /* Diagnostics: the FP64 FMA rate (TFLOP/s) the device sustains right now with `waves_per_simd` (1 .. 8) wavefronts on every SIMD — about
  * `ms` milliseconds of a pure stream of independent v_fma_f64, event-timed on the context's stream.  The measured ceiling of any FP64
  * vector kernel on this box at that occupancy (the 78.6 TFLOP/s vendor figure assumes one FMA per SIMD every 4 cycles at 2.4 GHz).

@@ -454,28 +454,22 @@ int download_grads(pioran_ctx* ctx, const GradPtrs& host, const GradPtrs& dev, i
 }
 
 // Sizing a chunk of draws.  `chunk` is halved while need(chunk) bytes of workspace exceed what the call may newly take (ws_allow) plus what
-// the buffers in `held`, the ones need() counts, hold already ...
+// the buffers in `held`, the ones need() counts, hold already, and halved again while ensure_all(chunk), which grows every buffer the chunk needs,
+// cannot allocate.  Returns ensure_all's code for the chunk it leaves in `chunk`.  shrink = false (EntryPlan::shrink: the plans that leave the
+// windowed kernels when memory is short): no second halving, PIORAN_ERR_ALLOC for the chunk the budget admits.
 using BufList = std::initializer_list<const pioran_ctx::Buf*>;
-template <class Need>
-int64_t budget_chunk(pioran_ctx* ctx, int64_t chunk, BufList held, Need need)
+template <class Need, class EnsureAll>
+int size_chunk(pioran_ctx* ctx, int64_t& chunk, BufList held, Need need, EnsureAll ensure_all, bool shrink = true)
 {
     size_t free_b = 0;
-    if (!device_free_bytes(free_b)) return chunk;
-    size_t allowed = ws_allow(ctx, free_b);
-    for (const pioran_ctx::Buf* b : held) allowed += b->cap;
-    while (chunk > 1 && need(chunk) > allowed) chunk /= 2;
-    return chunk;
-}
-
-// ... and halved again while ensure_all(chunk), which grows every buffer the chunk needs, cannot allocate.  Returns ensure_all's code for the
-// chunk it leaves in `chunk`.  (The entries that leave the windowed kernels when memory is short, instead of shrinking, use budget_chunk alone.)
-template <class Need, class EnsureAll>
-int size_chunk(pioran_ctx* ctx, int64_t& chunk, BufList held, Need need, EnsureAll ensure_all)
-{
-    chunk = budget_chunk(ctx, chunk, held, need);
+    if (device_free_bytes(free_b)) {
+        size_t allowed = ws_allow(ctx, free_b);
+        for (const pioran_ctx::Buf* b : held) allowed += b->cap;
+        while (chunk > 1 && need(chunk) > allowed) chunk /= 2;
+    }
     for (;;) {
         const int rc = ensure_all(chunk);
-        if (rc != PIORAN_ERR_ALLOC || chunk == 1) return rc;
+        if (rc != PIORAN_ERR_ALLOC || chunk == 1 || !shrink) return rc;
         chunk /= 2;
     }
 }
@@ -620,13 +614,15 @@ int ensure_btab(pioran_ds* ds, PrepState& s)
     return PIORAN_OK;
 }
 
-// An entry whose rows fit the windowed kernels (`windowed`) can run on them with (c, d) per draw, which bring their own tables, and with a shared
-// (c, d) where the state's forward table can be had: it is built here on first use, and `windowed` cleared where it cannot
-int windowed_ready(pioran_ds* ds, PrepState& s, bool per_draw, bool& windowed)
+// The plan of an entry (route.hip entry_plan) for the prepared state; a refusal comes before any upload or workspace.  A plan on the windowed kernels
+// can run on them with (c, d) per draw, which bring their own tables, and with a shared (c, d) where the state's forward table can be had: it is built
+// here on first use, and the plan leaves the windowed kernels where it cannot
+int plan_entry(pioran_ds* ds, PrepState& s, Entry entry, int64_t B, bool per_draw, int grad_flags, EntryPlan& plan)
 {
-    if (!windowed || per_draw) return PIORAN_OK;
+    plan = entry_plan(entry, s.R, s.J, s.npd_terms, B, per_draw, grad_flags, ds->ctx->opt);
+    if (plan.rc || !plan.windowed || per_draw) return plan.rc;
     const int rc = ensure_btab(ds, s);
-    if (rc == PIORAN_ERR_UNSUPPORTED) windowed = false;
+    if (rc == PIORAN_ERR_UNSUPPORTED) plan.leave_windowed();
     return rc == PIORAN_ERR_UNSUPPORTED ? PIORAN_OK : rc;
 }
 
@@ -912,6 +908,20 @@ int pioran_value_route_cd(int32_t n_two_row_terms, int32_t n_one_row_terms, int3
     std::snprintf(name, (size_t)name_len, "%s", fam ? fam : "");
     if (mixed_chunk) *mixed_chunk = chunk;
     return fam ? PIORAN_OK : PIORAN_ERR_UNSUPPORTED;
+}
+
+int pioran_entry_route(const char* entry, int32_t R, int32_t J, int32_t n_one_row_terms, int64_t B, int per_draw, int shift, int want_c, int want_d,
+                       int series_grads, const char* options, char* name, int name_len, int64_t* chunk_cap, int* shrink)
+{
+    if (!entry || J < 1 || n_one_row_terms < 0 || n_one_row_terms > J || R != 2 * J - n_one_row_terms || B < 1 || !name || name_len < 1) return PIORAN_ERR_ARG;
+    ScanOptions opt{};
+    if (const int rc = parse_options(options, opt)) return rc;
+    const int flags = (shift ? kGradShift : 0) | (want_c ? kGradC : 0) | (want_d ? kGradD : 0) | (series_grads ? kGradSeries : 0);
+    const EntryPlan plan = entry_route(entry, R, J, B, per_draw != 0, flags, opt);
+    std::snprintf(name, (size_t)name_len, "%s", plan.name);
+    if (chunk_cap) *chunk_cap = plan.chunk_cap;
+    if (shrink) *shrink = plan.shrink;
+    return plan.rc;
 }
 
 extern "C" {
@@ -1268,7 +1278,8 @@ int pioran_celerite_logl_batch_dev_cd(pioran_ds* ds, int64_t B, int64_t J, const
     return PIORAN_OK;
 }
 
-// kind[j] of a batch's terms (build_rowmap): 2 where (c, d) differ between the draws (per_draw: C, Dd are [B][J]; else [J]); 1 where the sin row is
+// kind[j] of a batch's terms (build_rowmap): 2 where (c, d) differ between the draws (per_draw: C, Dd are [B][J]; else [J], and C is not read:
+// rand_posterior_refuse passes none); 1 where the sin row is
 // identically zero for the whole batch (d_j = 0 and b_j = 0 in every draw): the term keeps only its cos row; 0 otherwise
 static std::vector<int32_t> classify_terms(int64_t B, int64_t J, const double* Bc, const double* C, const double* Dd, bool per_draw)
 {
@@ -1637,32 +1648,28 @@ int pioran_celerite_logl(pioran_ctx* ctx, int64_t N, int64_t J, const double* a,
 //   per_draw — (c, d) of their own in every term (posterior draws of QPO / CARMA / free Celerite models), several draws: every draw its own
 //   windowed-kernel tables, built per chunk, all draws of a chunk in one launch of every kernel.  There is no step-by-step leg: a shape the windowed
 //   kernels do not take is PIORAN_ERR_UNSUPPORTED before any upload or allocation, and the public entry goes draw by draw (each_draw).
-// The forms differ in the state they prepare (prepare_draws), in who builds the tables and when (build_tables), in the launch description
-// (chunk_params) and in what happens when memory is short: the per-draw form halves its chunk (size_chunk), the shared prediction and simulation leave
-// the windowed kernels (budget_chunk alone).  The argument checks are the public entries'.
+// The forms differ in the state they prepare (prepare_draws), in who builds the tables and when (build_tables), in the launch description (chunk_params).
+// Kernels, refusals, the chunk's cap and what a call short of memory does: the EntryPlan (route.hip entry_plan).  The argument checks: the public entries'.
 
-// Posterior mean of B draws at M times; chunks of at most 256 draws
+// Posterior mean of B draws at M times
 static int predict_batch(pioran_ds* ds, bool per_draw, int64_t B, int64_t J, const DrawChunk& in, int64_t M, const double* tau, double* mean_out,
                          int32_t* status)
 {
     pioran_ctx* ctx = ds->ctx;
     PrepState& s = ds->host;
-    if (per_draw && !windowed_allowed(ctx->opt, (int32_t)(2 * J), (int32_t)J)) return PIORAN_ERR_UNSUPPORTED;
+    if (per_draw && entry_plan(Entry::predict, (int32_t)(2 * J), (int32_t)J, 0, B, true, 0, ctx->opt).rc) return PIORAN_ERR_UNSUPPORTED;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     PendingGuard pending_guard(ctx);
     int rc;
     if ((rc = prepare_draws(ds, per_draw, B, J, in.Bc, in.C, in.D))) return rc;
-    if (s.R > pioran_predict_supported_rows() || s.npd_terms) return PIORAN_ERR_UNSUPPORTED;   // before any upload / workspace
+    EntryPlan plan;
+    if ((rc = plan_entry(ds, s, Entry::predict, B, per_draw, 0, plan))) return rc;
     const int64_t N = ds->N;
     // buffer roles: the per-window stores (step by step: the factor) | a chunk's forward tables (per_draw only) | the reverse table(s) | -z and the Q
     // recurrences | the tau-only factors | a chunk's means | tau
     pioran_ctx::Buf &stores = ctx->bwork, &btabs = ctx->bscratch, &gtabs = ctx->bgtab, &qws = ctx->bq, &tauws = ctx->bK, &mean = ctx->bY, &taus = ctx->bshift;
-    // Windowed path (round 3): z = K^-1 (y - mu) from the windowed factorisation and a block back-substitution (celerite_block.hip),
-    // then the two Q recurrences segment-parallel (celerite_predict.hip) — no step-by-step factor, no per-step wave reduction
-    bool windowed = per_draw || (windowed_allowed(ctx->opt, s.R, s.J) && s.R <= 63);
-    if ((rc = windowed_ready(ds, s, per_draw, windowed))) return rc;
-    int64_t chunk = B < 256 ? B : 256;
-    if (windowed) {
+    int64_t chunk = std::min(B, plan.chunk_cap);
+    if (plan.windowed) {
         const size_t bt = per_draw ? pioran_block_table_doubles(N, s.R, s.J) : 0, gt = pioran_block_gtab_doubles(N, s.R);
         auto ntab = [&](int64_t nb) { return per_draw ? nb : 1; };      // pairs of tables of nb draws
         auto need = [&](int64_t nb) {
@@ -1678,15 +1685,12 @@ static int predict_batch(pioran_ds* ds, bool per_draw, int64_t B, int64_t J, con
                                      {&tauws, pioran_predict_tau_workspace_doubles(M, s.R, ntab(nb)) * sizeof(double)},
                                      {&mean, per_draw ? (size_t)nb * (size_t)M * sizeof(double) : 0}});
         };
-        if (per_draw) {
-            rc = size_chunk(ctx, chunk, {&stores, &btabs, &gtabs, &tauws, &qws}, need, grow);
-        } else {   // (no memory for the chunk the budget admits: not a smaller chunk, the step-by-step kernels)
-            chunk = budget_chunk(ctx, chunk, {&stores, &qws}, need);
-            if ((rc = grow(chunk)) == PIORAN_ERR_ALLOC) { windowed = false; chunk = B < 256 ? B : 256; rc = PIORAN_OK; }
-        }
+        rc = size_chunk(ctx, chunk, per_draw ? BufList{&stores, &btabs, &gtabs, &tauws, &qws} : BufList{&stores, &qws}, need, grow, plan.shrink);
+        // (no memory for the chunk the budget admits: not a smaller chunk, the step-by-step kernels)
+        if (rc == PIORAN_ERR_ALLOC && !plan.shrink) { plan.leave_windowed(); chunk = std::min(B, plan.chunk_cap); rc = PIORAN_OK; }
         if (rc) return rc;
     }
-    if (!windowed && (rc = ensure(ctx, stores, pioran_predict_workspace_doubles(chunk, N, s.R) * sizeof(double)))) return rc;
+    if (!plan.windowed && (rc = ensure(ctx, stores, pioran_predict_workspace_doubles(chunk, N, s.R) * sizeof(double)))) return rc;
     if ((rc = upload(ctx, taus, tau, (size_t)M * sizeof(double)))) return rc;
     if ((rc = ensure(ctx, mean, (size_t)chunk * (size_t)M * sizeof(double)))) return rc;   // [chunk][M]
     if ((rc = ensure_results(ctx, chunk))) return rc;
@@ -1696,18 +1700,17 @@ static int predict_batch(pioran_ds* ds, bool per_draw, int64_t B, int64_t J, con
         const int64_t nb = std::min(B - b0, chunk);
         DrawChunk m;
         if ((rc = upload_draws(ctx, J, b0, nb, in.A, in.Bc, per_draw ? in.C : nullptr, in.D, in.mu, in.nu, m))) return rc;
-        if (windowed && (per_draw || b0 == 0) && (rc = build_tables(ds, s, per_draw, nb, m, btabs, &gtabs, tb))) return rc;
+        if (plan.windowed && (per_draw || b0 == 0) && (rc = build_tables(ds, s, per_draw, nb, m, btabs, &gtabs, tb))) return rc;
         ScanParams p = chunk_params(ds, s, per_draw, nb, m, tb);
         p.out = (double*)ctx->bout.p; p.status = (int32_t*)ctx->bst.p;
-        if (windowed) {
+        g_last_kernel = plan.name;
+        if (plan.windowed) {
             p.gw = (double*)stores.p;
-            g_last_kernel = per_draw ? "block (windowed prediction, per-draw tables)" : "block (windowed prediction)";
             // -z = -K^-1 (y - mu) [nb][N] into the head of the Q workspace
             rc = pioran_launch_block_solve(p, tb.btab, tb.gtab, (double*)qws.p, ctx->stream);
             if (!rc) rc = pioran_launch_predict_from_gy(p, (double*)qws.p, (double*)tauws.p, ds->t, M, (const double*)taus.p, (double*)mean.p, ctx->stream,
                                                         per_draw, tau_sorted);
         } else {
-            g_last_kernel = "wide (step-by-step prediction)";
             rc = pioran_launch_predict(p, (double*)stores.p, ds->t, M, (const double*)taus.p, (double*)mean.p, ctx->stream);
         }
         if (rc) { ctx->last_err = "prediction launch failed"; return rc; }
@@ -1731,7 +1734,7 @@ int pioran_celerite_predict(pioran_ds* ds, int64_t B, int64_t J, const double* A
 }
 
 // ---- posterior variance at new times through the factorisation (celerite_predict.hip) ------------------------------------------------
-// shared (c, d), tau ASCENDING (the caller below sorts); draws in chunks of at most 256 sized to the free memory
+// shared (c, d), tau ASCENDING (the caller below sorts); draws in chunks sized to the free memory
 static int predict_var_shared(pioran_ds* ds, int64_t B, int64_t J, const DrawChunk& in, int64_t M, const double* tau, double* var_out, int32_t* status)
 {
     pioran_ctx* ctx = ds->ctx;
@@ -1740,12 +1743,13 @@ static int predict_var_shared(pioran_ds* ds, int64_t B, int64_t J, const DrawChu
     PendingGuard pending_guard(ctx);
     int rc;
     if ((rc = prepare_shared(ds, B, J, in.Bc, in.C, in.D))) return rc;
-    if (s.R > 64 || s.npd_terms) return PIORAN_ERR_UNSUPPORTED;   // before any upload / workspace
+    EntryPlan plan;
+    if ((rc = plan_entry(ds, s, Entry::predict_var, B, false, 0, plan))) return rc;
     if (M == 0) {
         if (status) for (int64_t b = 0; b < B; ++b) status[b] = 0;
         return PIORAN_OK;
     }
-    int64_t chunk = B < 256 ? B : 256;
+    int64_t chunk = std::min(B, plan.chunk_cap);
     auto need = [&](int64_t nb) { return pioran_predict_var_workspace_doubles(nb, ds->N, s.R, M) * sizeof(double); };
     rc = size_chunk(ctx, chunk, {&ctx->bwork}, need, [&](int64_t nb) {
         return ensure_each(ctx, {{&ctx->bwork, need(nb)}, {&ctx->bY, (size_t)nb * (size_t)M * sizeof(double)}});
@@ -1760,7 +1764,7 @@ static int predict_var_shared(pioran_ds* ds, int64_t B, int64_t J, const DrawChu
         if ((rc = upload_draws(ctx, J, b0, nb, in.A, in.Bc, nullptr, nullptr, nullptr, in.nu, m))) return rc;
         ScanParams p = shared_params(ds, s, nb, m);
         p.out = (double*)ctx->bout.p;     // (the status comes from the variance kernel itself: bst below)
-        g_last_kernel = "wide (step-by-step variance)";
+        g_last_kernel = plan.name;
         rc = pioran_launch_predict_var(p, (double*)ctx->bwork.p, (double*)ctx->bK.p, ds->t, M, (const double*)ctx->bshift.p, (double*)ctx->bY.p,
                                        (int32_t*)ctx->bst.p, ctx->stream);
         if (rc) { ctx->last_err = "variance launch failed"; return rc; }
@@ -1814,35 +1818,23 @@ static int logl_grad_batch(pioran_ds* ds, bool per_draw, int64_t B, int64_t J, c
 {
     pioran_ctx* ctx = ds->ctx;
     PrepState& s = ds->host;
-    if (per_draw && (shift || !windowed_allowed(ctx->opt, (int32_t)(2 * J), (int32_t)J))) return PIORAN_ERR_UNSUPPORTED;
+    const int flags = (shift ? kGradShift : 0) | (grad.c ? kGradC : 0) | (grad.d ? kGradD : 0) | (grad.y || grad.s2 ? kGradSeries : 0);
+    if (per_draw && entry_plan(Entry::grad, (int32_t)(2 * J), (int32_t)J, 0, B, true, flags, ctx->opt).rc) return PIORAN_ERR_UNSUPPORTED;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     PendingGuard pending_guard(ctx);
     int rc;
     if ((rc = td ? prepare_state(ds, s, J, td->c.data(), td->d.data(), td->real.data()) : prepare_draws(ds, per_draw, B, J, in.Bc, in.C, in.D))) return rc;
-    if (s.R > pioran_wide_supported_rows_grad() || s.npd_terms) return PIORAN_ERR_UNSUPPORTED;
+    EntryPlan plan;
+    if ((rc = plan_entry(ds, s, Entry::grad, B, per_draw, flags, plan))) return rc;
     const int64_t N = ds->N;
     // buffer roles: the reverse mode's workspace | a chunk's forward tables (per_draw) or its transformed series Y | S2 (shift): never both | the reverse
     // table(s) | grad_a | grad_b | grad_c | grad_d of a chunk | grad_nu | grad_mu | shift | grad_shift.  The series gradients: bY, bS2.
     pioran_ctx::Buf &ws = ctx->bwork, &btabs = ctx->bscratch, &shifted = ctx->bscratch, &gtabs = ctx->bgtab, &terms = ctx->bK, &scalars = ctx->bq,
                     &shifts = ctx->bshift;
-    // Windowed reverse mode (celerite_block.hip, round 3) whenever the rows fit the windowed kernel, with or without d/d(c, d):
-    // 6.3 ms (7.0 with d/d(c, d)) instead of 25 at N = 1e4, J = 20 (series gradients and the shifted log-flux models included).
-    bool windowed = per_draw || windowed_allowed(ctx->opt, s.R, s.J);
-    if ((rc = windowed_ready(ds, s, per_draw, windowed))) return rc;
-    // Many chains (round 5): the one-draw-per-wavefront reverse mode (celerite_tile.hip) — value and d/d(a, b, mu, nu), since round 6 also d/d(c, d) of the
-    // SHARED (c, d) (both or neither), shared series.  Its
-    // forward pass keeps the lower tiles of T per window (12 KB at three block columns) and the reverse kernel recomputes the rest, where the
-    // small-batch kernels keep 41 KB per window and chain and hold one chain per CU.  scan_config = "tile" forces it for any chain count.
-    // From 513 chains on (measured, SHO-20 / SHO-12 at N = 1e4: 512 chains 15.1 / 9.3 ms against the small-batch kernels' 11.0 / 9.2; 640 chains 15.2 /
-    // 9.4 against 16.6 / 14.0; 2048 chains 27 / 16 against 44 / 36).
-    const bool tilegrad = !per_draw && windowed && (grad.c != nullptr) == (grad.d != nullptr) && !grad.y && !grad.s2 && !shift &&
-                          s.R <= pioran_tile_grad_supported_rows() && tile_grad_wanted(ctx->opt, B, s.R);
-    // (48 .. 63 rows — DRWCelerite-20 is 60: three draws per workgroup there (two with d/d(c, d)); 4096 chains take 126 ms (163 with d/d(c, d)) against 166 (175)
-    //  in 512-chain launches of the small-batch kernels: tools/ab_tile_grad_nb4.py, profiles/r06_tile_grad_four_block_columns.txt.  Until the reverse kernel
-    //  stopped spilling at four block columns — T_k and the window's U operands loaded at the head of their own window instead of a window ahead — it was 177 (208).)
+    // The windowed reverse mode (celerite_block.hip), many chains: the one-draw-per-wavefront reverse mode (celerite_tile.hip), else step by step
     auto ws_bytes = [&](int64_t nb) {
-        return (tilegrad ? pioran_tile_grad_workspace_doubles(nb, N, s.R)
-                         : (windowed ? pioran_block_grad_workspace_doubles(nb, N, s.R) : pioran_grad_workspace_doubles(nb, N, s.R))) * sizeof(double);
+        return (plan.tile ? pioran_tile_grad_workspace_doubles(nb, N, s.R)
+                         : (plan.windowed ? pioran_block_grad_workspace_doubles(nb, N, s.R) : pioran_grad_workspace_doubles(nb, N, s.R))) * sizeof(double);
     };
     // doubles of a draw's own forward and reverse table (per_draw: they are part of what a chunk needs)
     const size_t bt = per_draw ? pioran_block_table_doubles(N, s.R, s.J) : 0, gt = per_draw ? pioran_block_gtab_doubles(N, s.R) : 0;
@@ -1850,15 +1842,11 @@ static int logl_grad_batch(pioran_ds* ds, bool per_draw, int64_t B, int64_t J, c
     auto grow = [&](int64_t nb) {
         return ensure_each(ctx, {{&ws, ws_bytes(nb)}, {&btabs, (size_t)nb * bt * sizeof(double)}, {&gtabs, (size_t)nb * gt * sizeof(double)}});
     };
-    // Workspace per draw: (m, D) of every step + S at the checkpoints + two replayed segments (celerite_wide.hip): ~15 MB at
-    // N = 1e4, R = 40.  The chunk is bounded by half of the memory that is free right now (plus what the buffers it counts already
-    // hold) and halved again if the allocation still fails.
-    // windowed: 512 chains per launch pair (the forward pass then runs two workgroups per CU, the reverse pass two rounds of one); per-draw tables: 256
-    int64_t chunk = std::min<int64_t>(B, per_draw ? 256 : (windowed ? 512 : 1024));
-    if (tilegrad) {
-        // whole passes of 2048 (1024) chains: 7.7 GB of T per 1024 chains at N = 1e4, three block columns.  A sizing rule of its own: the limit holds for
-        // the buffer as a whole ("limit + what it holds" let the second call grow a 16 GB buffer to 31 GB), and the chunk is cut by 1024 chains, then halved
-        chunk = B < 4096 ? B : 4096;
+    // Step by step, the workspace per draw is (m, D) of every step + S at the checkpoints + two replayed segments (celerite_wide.hip)
+    int64_t chunk = std::min(B, plan.chunk_cap);
+    if (plan.tile) {
+        // whole passes of 2048 (1024) chains.  A sizing rule of its own: the limit holds for the buffer as a whole ("limit + what it holds" let the
+        // second call grow a 16 GB buffer to 31 GB), and the chunk is cut by 1024 chains, then halved
         size_t free_b = 0;
         if (device_free_bytes(free_b)) {
             const size_t allowed = ws_allow(ctx, free_b + ws.cap);
@@ -1871,7 +1859,7 @@ static int logl_grad_batch(pioran_ds* ds, bool per_draw, int64_t B, int64_t J, c
     }
     if (rc) return rc;
     // shared (c, d): the reverse pass's table (C o v, C o x in C/D order, C_K, sigma2): 13 KB per window, rebuilt per call (10 us)
-    if (windowed && !per_draw && (rc = ensure(ctx, gtabs, pioran_block_gtab_doubles(N, s.R) * sizeof(double)))) return rc;
+    if (plan.windowed && !per_draw && (rc = ensure(ctx, gtabs, pioran_block_gtab_doubles(N, s.R) * sizeof(double)))) return rc;
     const size_t cj = (size_t)chunk * (size_t)J * sizeof(double), cn = (size_t)chunk * (size_t)N * sizeof(double);
     if ((rc = ensure(ctx, terms, 4 * cj))) return rc;
     if ((rc = ensure(ctx, scalars, 2 * chunk * sizeof(double)))) return rc;
@@ -1893,7 +1881,7 @@ static int logl_grad_batch(pioran_ds* ds, bool per_draw, int64_t B, int64_t J, c
         if (b0 == 0) HIPCHK(ctx, mark(4));
         if ((rc = stage_draws(ctx, J, b0, nb, in, per_draw, td, m))) return rc;
         if (b0 == 0) HIPCHK(ctx, mark(5));
-        if (windowed && (per_draw || b0 == 0) && (rc = build_tables(ds, s, per_draw, nb, m, btabs, &gtabs, tb))) return rc;
+        if (plan.windowed && (per_draw || b0 == 0) && (rc = build_tables(ds, s, per_draw, nb, m, btabs, &gtabs, tb))) return rc;
         ScanParams p = chunk_params(ds, s, per_draw, nb, m, tb);
         p.out = (double*)ctx->bout.p; p.status = (int32_t*)ctx->bst.p;
         p.g_y = want_series ? (double*)ctx->bY.p : nullptr;
@@ -1906,16 +1894,14 @@ static int logl_grad_batch(pioran_ds* ds, bool per_draw, int64_t B, int64_t J, c
             p.Y = dYt; p.S2 = dSt;
         }
         double* const dgc = grad.c ? dev.c : nullptr; double* const dgd = grad.d ? dev.d : nullptr;
-        if (tilegrad) {
+        g_last_kernel = plan.name;
+        if (plan.tile) {
             p.gw = (double*)ws.p;
-            g_last_kernel = "tile (windowed gradient, one draw per wavefront)";
             rc = pioran_launch_tile_grad(p, tb.btab, tb.gtab, (double*)ctx->bpair.p, dev.a, dev.b, dev.nu, dev.mu, dgc, dgd, ctx->stream);
-        } else if (windowed) {
+        } else if (plan.windowed) {
             p.gw = (double*)ws.p;
-            g_last_kernel = per_draw ? "block (windowed gradient, per-draw tables)" : "block (windowed gradient)";
             rc = pioran_launch_block_grad(p, tb.btab, tb.gtab, dev.a, dev.b, dev.nu, dev.mu, dgc, dgd, ctx->stream);
         } else {
-            g_last_kernel = "wide (step-by-step gradient)";
             rc = pioran_launch_scan_wide_grad(p, (double*)ws.p, dev.a, dev.b, dgc, dgd, dev.nu, dev.mu, ctx->stream, ctx->aux, ctx->gev);
         }
         if (rc) { ctx->last_err = "gradient launch failed"; return rc; }
@@ -2033,11 +2019,11 @@ static int download_realisations(pioran_ctx* ctx, double* y_out, int64_t n)
     return PIORAN_OK;
 }
 
-// B realisations on the caller's time stamps from the normals q [B][N]; chunks of at most 256 draws
+// B realisations on the caller's time stamps from the normals q [B][N]
 static int simulate_batch(pioran_ctx* ctx, bool per_draw, int64_t N, int64_t B, int64_t J, const DrawChunk& in, const double* t, const double* sigma2,
                           const double* q, double* y_out)
 {
-    if (per_draw && !windowed_allowed(ctx->opt, (int32_t)(2 * J), (int32_t)J)) return PIORAN_ERR_UNSUPPORTED;
+    if (per_draw && entry_plan(Entry::simulate, (int32_t)(2 * J), (int32_t)J, 0, B, true, 0, ctx->opt).rc) return PIORAN_ERR_UNSUPPORTED;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     ScopedDataset series;
     int rc = series.create_zeros(ctx, N, t, sigma2);
@@ -2045,14 +2031,12 @@ static int simulate_batch(pioran_ctx* ctx, bool per_draw, int64_t N, int64_t B, 
     pioran_ds* ds = series.ds;
     if ((rc = prepare_draws(ds, per_draw, B, J, in.Bc, in.C, in.D))) return rc;
     PrepState& s = ds->host;
-    if (s.R > pioran_wide_supported_rows_modes() || s.npd_terms) return PIORAN_ERR_UNSUPPORTED;   // before any upload / workspace
+    EntryPlan plan;
+    if ((rc = plan_entry(ds, s, Entry::simulate, B, per_draw, 0, plan))) return rc;
     // buffer roles: the per-window stores | a chunk's forward tables (per_draw only) | xi | the normals | the realisations
     pioran_ctx::Buf &stores = ctx->bwork, &btabs = ctx->bscratch, &xi = ctx->bq, &noise = ctx->bY, &ysim = ctx->bS2;
-    // Windowed path (round 3; 6 .. 63 rows): the windowed factorisation with its per-window stores, then L applied window by window
-    bool windowed = per_draw || (windowed_allowed(ctx->opt, s.R, s.J) && s.R <= 63);
-    if ((rc = windowed_ready(ds, s, per_draw, windowed))) return rc;
-    int64_t chunk = B < 256 ? B : 256;
-    if (windowed) {
+    int64_t chunk = std::min(B, plan.chunk_cap);
+    if (plan.windowed) {
         const size_t bt = per_draw ? pioran_block_table_doubles(N, s.R, s.J) : 0;
         auto need = [&](int64_t nb) {
             size_t d = pioran_block_store_workspace_doubles(nb, N, s.R, 3);
@@ -2065,12 +2049,9 @@ static int simulate_batch(pioran_ctx* ctx, bool per_draw, int64_t N, int64_t B, 
                                      {&xi, (size_t)nb * (size_t)N * sizeof(double)},
                                      {&ctx->bst, nb * sizeof(int32_t)}});
         };
-        if (per_draw) {
-            rc = size_chunk(ctx, chunk, {&stores, &btabs, &xi}, need, grow);
-        } else {   // (no memory for the chunk the budget admits: not a smaller chunk, the step-by-step kernel)
-            chunk = budget_chunk(ctx, chunk, {&stores}, need);
-            if ((rc = grow(chunk)) == PIORAN_ERR_ALLOC) { windowed = false; chunk = B < 256 ? B : 256; rc = PIORAN_OK; }
-        }
+        rc = size_chunk(ctx, chunk, per_draw ? BufList{&stores, &btabs, &xi} : BufList{&stores}, need, grow, plan.shrink);
+        // (no memory for the chunk the budget admits: not a smaller chunk, the step-by-step kernel)
+        if (rc == PIORAN_ERR_ALLOC && !plan.shrink) { plan.leave_windowed(); chunk = std::min(B, plan.chunk_cap); rc = PIORAN_OK; }
         if (rc) return rc;
     }
     const size_t cn = (size_t)chunk * (size_t)N * sizeof(double);
@@ -2083,17 +2064,16 @@ static int simulate_batch(pioran_ctx* ctx, bool per_draw, int64_t N, int64_t B, 
         DrawChunk m;
         if ((rc = upload_draws(ctx, J, b0, nb, in.A, in.Bc, per_draw ? in.C : nullptr, in.D, nullptr, nullptr, m))) return rc;
         if ((rc = upload(ctx, noise, q + b0 * N, (size_t)nb * N * sizeof(double)))) return rc;
-        if (windowed && (per_draw || b0 == 0) && (rc = build_tables(ds, s, per_draw, nb, m, btabs, nullptr, tb))) return rc;
+        if (plan.windowed && (per_draw || b0 == 0) && (rc = build_tables(ds, s, per_draw, nb, m, btabs, nullptr, tb))) return rc;
         ScanParams p = chunk_params(ds, s, per_draw, nb, m, tb);
         p.out = (double*)ctx->bout.p;
         p.noise = (const double*)noise.p; p.ysim = (double*)ysim.p;
-        if (windowed) {
+        g_last_kernel = plan.name;
+        if (plan.windowed) {
             p.gw = (double*)stores.p;
             p.status = (int32_t*)ctx->bst.p;
-            g_last_kernel = per_draw ? "block (windowed simulation, per-draw tables)" : "block (windowed simulation)";
             rc = pioran_launch_block_sim(p, tb.btab, (double*)xi.p, ctx->stream);
         } else {
-            g_last_kernel = "wide (step-by-step simulation)";
             rc = pioran_launch_scan_wide_sim(p, ctx->stream);
         }
         if (rc) { ctx->last_err = "simulation launch failed"; return rc; }
@@ -2157,7 +2137,7 @@ struct DrawSink {
     DrawSink from_draw(int64_t b0, int64_t M) const { return {at(out, b0 * M), at(status, b0), at(dev_out, b0 * M), at(dev_status, b0)}; }
 };
 
-// B draws at M times on shared (c, d); chunks of at most 256 draws.  `simds`: the scratch data set on grid.T with y = 0, sigma2 = 0.
+// B draws at M times on shared (c, d).  `simds`: the scratch data set on grid.T with y = 0, sigma2 = 0.
 static int rand_posterior_batch(pioran_ds* ds, pioran_ds* simds, int64_t B, int64_t J, const DrawChunk& in, const double* shift, const MergedGrid& grid,
                                 int64_t M, const double* tau, const double* q_data, const double* q_new, const double* eps, const DrawSink& sink)
 {
@@ -2168,7 +2148,8 @@ static int rand_posterior_batch(pioran_ds* ds, pioran_ds* simds, int64_t B, int6
     int rc;
     if ((rc = prepare_shared(ds, B, J, in.Bc, in.C, in.D))) return rc;
     if ((rc = prepare_shared(simds, B, J, in.Bc, in.C, in.D))) return rc;
-    if (s.R > std::min(pioran_predict_supported_rows(), pioran_wide_supported_rows_modes()) || s.npd_terms) return PIORAN_ERR_UNSUPPORTED;   // before any upload / workspace
+    EntryPlan plan;
+    if ((rc = plan_entry(ds, s, Entry::rand_posterior, B, false, 0, plan))) return rc;
     const int64_t N = ds->N, P = grid.P;
     // Buffer roles.  The simulation's side and everything the chain adds live in buffers of their own (pioran_ctx::br*); the prediction's side keeps the
     // roles it has in predict_batch.  Alive together within a chunk, none shared between two roles:
@@ -2185,12 +2166,12 @@ static int rand_posterior_batch(pioran_ds* ds, pioran_ds* simds, int64_t B, int6
                     &sout = ctx->brsout, &sst = ctx->brsst, &maps = ctx->brmaps, &Yb = ctx->brY, &S2b = ctx->brS2, &shifts = ctx->brshift,
                     &stores = ctx->bwork, &gtabs = ctx->bgtab, &qws = ctx->bq, &tauws = ctx->bK, &mean = ctx->bY, &taus = ctx->bshift, &res = ctx->brres,
                     &rst = ctx->brst;
-    bool windowed = windowed_allowed(ctx->opt, s.R, s.J) && s.R <= 63;
-    if ((rc = windowed_ready(ds, s, false, windowed))) return rc;
-    if ((rc = windowed_ready(simds, ss, false, windowed))) return rc;
-    const size_t gt = windowed ? pioran_block_gtab_doubles(N, s.R) : 0;
+    // (the windowed tables of both states, or of neither)
+    if (plan.windowed && (rc = ensure_btab(simds, ss)) == PIORAN_ERR_UNSUPPORTED) { plan.leave_windowed(); rc = PIORAN_OK; }
+    if (rc) return rc;
+    const size_t gt = plan.windowed ? pioran_block_gtab_doubles(N, s.R) : 0;
     auto work_doubles = [&](int64_t nb) {   // the two kernel families' workspaces
-        return windowed ? pioran_block_store_workspace_doubles(nb, P, s.R, 3) + pioran_block_store_workspace_doubles(nb, N, s.R, 2) +
+        return plan.windowed ? pioran_block_store_workspace_doubles(nb, P, s.R, 3) + pioran_block_store_workspace_doubles(nb, N, s.R, 2) +
                               pioran_predict_q_workspace_doubles(nb, N, s.R)
                         : pioran_predict_workspace_doubles(nb, N, s.R);
     };
@@ -2198,15 +2179,15 @@ static int rand_posterior_batch(pioran_ds* ds, pioran_ds* simds, int64_t B, int6
     auto grow = [&](int64_t nb) {
         const size_t bn = (size_t)nb * (size_t)N * sizeof(double), bm = (size_t)nb * (size_t)M * sizeof(double), bp = (size_t)nb * (size_t)P * sizeof(double);
         return ensure_each(ctx, {{&qd, bn}, {&qn, bm}, {&ep, bn}, {&qT, bp}, {&fsim, bp}, {&Yb, bn}, {&S2b, bn}, {&mean, bm}, {&res, bm},
-                                 {&sstores, windowed ? pioran_block_store_workspace_doubles(nb, P, s.R, 3) * sizeof(double) : 0},
-                                 {&xi, windowed ? bp : 0},
-                                 {&stores, (windowed ? pioran_block_store_workspace_doubles(nb, N, s.R, 2) : pioran_predict_workspace_doubles(nb, N, s.R)) * sizeof(double)},
-                                 {&qws, windowed ? pioran_predict_q_workspace_doubles(nb, N, s.R) * sizeof(double) : 0},
+                                 {&sstores, plan.windowed ? pioran_block_store_workspace_doubles(nb, P, s.R, 3) * sizeof(double) : 0},
+                                 {&xi, plan.windowed ? bp : 0},
+                                 {&stores, (plan.windowed ? pioran_block_store_workspace_doubles(nb, N, s.R, 2) : pioran_predict_workspace_doubles(nb, N, s.R)) * sizeof(double)},
+                                 {&qws, plan.windowed ? pioran_predict_q_workspace_doubles(nb, N, s.R) * sizeof(double) : 0},
                                  {&sout, nb * sizeof(double)}, {&sst, nb * sizeof(int32_t)}, {&rst, nb * sizeof(int32_t)}, {&shifts, nb * sizeof(double)}});
     };
-    int64_t chunk = B < 256 ? B : 256;
+    int64_t chunk = std::min(B, plan.chunk_cap);
     if ((rc = size_chunk(ctx, chunk, {&qd, &qn, &ep, &qT, &fsim, &Yb, &S2b, &mean, &res, &sstores, &xi, &stores, &qws}, need, grow))) return rc;
-    if (windowed && (rc = ensure_each(ctx, {{&gtabs, gt * sizeof(double)}, {&tauws, pioran_predict_tau_workspace_doubles(M, s.R, 1) * sizeof(double)}}))) return rc;
+    if (plan.windowed && (rc = ensure_each(ctx, {{&gtabs, gt * sizeof(double)}, {&tauws, pioran_predict_tau_workspace_doubles(M, s.R, 1) * sizeof(double)}}))) return rc;
     if ((rc = upload(ctx, taus, tau, (size_t)M * sizeof(double)))) return rc;
     if ((rc = upload(ctx, maps, grid.maps.data(), grid.maps.size() * sizeof(int32_t)))) return rc;
     if ((rc = ensure_results(ctx, chunk))) return rc;
@@ -2223,7 +2204,7 @@ static int rand_posterior_batch(pioran_ds* ds, pioran_ds* simds, int64_t B, int6
         if ((rc = upload(ctx, qn, q_new + b0 * M, (size_t)nb * M * sizeof(double)))) return rc;
         if ((rc = upload(ctx, ep, eps + b0 * N, (size_t)nb * N * sizeof(double)))) return rc;
         if (shift && (rc = upload(ctx, shifts, shift + b0, (size_t)nb * sizeof(double)))) return rc;
-        if (windowed && b0 == 0) {
+        if (plan.windowed && b0 == 0) {
             // (shared (c, d): the states' own forward tables; the buffer of per-draw tables is not touched)
             if ((rc = build_tables(ds, s, false, nb, m, ctx->bscratch, &gtabs, tb))) return rc;
             if ((rc = build_tables(simds, ss, false, nb, m, ctx->bscratch, nullptr, stb))) return rc;
@@ -2238,7 +2219,7 @@ static int rand_posterior_batch(pioran_ds* ds, pioran_ds* simds, int64_t B, int6
         ScanParams ps = shared_params(simds, ss, nb, msim);
         ps.out = (double*)sout.p; ps.status = (int32_t*)sst.p;
         ps.noise = (const double*)qT.p; ps.ysim = (double*)fsim.p;
-        if (windowed) {
+        if (plan.windowed) {
             ps.gw = (double*)sstores.p;
             rc = pioran_launch_block_sim(ps, stb.btab, (double*)xi.p, ctx->stream);
         } else {
@@ -2255,14 +2236,13 @@ static int rand_posterior_batch(pioran_ds* ds, pioran_ds* simds, int64_t B, int6
         m.Y = (const double*)Yb.p; m.S2 = (const double*)S2b.p;
         ScanParams p = shared_params(ds, s, nb, m);
         p.out = (double*)ctx->bout.p; p.status = (int32_t*)ctx->bst.p;
-        if (windowed) {
+        g_last_kernel = plan.name;
+        if (plan.windowed) {
             p.gw = (double*)stores.p;
-            g_last_kernel = "block (windowed posterior draw)";
             rc = pioran_launch_block_solve(p, tb.btab, tb.gtab, (double*)qws.p, ctx->stream);
             if (!rc) rc = pioran_launch_predict_from_gy(p, (double*)qws.p, (double*)tauws.p, ds->t, M, (const double*)taus.p, (double*)mean.p, ctx->stream, 0,
                                                         tau_sorted);
         } else {
-            g_last_kernel = "wide (step-by-step posterior draw)";
             rc = pioran_launch_predict(p, (double*)stores.p, ds->t, M, (const double*)taus.p, (double*)mean.p, ctx->stream);
         }
         if (rc) { ctx->last_err = "posterior draw: prediction launch failed"; return rc; }
@@ -2293,19 +2273,14 @@ static int rand_posterior_refuse(pioran_ds* ds, int64_t B, int64_t J, const doub
     if (N + M > 0x7fffffff) return PIORAN_ERR_UNSUPPORTED;
     // rows past the step-by-step kernels: refused before any upload or allocation (the row count prepare_shared arrives at: a term with d = 0 and
     // b = 0 in every draw of the batch keeps one row)
-    auto rows_of = [&](int64_t nb, const double* bc, const double* dd) {
-        int64_t R = 0;
-        for (int64_t j = 0; j < J; ++j) {
-            bool one_row = dd[j] == 0.0;
-            for (int64_t b = 0; b < nb && one_row; ++b) one_row = bc[b * J + j] == 0.0;
-            R += one_row ? 1 : 2;
-        }
-        return R;
+    auto refused = [&](int64_t nb, const double* bc, const double* dd) {
+        const std::vector<int32_t> kind = classify_terms(nb, J, bc, nullptr, dd, false);
+        const int64_t rows = 2 * J - std::count(kind.begin(), kind.end(), 1), cap = 1 << 20;   // (beyond any kernel: no overflow of the rule's 32 bits)
+        return entry_plan(Entry::rand_posterior, (int32_t)std::min(rows, cap), (int32_t)std::min(J, cap), 0, nb, false, 0, ds->ctx->opt).rc != PIORAN_OK;
     };
-    const int64_t max_rows = std::min(pioran_predict_supported_rows(), pioran_wide_supported_rows_modes());
     const bool one_batch = cd_shared || B == 1;
     for (int64_t b = 0; b < (one_batch ? 1 : B); ++b)
-        if (rows_of(one_batch ? B : 1, Bc + b * J, Dd + b * J) > max_rows) return PIORAN_ERR_UNSUPPORTED;
+        if (refused(one_batch ? B : 1, Bc + b * J, Dd + b * J)) return PIORAN_ERR_UNSUPPORTED;
     return PIORAN_OK;
 }
 

@@ -2,6 +2,7 @@
 // runtime call, no context, no data set.  capi.hip fills the query once per launch, asks the rules in the ladder's order (time-parallel, tile,
 // windowed, remainder split, scan / latency layout, fallback) and does the rest: tables, workspaces, streams, the launches.  Draws with (c, d) of
 // their own are planned before the ladder: mixed_plan where only a few terms differ between the draws, perdraw_form where the caller says all do.
+// The other batched entries (prediction, gradient, simulation, posterior draws) have one rule, entry_plan, at the end.
 #pragma once
 #include "common.h"
 
@@ -66,6 +67,23 @@ MixedPlan mixed_plan(const ScanOptions& o, int64_t B, int64_t N, int32_t J, int3
 const char* value_route_cd(const ScanOptions& o, int32_t n_two_row, int32_t n_one_row, int32_t npd, int64_t B, int64_t N, bool per_draw_series,
                            bool must_run, int64_t* chunk);
 
-// the other entries' one-line rules
-bool windowed_allowed(const ScanOptions& o, int32_t R, int32_t J);
-bool tile_grad_wanted(const ScanOptions& o, int64_t B, int32_t R);
+// The other batched entries (capi.hip predict_batch, predict_var_shared, logl_grad_batch, simulate_batch, rand_posterior_batch): one rule, entry_plan.
+// A body asks it before it prepares its state (per_draw, R = 2 J: refused before any work) and for the prepared state (npd_terms: its terms with
+// per-draw rows, which no entry here takes).  grad_flags, gradient only: the shifted log-flux form, d/dc, d/dd, d/dy or d/dsigma2 asked for.
+enum class Entry { predict, predict_var, grad, simulate, rand_posterior };
+enum { kGradShift = 1, kGradC = 2, kGradD = 4, kGradSeries = 8 };
+struct EntryPlan {
+    int rc;                  // PIORAN_OK / PIORAN_ERR_UNSUPPORTED
+    bool windowed, tile;     // the windowed kernels (celerite_block.hip); of those, the reverse mode with one draw per wavefront (celerite_tile.hip)
+    bool shrink;             // short memory: halve the chunk (true) or leave the windowed kernels (false)
+    int64_t chunk_cap;       // draws per chunk before any memory budget
+    const char* name;        // what pioran_celerite_config_name(-1) reports
+    int64_t wide_cap;        // cap and name of the same call step by step: what a shared call falls to where the windowed kernels' table or
+    const char* wide_name;   // workspace cannot be had
+    void leave_windowed() { windowed = tile = false; shrink = true; chunk_cap = wide_cap; name = wide_name; }
+};
+EntryPlan entry_plan(Entry entry, int32_t R, int32_t J, int32_t npd_terms, int64_t B, bool per_draw, int grad_flags, const ScanOptions& o);
+
+// what pioran_celerite_config_name(-1) reports after the public entry's call with every resource granted (pioran_entry_route): the batch form's plan,
+// or — per_draw and the batch form refuses — the plan of the one-draw shared calls the entry falls back to.  rc PIORAN_ERR_ARG: no such entry
+EntryPlan entry_route(const char* entry, int32_t R, int32_t J, int64_t B, bool per_draw, int grad_flags, const ScanOptions& o);

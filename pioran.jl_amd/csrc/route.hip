@@ -1,6 +1,8 @@
-// The routing rules of the value path (route.h): thresholds and time models, each with the measurements it was set from.  Pure host functions.
+// The routing rules of the value path and of the other batched entries (route.h): thresholds and time models, each with the measurements it was set
+// from.  Pure host functions.
 #include "route.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
@@ -274,12 +276,6 @@ const char* value_route(const RouteQuery& q, int64_t pass, TpPlan* tp)
     return "fallback";
 }
 
-// May an entry (prediction, gradient, simulation) run on the windowed kernels (celerite_block.hip) with R rows of J terms?
-bool windowed_allowed(const ScanOptions& o, int32_t R, int32_t J)
-{
-    return !o.no_block && !o.force_fallback && !o.scan_config[0] && pioran_block_fits(R, J);
-}
-
 // Every term with (c, d) of its own in every draw (pioran_celerite_logl_batch_dev_cd: R = 2 J rows, no shared table)
 PerDrawForm perdraw_form(const ScanOptions& o, int64_t B, int32_t R, int32_t J)
 {
@@ -354,8 +350,64 @@ const char* value_route_cd(const ScanOptions& o, int32_t n_two_row, int32_t n_on
     return value_route(q, 0, nullptr);
 }
 
-// value and gradient: the reverse mode with one draw per wavefront (celerite_tile.hip) above the windowed kernel's batch range
-bool tile_grad_wanted(const ScanOptions& o, int64_t B, int32_t R)
+// ---- the other batched entries: posterior mean and variance, value and gradient, simulation, posterior draws (route.h entry_plan) -------------------
+
+// [entry][step by step, windowed, windowed with per-draw tables, tile]
+static const char* const kEntryNames[5][4] = {
+    {"wide (step-by-step prediction)", "block (windowed prediction)", "block (windowed prediction, per-draw tables)"},
+    {"wide (step-by-step variance)"},
+    {"wide (step-by-step gradient)", "block (windowed gradient)", "block (windowed gradient, per-draw tables)", "tile (windowed gradient, one draw per wavefront)"},
+    {"wide (step-by-step simulation)", "block (windowed simulation)", "block (windowed simulation, per-draw tables)"},
+    {"wide (step-by-step posterior draw)", "block (windowed posterior draw)"}};
+
+EntryPlan entry_plan(Entry entry, int32_t R, int32_t J, int32_t npd_terms, int64_t B, bool per_draw, int grad_flags, const ScanOptions& o)
 {
-    return o.force_tile || (!o.no_tile && B > 512 && R >= 17);
+    const bool grad = entry == Entry::grad, var = entry == Entry::predict_var, has_per_draw = !var && entry != Entry::rand_posterior;
+    const bool shift = grad_flags & kGradShift, series = grad_flags & kGradSeries, cd_alike = !(grad_flags & kGradC) == !(grad_flags & kGradD);
+    // rows past which an entry refuses (the variance kernels of celerite_predict.hip: 64; posterior draws chain the simulation and the prediction)
+    const int32_t predict = pioran_predict_supported_rows(), modes = pioran_wide_supported_rows_modes();
+    const int32_t max_rows[5] = {predict, 64, pioran_wide_supported_rows_grad(), modes, std::min(predict, modes)};
+    // The windowed kernels (celerite_block.hip) whenever the rows fit them: pioran_block_fits bounds the block columns to four, R <= 63.  scan_config: ANY
+    // name held in the string forbids, "block" too — forcing the small-batch VALUE kernel sends these entries step by step — while "tile" does not:
+    // set_option clears the string for it and sets force_tile.  (tests/test_route.py pins both.)
+    // Prediction (round 3): z = K^-1 (y - mu) from the windowed factorisation and a block back-substitution, then the two Q recurrences segment-parallel
+    // — no step-by-step factor, no per-step wave reduction; simulation: the windowed factorisation with its per-window stores, then L applied window by
+    // window; gradient, with or without d/d(c, d): 6.3 ms (7.0 with d/d(c, d)) instead of 25 at N = 1e4, J = 20 (series gradients and the shifted
+    // log-flux models included).
+    const bool windowed = !var && !o.no_block && !o.force_fallback && !o.scan_config[0] && pioran_block_fits(R, J);
+    // (c, d) per draw: every draw its own windowed-kernel tables or nothing — there is no step-by-step leg, and the shifted gradient has no such form
+    if ((per_draw && (!has_per_draw || shift || !windowed)) || R > max_rows[(int)entry] || npd_terms != 0)
+        return {PIORAN_ERR_UNSUPPORTED, false, false, true, 0, "", 0, ""};
+    // Gradient of many chains (round 5): the one-draw-per-wavefront reverse mode (celerite_tile.hip) — value and d/d(a, b, mu, nu), since round 6 also
+    // d/d(c, d) of the SHARED (c, d) (both or neither), shared series.  Its forward pass keeps the lower tiles of T per window (12 KB at three block
+    // columns) and the reverse kernel recomputes the rest, where the small-batch kernels keep 41 KB per window and chain and hold one chain per CU.
+    // scan_config = "tile" forces it for any chain count.  From 513 chains on (measured, SHO-20 / SHO-12 at N = 1e4: 512 chains 15.1 / 9.3 ms against
+    // the small-batch kernels' 11.0 / 9.2; 640 chains 15.2 / 9.4 against 16.6 / 14.0; 2048 chains 27 / 16 against 44 / 36).
+    // (48 .. 63 rows — DRWCelerite-20 is 60: three draws per workgroup there (two with d/d(c, d)); 4096 chains take 126 ms (163 with d/d(c, d)) against
+    //  166 (175) in 512-chain launches of the small-batch kernels: tools/ab_tile_grad_nb4.py, profiles/r06_tile_grad_four_block_columns.txt.  Until the
+    //  reverse kernel stopped spilling at four block columns — T_k and the window's U operands loaded at the head of their own window instead of a
+    //  window ahead — it was 177 (208).)
+    const bool tile = grad && !per_draw && windowed && cd_alike && !series && !shift && R <= pioran_tile_grad_supported_rows() &&
+                      (o.force_tile || (!o.no_tile && B > 512 && R >= 17));
+    // Draws per chunk.  Gradient — tile: whole passes of 2048 (1024) chains, 7.7 GB of T per 1024 chains at N = 1e4, three block columns; windowed: 512
+    // chains per launch pair (the forward pass then runs two workgroups per CU, the reverse pass two rounds of one), 256 with per-draw tables; step by
+    // step: ~15 MB of workspace per draw at N = 1e4, R = 40.  Every other entry: 256.
+    // Short memory: a smaller chunk — but the shared prediction and simulation leave the windowed kernels for the step-by-step ones instead
+    const char* const* names = kEntryNames[(int)entry];
+    return {PIORAN_OK, windowed, tile, !(windowed && !per_draw && (entry == Entry::predict || entry == Entry::simulate)),
+            !grad || per_draw ? 256 : (tile ? 4096 : (windowed ? 512 : 1024)), names[tile ? 3 : (windowed ? (per_draw ? 2 : 1) : 0)], grad ? 1024 : 256, names[0]};
+}
+
+EntryPlan entry_route(const char* entry, int32_t R, int32_t J, int64_t B, bool per_draw, int grad_flags, const ScanOptions& o)
+{
+    static const char* const entries[5] = {"predict", "predict_var", "grad", "simulate", "rand_posterior"};
+    int e = 0;
+    while (e < 5 && std::strcmp(entry, entries[e])) ++e;
+    if (e == 5) return {PIORAN_ERR_ARG, false, false, true, 0, "", 0, ""};
+    if (per_draw && B > 1) {   // (one draw is the shared case to the public entry)
+        const EntryPlan batch = entry_plan((Entry)e, 2 * J, J, 0, B, true, grad_flags, o);
+        if (!batch.rc) return batch;
+        B = 1;   // draw by draw (capi.hip each_draw)
+    }
+    return entry_plan((Entry)e, R, J, 0, B, false, grad_flags, o);
 }

@@ -1,6 +1,7 @@
 """CPU tests of the routing rules of the value path (csrc/route.hip) through pioran_value_route: the family the ladder of capi.hip's launch()
 takes when every resource is granted.  Routes the GPU tests already assert, transcribed; properties over a grid of ~89 000 queries; the
-time-parallel plans against the conditions pioran_launch_tp refuses on."""
+time-parallel plans against the conditions pioran_launch_tp refuses on.  Likewise pioran_value_route_cd for draws with (c, d) of their own, and
+pioran_entry_route for the other batched entries (route.hip entry_plan) against the rules written out in entry_truth."""
 import importlib.util
 import itertools
 from pathlib import Path
@@ -367,3 +368,225 @@ def test_per_draw_argument_validation():
     # the theta entry with more rows than the scan holds: refused (PIORAN_ERR_UNSUPPORTED), where the host entry goes on to the generic path
     assert L.pioran_value_route_cd(40, 0, 1, 24, 100, 0, 1, None, name, 8, ctypes.byref(chunk)) == -4 and name.value == b"" and chunk.value == 0
     assert L.pioran_value_route_cd(40, 0, 1, 24, 100, 0, 0, None, name, 8, None) == 0 and name.value == b"wide (p"
+
+
+# ---- the other batched entries: pioran_entry_route (route.hip entry_plan) --------------------------------------------------------------------------
+P, V, GR, S, RP = "predict", "predict_var", "grad", "simulate", "rand_posterior"
+ENTRY_NAMES = G.ENTRY_NAME_TABLE      # the strings of route.hip kEntryNames: wide, block, block with per-draw tables, tile
+
+
+def entry(which, rows, n_one, B, per_draw=False, shift=False, cd=(True, True), series=False, options=""):
+    assert (rows + n_one) % 2 == 0
+    return G.entry_route(which, rows, (rows + n_one) // 2, n_one, B, per_draw, shift, cd[0], cd[1], series, options)
+
+
+# (entry, rows, one-row terms, B, per draw, shift, (d/dc, d/dd), series gradients, options) -> name, each from an assertion on
+# pioran_celerite_config_name(-1) in the suite.  Dataset.logl_grad asks for d/d(c, d) unless cd_grad=False.
+PINNED_ENTRY = [
+    ((P, 20, 0, 23, False, False, (1, 1), False, ""), ENTRY_NAMES[P][1]),                       # test_gpu_chunking.py:116 (SHO-10, 23 draws)
+    ((P, 20, 0, 23, False, False, (1, 1), False, "no_block=1"), ENTRY_NAMES[P][0]),             # test_gpu_chunking.py:116
+    ((P, 20, 0, 23, True, False, (1, 1), False, ""), ENTRY_NAMES[P][2]),                        # test_gpu_chunking.py:135
+    ((V, 20, 0, 23, False, False, (1, 1), False, ""), ENTRY_NAMES[V][0]),                       # test_gpu_chunking.py:153
+    ((GR, 20, 0, 23, False, False, (1, 1), False, ""), ENTRY_NAMES[GR][1]),                     # test_gpu_chunking.py:172
+    ((GR, 20, 0, 23, False, False, (1, 1), False, "no_block=1"), ENTRY_NAMES[GR][0]),           # test_gpu_chunking.py:172
+    ((GR, 20, 0, 23, False, False, (1, 1), True, ""), ENTRY_NAMES[GR][1]),                      # test_gpu_chunking.py:172 (series gradients)
+    ((GR, 20, 0, 23, True, False, (1, 1), False, ""), ENTRY_NAMES[GR][2]),                      # test_gpu_chunking.py:190
+    ((S, 20, 0, 23, False, False, (1, 1), False, ""), ENTRY_NAMES[S][1]),                       # test_gpu_chunking.py:209
+    ((S, 20, 0, 23, True, False, (1, 1), False, ""), ENTRY_NAMES[S][2]),                        # test_gpu_chunking.py:209
+    ((P, 20, 0, 23, True, False, (1, 1), False, "no_block=1"), ENTRY_NAMES[P][0]),              # test_gpu_chunking.py:271 (draw by draw)
+    ((V, 20, 0, 23, True, False, (1, 1), False, ""), ENTRY_NAMES[V][0]),                        # test_gpu_chunking.py:285 (no per-draw form)
+    ((S, 20, 0, 23, True, False, (1, 1), False, "no_block=1"), ENTRY_NAMES[S][0]),              # test_gpu_chunking.py:293
+    ((GR, 20, 0, 23, True, False, (1, 1), True, "no_block=1"), ENTRY_NAMES[GR][0]),             # test_gpu_chunking.py:304
+    ((GR, 20, 0, 23, True, True, (1, 1), False, ""), ENTRY_NAMES[GR][1]),                       # test_gpu_chunking.py:319 (the shifted form: draw by draw)
+    ((P, 40, 0, 601, False, False, (1, 1), False, ""), ENTRY_NAMES[P][1]),                      # test_gpu_big.py:31 (SHO-20, three chunks)
+    ((S, 40, 0, 601, False, False, (1, 1), False, ""), ENTRY_NAMES[S][1]),                      # test_gpu_big.py:65
+    ((V, 1, 1, 70, False, False, (1, 1), False, ""), ENTRY_NAMES[V][0]),                        # test_gpu_predict_var.py:334 (R = 1)
+    ((V, 64, 0, 70, False, False, (1, 1), False, ""), ENTRY_NAMES[V][0]),                       # test_gpu_predict_var.py:334 (the last row count it takes)
+    ((V, 40, 0, 5, False, False, (1, 1), False, ""), ENTRY_NAMES[V][0]),                        # test_gpu_predict_var.py:81, :260 (families of cases)
+    ((RP, 40, 0, 5, False, False, (1, 1), False, ""), ENTRY_NAMES[RP][1]),                      # test_gpu_rand_posterior.py:58, :114 (_family :39: up to 63 rows), :182
+    ((RP, 63, 1, 5, False, False, (1, 1), False, ""), ENTRY_NAMES[RP][1]),                      # test_gpu_rand_posterior.py:58 (63 rows, one one-row term)
+    ((RP, 64, 0, 5, False, False, (1, 1), False, ""), ENTRY_NAMES[RP][0]),                      # test_gpu_rand_posterior.py:58 (_family :39: above)
+    ((RP, 40, 0, 5, False, False, (1, 1), False, "no_block=1"), ENTRY_NAMES[RP][0]),            # test_gpu_rand_posterior.py:58, :114 (_family :39: no_block)
+    ((GR, 40, 0, 5, False, False, (1, 1), True, ""), ENTRY_NAMES[GR][1]),                       # test_gpu_grad_truth.py:66 (legs :74: default routing, up to 63 rows)
+    ((GR, 80, 0, 5, False, False, (1, 1), True, ""), ENTRY_NAMES[GR][0]),                       # test_gpu_grad_truth.py:66 (legs :74: above)
+    ((GR, 40, 0, 5, False, False, (1, 1), False, "no_block=1"), ENTRY_NAMES[GR][0]),            # test_gpu_grad_truth.py:66 (legs :86), :174 (leg no_block)
+    ((GR, 40, 0, 5, False, False, (0, 0), False, "scan_config=tile"), ENTRY_NAMES[GR][3]),      # test_gpu_grad_truth.py:66 (legs :91), :174 (leg tile)
+    ((GR, 40, 0, 5, False, False, (1, 1), False, "scan_config=tile"), ENTRY_NAMES[GR][3]),      # test_gpu_grad_truth.py:66 (legs :92: with d/d(c, d))
+    ((GR, 16, 0, 5, True, False, (1, 1), False, ""), ENTRY_NAMES[GR][2]),                       # test_gpu_grad_truth.py:66 (legs :82: 2 J <= 63), :174 (leg per-draw tables)
+    ((GR, 80, 0, 5, True, False, (1, 1), False, ""), ENTRY_NAMES[GR][0]),                       # test_gpu_grad_truth.py:66 (legs :82: else draw by draw)
+    ((GR, 12, 0, 3, False, False, (1, 1), True, ""), ENTRY_NAMES[GR][1]),                       # test_gpu_fuzz.py:92 (windowed gradient fuzz)
+    ((GR, 12, 0, 3, True, False, (1, 1), False, ""), ENTRY_NAMES[GR][2]),                       # test_gpu_fuzz.py:92 (per draw)
+    ((P, 30, 0, 3, False, False, (1, 1), False, ""), ENTRY_NAMES[P][1]),                        # test_gpu_fuzz.py:151
+    ((S, 30, 0, 3, False, False, (1, 1), False, ""), ENTRY_NAMES[S][1]),                        # test_gpu_fuzz.py:153
+    ((P, 30, 0, 3, True, False, (1, 1), False, ""), ENTRY_NAMES[P][2]),                         # test_gpu_fuzz.py:205
+    ((S, 30, 0, 3, True, False, (1, 1), False, ""), ENTRY_NAMES[S][2]),                         # test_gpu_fuzz.py:207
+    ((GR, 100, 0, 3, False, False, (1, 1), False, ""), ENTRY_NAMES[GR][0]),                     # test_gpu_fuzz.py:278 (past the windowed kernels)
+    ((S, 100, 0, 3, False, False, (1, 1), False, ""), ENTRY_NAMES[S][0]),                       # test_gpu_fuzz.py:286
+    ((P, 100, 0, 3, False, False, (1, 1), False, ""), ENTRY_NAMES[P][0]),                       # test_gpu_fuzz.py:292
+    ((P, 40, 0, 5, False, False, (1, 1), False, ""), ENTRY_NAMES[P][1]),                        # test_gpu_predict_mean_sim.py:71 (_family :46: default, shared)
+    ((P, 80, 0, 5, False, False, (1, 1), False, ""), ENTRY_NAMES[P][0]),                        # test_gpu_predict_mean_sim.py:71 (_family :46: above 63 rows)
+    ((S, 16, 0, 5, True, False, (1, 1), False, ""), ENTRY_NAMES[S][2]),                         # test_gpu_predict_mean_sim.py:79 (_family :48: 2 J <= 63)
+    ((S, 40, 0, 5, False, False, (1, 1), False, "no_block=1"), ENTRY_NAMES[S][0]),              # test_gpu_predict_mean_sim.py:79 (_family :46: no_block)
+    ((S, 40, 0, 5, False, False, (1, 1), False, ""), ENTRY_NAMES[S][1]),                        # test_gpu_predict_mean_sim.py:172
+    ((GR, 20, 0, 700, False, False, (0, 0), False, ""), ENTRY_NAMES[GR][3]),                    # test_gpu_parity.py:2281, :2313, :2316 (700 chains, 20 rows: the same query)
+    ((GR, 20, 0, 700, False, False, (0, 0), False, "workspace_limit_mb=1"), ENTRY_NAMES[GR][3]),  # test_gpu_parity.py:2306 (several launches: the same family)
+    ((GR, 20, 0, 512, False, False, (0, 0), False, ""), ENTRY_NAMES[GR][1]),                    # test_gpu_parity.py:2282 (512: the windowed kernels' last)
+    ((GR, 20, 0, 700, False, False, (1, 1), False, ""), ENTRY_NAMES[GR][3]),                    # test_gpu_parity.py:2284 (with d/d(c, d))
+    ((GR, 16, 0, 700, False, False, (0, 0), False, ""), ENTRY_NAMES[GR][1]),                    # test_gpu_parity.py:2285 (16 rows: below the tile range)
+    ((GR, 20, 0, 700, False, False, (0, 0), False, "no_tile=1"), ENTRY_NAMES[GR][1]),           # test_gpu_parity.py:2289
+    ((GR, 20, 0, 700, False, False, (1, 1), False, "no_tile=1"), ENTRY_NAMES[GR][1]),           # test_gpu_parity.py:2298
+    ((GR, 72, 0, 2, False, True, (1, 1), False, ""), ENTRY_NAMES[GR][0]),                       # test_gpu_parity.py:2667 (36 components, shifted)
+    ((GR, 104, 0, 2, False, True, (1, 1), False, ""), ENTRY_NAMES[GR][0]),                      # test_gpu_parity.py:2667 (52 components)
+    ((GR, 72, 0, 5, False, False, (1, 1), True, "no_wide2=1"), ENTRY_NAMES[GR][0]),             # test_gpu_grad_truth.py:66 (legs :89), :174 (leg no_wide2)
+    ((GR, 48, 0, 5, False, False, (1, 1), True, "no_wide2=1;no_block=1"), ENTRY_NAMES[GR][0]),  # test_gpu_grad_truth.py:66 (legs :89: with no_block below 64 rows)
+    ((GR, 63, 35, 1, False, False, (0, 0), False, ""), (ENTRY_NAMES[GR][1], ENTRY_NAMES[GR][0])),  # test_gpu_grad_truth.py:104 (49 terms: either family)
+    ((GR, 20, 0, 5, False, False, (1, 1), True, ""), ENTRY_NAMES[GR][1]),                       # test_gpu_grad_truth.py:174 (leg block)
+    ((GR, 100, 0, 5, False, False, (1, 1), True, ""), ENTRY_NAMES[GR][0]),                      # test_gpu_grad_truth.py:174 (leg wide)
+    ((P, 16, 0, 5, True, False, (1, 1), False, ""), ENTRY_NAMES[P][2]),                         # test_gpu_predict_mean_sim.py:71 (_family :48)
+    ((P, 40, 0, 5, False, False, (1, 1), False, "no_block=1"), ENTRY_NAMES[P][0]),              # test_gpu_predict_mean_sim.py:71 (_family :46: no_block)
+    ((S, 80, 0, 5, False, False, (1, 1), False, ""), ENTRY_NAMES[S][0]),                        # test_gpu_predict_mean_sim.py:79 (_family :46: above 63 rows)
+    ((P, 40, 0, 40, False, False, (1, 1), False, ""), ENTRY_NAMES[P][1]),                       # test_gpu_parity.py:1654 (SHO-20, 40 draws)
+    ((P, 40, 0, 40, False, False, (1, 1), False, "no_block=1"), ENTRY_NAMES[P][0]),             # test_gpu_parity.py:1654
+    ((P, 62, 0, 2, False, False, (1, 1), False, ""), ENTRY_NAMES[P][1]),                        # test_gpu_parity.py:1654 (J = 31)
+    ((P, 24, 0, 9, True, False, (1, 1), False, ""), ENTRY_NAMES[P][2]),                         # test_gpu_parity.py:1672 (J = 12)
+    ((P, 40, 0, 20, True, False, (1, 1), False, ""), ENTRY_NAMES[P][2]),                        # test_gpu_parity.py:1672 (J = 20)
+    ((S, 24, 0, 9, True, False, (1, 1), False, ""), ENTRY_NAMES[S][2]),                         # test_gpu_parity.py:1687
+    ((S, 6, 0, 3, True, False, (1, 1), False, ""), ENTRY_NAMES[S][2]),                          # test_gpu_parity.py:1687 (J = 3)
+    ((S, 64, 0, 3, False, False, (1, 1), False, ""), ENTRY_NAMES[S][0]),                        # test_gpu_parity.py:1739 (J = 32)
+    ((S, 142, 0, 2, False, False, (1, 1), False, ""), ENTRY_NAMES[S][0]),                       # test_gpu_parity.py:1739 (J = 71)
+    ((P, 64, 0, 3, False, False, (1, 1), False, ""), ENTRY_NAMES[P][0]),                        # test_gpu_parity.py:1744
+    ((P, 142, 0, 2, False, False, (1, 1), False, ""), ENTRY_NAMES[P][0]),                       # test_gpu_parity.py:1744
+    ((P, 2, 0, 3, False, False, (1, 1), False, ""), ENTRY_NAMES[P][1]),                         # test_gpu_parity.py:1804 (one term: fewer than six rows)
+    ((S, 1, 1, 2, False, False, (1, 1), False, ""), ENTRY_NAMES[S][1]),                         # test_gpu_parity.py:1804 (one row)
+    ((P, 2, 0, 3, False, False, (1, 1), False, "no_block=1"), ENTRY_NAMES[P][0]),               # test_gpu_parity.py:1811
+    ((S, 1, 1, 2, False, False, (1, 1), False, "no_block=1"), ENTRY_NAMES[S][0]),               # test_gpu_parity.py:1811
+    ((S, 40, 0, 40, False, False, (1, 1), False, ""), ENTRY_NAMES[S][1]),                       # test_gpu_parity.py:1840
+    ((S, 40, 0, 40, False, False, (1, 1), False, "no_block=1"), ENTRY_NAMES[S][0]),             # test_gpu_parity.py:1840
+    ((GR, 2, 0, 3, False, False, (1, 1), False, ""), ENTRY_NAMES[GR][1]),                       # test_gpu_parity.py:1938 (J = 1)
+    ((GR, 40, 0, 3, False, False, (1, 1), False, ""), ENTRY_NAMES[GR][1]),                      # test_gpu_parity.py:1938 (J = 20)
+    ((GR, 40, 0, 3, False, False, (1, 1), False, "no_block=1"), ENTRY_NAMES[GR][0]),            # test_gpu_parity.py:1955
+    ((GR, 40, 0, 3, False, False, (0, 0), True, ""), ENTRY_NAMES[GR][1]),                       # test_gpu_parity.py:1969 (series gradients, no d/d(c, d))
+    ((GR, 2, 0, 3, False, False, (0, 0), False, "scan_config=tile"), ENTRY_NAMES[GR][3]),       # test_gpu_parity.py:2242 (J = 1, forced)
+    ((GR, 30, 0, 5, False, False, (1, 1), False, "scan_config=tile"), ENTRY_NAMES[GR][3]),      # test_gpu_parity.py:2246 (with d/d(c, d))
+    ((GR, 30, 0, 5, False, False, (1, 1), False, ""), ENTRY_NAMES[GR][1]),                      # test_gpu_parity.py:2250 (the automatic choice at 5 chains)
+    ((GR, 60, 20, 300, False, False, (0, 0), False, ""), ENTRY_NAMES[GR][1]),                   # test_gpu_parity.py:2341 (DRWCelerite-20, 300 chains)
+    ((GR, 40, 0, 1024, False, False, (0, 0), False, ""), ENTRY_NAMES[GR][3]),                   # test_gpu_parity.py:2345 (SHO-20, 1024 chains)
+    ((GR, 45, 15, 1024, False, False, (0, 0), False, ""), ENTRY_NAMES[GR][3]),                  # test_gpu_parity.py:2345 (DRWCelerite-15)
+    ((GR, 60, 20, 1024, False, False, (0, 0), False, ""), ENTRY_NAMES[GR][3]),                  # test_gpu_parity.py:2345 (DRWCelerite-20: four block columns)
+    ((GR, 60, 20, 1024, False, False, (0, 0), False, "no_tile=1"), ENTRY_NAMES[GR][1]),         # test_gpu_parity.py:2349
+    ((GR, 2, 0, 3, True, False, (1, 1), False, ""), ENTRY_NAMES[GR][2]),                        # test_gpu_parity.py:2386 (J = 1)
+    ((GR, 62, 0, 2, True, False, (1, 1), False, ""), ENTRY_NAMES[GR][2]),                       # test_gpu_parity.py:2386 (J = 31)
+    ((GR, 40, 0, 6, False, True, (1, 1), False, ""), ENTRY_NAMES[GR][1]),                       # test_gpu_parity.py:2407 (shifted log-flux model)
+    ((GR, 40, 0, 6, False, True, (1, 1), False, "no_block=1"), ENTRY_NAMES[GR][0]),             # test_gpu_parity.py:2413
+    ((GR, 60, 20, 3, False, False, (1, 1), False, ""), ENTRY_NAMES[GR][1]),                     # test_gpu_parity.py:2433 (DRWCelerite-20, windowed)
+    ((GR, 60, 20, 3, False, False, (1, 1), False, "no_block=1"), ENTRY_NAMES[GR][0]),           # test_gpu_parity.py:2433
+]
+
+
+@pytest.mark.parametrize("query,name", PINNED_ENTRY)
+def test_entry_routes_the_suite_already_asserts(query, name):
+    which, rows, n_one, B, per_draw, shift, cd, series, options = query
+    assert entry(which, rows, n_one, B, per_draw, shift, cd, series, options)[0] in ((name,) if isinstance(name, str) else name)
+
+
+def test_every_entry_name_is_pinned_twice():
+    names = [n for _, n in PINNED_ENTRY if isinstance(n, str)]
+    for which, table in ENTRY_NAMES.items():
+        for n in table:
+            assert names.count(n) >= 2, n
+
+
+ENTRY_B = (1, 2, 256, 257, 512, 513, 1024, 1025, 4096, 4097)
+ENTRY_LIMIT = {P: 143, V: 64, GR: 143, S: 143, RP: 143}      # pioran_*_supported_rows*(); rand_posterior: the smaller of prediction's and simulation's
+# options that take the windowed kernels away.  scan_config=block is the quirk: any name held in the option string forbids them, so forcing
+# the small-batch VALUE kernel sends these entries step by step; scan_config=tile does not (set_option turns it into force_tile)
+NO_WINDOWED = ("no_block=1", "force_fallback=1", "scan_config=block")
+ENTRY_OPTIONS = ("", "no_tile=1", "scan_config=tile") + NO_WINDOWED
+
+
+def entry_truth(which, rows, J, B, per_draw, shift, cd, series, options):
+    """The rules as the issue that introduced pioran_entry_route lists them: (name, chunk cap, shrink), name None where the entry refuses.
+    Up to 63 rows of at most 32 terms always fit the windowed kernels' LDS (celerite_block.hip pioran_block_fits: four block columns)."""
+    allowed = lambda R: options not in NO_WINDOWED and R <= 63
+    batch = per_draw and B > 1 and which in (P, GR, S) and not (which == GR and shift) and allowed(2 * J)
+    if batch:
+        rows = 2 * J
+    elif per_draw and B > 1:
+        B = 1       # draw by draw
+    if rows > ENTRY_LIMIT[which]:
+        return None, 0, True
+    windowed = batch or (which != V and allowed(rows))
+    tile = (which == GR and not batch and windowed and cd[0] == cd[1] and not series and not shift and rows <= 63 and
+            (options == "scan_config=tile" or (options != "no_tile=1" and B > 512 and rows >= 17)))
+    name = ENTRY_NAMES[which][3 if tile else (2 if batch else 1) if windowed else 0]
+    cap = 256 if which != GR or batch else 4096 if tile else 512 if windowed else 1024
+    return name, cap, not (windowed and not batch and which in (P, S))
+
+
+def test_entry_properties_over_the_grid():
+    """rows 1 .. 150 x B x per draw x the gradient's flags under the default options and every option that forbids or forces a family."""
+    n = 0
+    seen = set()
+    for rows, B, per_draw, options in itertools.product(range(1, 151), ENTRY_B, (False, True), ENTRY_OPTIONS):
+        n_one = rows % 2
+        J = (rows + n_one) // 2
+        for which in (P, V, GR, S, RP):
+            flags = itertools.product((False, True), ((1, 1), (0, 0), (1, 0), (0, 1)), (False, True)) if which == GR else (((False, (1, 1), False)),)
+            for shift, cd, series in flags:
+                q = (which, rows, J, B, per_draw, shift, cd, series, options)
+                got = entry(which, rows, n_one, B, per_draw, shift, cd, series, options)
+                n += 1
+                assert got == entry_truth(*q), (q, got)
+                name, cap, shrink = got
+                # refused exactly past the entry's rows — whatever the form of (c, d): the draw-by-draw calls refuse the same rows
+                assert (name is None) == (rows > ENTRY_LIMIT[which]), q
+                if name is None:
+                    continue
+                assert name in ENTRY_NAMES[which], q
+                seen.add(name)
+                batch = "per-draw tables" in name
+                if name.startswith("tile"):
+                    assert not shift and not series and cd[0] == cd[1] and rows <= 63 and options != "no_tile=1" and not batch, q
+                    assert options == "scan_config=tile" or (B > 512 and rows >= 17), q
+                elif (options == "scan_config=tile" and which == GR and rows <= 63 and not shift and not series and cd[0] == cd[1] and
+                      not (per_draw and B > 1)):
+                    raise AssertionError(("tile forced and not taken", q, name))
+                if options in NO_WINDOWED:
+                    assert name.startswith("wide"), q
+                if batch:
+                    assert per_draw and B > 1 and 2 * J <= 63 and not shift, q
+                assert cap == (256 if which != GR or batch else {"tile": 4096, "block": 512, "wide": 1024}[name.split(" ")[0]]), q
+                assert shrink == (not (which in (P, S) and name.startswith("block") and not batch)), q
+    assert n >= 150 * 10 * 2 * 6 * 20
+    # every string the library can report for these entries is in the table the tests pin, and the other way round
+    assert seen == {name for table in ENTRY_NAMES.values() for name in table}
+
+
+@pytest.mark.parametrize("rows,refused", [(63, ()), (64, ()), (65, (V,)), (143, (V,)), (144, (P, V, GR, S, RP))])
+def test_entry_row_limits(rows, refused):
+    for which in (P, V, GR, S, RP):
+        for B, per_draw in ((1, False), (8, False), (8, True)):
+            name, cap, shrink = entry(which, rows, rows % 2, B, per_draw)
+            assert (name is None) == (which in refused), (which, rows, B, per_draw, name)
+            if name is not None and which != V:
+                # (63 rows of 32 terms with (c, d) per draw: 2 J = 64 rows refuse the batch form, the one-draw calls keep their one-row term)
+                assert name.startswith("block") == (rows <= 63), (which, rows, name)
+                assert ("per-draw tables" in name) == (per_draw and rows < 63 and which != RP), (which, rows, name)
+
+
+def test_entry_argument_validation():
+    import ctypes
+    L = pj._lib.lib()
+    name = ctypes.create_string_buffer(8)
+    cap, shrink = ctypes.c_int64(-1), ctypes.c_int(-1)
+    args = (0, 0, 1, 1, 0)
+    assert L.pioran_entry_route(b"grad", 40, 20, 0, 8, *args, None, name, 8, ctypes.byref(cap), ctypes.byref(shrink)) == 0
+    assert name.value == b"block (" and cap.value == 512 and shrink.value == 1        # cut to the buffer
+    assert L.pioran_entry_route(b"predict", 40, 20, 0, 8, *args, None, name, 8, None, ctypes.byref(shrink)) == 0 and shrink.value == 0
+    assert L.pioran_entry_route(b"predict_var", 66, 33, 0, 8, *args, None, name, 8, ctypes.byref(cap), None) == -4 and name.value == b""
+    assert L.pioran_entry_route(b"value", 40, 20, 0, 8, *args, None, name, 8, None, None) == -1
+    assert L.pioran_entry_route(None, 40, 20, 0, 8, *args, None, name, 8, None, None) == -1
+    assert L.pioran_entry_route(b"grad", 40, 20, 1, 8, *args, None, name, 8, None, None) == -1      # 40 rows are not 20 terms with a one-row term
+    assert L.pioran_entry_route(b"grad", 40, 20, 0, 0, *args, None, name, 8, None, None) == -1
+    assert L.pioran_entry_route(b"grad", 40, 20, 0, 8, *args, b"no_such_option=1", name, 8, None, None) == -1
+    assert L.pioran_entry_route(b"grad", 40, 20, 0, 8, *args, None, None, 8, None, None) == -1

@@ -9,6 +9,11 @@ arrays — a different segment count, mode or chunking changes bits, so two libr
     PIORAN_HIP_LIB=/path/to/other/libpioran_hip.so python tools/route_grid.py [--before-value-route] [--before-value-route-cd] > listing.txt
 
 (--before-value-route[-cd]: the library is from before pioran_value_route[_cd] existed; the binding does not ask for the symbol.)
+
+`entry_points()` is the grid of tests/test_gpu_entry_route.py — posterior mean and variance, value and gradient, simulation, posterior draws —
+`run_entry_point` makes one call, `entry_route` asks pioran_entry_route.  `--entries [--save FILE.npz] [--against FILE.npz]` lists that grid
+instead: name, return code and a hash of the outputs per point; the gradient arrays are saved / compared with the saved ones
+(--before-entry-route: the library is from before pioran_entry_route existed).
 """
 import ctypes
 import hashlib
@@ -97,6 +102,89 @@ def theta_points():
     return [ThetaPoint(5, n_qpo, 8, CD_N) for n_qpo in (1, 3)]
 
 
+# ---- the other batched entries (route.hip entry_plan).  N = 130: nine 16-step windows, the last ragged; M = 7 evaluation times, one on a data time.
+# Rows at the smallest values where a rule flips: 4; 16 / 18 either side of the tile reverse mode's 17; 40; 60 as DRWCelerite-20 (three draws per
+# workgroup there); 62 / 64 either side of the windowed kernels; 80: step by step only; 144: refused.  Batches either side of the gradient's 512 and of
+# the 256-draw chunk.  The base grid asks the gradient without d/d(c, d) -----------------------------------------------------------------------------
+EntryPoint = namedtuple("EntryPoint", "entry J n_one B per_draw shift cd_grad series options")
+ENTRIES = ("predict", "predict_var", "grad", "simulate", "rand_posterior")
+ENTRY_N, ENTRY_M = 130, 7
+# what pioran_celerite_config_name(-1) reports after these entries, per entry: step by step, windowed, windowed with per-draw tables, tile
+ENTRY_NAME_TABLE = {
+    "predict": ("wide (step-by-step prediction)", "block (windowed prediction)", "block (windowed prediction, per-draw tables)"),
+    "predict_var": ("wide (step-by-step variance)",),
+    "grad": ("wide (step-by-step gradient)", "block (windowed gradient)", "block (windowed gradient, per-draw tables)",
+             "tile (windowed gradient, one draw per wavefront)"),
+    "simulate": ("wide (step-by-step simulation)", "block (windowed simulation)", "block (windowed simulation, per-draw tables)"),
+    "rand_posterior": ("wide (step-by-step posterior draw)", "block (windowed posterior draw)"),
+}
+ENTRY_ROWS = (4, 16, 18, 40, 60, 62, 64, 80, 144)
+ENTRY_B = {"grad": (1, 8, 512, 513)}
+ENTRY_OPTION_VARIANTS = ("no_block=1", "no_tile=1", "scan_config=tile", "scan_config=block")
+
+
+def entry_points():
+    def pt(entry, rows, B, per_draw=False, shift=False, cd_grad=False, series=False, options=""):
+        return EntryPoint(entry, *_terms(rows), B, per_draw, shift, cd_grad, series, options)
+    pts = [pt(e, rows, B) for rows in ENTRY_ROWS for e in ENTRIES for B in ENTRY_B.get(e, (1, 8, 257))]
+    pts.append(pt("grad", 4, 1025, options="no_block=1"))        # two chunks of the step-by-step reverse mode
+    pts.append(pt("grad", 16, 257, per_draw=True))               # two chunks of per-draw tables
+    # 40 rows under the options: every entry at 8 draws, the gradient also past 512 (but scan_config=tile: it forces the family at any size)
+    for options in ENTRY_OPTION_VARIANTS:
+        pts += [pt(e, 40, 8, options=options) for e in ENTRIES]
+        if options != "scan_config=tile":
+            pts.append(pt("grad", 40, 513, options=options))
+    for B in (8, 513):
+        pts += [pt("grad", 40, B, shift=True), pt("grad", 40, B, cd_grad=True), pt("grad", 40, B, series=True)]
+    # (c, d) per draw: 8 terms on per-draw tables; 40 terms are 80 rows, refused, so draw by draw
+    pts += [pt(e, rows, 8, per_draw=True) for rows in (16, 80) for e in ENTRIES]
+    return pts
+
+
+def entry_expected(pt):
+    """(name, chunk cap, shrink) of pioran_entry_route for an EntryPoint."""
+    return entry_route(pt.entry, rows_of(pt), pt.J, pt.n_one, pt.B, pt.per_draw, pt.shift, pt.cd_grad, pt.cd_grad, pt.series, pt.options)
+
+
+def run_entry_point(ctx, pt):
+    """One call of the entry through the Python API under the point's options: (name that ran, return code, dict of outputs)."""
+    import pioran_jl_amd as pj
+    shape = Point(pt.J, pt.n_one, pt.B, ENTRY_N, "")
+    t, y, s2, A, Bc, C, Dd, mu, nu = inputs_cd(CdPoint(pt.J, pt.J, pt.B, ENTRY_N, "")) if pt.per_draw else inputs(shape)
+    rng = np.random.default_rng([pt.J, pt.n_one, pt.B, ENTRY_N, 3])
+    tau = np.concatenate([rng.uniform(t[0] - 1, t[-1] + 1, ENTRY_M - 1), t[[ENTRY_N // 2]]])
+    q_data, q_new, eps = rng.standard_normal((pt.B, ENTRY_N)), rng.standard_normal((pt.B, ENTRY_M)), rng.standard_normal((pt.B, ENTRY_N))
+    if pt.shift:        # the shifted log-flux form: the data set holds a positive series, every shift lies below its minimum
+        y = np.exp(0.5 * y)
+    opts = [kv.split("=") for kv in pt.options.split(";") if kv]
+    ds = pj.Dataset(t, y, s2, ctx)
+    try:
+        for k, v in opts:
+            ctx.set_option(k, v)
+        if pt.entry == "predict":
+            mean, st = ds.predict(A, Bc, C, Dd, tau, mu=mu, nu=nu, return_status=True)
+            out = dict(mean=mean, status=st)
+        elif pt.entry == "predict_var":
+            var, st = ds.predict_var(A, Bc, C, Dd, tau, nu=nu, return_status=True)
+            out = dict(var=var, status=st)
+        elif pt.entry == "simulate":
+            out = dict(y=ctx.simulate(A, Bc, C, Dd, t, s2, q_data))
+        elif pt.entry == "rand_posterior":
+            draws, st = ds.rand_posterior(A, Bc, C, Dd, tau, q_data, q_new, eps, mu=mu, nu=nu, return_status=True)
+            out = dict(draws=draws, status=st)
+        else:
+            shift = y.min() * np.linspace(0.1, 0.9, pt.B) if pt.shift else None
+            out = ds.logl_grad(A, Bc, C, Dd, mu=mu, nu=nu, series_grad=pt.series, shift=shift, cd_grad=pt.cd_grad)
+            out = {k: v for k, v in out.items() if v is not None}
+        return pj._lib.lib().pioran_celerite_config_name(-1).decode(), 0, out
+    except pj._lib.PioranHipError as e:
+        return None, int(str(e).split()[2].rstrip(":")), {}
+    finally:
+        for k, _ in opts:
+            ctx.set_option(k, None)
+        ds.close()
+
+
 def value_route(rows, J, n_one, B, N, per_draw_series=False, pass_draws=0, options=""):
     """(family, (scan, RP, nseg, L)) of pioran_value_route."""
     import pioran_jl_amd as pj
@@ -118,6 +206,18 @@ def value_route_cd(n_two, n_one, npd, B, N, per_draw_series=False, must_run=Fals
     if rc not in (0, -4):
         raise ValueError(f"pioran_value_route_cd: error {rc}")
     return (name.value.decode() if rc == 0 else None), chunk.value
+
+
+def entry_route(entry, rows, J, n_one, B, per_draw=False, shift=False, want_c=True, want_d=True, series_grads=False, options=""):
+    """(name, chunk cap, shrink) of pioran_entry_route; name None: the entry refuses the rows."""
+    import pioran_jl_amd as pj
+    name = ctypes.create_string_buffer(64)
+    cap, shrink = ctypes.c_int64(0), ctypes.c_int(0)
+    rc = pj._lib.lib().pioran_entry_route(entry.encode(), rows, J, n_one, B, int(per_draw), int(shift), int(want_c), int(want_d), int(series_grads),
+                                          options.encode(), name, len(name), ctypes.byref(cap), ctypes.byref(shrink))
+    if rc not in (0, -4):
+        raise ValueError(f"pioran_entry_route: error {rc}")
+    return (name.value.decode() if rc == 0 else None), cap.value, bool(shrink.value)
 
 
 def expected(pt):
@@ -193,13 +293,49 @@ def run_point(ctx, pt):
         ds.close()
 
 
+GRAD_ARRAYS = ("grad_a", "grad_b", "grad_c", "grad_d", "grad_mu", "grad_nu", "grad_y", "grad_sigma2", "grad_shift")
+
+
+def run_entries(ctx, save=None, against=None):
+    """The listing of entry_points(): per point the name that ran, the return code and a hash of every output that is one workgroup per draw.  The
+    gradient arrays' lane sums go through LDS atomics whose order is not fixed: with `against` (an .npz of `save`) their largest deviation from it,
+    max |delta| / (1 + max |ref|), is printed instead, and its maximum over the grid last."""
+    ref = np.load(against) if against else None
+    kept, worst = {}, 0.0
+    for i, pt in enumerate(entry_points()):
+        name, rc, out = run_entry_point(ctx, pt)
+        h = hashlib.sha256(b"".join(np.ascontiguousarray(v).tobytes() for k, v in sorted(out.items()) if k not in GRAD_ARRAYS)).hexdigest()[:16]
+        line = (f"{pt.entry:14s} rows {rows_of(pt):3d} J {pt.J:2d} B {pt.B:4d} per-draw {int(pt.per_draw)} shift {int(pt.shift)} cd {int(pt.cd_grad)} "
+                f"series {int(pt.series)} [{pt.options}] rc {rc} {name} {h if out else '-'}")
+        for k in GRAD_ARRAYS:
+            if k in out:
+                kept[f"{i}:{k}"] = out[k]
+                if ref is not None:
+                    r = ref[f"{i}:{k}"]
+                    ok = np.isfinite(r)
+                    assert np.array_equal(ok, np.isfinite(out[k])), (pt, k)
+                    dev = float(np.max(np.abs(out[k][ok] - r[ok])) / (1 + np.max(np.abs(r[ok])))) if ok.any() else 0.0
+                    worst = max(worst, dev)
+                    line += f" {k} {dev:.1e}"
+        print(line, flush=True)
+    if save:
+        np.savez(save, **kept)
+    if ref is not None:
+        print(f"largest gradient deviation max |delta| / (1 + max |ref|): {worst:.2e}")
+
+
 def main():
     import pioran_jl_amd as pj
     if "--before-value-route" in sys.argv:
         pj._lib.SIGNATURES.pop("pioran_value_route", None)
     if "--before-value-route-cd" in sys.argv:
         pj._lib.SIGNATURES.pop("pioran_value_route_cd", None)
+    if "--before-entry-route" in sys.argv:
+        pj._lib.SIGNATURES.pop("pioran_entry_route", None)
     ctx = pj.Context(0)
+    if "--entries" in sys.argv:
+        arg = lambda flag: sys.argv[sys.argv.index(flag) + 1] if flag in sys.argv else None
+        return run_entries(ctx, arg("--save"), arg("--against"))
     for pt in points() + cd_points() + theta_points():
         fam, out, st = run_point(ctx, pt)
         digest = hashlib.sha256(out.tobytes() + st.tobytes()).hexdigest()[:16]
