@@ -7,7 +7,8 @@ on a synthetic irregular series, then the vectorised forms a sampler would call:
   2. a batch of live points, theta -> log L in one call (approx on the device),
   3. value + gradient with respect to the sampled parameters (reverse mode on the device, chain rule through approx),
   4. posterior mean / standard deviation at new times and a prior draw for one posterior sample,
-  5. the Lomb-Scargle posterior predictive check: periodograms of series simulated under a set of draws, all in one call.
+  5. the Lomb-Scargle posterior predictive check: periodograms of series simulated under a set of draws, all in one call,
+  6. the prior check of the PSD approximation (run_diagnostics): residuals and ratios of model against approximation, reduced on the device.
 """
 import os, sys, time
 import numpy as np
@@ -61,3 +62,9 @@ fq, power, quant = pj.lsp_ppc(rng, t, yerr, A5, B5, C5, D5, mu=mu[kk], nu=nu[kk]
 print(f"periodograms of {len(kk)} simulated series at {len(fq)} frequencies in {(time.perf_counter() - t0) * 1e3:.1f} ms; "
       f"median power at the lowest / highest frequency: {quant[2, 0]:.3f} / {quant[2, -1]:.2e}; "
       f"the data: {pj.lombscargle(t, y, yerr, frequencies=fq)[[0, -1]]}")
+
+# 6. the prior check of the approximation (run_diagnostics): is 20 SHO components enough for this prior and this observed window?
+d = pj.run_diagnostics(theta[:2000].T, var[:2000], f_min, f_max, pj.SingleBendingPowerLaw, n_components=20)
+inside = (d["f"] >= f_min) & (d["f"] <= f_max)
+print(f"approximation check over {d['kept']} prior draws at {len(d['f'])} frequencies: 95 % of the ratios approx / model inside the observed window lie in "
+      f"[{d['rat_quantiles'][0][inside].min():.3f}, {d['rat_quantiles'][4][inside].max():.3f}]; worst max |ratio| of a draw: {np.nanmax(d['meta_max_rat']):.3f}")

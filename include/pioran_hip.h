@@ -109,6 +109,8 @@ int pioran_ctx_trim(pioran_ctx* ctx);
  *   "dense_old_chain" 0 one launch per block column (default), 1 the panel / update chain of rounds 1-3 (any other value: PIORAN_ERR_ARG);
  *                     "dense_no_pairs", "dense_no_halves", "dense_pair_tiles", "dense_half_tile_limit", "dense_quad_threshold", "dense_batch_pair_threshold", "dense_streams": schedule knobs
  *   "block_emode", "exp"   tuning / experiment selectors of single kernels (tools/ only; "exp" can make results meaningless)
+ *   "pc_events"       timing tools only: the first chunk of a pioran_psd_check_* call records the event slots 4 .. 6 (before the per-draw kernel | after it |
+ *                     after the evaluation kernel)
  * Initial values come from the environment variables PIORAN_SCAN_CONFIG, PIORAN_NO_WIDE, PIORAN_NO_BLOCK, PIORAN_NO_TILE, PIORAN_NO_TP, PIORAN_NO_PAIRED,
  * PIORAN_NO_MIXED, PIORAN_FORCE_FALLBACK, PIORAN_WIN2, PIORAN_NO_WIN2, PIORAN_WIDE2, PIORAN_NO_WIDE2, read once when the context is created. */
 int pioran_ctx_set_option(pioran_ctx* ctx, const char* key, const char* value);
@@ -422,12 +424,60 @@ int pioran_celerite_rand_posterior_summary(pioran_ds* ds, int64_t B, int64_t J, 
                                            int backtransform, int64_t Q, const double* probs, double* ts_quant, double* ts_mean,
                                            int64_t Nres, const int32_t* res_cols, const double* res_ref, const double* res_scale,
                                            double* res_quant, double* res_mean, int32_t* status, int32_t* kept);
+/* ---- the PSD model against its basis-function approximation (sample_approx_model, src/plots_diagnostics.jl:195-213; the prior check
+ * run_diagnostics :232-240 and the posterior check plot_psd_ppc :371-487 are reductions of it) ------------------------------------------------
+ * For B draws theta [B][P], norm [B] of a continuum model (model 0 = SingleBendingPowerLaw, P = 3; 1 = DoubleBendingPowerLaw, P = 5) and F frequencies,
+ * with the grid of `approx` (basis 0 = SHO, power p = 4; 1 = DRWCelerite, p = 6; 2 <= n_components = J <= 256; f0 = f_min / S_low, fM = f_max S_high,
+ * sp_j = f0 (fM / f0)^(j / (J - 1)), B_jk = 1 / (1 + (sp_j / sp_k)^p), factorised once per call on the host as pioran_logpdf_batch_theta does):
+ *     amp_b = B \ (P_b(sp) / P_b(sp_0))                                                   get_approx_coefficients, src/psd.jl:129-135
+ *     psd[b][f] = P_b(freq_f) / P_b(freq_0) * norm_b                                      :202-205 — the normaliser is the model at the FIRST frequency passed
+ *     psd_approx[b][f] = sum_j (amp_bj norm_b) / (1 + (freq_f / sp_j)^p)                  :207, src/psd.jl:171-179; j ascending, the power formed by squaring
+ *     normalise != 0 (plot_psd_ppc): both divided by integ_b = get_norm_psd(amp_b, sp, f_min, f_max, basis, is_integrated_power)   :404-409
+ *     times_f != 0 (plot_f_P): both multiplied by freq_f after that                       :419-420
+ *     residuals = psd - psd_approx,   ratios = psd_approx / psd                           :210-211, of the arrays as divided and multiplied
+ * every operation rounded on its own in fp64; tools/psd_check_proto.py is the definition.  amplitudes [B][J] and integ [B] (computed whatever
+ * `normalise` says) are the amplitudes before any scaling and the normalising integral that pioran_logpdf_batch_theta folds into (a, b).
+ * status[b]: 2, with NaN in every output row of the draw (amplitudes and integ included), when a theta or the norm of the draw is not finite, when
+ * P_b(freq_0) or P_b(sp_0) is not positive and finite, or, with normalise, when integ_b is zero or not finite; 0 otherwise.  The other draws
+ * are not affected, and no output depends on which other outputs are requested or on how the call is chunked.
+ *   theta [B][P], norm [B], freq [F] positive and finite (any order), psd / psd_approx / residuals / ratios [B][F] each or NULL,
+ *   amplitudes [B][J] or NULL, integ [B] or NULL, status [B] or NULL.
+ * Out of scope: QPO features, PowerLaw, and the CARMA variant plot_psd_ppc_CARMA.
+ * pioran_psd_check_batch uploads, runs chunk by chunk under "workspace_limit_mb" and downloads, and blocks; pioran_psd_check_batch_dev takes
+ * device pointers for every array and is asynchronous on the context's stream (a call with another grid than the previous one waits for the stream first).
+ * pioran_psd_check_summary keeps the four arrays in buffers of the context (pioran_ctx_trim releases them; PIORAN_ERR_ALLOC where they do not fit
+ * what the context may take) and returns their reductions over the draws with status 0, whose number is `kept`:
+ *   quant [4][Q][F], mean [4][F] or NULL: per frequency, the Q quantiles and the mean over the draws of psd, psd_approx, residuals, ratios in this
+ *     order (plot_quantiles_approx :93-94, plot_mean_approx :150-151, plot_psd_ppc :446-447) — pioran_quantiles_batch_dev on each [B][F] array,
+ *     so the bits of pioran_quantiles_batch applied to what pioran_psd_check_batch returns;
+ *   meta [B][8] or NULL: per draw, over the F frequencies, mean, median, min |.|, max |.| of the residuals, then the same four of the ratios
+ *     (plot_boxplot_psd_approx :43-51, :72); mean and median (the quantile at 0.5) are pioran_quantiles_batch_dev's on transposed [F][B] copies,
+ *     min and max are exact; NaN in the eight entries of a draw with status 2.
+ * The quantile kernel sorts a column inside one workgroup: B > 4096 or F > 4096 is PIORAN_ERR_UNSUPPORTED in the summary form, before any GPU call
+ * (the array forms have no such limit).
+ * PIORAN_ERR_ARG, before any GPU call: NULL ctx / theta / norm / freq; every output NULL (summary: NULL quant or probs); B, F, Q < 1; model, basis or
+ * n_components out of range; f_min, f_max, S_low, S_high not positive and finite, or f_min >= f_max; a prob outside [0, 1] or NaN; and in the host
+ * forms a freq that is not positive and finite (the device form cannot look at its arrays).
+ * pioran_celerite_config_name(-1) afterwards: "psd check (model against approximation)". */
+int pioran_psd_check_batch(pioran_ctx* ctx, int64_t B, int model, int64_t n_components, int basis, int is_integrated_power,
+                           double f_min, double f_max, double S_low, double S_high, const double* theta, const double* norm,
+                           int64_t F, const double* freq, int normalise, int times_f, double* psd, double* psd_approx,
+                           double* residuals, double* ratios, double* amplitudes, double* integ, int32_t* status);
+int pioran_psd_check_batch_dev(pioran_ctx* ctx, int64_t B, int model, int64_t n_components, int basis, int is_integrated_power,
+                               double f_min, double f_max, double S_low, double S_high, const double* dtheta, const double* dnorm,
+                               int64_t F, const double* dfreq, int normalise, int times_f, double* dpsd, double* dpsd_approx,
+                               double* dresiduals, double* dratios, double* damplitudes, double* dinteg, int32_t* dstatus);
+int pioran_psd_check_summary(pioran_ctx* ctx, int64_t B, int model, int64_t n_components, int basis, int is_integrated_power,
+                             double f_min, double f_max, double S_low, double S_high, const double* theta, const double* norm,
+                             int64_t F, const double* freq, int normalise, int times_f, int64_t Q, const double* probs,
+                             double* quant, double* mean, double* meta, int32_t* status, int32_t* kept);
 /* Name of the kernel configuration a large batch with R active rows (all terms with both rows when R is even) runs on;
  * R == 0: the configuration the calling thread's last throughput-layout launch actually ran on; R < 0: the kernel FAMILY of the
  * calling thread's last launch — "tile" (windowed form, one draw per wavefront: large batches from 49 rows on and batch sizes between the
  * passes of the throughput layouts), "block" (windowed kernel), "block+pd" (with per-draw rows), "block (per-draw tables)", "wide"
  * (latency layout), "scan" (throughput layouts), "fallback", "block (windowed gradient[, per-draw tables])",
- * "wide (step-by-step gradient)", "wide (step-by-step variance)", "periodogram (fp64 matrix product)", "quantiles (sort over draws)" (diagnostics). */
+ * "wide (step-by-step gradient)", "wide (step-by-step variance)", "periodogram (fp64 matrix product)", "quantiles (sort over draws)",
+ * "psd check (model against approximation)" (diagnostics). */
 const char* pioran_celerite_config_name(int64_t R);
 /* Diagnostics (no GPU needed): the automatic choice between the windowed form with one draw per wavefront (1, "tile") and the other families (0)
  * for a shared-table batch of B draws with R active rows; `pass` = draws per pass of the step-by-step layout of these rows (0 = unknown:

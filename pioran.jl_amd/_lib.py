@@ -64,6 +64,12 @@ SIGNATURES = {
     "pioran_quantiles_batch_dev": (ctypes.c_int, [c_void_p, i64, i64, i64] + [c_void_p] * 3 + [i64] + [c_void_p] * 3 + [i64] + [c_void_p] * 4),
     "pioran_celerite_rand_posterior_summary": (ctypes.c_int, [c_void_p, i64, i64] + [c_void_p] * 4 + [ctypes.c_int] + [c_void_p] * 3 + [i64] + [c_void_p] * 4 +
                                                [ctypes.c_int, i64] + [c_void_p] * 3 + [i64] + [c_void_p] * 7),
+    "pioran_psd_check_batch": (ctypes.c_int, [c_void_p, i64, ctypes.c_int, i64, ctypes.c_int, ctypes.c_int] + [ctypes.c_double] * 4 + [c_void_p] * 2 +
+                               [i64, c_void_p, ctypes.c_int, ctypes.c_int] + [c_void_p] * 7),
+    "pioran_psd_check_batch_dev": (ctypes.c_int, [c_void_p, i64, ctypes.c_int, i64, ctypes.c_int, ctypes.c_int] + [ctypes.c_double] * 4 + [c_void_p] * 2 +
+                                   [i64, c_void_p, ctypes.c_int, ctypes.c_int] + [c_void_p] * 7),
+    "pioran_psd_check_summary": (ctypes.c_int, [c_void_p, i64, ctypes.c_int, i64, ctypes.c_int, ctypes.c_int] + [ctypes.c_double] * 4 + [c_void_p] * 2 +
+                                 [i64, c_void_p, ctypes.c_int, ctypes.c_int, i64] + [c_void_p] * 6),
     "pioran_celerite_config_name": (ctypes.c_char_p, [i64]),
     "pioran_ctx_fp64_probe": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_double, ctypes.POINTER(ctypes.c_double)]),
     "pioran_tile_choice": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),

@@ -16,21 +16,14 @@
 // PSD models are Tonari.jl's closed forms (test/test_psd.jl:3-13).  The J x J matrix B is LU-factorised once
 // on the host (partial pivoting, like Julia's `\`); each draw is one thread doing 2 J^2 flops of triangular
 // solves in its own output row.  Cost ~ J (2 pow + log + atan2) + 2 J^2 flop per draw: microseconds per batch.
+// The model's closed forms, the solve and the continuum's normalising integral are psd_device.h's, shared with psd_check.hip.
 #include "common.h"
+#include "psd_device.h"
 
 #include <cmath>
 #include <vector>
 
 namespace {
-
-__device__ __forceinline__ double psd_model(int model, const double* th, double f)
-{
-    // 0: SingleBendingPowerLaw(alpha1, f1, alpha2); 1: DoubleBendingPowerLaw(alpha1, f1, alpha2, f2, alpha3)
-    const double x = f / th[1];
-    double v = pow(x, -th[0]) / (1.0 + pow(x, th[2] - th[0]));
-    if (model == 1) v /= 1.0 + pow(f / th[3], th[4] - th[2]);
-    return v;
-}
 
 __global__ void __launch_bounds__(64) approx_kernel(int64_t B, int model, int P, int J, int basis, int integrated,
                                                     double f_min, double f_max, const double* __restrict__ sp,
@@ -46,46 +39,11 @@ __global__ void __launch_bounds__(64) approx_kernel(int64_t B, int model, int P,
     double* x = A + b * Jt;                      // work in place in the output row (first J entries)
     const double* th = theta + b * P;
     const double p0 = psd_model(model, th, sp[0]);
-    for (int j = 0; j < J; ++j) x[j] = psd_model(model, th, sp[j]) / p0;
-    // row interchanges, then L y = P p (unit lower), U x = y
-    for (int j = 0; j < J; ++j) {
-        const int pj = piv[j];
-        if (pj != j) { const double tmp = x[j]; x[j] = x[pj]; x[pj] = tmp; }
-    }
-    for (int i = 1; i < J; ++i) {
-        double acc = x[i];
-        for (int k = 0; k < i; ++k) acc = fma(-LU[i * J + k], x[k], acc);
-        x[i] = acc;
-    }
-    for (int i = J - 1; i >= 0; --i) {
-        double acc = x[i];
-        for (int k = i + 1; k < J; ++k) acc = fma(-LU[i * J + k], x[k], acc);
-        x[i] = acc / LU[i * J + i];
-    }
+    psd_normalised_on_grid(model, th, J, sp, p0, x, 1);
+    psd_lu_solve(J, LU, piv, x, 1);
     // normalisation (src/psd.jl:375-395)
-    double integ;
+    double integ = psd_norm_integral(J, basis, integrated, f_min, f_max, sp, x, 1);
     if (integrated) {
-        double hi = 0.0, lo = 0.0;
-        if (basis == 0) {            // integral_sho :301-305
-            const double s2 = 1.4142135623730951;
-            for (int j = 0; j < J; ++j) {
-                const double c = sp[j], nrm = c * x[j] / (4.0 * s2);
-                const double ph = (f_max * f_max + s2 * c * f_max + c * c) / (f_max * f_max - s2 * c * f_max + c * c);
-                const double pl = (f_min * f_min + s2 * c * f_min + c * c) / (f_min * f_min - s2 * c * f_min + c * c);
-                hi += nrm * (log(ph) + 2.0 * atan2(c * s2 * f_max, c * c - f_max * f_max));
-                lo += nrm * (log(pl) + 2.0 * atan2(c * s2 * f_min, c * c - f_min * f_min));
-            }
-        } else {                     // integral_drwcelerite :318-324
-            const double s3 = 1.7320508075688772;
-            for (int j = 0; j < J; ++j) {
-                const double c = sp[j], nrm = x[j] * c / 3.0;
-                const double ph = (f_max * f_max + s3 * c * f_max + c * c) / (f_max * f_max - s3 * c * f_max + c * c);
-                const double pl = (f_min * f_min + s3 * c * f_min + c * c) / (f_min * f_min - s3 * c * f_min + c * c);
-                hi += nrm * (atan(f_max / c) + 0.5 * atan2(f_max * f_max - c * c, c * f_max) + s3 / 4.0 * log(ph));
-                lo += nrm * (atan(f_min / c) + 0.5 * atan2(f_min * f_min - c * c, c * f_min) + s3 / 4.0 * log(pl));
-            }
-        }
-        integ = hi - lo;
         // features: integral of the celerite power spectrum between f_min and f_max   (src/psd.jl:330-334, 356-358)
         for (int q = 0; q < n_qpo; ++q) {
             const double S0 = qpo[(b * n_qpo + q) * 3], f0q = qpo[(b * n_qpo + q) * 3 + 1], Q = qpo[(b * n_qpo + q) * 3 + 2];
@@ -98,10 +56,6 @@ __global__ void __launch_bounds__(64) approx_kernel(int64_t B, int model, int P,
             };
             integ += icel(f_max) - icel(f_min);
         }
-    } else {
-        double acc = 0.0;
-        for (int j = 0; j < J; ++j) acc += x[j] * sp[j];
-        integ = basis == 0 ? acc * M_PI / 1.4142135623730951 : acc * 2.0 * M_PI / 3.0;
     }
     const double scale = norm[b] / integ;
     double* bb = Bc + b * Jt;
@@ -180,22 +134,9 @@ __global__ void __launch_bounds__(64) approx_vjp_kernel(int64_t B, int model, in
     const double* th = theta + b * P;
     double d0[5], dj[5];
     const double p0 = psd_model_dlog(model, th, sp[0], d0);
-    for (int j = 0; j < J; ++j) x[(int64_t)j * B] = psd_model(model, th, sp[j]) / p0;
-    // forward: row interchanges, L y = P p, U x = y (as approx_kernel)
-    for (int j = 0; j < J; ++j) {
-        const int pj = piv[j];
-        if (pj != j) { const double tmp = x[(int64_t)j * B]; x[(int64_t)j * B] = x[(int64_t)pj * B]; x[(int64_t)pj * B] = tmp; }
-    }
-    for (int i = 1; i < J; ++i) {
-        double acc = x[(int64_t)i * B];
-        for (int k = 0; k < i; ++k) acc = fma(-LU[i * J + k], x[(int64_t)k * B], acc);
-        x[(int64_t)i * B] = acc;
-    }
-    for (int i = J - 1; i >= 0; --i) {
-        double acc = x[(int64_t)i * B];
-        for (int k = i + 1; k < J; ++k) acc = fma(-LU[i * J + k], x[(int64_t)k * B], acc);
-        x[(int64_t)i * B] = acc / LU[i * J + i];
-    }
+    // forward: p, then x = B^-1 p (as approx_kernel)
+    psd_normalised_on_grid(model, th, J, sp, p0, x, B);
+    psd_lu_solve(J, LU, piv, x, B);
     // h, I = w'x, h'x
     const double* gar = ga + b * Jt;
     const double* gbr = gb + b * Jt;

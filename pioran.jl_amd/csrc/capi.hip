@@ -52,6 +52,11 @@ struct pioran_ctx {
     // approx and its reverse mode as the two ends of the gradient (ThetaDraws): the grid's sp | w | LU | piv and the batch's theta | norm, a chunk's
     // grad_theta | grad_norm | the kernel's scratch
     Buf bthin, bthout;
+    // PSD check (psd_check.hip): the grid's sp | LU | piv, the host forms' theta | norm | freq, a chunk's amp | integ | pf0 | status, a chunk's
+    // (the summary: the batch's) arrays psd | psd_approx | residuals | ratios, the summary's transposed copies | partials, its small inputs and results
+    Buf bpcgrid, bpcin, bpcdraw, bpcout, bpcT, bpcq;
+    std::vector<double> pcgrid_host;   // what bpcgrid is filled from: the device form returns before the copy has run
+    double pcgrid_key[6] = {};         // ... and the (J, basis, f_min, f_max, S_low, S_high) it was built for
     // scalar entry point: the last series' time stamps stay resident (samplers call logl with the same t)
     pioran_ds* scalar_ds = nullptr;
     std::vector<double> scalar_t;
@@ -857,6 +862,7 @@ int set_option(ScanOptions& o, const char* key, const char* value)
     else if (!std::strcmp(key, "ls_only")) o.ls_only = (value && value[0]) ? std::atoi(value) : 0;
     else if (!std::strcmp(key, "rp_events")) o.rp_events = on ? 1 : 0;
     else if (!std::strcmp(key, "theta_events")) o.theta_events = on ? 1 : 0;
+    else if (!std::strcmp(key, "pc_events")) o.pc_events = on ? 1 : 0;
     else if (!std::strcmp(key, "wide2")) o.wide2 = on;
     else if (!std::strcmp(key, "no_wide2")) o.no_wide2 = on;
     else return PIORAN_ERR_ARG;
@@ -1025,7 +1031,7 @@ int pioran_ctx_destroy(pioran_ctx* ctx)
     pioran_ctx::Buf* bufs[] = {&ctx->bA, &ctx->bB, &ctx->bC, &ctx->bD, &ctx->bmu, &ctx->bnu, &ctx->bY,
                                &ctx->bS2, &ctx->bout, &ctx->bst, &ctx->bscratch, &ctx->bK, &ctx->bwork, &ctx->bshift, &ctx->bgtab, &ctx->bq, &ctx->bpair, &ctx->btp, &ctx->btprow, &ctx->brqd, &ctx->brqn, &ctx->breps, &ctx->brqT, &ctx->brstores, &ctx->brxi, &ctx->brf, &ctx->brsout, &ctx->brsst, &ctx->brmaps,
                                &ctx->brY, &ctx->brS2, &ctx->brshift, &ctx->brres, &ctx->brst, &ctx->bqX, &ctx->bqst, &ctx->bqin, &ctx->bqidx, &ctx->bqout,
-                               &ctx->bthin, &ctx->bthout};
+                               &ctx->bthin, &ctx->bthout, &ctx->bpcgrid, &ctx->bpcin, &ctx->bpcdraw, &ctx->bpcout, &ctx->bpcT, &ctx->bpcq};
     for (auto* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto& e : ctx->ev)
@@ -1052,7 +1058,7 @@ int pioran_ctx_trim(pioran_ctx* ctx)
                                &ctx->bS2, &ctx->bout, &ctx->bst, &ctx->bscratch, &ctx->bK, &ctx->bwork, &ctx->bshift, &ctx->bgtab, &ctx->bq, &ctx->bpair, &ctx->btp, &ctx->btprow,
                                &ctx->blstab, &ctx->blsaux, &ctx->brqd, &ctx->brqn, &ctx->breps, &ctx->brqT, &ctx->brstores, &ctx->brxi, &ctx->brf, &ctx->brsout, &ctx->brsst, &ctx->brmaps,
                                &ctx->brY, &ctx->brS2, &ctx->brshift, &ctx->brres, &ctx->brst, &ctx->bqX, &ctx->bqst, &ctx->bqin, &ctx->bqidx, &ctx->bqout,
-                               &ctx->bthin, &ctx->bthout};
+                               &ctx->bthin, &ctx->bthout, &ctx->bpcgrid, &ctx->bpcin, &ctx->bpcdraw, &ctx->bpcout, &ctx->bpcT, &ctx->bpcq};
     for (auto* b : bufs) {
         if (b->p) (void)hipFree(b->p);
         b->p = nullptr;
@@ -2556,6 +2562,254 @@ int pioran_lombscargle_batch(pioran_ctx* ctx, int64_t N, int64_t B, int64_t F, c
         if (status && (rc = download(ctx, status + b0, ctx->bst.p, nb * sizeof(int32_t)))) return rc;
         SYNC(ctx);   // the staging buffers are reused by the next chunk
     }
+    return PIORAN_OK;
+}
+
+// ---- PSD model against its basis-function approximation (psd_check.hip) -----------------------------------------------------------------------
+static const char* const kPsdCheckName = "psd check (model against approximation)";
+
+struct PsdCheckCfg {
+    int model, P, J, basis, integrated, normalise, times_f;
+    double f_min, f_max, S_low, S_high;
+};
+
+// what every form can see without looking at an array
+static int psd_check_refuse(const void* ctx, int64_t B, int model, int64_t J, int basis, double f_min, double f_max, double S_low, double S_high,
+                            const void* theta, const void* norm, int64_t F, const void* freq, bool any_output)
+{
+    if (!ctx || !theta || !norm || !freq || !any_output || B < 1 || F < 1) return PIORAN_ERR_ARG;
+    if (model < 0 || model > 1 || basis < 0 || basis > 1 || J < 2 || J > 256) return PIORAN_ERR_ARG;
+    for (const double v : {f_min, f_max, S_low, S_high})
+        if (!(std::isfinite(v) && v > 0.0)) return PIORAN_ERR_ARG;
+    return f_min < f_max ? PIORAN_OK : PIORAN_ERR_ARG;
+}
+
+// ... and what only a host array shows
+static int psd_check_refuse_freq(int64_t F, const double* freq)
+{
+    for (int64_t f = 0; f < F; ++f)
+        if (!(std::isfinite(freq[f]) && freq[f] > 0.0)) return PIORAN_ERR_ARG;
+    return PIORAN_OK;
+}
+
+static PsdCheckCfg psd_check_cfg(int model, int64_t J, int basis, int integrated, double f_min, double f_max, double S_low, double S_high, int normalise,
+                                 int times_f)
+{
+    return {model, model == 0 ? 3 : 5, (int)J, basis, integrated != 0, normalise != 0, times_f != 0, f_min, f_max, S_low, S_high};
+}
+
+// The grid of the approximation on the device, as pioran_logpdf_batch_theta prepares it: sp [J] | LU [J][J] | piv [J] in bpcgrid
+struct PsdCheckGrid { const double *sp, *LU; const int32_t* piv; };
+static int psd_check_grid(pioran_ctx* ctx, const PsdCheckCfg& c, PsdCheckGrid& g)
+{
+    const size_t nJ = (size_t)c.J, n = nJ + nJ * nJ + (nJ + 1) / 2;
+    const double key[6] = {(double)c.J, (double)c.basis, c.f_min, c.f_max, c.S_low, c.S_high};
+    double* dev = (double*)ctx->bpcgrid.p;
+    // the grid of the previous call is still there (a sampler's repeated calls: nothing to do, and the device form stays asynchronous)
+    if (dev && ctx->pcgrid_host.size() == n && !std::memcmp(key, ctx->pcgrid_key, sizeof(key))) {
+        g.sp = dev; g.LU = dev + nJ; g.piv = (const int32_t*)(dev + nJ + nJ * nJ);
+        return PIORAN_OK;
+    }
+    std::vector<double> sp, LU, cc, dd;
+    std::vector<int32_t> piv, real;
+    int rc = pioran_approx_setup_host(c.J, c.basis, c.f_min, c.f_max, c.S_low, c.S_high, sp, LU, piv, cc, dd, real);
+    if (rc) return rc;
+    // an earlier call's kernels may still read the old grid, or its copy out of the host image may not have run: wait before either is rewritten
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->pcgrid_host.clear();
+    if ((rc = ensure(ctx, ctx->bpcgrid, n * sizeof(double)))) return rc;
+    std::memcpy(ctx->pcgrid_key, key, sizeof(key));
+    ctx->pcgrid_host.assign(n, 0.0);
+    std::memcpy(ctx->pcgrid_host.data(), sp.data(), nJ * sizeof(double));
+    std::memcpy(ctx->pcgrid_host.data() + nJ, LU.data(), nJ * nJ * sizeof(double));
+    std::memcpy(ctx->pcgrid_host.data() + nJ + nJ * nJ, piv.data(), nJ * sizeof(int32_t));
+    dev = (double*)ctx->bpcgrid.p;
+    if ((rc = upload_to(ctx, dev, ctx->pcgrid_host.data(), n * sizeof(double)))) return rc;
+    g.sp = dev; g.LU = dev + nJ; g.piv = (const int32_t*)(dev + nJ + nJ * nJ);
+    return PIORAN_OK;
+}
+
+// a chunk's amp [nb][J] | integ [nb] | pf0 [nb] | status [nb] in bpcdraw
+struct PsdCheckDraws { double *amp, *integ, *pf0; int32_t* status; };
+static size_t psd_check_draw_bytes(int64_t nb, int J) { return (size_t)nb * ((size_t)J + 2) * sizeof(double) + (size_t)nb * sizeof(int32_t); }
+static PsdCheckDraws psd_check_draws_of(pioran_ctx* ctx, int64_t nb, int J)
+{
+    double* a = (double*)ctx->bpcdraw.p;
+    return {a, a + (size_t)nb * J, a + (size_t)nb * J + nb, (int32_t*)(a + (size_t)nb * J + 2 * nb)};
+}
+
+// nb draws on the device through the two kernels: `dr` receives the per-draw results, `e` names the arrays that are wanted (its inputs are filled here)
+static int psd_check_chunk(pioran_ctx* ctx, const PsdCheckCfg& c, const PsdCheckGrid& g, int64_t nb, const double* dtheta, const double* dnorm, int64_t F,
+                           const double* dfreq, const PsdCheckDraws& dr, PsdCheckEval e, bool timed)
+{
+    auto mark = [&](int slot) { return timed ? hipEventRecord(ctx->ev[slot], ctx->stream) : hipSuccess; };
+    int rc;
+    g_last_kernel = kPsdCheckName;
+    HIPCHK(ctx, mark(4));
+    if ((rc = pioran_launch_psd_check_draws(nb, c.model, c.P, c.J, c.basis, c.integrated, c.normalise, c.f_min, c.f_max, g.sp, g.LU, g.piv, dtheta, dnorm,
+                                            dfreq, dr.amp, dr.integ, dr.pf0, dr.status, ctx->stream)))
+        return rc;
+    HIPCHK(ctx, mark(5));
+    if (e.psd || e.approx || e.res || e.rat || e.resT || e.ratT || e.part) {
+        e.B = nb; e.F = F; e.model = c.model; e.P = c.P; e.J = c.J; e.basis = c.basis; e.normalise = c.normalise; e.times_f = c.times_f;
+        e.sp = g.sp; e.theta = dtheta; e.norm = dnorm; e.freq = dfreq; e.amp = dr.amp; e.integ = dr.integ; e.pf0 = dr.pf0; e.status = dr.status;
+        if ((rc = pioran_launch_psd_check_eval(e, ctx->stream))) return rc;
+    }
+    HIPCHK(ctx, mark(6));
+    return PIORAN_OK;
+}
+
+int pioran_psd_check_batch_dev(pioran_ctx* ctx, int64_t B, int model, int64_t n_components, int basis, int is_integrated_power, double f_min, double f_max,
+                               double S_low, double S_high, const double* dtheta, const double* dnorm, int64_t F, const double* dfreq, int normalise,
+                               int times_f, double* dpsd, double* dpsd_approx, double* dresiduals, double* dratios, double* damplitudes, double* dinteg,
+                               int32_t* dstatus)
+{
+    const bool any = dpsd || dpsd_approx || dresiduals || dratios || damplitudes || dinteg || dstatus;
+    if (const int rc = psd_check_refuse(ctx, B, model, n_components, basis, f_min, f_max, S_low, S_high, dtheta, dnorm, F, dfreq, any)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const PsdCheckCfg c = psd_check_cfg(model, n_components, basis, is_integrated_power, f_min, f_max, S_low, S_high, normalise, times_f);
+    PsdCheckGrid g;
+    int rc;
+    if ((rc = psd_check_grid(ctx, c, g))) return rc;
+    if ((rc = ensure(ctx, ctx->bpcdraw, psd_check_draw_bytes(B, c.J)))) return rc;
+    PsdCheckDraws dr = psd_check_draws_of(ctx, B, c.J);
+    if (damplitudes) dr.amp = damplitudes;
+    if (dinteg) dr.integ = dinteg;
+    if (dstatus) dr.status = dstatus;
+    PsdCheckEval e{};
+    e.psd = dpsd; e.approx = dpsd_approx; e.res = dresiduals; e.rat = dratios;
+    return psd_check_chunk(ctx, c, g, B, dtheta, dnorm, F, dfreq, dr, e, ctx->opt.pc_events != 0);
+}
+
+// theta [B][P] | norm [B] | freq [F] of a host form into bpcin
+static int psd_check_upload(pioran_ctx* ctx, const PsdCheckCfg& c, int64_t B, const double* theta, const double* norm, int64_t F, const double* freq,
+                            const double*& dtheta, const double*& dnorm, const double*& dfreq)
+{
+    const size_t nth = (size_t)B * c.P;
+    int rc;
+    if ((rc = ensure(ctx, ctx->bpcin, (nth + (size_t)B + (size_t)F) * sizeof(double)))) return rc;
+    double* dev = (double*)ctx->bpcin.p;
+    if ((rc = upload_to(ctx, dev, theta, nth * sizeof(double)))) return rc;
+    if ((rc = upload_to(ctx, dev + nth, norm, (size_t)B * sizeof(double)))) return rc;
+    if ((rc = upload_to(ctx, dev + nth + B, freq, (size_t)F * sizeof(double)))) return rc;
+    dtheta = dev; dnorm = dev + nth; dfreq = dev + nth + B;
+    return PIORAN_OK;
+}
+
+int pioran_psd_check_batch(pioran_ctx* ctx, int64_t B, int model, int64_t n_components, int basis, int is_integrated_power, double f_min, double f_max,
+                           double S_low, double S_high, const double* theta, const double* norm, int64_t F, const double* freq, int normalise, int times_f,
+                           double* psd, double* psd_approx, double* residuals, double* ratios, double* amplitudes, double* integ, int32_t* status)
+{
+    const bool any = psd || psd_approx || residuals || ratios || amplitudes || integ || status;
+    if (const int rc = psd_check_refuse(ctx, B, model, n_components, basis, f_min, f_max, S_low, S_high, theta, norm, F, freq, any)) return rc;
+    if (const int rc = psd_check_refuse_freq(F, freq)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    PendingGuard guard(ctx);
+    const PsdCheckCfg c = psd_check_cfg(model, n_components, basis, is_integrated_power, f_min, f_max, S_low, S_high, normalise, times_f);
+    PsdCheckGrid g;
+    int rc;
+    if ((rc = psd_check_grid(ctx, c, g))) return rc;
+    const double *dtheta, *dnorm, *dfreq;
+    if ((rc = psd_check_upload(ctx, c, B, theta, norm, F, freq, dtheta, dnorm, dfreq))) return rc;
+    double* const host[4] = {psd, psd_approx, residuals, ratios};
+    size_t narr = 0;
+    for (double* h : host) narr += h != nullptr;
+    // the arrays of a chunk of draws, chunk by chunk under the workspace budget, as the periodogram's host form goes
+    auto out_bytes = [&](int64_t nb) { return (size_t)nb * (size_t)F * narr * sizeof(double) + 8; };
+    int64_t chunk = B;
+    rc = size_chunk(ctx, chunk, {&ctx->bpcout, &ctx->bpcdraw}, [&](int64_t nb) { return out_bytes(nb) + psd_check_draw_bytes(nb, c.J); },
+                    [&](int64_t nb) { return ensure_each(ctx, {{&ctx->bpcout, out_bytes(nb)}, {&ctx->bpcdraw, psd_check_draw_bytes(nb, c.J)}}); });
+    if (rc) return rc;
+    const bool timed = ctx->opt.pc_events != 0;
+    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+        const int64_t nb = std::min(B - b0, chunk);
+        const PsdCheckDraws dr = psd_check_draws_of(ctx, nb, c.J);
+        double* dev[4] = {nullptr, nullptr, nullptr, nullptr};
+        double* next = (double*)ctx->bpcout.p;
+        for (int a = 0; a < 4; ++a)
+            if (host[a]) { dev[a] = next; next += (size_t)nb * (size_t)F; }
+        PsdCheckEval e{};
+        e.psd = dev[0]; e.approx = dev[1]; e.res = dev[2]; e.rat = dev[3];
+        rc = psd_check_chunk(ctx, c, g, nb, dtheta + b0 * c.P, dnorm + b0, F, dfreq, dr, e, timed && b0 == 0);
+        if (rc) { if (rc == PIORAN_ERR_HIP && ctx->last_err.empty()) ctx->last_err = "psd check launch failed"; return rc; }
+        for (int a = 0; a < 4; ++a)
+            if (host[a] && (rc = download(ctx, host[a] + b0 * F, dev[a], (size_t)nb * (size_t)F * sizeof(double)))) return rc;
+        if (amplitudes && (rc = download(ctx, amplitudes + b0 * c.J, dr.amp, (size_t)nb * c.J * sizeof(double)))) return rc;
+        if (integ && (rc = download(ctx, integ + b0, dr.integ, (size_t)nb * sizeof(double)))) return rc;
+        if (status && (rc = download(ctx, status + b0, dr.status, (size_t)nb * sizeof(int32_t)))) return rc;
+        SYNC(ctx);   // the chunk's buffers are reused by the next
+    }
+    return PIORAN_OK;
+}
+
+int pioran_psd_check_summary(pioran_ctx* ctx, int64_t B, int model, int64_t n_components, int basis, int is_integrated_power, double f_min, double f_max,
+                             double S_low, double S_high, const double* theta, const double* norm, int64_t F, const double* freq, int normalise,
+                             int times_f, int64_t Q, const double* probs, double* quant, double* mean, double* meta, int32_t* status, int32_t* kept)
+{
+    // every bad argument first, then what is not supported; nothing here touches the GPU
+    if (const int rc = psd_check_refuse(ctx, B, model, n_components, basis, f_min, f_max, S_low, S_high, theta, norm, F, freq, quant != nullptr)) return rc;
+    if (const int rc = psd_check_refuse_freq(F, freq)) return rc;
+    if (!probs || Q < 1) return PIORAN_ERR_ARG;
+    for (int64_t q = 0; q < Q; ++q)
+        if (!(probs[q] >= 0.0 && probs[q] <= 1.0)) return PIORAN_ERR_ARG;   // NaN included
+    // the draws of a frequency, and for meta the frequencies of a draw, are sorted inside one workgroup's LDS
+    if (B > pioran_quantiles_max_draws() || F > pioran_quantiles_max_draws()) return PIORAN_ERR_UNSUPPORTED;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    PendingGuard guard(ctx);
+    const PsdCheckCfg c = psd_check_cfg(model, n_components, basis, is_integrated_power, f_min, f_max, S_low, S_high, normalise, times_f);
+    const size_t bf = (size_t)B * (size_t)F, npart = (size_t)pioran_psd_check_ftiles(F);
+    const size_t x_bytes = 4 * bf * sizeof(double), t_bytes = meta ? (2 * bf + (size_t)B * npart * 4) * sizeof(double) : 0;
+    if (!ws_fits(ctx, ctx->bpcout, x_bytes) || !ws_fits(ctx, ctx->bpcT, t_bytes)) {
+        ctx->last_err = "the arrays do not fit the context's workspace budget";
+        return PIORAN_ERR_ALLOC;
+    }
+    // bpcq = probs [Q] | 0.5 | quant [4][Q][F] | mean [4][F] | medians [2][B] | means [2][B] | meta [B][8] | kept
+    const size_t o_quant = (size_t)Q + 1, o_mean = o_quant + 4 * (size_t)Q * F, o_med = o_mean + 4 * (size_t)F, o_mm = o_med + 2 * (size_t)B,
+                 o_meta = o_mm + 2 * (size_t)B, o_kept = o_meta + 8 * (size_t)B;
+    PsdCheckGrid g;
+    int rc;
+    if ((rc = psd_check_grid(ctx, c, g))) return rc;
+    const double *dtheta, *dnorm, *dfreq;
+    if ((rc = psd_check_upload(ctx, c, B, theta, norm, F, freq, dtheta, dnorm, dfreq))) return rc;
+    if ((rc = ensure_each(ctx, {{&ctx->bpcout, x_bytes}, {&ctx->bpcT, t_bytes}, {&ctx->bpcdraw, psd_check_draw_bytes(B, c.J)},
+                                {&ctx->bpcq, (o_kept + 1) * sizeof(double)}})))
+        return rc;
+    std::vector<double> small(probs, probs + Q);
+    small.push_back(0.5);
+    double* dq = (double*)ctx->bpcq.p;
+    if ((rc = upload_to(ctx, dq, small.data(), small.size() * sizeof(double)))) return rc;
+    const PsdCheckDraws dr = psd_check_draws_of(ctx, B, c.J);
+    double* X = (double*)ctx->bpcout.p;
+    double* T = (double*)ctx->bpcT.p;
+    PsdCheckEval e{};
+    e.psd = X; e.approx = X + bf; e.res = X + 2 * bf; e.rat = X + 3 * bf;
+    if (meta) { e.resT = T; e.ratT = T + bf; e.ldT = B; e.part = T + 2 * bf; e.npart = (int64_t)npart; }
+    if ((rc = psd_check_chunk(ctx, c, g, B, dtheta, dnorm, F, dfreq, dr, e, ctx->opt.pc_events != 0))) {
+        if (rc == PIORAN_ERR_HIP && ctx->last_err.empty()) ctx->last_err = "psd check launch failed";
+        return rc;
+    }
+    // per frequency, over the draws with status 0: the reduction of pioran_quantiles_batch_dev on each [B][F] array
+    int32_t* dkept = (int32_t*)(dq + o_kept);
+    for (int a = 0; a < 4; ++a)
+        if ((rc = pioran_launch_quantiles(B, F, F, X + a * bf, dr.status, nullptr, F, nullptr, nullptr, nullptr, Q, dq, dq + o_quant + (size_t)a * Q * F,
+                                          mean ? dq + o_mean + (size_t)a * F : nullptr, a == 0 ? dkept : nullptr, ctx->stream)))
+            return rc;
+    // per draw, over the frequencies: mean and median of the rows of the transposed copies (rows there are frequencies, all kept)
+    if (meta) {
+        for (int k = 0; k < 2; ++k)
+            if ((rc = pioran_launch_quantiles(F, B, B, T + k * bf, nullptr, nullptr, B, nullptr, nullptr, nullptr, 1, dq + Q, dq + o_med + (size_t)k * B,
+                                              dq + o_mm + (size_t)k * B, nullptr, ctx->stream)))
+                return rc;
+        if ((rc = pioran_launch_psd_check_meta(B, (int64_t)npart, e.part, dr.status, dq + o_med, dq + o_mm, dq + o_med + B, dq + o_mm + B, dq + o_meta,
+                                               ctx->stream)))
+            return rc;
+        if ((rc = download(ctx, meta, dq + o_meta, 8 * (size_t)B * sizeof(double)))) return rc;
+    }
+    if ((rc = download(ctx, quant, dq + o_quant, 4 * (size_t)Q * F * sizeof(double)))) return rc;
+    if (mean && (rc = download(ctx, mean, dq + o_mean, 4 * (size_t)F * sizeof(double)))) return rc;
+    if (status && (rc = download(ctx, status, dr.status, (size_t)B * sizeof(int32_t)))) return rc;
+    if (kept && (rc = download(ctx, kept, dkept, sizeof(int32_t)))) return rc;
+    SYNC(ctx);
     return PIORAN_OK;
 }
 

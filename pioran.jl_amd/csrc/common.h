@@ -57,6 +57,8 @@ struct ScanOptions {
                           // slots 4 .. 9 (before the gather | after it | after the simulation | the residual | the prediction | the combination)
     int theta_events = 0; // theta gradient (capi.hip logl_grad_batch fed by approx), timing tools ONLY: 1 = a call's first chunk records the context's event slots
                           // 4 .. 7 (before approx_kernel | after it | before approx_vjp_kernel | after it)
+    int pc_events = 0;    // PSD check (capi.hip psd_check_chunk), timing tools ONLY: 1 = a call's first chunk records the context's event slots
+                          // 4 .. 6 (before psd_check_draw_kernel | after it | after psd_check_eval_kernel)
 };
 
 struct ScanParams {
@@ -259,6 +261,26 @@ int pioran_launch_quantiles(int64_t B, int64_t M, int64_t ldx, const double* X, 
                             const double* ref /*nullptr, or with scale [Mc]: v = (ref - v) / scale*/, const double* scale, int64_t Q,
                             const double* probs, double* quant /*[Q][Mc]*/, double* mean /*[Mc] or nullptr*/, int32_t* kept /*[1] or nullptr*/,
                             hipStream_t stream);
+// psd_check.hip: the PSD model against its basis-function approximation, per draw and frequency (sample_approx_model, src/plots_diagnostics.jl:195-213)
+struct PsdCheckEval {
+    int64_t B, F;
+    int model, P, J, basis, normalise, times_f;
+    const double *sp, *theta, *norm, *freq;        // [J], [B][P], [B], [F]
+    const double *amp, *integ, *pf0;               // [B][J], [B], [B]: what pioran_launch_psd_check_draws left
+    const int32_t* status;                         // [B]: ... and the draws it refused (their rows are NaN)
+    double *psd, *approx, *res, *rat;              // [B][F] each, or nullptr: not wanted
+    double *resT, *ratT;                           // [F][ldT] transposed copies of residuals and ratios, or nullptr
+    int64_t ldT;
+    double* part;                                  // [B][npart][4]: min |res|, max |res|, min |rat|, max |rat| per frequency tile, or nullptr
+    int64_t npart;                                 // pioran_psd_check_ftiles(F)
+};
+int64_t pioran_psd_check_ftiles(int64_t F);
+int pioran_launch_psd_check_draws(int64_t B, int model, int P, int J, int basis, int integrated, int normalise, double f_min, double f_max,
+                                  const double* sp, const double* LU, const int32_t* piv, const double* theta, const double* norm, const double* freq,
+                                  double* amp, double* integ, double* pf0, int32_t* status, hipStream_t stream);
+int pioran_launch_psd_check_eval(const PsdCheckEval& p, hipStream_t stream);
+int pioran_launch_psd_check_meta(int64_t B, int64_t npart, const double* part, const int32_t* status, const double* med_res, const double* mean_res,
+                                 const double* med_rat, const double* mean_rat, double* meta /*[B][8]*/, hipStream_t stream);
 // approx.hip
 #ifdef __cplusplus
 #include <vector>

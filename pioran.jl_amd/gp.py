@@ -213,6 +213,80 @@ class Context:
                                                          v(dcols or None), v(dref or None), v(dscale or None), len(probs), _ptr(probs), v(dquant),
                                                          v(dmean or None), v(dkept or None)), self._h)
 
+    # -- the PSD model against its basis-function approximation ------------------------------------
+    def _psd_check_args(self, model, theta, norm, freq, basis_function):
+        mid, basis, theta, norm = _theta_args(model, theta, norm, basis_function)
+        freq = _f64(freq).reshape(-1)
+        if len(freq) < 1:
+            raise ValueError("freq must hold at least one frequency")
+        return mid, basis, theta, norm, freq
+
+    def psd_check(self, model, theta, norm, freq, f_min, f_max, n_components=20, S_low=20.0, S_high=20.0, *, basis_function="SHO",
+                  is_integrated_power=True, normalise=False, times_f=False, outputs=("psd", "psd_approx", "residuals", "ratios"),
+                  amplitudes=False, integ=False):
+        """The PSD model and its basis-function approximation for the B draws theta (B, P), norm (B,) at the frequencies freq (F,):
+        pioran_psd_check_batch, the arrays of sample_approx_model (src/plots_diagnostics.jl:195-213) with one draw per ROW.  model, theta, norm
+        and the grid arguments as in Dataset.logpdf_theta.  normalise: divide both spectra by get_norm_psd as plot_psd_ppc does (:404-409);
+        times_f: multiply them by the frequency after that (plot_f_P).  outputs: which of "psd", "psd_approx", "residuals", "ratios" to compute
+        and return, (B, F) each; amplitudes / integ: also the amplitudes (B, J) before any scaling and the normalising integral (B,).
+        Returns a dict of the requested arrays and "status" (B,): 2, with NaN in the draw's rows, for a draw that cannot be evaluated.
+        The call goes chunk by chunk under the context's "workspace_limit_mb"; no limit on B or F."""
+        mid, basis, theta, norm, freq = self._psd_check_args(model, theta, norm, freq, basis_function)
+        names = ("psd", "psd_approx", "residuals", "ratios")
+        if any(o not in names for o in outputs):
+            raise ValueError(f"outputs must be among {names}")
+        B, F, J = theta.shape[0], len(freq), int(n_components)
+        out = {n: np.empty((B, F)) for n in names if n in outputs}
+        if amplitudes:
+            out["amplitudes"] = np.empty((B, J))
+        if integ:
+            out["integ"] = np.empty(B)
+        out["status"] = np.zeros(B, dtype=np.int32)
+        _lib.check(_lib.lib().pioran_psd_check_batch(self._h, B, mid, J, basis, int(bool(is_integrated_power)), float(f_min), float(f_max), float(S_low),
+                                                     float(S_high), _ptr(theta), _ptr(norm), F, _ptr(freq), int(bool(normalise)), int(bool(times_f)),
+                                                     *(_ptr(out.get(n)) for n in names), _ptr(out.get("amplitudes")), _ptr(out.get("integ")),
+                                                     _ptr(out["status"])), self._h)
+        return out
+
+    def psd_check_dev(self, B, F, model, dtheta, dnorm, dfreq, f_min, f_max, n_components=20, S_low=20.0, S_high=20.0, *, basis_function="SHO",
+                      is_integrated_power=True, normalise=False, times_f=False, dpsd=0, dpsd_approx=0, dresiduals=0, dratios=0, damplitudes=0,
+                      dinteg=0, dstatus=0):
+        """Device-pointer (int addresses) asynchronous variant: dtheta (B, P), dnorm (B,), dfreq (F,), the outputs (B, F), damplitudes (B, J),
+        dinteg (B,), dstatus (B,) int32 in HBM; enqueues on the context's stream (pioran_psd_check_batch_dev).  Any output may be 0, not all."""
+        from .psd import DoubleBendingPowerLaw, SingleBendingPowerLaw
+        mid = {SingleBendingPowerLaw: 0, DoubleBendingPowerLaw: 1}.get(model)
+        if mid is None or basis_function not in ("SHO", "DRWCelerite"):
+            raise ValueError("model must be SingleBendingPowerLaw or DoubleBendingPowerLaw and basis_function SHO or DRWCelerite")
+        v = ctypes.c_void_p
+        _lib.check(_lib.lib().pioran_psd_check_batch_dev(self._h, int(B), mid, int(n_components), 0 if basis_function == "SHO" else 1,
+                                                         int(bool(is_integrated_power)), float(f_min), float(f_max), float(S_low), float(S_high),
+                                                         v(dtheta), v(dnorm), int(F), v(dfreq), int(bool(normalise)), int(bool(times_f)),
+                                                         v(dpsd or None), v(dpsd_approx or None), v(dresiduals or None), v(dratios or None),
+                                                         v(damplitudes or None), v(dinteg or None), v(dstatus or None)), self._h)
+
+    def psd_check_summary(self, model, theta, norm, freq, f_min, f_max, n_components=20, S_low=20.0, S_high=20.0, *, basis_function="SHO",
+                          is_integrated_power=True, normalise=False, times_f=False, probs=PPC_QUANTILES, mean=True, meta=True):
+        """Context.psd_check with its arrays kept on the device and reduced there (pioran_psd_check_summary).  Returns a dict with
+        quant (4, Q, F) and mean (4, F): per frequency, over the draws with status 0, of psd, psd_approx, residuals, ratios in this order;
+        meta (B, 8): per draw, over the frequencies, mean, median, min |.|, max |.| of the residuals, then of the ratios (NaN for a draw with
+        status 2); status (B,) and kept.  At most 4096 draws and 4096 frequencies (the quantile kernel's limit)."""
+        mid, basis, theta, norm, freq = self._psd_check_args(model, theta, norm, freq, basis_function)
+        probs = _f64(probs).reshape(-1)
+        B, F, Q = theta.shape[0], len(freq), len(probs)
+        out = dict(quant=np.empty((4, Q, F)), status=np.zeros(B, dtype=np.int32))
+        if mean:
+            out["mean"] = np.empty((4, F))
+        if meta:
+            out["meta"] = np.empty((B, 8))
+        kept = ctypes.c_int32(-1)
+        _lib.check(_lib.lib().pioran_psd_check_summary(self._h, B, mid, int(n_components), basis, int(bool(is_integrated_power)), float(f_min),
+                                                       float(f_max), float(S_low), float(S_high), _ptr(theta), _ptr(norm), F, _ptr(freq),
+                                                       int(bool(normalise)), int(bool(times_f)), Q, _ptr(probs), _ptr(out["quant"]), _ptr(out.get("mean")),
+                                                       _ptr(out.get("meta")), _ptr(out["status"]), ctypes.cast(ctypes.byref(kept), ctypes.c_void_p)),
+                   self._h)
+        out["kept"] = kept.value
+        return out
+
     def dense_nll(self, a, b, c, d, t, y, sigma2, return_info=False):
         a, b, c, d, t, y, sigma2 = map(_f64, (a, b, c, d, t, y, sigma2))
         out = ctypes.c_double()
@@ -995,3 +1069,160 @@ def ppc_timeseries_summary(rng, t, y, yerr, A, Bc, C, Dd, mu=None, nu=None, shif
         ds.close()
     return dict(t_pred=t_pred, ts_quantiles=r["ts_quantiles"], res_quantiles=r["res_quantiles"], mean_res=r["res_mean"], status=r["status"],
                 kept=r["kept"])
+
+
+# ---- the PSD approximation checks: run_diagnostics, plot_psd_ppc, run_posterior_predict_checks as numbers ---------------------------------
+_META_NAMES = ("meta_mean", "meta_median", "meta_min", "meta_max", "meta_mean_rat", "meta_median_rat", "meta_min_rat", "meta_max_rat")
+_MAX_SUMMARY = 4096     # draws / frequencies of one pioran_psd_check_summary call (the quantile kernel sorts a column in one workgroup)
+
+
+def _quantiles_host(X, probs, status=None):
+    """(quant (Q, M), mean (M,), kept) of the rows of X with status 0, on the host, by the definition of tools/quantiles_proto.py (type 7 with
+    its rule for close neighbours; the mean is the long-double sum over the kept rows): the route of the checks above 4096 draws."""
+    V = np.asarray(X, dtype=np.float64)
+    if status is not None:
+        V = V[np.asarray(status) == 0]
+    K, M = V.shape
+    probs = _f64(probs).reshape(-1)
+    quant = np.full((len(probs), M), np.nan)
+    if K == 0:
+        return quant, np.full(M, np.nan), 0
+    S = np.sort(V, axis=0)
+    with np.errstate(invalid="ignore", over="ignore"):
+        mean = (np.sum(V.astype(np.longdouble), axis=0) / np.longdouble(K)).astype(np.float64)
+        has_nan = np.isnan(S[-1])
+        for q, p in enumerate(probs):
+            aleph = np.float64(K) * p + (np.float64(1.0) - p)
+            j = min(max(int(np.trunc(aleph)), 1), K - 1) if K > 1 else 1
+            g = min(max(aleph - np.float64(j), np.float64(0.0)), np.float64(1.0))
+            a, b = (S[0], S[0]) if K == 1 else (S[j - 1], S[j])
+            close = np.isfinite(a) & np.isfinite(b) & (np.abs(a - b) <= np.float64(2.0 ** -26) * np.maximum(np.abs(a), np.abs(b)))
+            quant[q] = np.where(has_nan, np.nan, np.where(close, a + g * (b - a), (np.float64(1.0) - g) * a + g * b))
+    return quant, mean, K
+
+
+def _check_grid(f0, fM, n_frequencies):
+    """collect(10 .^ range(log10(f0), log10(fM), n_frequencies))   src/plots_diagnostics.jl:200"""
+    return 10.0 ** np.linspace(np.log10(f0), np.log10(fM), int(n_frequencies))
+
+
+def _draws_by_row(samples):
+    """the reference's samples (P_params, B), one draw per COLUMN, as (B, P_params); a vector of P_params values is one draw"""
+    samples = np.asarray(samples, dtype=np.float64)
+    return np.ascontiguousarray(samples.reshape(-1, 1).T if samples.ndim == 1 else samples.T)
+
+
+def sample_approx_model(samples, norm_samples, f0, fM, model, n_frequencies=1000, basis_function="SHO", n_components=20, ctx: Context | None = None):
+    """sample_approx_model(samples, norm_samples, f0, fM, model; n_frequencies, basis_function, n_components) of src/plots_diagnostics.jl:195-213
+    in one device call (Context.psd_check).  samples: (P_params, B) like the reference's, one draw per column; model: SingleBendingPowerLaw or
+    DoubleBendingPowerLaw (the class).  Returns psd, psd_approx, residuals, ratios, f with the arrays (F, B) like the reference's — transposed
+    VIEWS of the (B, F) arrays the device writes — and f the reference's grid 10 .^ range(log10(f0), log10(fM), n_frequencies).  A draw that
+    cannot be evaluated (non-finite parameter, model not positive at f[0] or at f0) has NaN in its column."""
+    theta = _draws_by_row(samples)
+    f = _check_grid(f0, fM, n_frequencies)
+    r = (ctx or default_context()).psd_check(model, theta, norm_samples, f, f0, fM, n_components, 1.0, 1.0, basis_function=basis_function)
+    return r["psd"].T, r["psd_approx"].T, r["residuals"].T, r["ratios"].T, f
+
+
+def _diagnostics_dict(f, quant_res, quant_rat, mean_res, mean_rat, meta, kept):
+    out = dict(f=f, mean_res=mean_res, mean_rat=mean_rat, res_quantiles=quant_res, rat_quantiles=quant_rat, kept=kept)
+    out.update({name: meta[:, k] for k, name in enumerate(_META_NAMES)})
+    return out
+
+
+def run_diagnostics(prior_samples, norm_samples, f_min, f_max, model, S_low=20.0, S_high=20.0, basis_function="SHO", n_components=20,
+                    n_frequencies=1000, ctx: Context | None = None):
+    """run_diagnostics(prior_samples, norm_samples, f_min, f_max, model, S_low, S_high; basis_function, n_components) of
+    src/plots_diagnostics.jl:232-240 as numbers: the content of the three text files the reference writes.  prior_samples (P_params, B).
+    Returns a dict with f (F,); mean_res, mean_rat (F,) (plot_mean_approx :150-151); res_quantiles, rat_quantiles (5, F) at PPC_QUANTILES
+    (plot_quantiles_approx :93-94); meta_mean, meta_median, meta_min, meta_max, meta_mean_rat, meta_median_rat, meta_min_rat, meta_max_rat (B,)
+    (plot_boxplot_psd_approx :43-51); kept: the number of draws that entered the reductions over draws (a draw that cannot be evaluated is left
+    out of them and has NaN in its meta entries).
+    Up to 4096 draws everything happens in one device call (Context.psd_check_summary) and only these vectors come back.  With more draws —
+    or more than 4096 frequencies — the quantile kernel's limit is exceeded: the residuals and ratios are then taken from Context.psd_check
+    chunk by chunk and reduced on the host with the definition of tools/quantiles_proto.py (same quantile rule; the means are long-double sums,
+    so they may differ from the device's in the last bits)."""
+    ctx = ctx or default_context()
+    theta = _draws_by_row(prior_samples)
+    f0, fM = f_min / S_low, f_max * S_high
+    f = _check_grid(f0, fM, n_frequencies)
+    B = theta.shape[0]
+    if B <= _MAX_SUMMARY and len(f) <= _MAX_SUMMARY:
+        r = ctx.psd_check_summary(model, theta, norm_samples, f, f0, fM, n_components, 1.0, 1.0, basis_function=basis_function)
+        return _diagnostics_dict(f, r["quant"][2], r["quant"][3], r["mean"][2], r["mean"][3], r["meta"], r["kept"])
+    r = ctx.psd_check(model, theta, norm_samples, f, f0, fM, n_components, 1.0, 1.0, basis_function=basis_function, outputs=("residuals", "ratios"))
+    st = r["status"]
+    meta = np.full((B, 8), np.nan)
+    ok = st == 0
+    red = {}
+    for k, name in enumerate(("residuals", "ratios")):
+        X = r[name]
+        red[name] = _quantiles_host(X, PPC_QUANTILES, st)
+        med, mean, _ = _quantiles_host(X[ok].T, [0.5])
+        meta[ok, 4 * k], meta[ok, 4 * k + 1] = mean, med[0]
+        meta[ok, 4 * k + 2], meta[ok, 4 * k + 3] = np.min(np.abs(X[ok]), axis=1), np.max(np.abs(X[ok]), axis=1)
+    return _diagnostics_dict(f, red["residuals"][0], red["ratios"][0], red["residuals"][1], red["ratios"][1], meta, red["residuals"][2])
+
+
+def psd_ppc(samples_psd, samples_norm, samples_nu, t, y, yerr, model, S_low=20.0, S_high=20.0, plot_f_P=False, n_frequencies=1000, n_components=20,
+            basis_function="SHO", is_integrated_power=True, with_log_transform=False, ctx: Context | None = None):
+    """plot_psd_ppc(samples_psd, samples_norm, samples_nu, t, y, yerr, model; ...) of src/plots_diagnostics.jl:371-487 as numbers.  samples_psd
+    (B, P_params), one posterior sample per row, as the reference takes them here.  Returns a dict with f (F,); psd_quantiles,
+    psd_approx_quantiles (5, F) at PPC_QUANTILES of the model PSD and of its approximation, both divided by get_norm_psd (:404-409) and, with
+    plot_f_P, multiplied by f (:419-420); mean_noise_level, median_noise_level (:379-397, host scalars; multiply by f yourself with plot_f_P as
+    :435-436 do); f_min, f_max of the data; kept.
+    Up to 4096 samples: one device call (Context.psd_check_summary).  With more — a nested-sampling posterior routinely has more equal-weight
+    samples, and the reference uses all of them — the two arrays are taken from Context.psd_check chunk by chunk and reduced on the host with
+    the definition of tools/quantiles_proto.py."""
+    ctx = ctx or default_context()
+    t, y, yerr = _f64(t).reshape(-1), _f64(y).reshape(-1), _f64(yerr).reshape(-1)
+    theta = _f64(np.atleast_2d(samples_psd))
+    dt = np.diff(t)
+    f_min, f_max = 1.0 / (t[-1] - t[0]), 1.0 / np.min(dt) / 2.0
+    f0, fM = f_min / S_low, f_max * S_high
+    sq_err = (yerr / y) ** 2 if with_log_transform else yerr ** 2
+    nu = _f64(samples_nu).reshape(-1)
+    mean_noise_level = 2.0 * np.mean(nu) * np.mean(sq_err) * np.mean(dt)
+    median_noise_level = 2.0 * np.median(nu) * np.median(sq_err) * np.median(dt)
+    f = _check_grid(f0, fM, n_frequencies)
+    kw = dict(basis_function=basis_function, is_integrated_power=is_integrated_power, normalise=True, times_f=plot_f_P)
+    if theta.shape[0] <= _MAX_SUMMARY and len(f) <= _MAX_SUMMARY:
+        r = ctx.psd_check_summary(model, theta, samples_norm, f, f_min, f_max, n_components, S_low, S_high, mean=False, meta=False, **kw)
+        q_psd, q_approx, kept = r["quant"][0], r["quant"][1], r["kept"]
+    else:
+        r = ctx.psd_check(model, theta, samples_norm, f, f_min, f_max, n_components, S_low, S_high, outputs=("psd", "psd_approx"), **kw)
+        q_psd, _, kept = _quantiles_host(r["psd"], PPC_QUANTILES, r["status"])
+        q_approx, _, _ = _quantiles_host(r["psd_approx"], PPC_QUANTILES, r["status"])
+    return dict(f=f, psd_quantiles=q_psd, psd_approx_quantiles=q_approx, mean_noise_level=mean_noise_level, median_noise_level=median_noise_level,
+                f_min=f_min, f_max=f_max, kept=kept)
+
+
+def posterior_predict_checks(rng, samples_psd, samples_norm, samples_nu, samples_mu, samples_c, t, y, yerr, model, with_log_transform=False,
+                             S_low=20.0, S_high=20.0, is_integrated_power=True, plots="all", basis_function="SHO", n_frequencies=1000, plot_f_P=False,
+                             n_components=20, ctx: Context | None = None):
+    """run_posterior_predict_checks (src/plots_diagnostics.jl:276-344) for the models that go through `approx`, as numbers: the three checks in
+    the reference's order (:282-307) — pj.psd_ppc, pj.lsp_ppc, pj.ppc_timeseries_summary — on the posterior samples samples_psd (B, P_params),
+    samples_norm, samples_nu, samples_mu (B,) or None, and samples_c (B,), the log-transform's constant, used when with_log_transform.  The
+    celerite coefficients of the second and third check come from psd.approx_batch.  plots: "all", or a list among "psd", "lsp", "timeseries"
+    (:310-341).  rng: numpy Generator, consumed by the periodogram check first, then by the time-series check.
+    Returns {"psd": ..., "lsp": ..., "timeseries": ...} with the selected keys, each value what the single call returns for the same generator state."""
+    from .psd import approx_batch
+    want = ("psd", "lsp", "timeseries") if isinstance(plots, str) and plots == "all" else tuple(plots)
+    if any(w not in ("psd", "lsp", "timeseries") for w in want):
+        raise ValueError('plots must be "all" or a list among "psd", "lsp", "timeseries"')
+    t, y, yerr = _f64(t).reshape(-1), _f64(y).reshape(-1), _f64(yerr).reshape(-1)
+    out = {}
+    if "psd" in want:
+        out["psd"] = psd_ppc(samples_psd, samples_norm, samples_nu, t, y, yerr, model, S_low=S_low, S_high=S_high, plot_f_P=plot_f_P,
+                             n_frequencies=n_frequencies, n_components=n_components, basis_function=basis_function,
+                             is_integrated_power=is_integrated_power, with_log_transform=with_log_transform, ctx=ctx)
+    if "lsp" in want or "timeseries" in want:
+        f_min, f_max = 1.0 / (t[-1] - t[0]), 1.0 / np.min(np.diff(t)) / 2.0
+        A, Bc, C, Dd = approx_batch(model, samples_psd, f_min, f_max, n_components, samples_norm, S_low, S_high,
+                                    is_integrated_power=is_integrated_power, basis_function=basis_function)
+        if "lsp" in want:
+            out["lsp"] = lsp_ppc(rng, t, yerr, A, Bc, C, Dd, mu=samples_mu, nu=samples_nu, S_low=S_low, S_high=S_high, n_frequencies=n_frequencies, ctx=ctx)
+        if "timeseries" in want:
+            out["timeseries"] = ppc_timeseries_summary(rng, t, y, yerr, A, Bc, C, Dd, mu=samples_mu, nu=samples_nu,
+                                                       shift=samples_c if with_log_transform else None, ctx=ctx)
+    return out

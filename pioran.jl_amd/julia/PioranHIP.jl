@@ -548,6 +548,119 @@ function quantiles_batch_dev(ctx, B::Integer, M::Integer, ldx::Integer, dX::Ptr{
     return nothing
 end
 
+_psd_check_ids(model::Symbol, basis::String) =
+    (model === :SingleBendingPowerLaw ? 0 : model === :DoubleBendingPowerLaw ? 1 : error("model $model not supported on the device"),
+     basis == "SHO" ? 0 : basis == "DRWCelerite" ? 1 : error("basis $basis not supported on the device"))
+
+"""
+    psd_check_batch(model, samples, norm_samples, f, f_min, f_max, n_components; basis_function, S_low, S_high, is_integrated_power,
+                    normalise, times_f)
+
+The PSD model and its basis-function approximation for every column of `samples` (`P_params × nbatch`, as the reference passes them) at the
+frequencies `f`: `(psd, psd_approx, residuals, ratios, amplitudes, integ, status)` with the four arrays `length(f) × nbatch` as
+`sample_approx_model` returns them (src/plots_diagnostics.jl:195-213), `amplitudes` `n_components × nbatch` (`get_approx_coefficients`), `integ`
+(`get_norm_psd`) and `status[k] == 2` for a draw that cannot be evaluated (its columns are NaN).  `normalise`: both spectra divided by `integ` as
+`plot_psd_ppc` does (:404-409); `times_f`: multiplied by `f` after that (`plot_f_P`).  Continuum models only.
+"""
+function psd_check_batch(model::Symbol, samples::Matrix{Float64}, norm_samples::Vector{Float64}, f::Vector{Float64}, f_min::Real, f_max::Real,
+                         n_components::Integer = 20; basis_function::String = "SHO", S_low::Real = 20.0, S_high::Real = 20.0,
+                         is_integrated_power::Bool = true, normalise::Bool = false, times_f::Bool = false, ctx = default_context())
+    m, bs = _psd_check_ids(model, basis_function)
+    size(samples, 1) == (m == 0 ? 3 : 5) || error("samples must be $(m == 0 ? 3 : 5) × nbatch")
+    nb, F = size(samples, 2), length(f)
+    length(norm_samples) == nb || error("norm_samples must have one entry per draw")
+    psd, psd_approx, residuals, ratios = (Matrix{Float64}(undef, F, nb) for _ in 1:4)
+    amplitudes = Matrix{Float64}(undef, n_components, nb); integ = Vector{Float64}(undef, nb); status = Vector{Int32}(undef, nb)
+    GC.@preserve samples norm_samples f psd psd_approx residuals ratios amplitudes integ status begin
+        check(ccall((:pioran_psd_check_batch, LIB), Cint,
+                    (Ptr{Cvoid}, Int64, Cint, Int64, Cint, Cint, Cdouble, Cdouble, Cdouble, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Int64,
+                     Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}),
+                    ctx.h, nb, m, n_components, bs, is_integrated_power ? 1 : 0, f_min, f_max, S_low, S_high, samples, norm_samples, F, f,
+                    normalise ? 1 : 0, times_f ? 1 : 0, psd, psd_approx, residuals, ratios, amplitudes, integ, status))
+    end
+    return psd, psd_approx, residuals, ratios, amplitudes, integ, status
+end
+
+"""
+    psd_check_batch_dev(ctx, B, model, n_components, dθ, dnorm, F, dfreq, f_min, f_max; dpsd, dpsd_approx, dresiduals, dratios, ...)
+
+The same on arrays already in device memory (`Ptr`s into HBM; any output may be `C_NULL`, not all), asynchronous on the context's stream.
+"""
+function psd_check_batch_dev(ctx, B::Integer, model::Symbol, n_components::Integer, dθ::Ptr{Cdouble}, dnorm::Ptr{Cdouble}, F::Integer,
+                             dfreq::Ptr{Cdouble}, f_min::Real, f_max::Real; basis_function::String = "SHO", S_low::Real = 20.0,
+                             S_high::Real = 20.0, is_integrated_power::Bool = true, normalise::Bool = false, times_f::Bool = false,
+                             dpsd = Ptr{Cdouble}(C_NULL), dpsd_approx = Ptr{Cdouble}(C_NULL), dresiduals = Ptr{Cdouble}(C_NULL),
+                             dratios = Ptr{Cdouble}(C_NULL), damplitudes = Ptr{Cdouble}(C_NULL), dinteg = Ptr{Cdouble}(C_NULL),
+                             dstatus = Ptr{Int32}(C_NULL))
+    m, bs = _psd_check_ids(model, basis_function)
+    check(ccall((:pioran_psd_check_batch_dev, LIB), Cint,
+                (Ptr{Cvoid}, Int64, Cint, Int64, Cint, Cint, Cdouble, Cdouble, Cdouble, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Int64,
+                 Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}),
+                ctx.h, B, m, n_components, bs, is_integrated_power ? 1 : 0, f_min, f_max, S_low, S_high, dθ, dnorm, F, dfreq,
+                normalise ? 1 : 0, times_f ? 1 : 0, dpsd, dpsd_approx, dresiduals, dratios, damplitudes, dinteg, dstatus))
+    return nothing
+end
+
+"""
+    psd_check_summary(model, samples, norm_samples, f, f_min, f_max, n_components, probs = PPC_QUANTILES; ...)
+
+`psd_check_batch` with the arrays left on the device and reduced there: `(quant, mean, meta, status, kept)` with `quant` `length(f) × length(probs) × 4`
+and `mean` `length(f) × 4` over the draws with status 0 (the last index: psd, psd_approx, residuals, ratios), and `meta` `8 × nbatch`: per draw,
+over the frequencies, mean, median, min |·|, max |·| of the residuals, then of the ratios (plot_boxplot_psd_approx, src/plots_diagnostics.jl:43-51).
+At most 4096 draws and 4096 frequencies.
+"""
+function psd_check_summary(model::Symbol, samples::Matrix{Float64}, norm_samples::Vector{Float64}, f::Vector{Float64}, f_min::Real, f_max::Real,
+                           n_components::Integer = 20, probs::Vector{Float64} = PPC_QUANTILES; basis_function::String = "SHO", S_low::Real = 20.0,
+                           S_high::Real = 20.0, is_integrated_power::Bool = true, normalise::Bool = false, times_f::Bool = false,
+                           ctx = default_context())
+    m, bs = _psd_check_ids(model, basis_function)
+    size(samples, 1) == (m == 0 ? 3 : 5) || error("samples must be $(m == 0 ? 3 : 5) × nbatch")
+    nb, F, Q = size(samples, 2), length(f), length(probs)
+    length(norm_samples) == nb || error("norm_samples must have one entry per draw")
+    quant = Array{Float64, 3}(undef, F, Q, 4); mean = Matrix{Float64}(undef, F, 4); meta = Matrix{Float64}(undef, 8, nb)
+    status = Vector{Int32}(undef, nb); kept = Ref{Int32}(-1)
+    GC.@preserve samples norm_samples f probs quant mean meta status begin
+        check(ccall((:pioran_psd_check_summary, LIB), Cint,
+                    (Ptr{Cvoid}, Int64, Cint, Int64, Cint, Cint, Cdouble, Cdouble, Cdouble, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Int64,
+                     Ptr{Cdouble}, Cint, Cint, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ref{Int32}),
+                    ctx.h, nb, m, n_components, bs, is_integrated_power ? 1 : 0, f_min, f_max, S_low, S_high, samples, norm_samples, F, f,
+                    normalise ? 1 : 0, times_f ? 1 : 0, Q, probs, quant, mean, meta, status, kept))
+    end
+    return quant, mean, meta, status, Int(kept[])
+end
+
+"""
+    sample_approx_model(samples, norm_samples, f0, fM, model; n_frequencies = 1000, basis_function = "SHO", n_components = 20)
+
+`sample_approx_model` of src/plots_diagnostics.jl:195-213 in one device call: `(psd, psd_approx, residuals, ratios, f)`, the arrays
+`n_frequencies × nbatch`.  `model` is `:SingleBendingPowerLaw` or `:DoubleBendingPowerLaw`.
+"""
+function sample_approx_model(samples::Matrix{Float64}, norm_samples::Vector{Float64}, f0::Real, fM::Real, model::Symbol; n_frequencies::Integer = 1000,
+                             basis_function::String = "SHO", n_components::Integer = 20, ctx = default_context())
+    f = collect(10 .^ range(log10(f0), log10(fM), n_frequencies))
+    psd, psd_approx, residuals, ratios, _, _, _ = psd_check_batch(model, samples, norm_samples, f, f0, fM, n_components;
+                                                                  basis_function = basis_function, S_low = 1.0, S_high = 1.0, ctx = ctx)
+    return psd, psd_approx, residuals, ratios, f
+end
+
+"""
+    run_diagnostics(prior_samples, norm_samples, f_min, f_max, model, S_low = 20.0, S_high = 20.0; basis_function = "SHO", n_components = 20)
+
+The numbers of `run_diagnostics` (src/plots_diagnostics.jl:232-240), what its three text files hold: a named tuple with `f`, `mean_res`, `mean_rat`,
+`res_quantiles`, `rat_quantiles` (`length(f) × 5`, at `PPC_QUANTILES`), `meta` (`8 × nbatch`: meta_mean, meta_median, meta_min, meta_max, then the
+same of the ratios) and `kept`.  One device call; at most 4096 draws (with more, reduce the arrays of `sample_approx_model` on the host).
+"""
+function run_diagnostics(prior_samples::Matrix{Float64}, norm_samples::Vector{Float64}, f_min::Real, f_max::Real, model::Symbol, S_low::Real = 20.0,
+                         S_high::Real = 20.0; basis_function::String = "SHO", n_components::Integer = 20, n_frequencies::Integer = 1000,
+                         ctx = default_context())
+    f0, fM = f_min / S_low, f_max * S_high
+    f = collect(10 .^ range(log10(f0), log10(fM), n_frequencies))
+    quant, mean, meta, _, kept = psd_check_summary(model, prior_samples, norm_samples, f, f0, fM, n_components; basis_function = basis_function,
+                                                   S_low = 1.0, S_high = 1.0, ctx = ctx)
+    return (f = f, mean_res = mean[:, 3], mean_rat = mean[:, 4], res_quantiles = quant[:, :, 3], rat_quantiles = quant[:, :, 4], meta = meta,
+            kept = kept)
+end
+
 """
     rand_posterior_summary(ds, A, B, c, d, τ, q_data, q_new, ϵ, probs = PPC_QUANTILES; μ, ν, shift, backtransform, res_cols, res_ref, res_scale)
 

@@ -111,6 +111,25 @@ def get_approx_coefficients(psd_model, f0, fM, n_components=20, basis_function="
     return psd_decomp(p / p[0], Bm)
 
 
+def approximated_psd(f, psd_model, f0, fM, n_components=20, norm=1.0, basis_function="SHO", individual=False):
+    """approximated_psd(f, psd_model, f0, fM; n_components, norm, basis_function, individual) of src/psd.jl:152-185, on the host for one model:
+    sum_j amplitudes_j norm / (1 + (f / spectral_points_j)^{4|6}) at the frequencies f (F,), j ascending; individual=True returns the (F, J)
+    components instead of their sum.  The batched form over many models is Context.psd_check / pj.sample_approx_model."""
+    sp, Bm = build_approx(n_components, f0, fM, basis_function)
+    p = psd_model(sp)
+    amplitudes = psd_decomp(p / p[0], Bm)
+    f = np.asarray(f, float).reshape(-1)
+    r2 = (f[:, None] / sp[None, :]) ** 2
+    r4 = r2 * r2
+    comps = (amplitudes * norm)[None, :] / (1.0 + (r4 if basis_function == "SHO" else r4 * r2))
+    if individual:
+        return comps
+    psd = np.zeros(len(f))
+    for j in range(n_components):
+        psd = psd + comps[:, j]
+    return psd
+
+
 def _integral_sho(a, c, x):
     # src/psd.jl:301-305; a may carry leading batch axes
     norm = c * a / (4 * math.sqrt(2))
