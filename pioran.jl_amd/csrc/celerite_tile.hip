@@ -259,6 +259,7 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
     // the y row's column of X': v = y_n - mu in the lane column ry of block Jy (z_n = y_n - u'f, :141); the other lane columns of that block take mu_y = 0
     const double mu_y = c16 == ry ? mu : 0.0;
     const int64_t k_ragged = (N % KW) ? NW - 1 : NW;   // the window whose steps past N are padding (none if N is a multiple of 16)
+    const bool pad_lane = k_ragged * KW + c16 >= N;    // ... and whether this lane's step of that window is one of them (formed once: the diagonal of Sigma below)
     double quad = 0.0;                 // block column Jy's; meaningful in the y-row lanes
     double Pm = 1.0;                   // per lane (step c16 of every window): running product of |D| (sign of D_1 kept: :126)
     int Pe = 0;
@@ -271,9 +272,16 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
     // +0.7 %, SHO-40 +0.7 % with it here, same box).
     constexpr bool PRE = NB <= 3;
     [[maybe_unused]] double ckl[4], ckcl[NB], cku[NB > 1 ? NB - 1 : 1][4];
+    // Padding registers (round 10): register g of a tile of row block NB - 1 holds the rows 16 (NB - 1) + 4 g + q, and 4 (KL - 1) < R - 16 (NB - 1) <= 4 KL puts
+    // the y row (row R) in register KL - 1 or KL: every register g > KL holds padding rows r > R in all four q.  Those registers are +0 from the initialisation
+    // on and every term added to them is a product with an exact zero (albe, C_K and the table's (C_K / C) o v are 0 on the padding rows, so U~, M', X' and Y^'
+    // are 0 in the padding columns) — and whatever they hold stays in the padding rows and columns: the K-steps that would read them are the ones KL drops, and
+    // neither Sigma nor the y row's quadratic form takes a term from them.  Their rescaling is not issued (SHO-20: g = 3 of three tiles, 6 v_mul_f64 per window).
+    auto pad_reg = [](int I, int g) constexpr { return I == NB - 1 && g > KL; };
     [[maybe_unused]] auto rescale_tile = [&](int I, int Jc, const double (&row)[4]) __attribute__((always_inline)) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
+            if (pad_reg(I, g)) continue;
             T[tix(I, Jc)][g] *= row[g] * ckcl[Jc];
             if (!(KL == 0 && I == NB - 1 && Jc == NB - 1)) asm volatile("" : "+v"(T[tix(I, Jc)][g]));   // formed HERE (KL = 0: nothing reads that tile, it stays dead)
         }
@@ -420,7 +428,11 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
         }
         {
             const double s2n = sw.ck[16 * NB + c16];
-            const double dg = k * KW + c16 < N ? suma + (has_nu ? nu * s2n : s2n) : 1.0;   // :92; padded steps of the last window: D = 1
+            double dg = suma + (has_nu ? nu * s2n : s2n);   // :92
+            // padded steps of the last, ragged window: D = 1.  The wave-uniform test of the fix-up of V^' above and a lane mask formed before the loop (round 10; as a
+            // per-lane test of the step in EVERY window: a 64-bit vector compare, an exec mask and a branch around the diagonal.  As a branch under k == k_ragged the
+            // compiler peels the loop and the headline instantiation spills two scalar registers)
+            dg = (k == k_ragged && pad_lane) ? 1.0 : dg;
 #pragma unroll
             for (int g = 0; g < 4; ++g) sw.scr[(4 * g + q) * 16 + c16] = ((on_diag && g == gd) ? dg : apre[g]) - G[g];
         }
@@ -533,7 +545,8 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
             for (int I = Jc; I < NB; ++I) {
                 if constexpr (!PRE) {
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) T[tix(I, Jc)][g] *= ck_row(I, g) * ckc;
+                    for (int g = 0; g < 4; ++g)
+                        if (!pad_reg(I, g)) T[tix(I, Jc)][g] *= ck_row(I, g) * ckc;      // (the padding registers stay as they are: rescale_tile)
                 }
 #pragma unroll
                 for (int ks = 0; ks < 4; ++ks) T[tix(I, Jc)] = __builtin_amdgcn_mfma_f64_16x16x4f64(yt[I][ks], ysc[ks], T[tix(I, Jc)], 0, 0, 0);

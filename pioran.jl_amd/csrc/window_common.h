@@ -37,7 +37,9 @@ __host__ __device__ inline int64_t block_rec_doubles(int NB, int J) { return ((3
 // with j < n is left-over Sigma (the readers mask it).
 // One elimination step with the NEXT pivot's multiplier chain spread between the rank-1 updates of this step, which do not depend on it: the
 // wavefront issues in order, so the order of the instructions is the schedule.  `mult` is this step's multiplier (ldl_mult_of, device_util.h), on return the next step's; D_P stays
-// in m[P] of lane P.  The steps themselves are ldl_step_fused<P> (ldl_steps.inc through device_util.h).
+// in m[P] of lane P.  The steps themselves are ldl_step_fused<P> (ldl_steps.inc through device_util.h).  Step 14 is its one update and leaves `mult` alone (round 10):
+// pivot 15 eliminates nothing, step 15 is empty, and no caller (celerite_tile.hip forward and reverse, celerite_block.hip, dense.hip gj_sweep) reads `mult` behind the
+// last step — after ldl_step<14> it still holds pivot 14's multiplier, not pivot 15's.
 template <int P>
 __device__ __forceinline__ void ldl_step(double (&m)[16], double& mult, int c16)
 {
