@@ -66,9 +66,15 @@ struct TileWave {                  // LDS of one wavefront
 // The contraction is a GEMM — out[draw][(window, pair)] = sum over (t, cos | sin) of coef[draw][(t, cos | sin)] E[(t, cos | sin)][(window, pair)],
 // 4096 x 2 J x 80 000 at the bench shape — on v_mfma_f64_16x16x4_f64: a wavefront owns 16 draws (their coefficients as A operands in 2 JQ registers for
 // the whole launch) and walks kPairWin windows x 8 tiles of 16 pairs; per tile JQ 16-byte table reads per lane (cos and sin of one term: both halves feed a
-// matrix instruction), 2 JQ matrix instructions, one 32-byte store per lane (128 contiguous bytes per draw).  JQ = ceil(J / 4), compile-time.
+// matrix instruction), 2 JQ matrix instructions, and the tile's 32 bytes per lane into the wavefront's own LDS scratch (16 draw rows x 1 KB).  After the eight
+// tiles of a window the scratch is read back row-major and leaves in sixteen store instructions, each ONE draw's whole 1 KB window row (64 lanes x 16
+// contiguous bytes: eight whole 128-byte lines), and the first fragments of the next window are fetched before that read-back so that they are on their
+// way across it (round 11, docs/EXPERIMENTS.md section 33: 0.760 -> 0.611 ms at the bench shape; before, a store instruction wrote four 16-byte pieces at a
+// 32-byte stride in each of sixteen rows, and no line whole).  The scratch (66 560 bytes per workgroup) holds two workgroups on a CU.  JQ = ceil(J / 4), compile-time.
 // (Vector forms of round 5, removed in round 6: 0.93 ms per 4096 draws at 20 terms with the table in registers, 1.97 ms at 40 terms with the coefficients in LDS.)
 constexpr int kPairWin = 5;
+constexpr int kPairRow = 128 + 2;  // doubles per draw row of the scratch: the 16 rows of a 32-byte write then fall on different banks
+typedef double d2v __attribute__((ext_vector_type(2)));
 template <int JQ>
 __global__ void __launch_bounds__(256) tile_pairs_mfma_kernel(const ScanParams p, const double* __restrict__ btab, int64_t rsb, int64_t tsp, double* __restrict__ out)
 {
@@ -79,8 +85,9 @@ __global__ void __launch_bounds__(256) tile_pairs_mfma_kernel(const ScanParams p
     if (b0 >= p.B) return;                         // (no workgroup-level synchronisation in this kernel)
     const int64_t draw = b0 + li < p.B ? b0 + li : p.B - 1;
     // The PAIRS are the rows of the product (table entries as A operands), the draws its columns (coefficients as B operands), and row r of a tile is
-    // pair 4 (r & 3) + (r >> 2): result register g of lane (lk, li) is then pair 4 lk + g of draw li — four ADJACENT pairs, one 32-byte store per
-    // lane and tile (up to round 5 the draws were the rows: four 8-byte stores per lane; the kernel is bound by its 2.6 GB of stores).
+    // pair 4 (r & 3) + (r >> 2): result register g of lane (lk, li) is then pair 4 lk + g of draw li — four ADJACENT pairs, 32 contiguous bytes of
+    // the scratch per lane and tile (up to round 5 the draws were the rows: four 8-byte stores per lane; rounds 6 to 10 stored those 32 bytes to the
+    // workspace as they stood; the kernel is bound by its 2.6 GB of stores).
     double aop[JQ], bop[JQ];
     int toff[JQ];
 #pragma unroll
@@ -90,23 +97,46 @@ __global__ void __launch_bounds__(256) tile_pairs_mfma_kernel(const ScanParams p
         bop[q] = t < J ? p.Bc[draw * J + t] : 0.0;
         toff[q] = (t < J ? t : J - 1) * 128 + 4 * (li & 3) + (li >> 2);
     }
-    const bool live = b0 + li < p.B;
-    double* orow = out + (b0 + li) * NW * 128 + 4 * lk;
     const int64_t k0 = (int64_t)blockIdx.x * kPairWin, k1 = k0 + kPairWin < NW ? k0 + kPairWin : NW;
-    for (int64_t k = k0; k < k1; ++k) {
+    // The scratch belongs to this wavefront alone: the LDS executes a wavefront's operations in order, so between its writes and its read-back only the
+    // compiler's order has to be kept (PIORAN_LDS_ORDER) — no barrier, no counter wait beyond the one the read's own result needs.
+    __shared__ __attribute__((aligned(16))) double scr_[4][16 * kPairRow];
+    double* wr = scr_[w] + li * kPairRow + 4 * lk;       // write: draw row li, pairs 4 lk .. 4 lk + 3 of the tile
+    const double* rd = scr_[w] + 2 * lane;               // read-back i: draw row i, pairs 2 lane, 2 lane + 1 of the window
+    double* orow = out + b0 * NW * 128 + 2 * lane;       // ... and that row's place in the workspace; row b0 + i exists only if b0 + i < B
+    const int64_t rstep = NW * 128;
+    auto load_e = [&](double2 (&e)[JQ], int64_t k, int pt) __attribute__((always_inline)) {
         const double2* E = reinterpret_cast<const double2*>(btab + k * rsb + tsp);
+#pragma unroll
+        for (int q = 0; q < JQ; ++q) e[q] = E[toff[q] + 16 * pt];
+    };
+    double2 e[JQ];
+    load_e(e, k0, 0);
+    for (int64_t k = k0; k < k1; ++k) {
 #pragma unroll 2
         for (int pt = 0; pt < 8; ++pt) {
-            double2 e[JQ];
-#pragma unroll
-            for (int q = 0; q < JQ; ++q) e[q] = E[toff[q] + 16 * pt];
             d4 acc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
             for (int q = 0; q < JQ; ++q) {
                 acc = __builtin_amdgcn_mfma_f64_16x16x4f64(e[q].x, aop[q], acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f64_16x16x4f64(e[q].y, bop[q], acc, 0, 0, 0);
             }
-            if (live) *reinterpret_cast<d4*>(orow + k * 128 + 16 * pt) = acc;
+            {   // the next tile's fragments (the last tile of the last window fetches itself again: nothing past the table is read)
+                const bool last = pt == 7 && k + 1 == k1;
+                load_e(e, pt == 7 && !last ? k + 1 : k, last ? 7 : (pt + 1) & 7);
+            }
+            *reinterpret_cast<d2v*>(wr + 16 * pt) = d2v{acc[0], acc[1]};
+            *reinterpret_cast<d2v*>(wr + 16 * pt + 2) = d2v{acc[2], acc[3]};
+        }
+        PIORAN_LDS_ORDER();
+#pragma unroll
+        for (int i0 = 0; i0 < 16; i0 += 4) {             // (as compiled each read sits behind its row's test; four reads in front of four stores measured the same)
+#pragma unroll
+            for (int i = i0; i < i0 + 4; ++i) {
+                const d2v v = *reinterpret_cast<const d2v*>(rd + i * kPairRow);
+                if (b0 + i < p.B) *reinterpret_cast<d2v*>(orow + i * rstep + k * 128) = v;
+            }
+            PIORAN_LDS_ORDER();
         }
     }
 }
