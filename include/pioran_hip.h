@@ -472,7 +472,8 @@ int pioran_psd_check_summary(pioran_ctx* ctx, int64_t B, int model, int64_t n_co
                              int64_t F, const double* freq, int normalise, int times_f, int64_t Q, const double* probs,
                              double* quant, double* mean, double* meta, int32_t* status, int32_t* kept);
 /* Name of the kernel configuration a large batch with R active rows (all terms with both rows when R is even) runs on;
- * R == 0: the configuration the calling thread's last throughput-layout launch actually ran on; R < 0: the kernel FAMILY of the
+ * R == 0: the kernel instantiation the calling thread's last step-by-step launch (throughput or latency layout) actually ran on, as
+ * pioran_step_route names it; R < 0: the kernel FAMILY of the
  * calling thread's last launch — "tile" (windowed form, one draw per wavefront: large batches from 49 rows on and batch sizes between the
  * passes of the throughput layouts), "block" (windowed kernel), "block+pd" (with per-draw rows), "block (per-draw tables)", "wide"
  * (latency layout), "scan" (throughput layouts), "fallback", "block (windowed gradient[, per-draw tables])",
@@ -522,6 +523,20 @@ int pioran_value_route_cd(int32_t n_two_row_terms, int32_t n_one_row_terms, int3
  * tests/test_gpu_entry_route.py holds the calls to it. */
 int pioran_entry_route(const char* entry, int32_t R, int32_t J, int32_t n_one_row_terms, int64_t B, int per_draw, int shift, int want_c, int want_d,
                        int series_grads, const char* options, char* name, int name_len, int64_t* chunk_cap, int* shrink);
+/* Diagnostics (no GPU needed): one level below the families — the kernel instantiation a step-by-step launch runs.  family = "scan": the throughput
+ * layout (csrc/route.hip scan_plan) for R active rows, standard_rows the row map's kind (0: any; 1: every term has both rows; 2: n_complex two-row
+ * terms, then one-row terms), B draws, shared_table != 0: the draws share a table, npd_rows per-draw rows beside it.  family = "value", "store",
+ * "simulate" or "gradient": the latency layout's modes (wide_plan) — log-likelihood, factor store of the prediction, simulation, reverse mode — for
+ * R rows, npd_rows per-draw rows, per_draw_tables != 0: a table per draw (standard_rows, n_complex, B and shared_table are not read).  `name`
+ * receives what pioran_celerite_config_name(0) reports after that launch: the throughput configuration's name with "+win3" on the three-step form
+ * ("rpl2_cbr1_nsrc16_p+win3"); "wide_rpl<rows per lane>" (celerite_wide_kernel) or "wide2_rpl<rows per lane>[_y]" (the lean kernel[, y as a
+ * vector]), the gradient with "+adjoint" / "+adjoint2" for its reverse pass; "none" where the family refuses (PIORAN_ERR_UNSUPPORTED).  plan, where not
+ * NULL, receives 8 integers — scan: {index of the configuration in csrc/scan_configs.h or -1, steps per pass (1, 2, 3), shared table, per-draw rows,
+ * y as a vector, pairs per block of the block layout, 1 if celerite_scan.hip holds a kernel for the plan, rows the configuration holds}; latency modes:
+ * {rows per lane, lean forward kernel, y as a vector, lean reverse pass, 0 ...}.  options, name, PIORAN_ERR_ARG: as for pioran_value_route; also an
+ * unknown family.  tests/test_route.py holds the rules, tests/test_gpu_step_route.py the launches to them. */
+int pioran_step_route(const char* family, int32_t R, int32_t standard_rows, int32_t n_complex, int64_t B, int shared_table, int32_t npd_rows,
+                      int per_draw_tables, const char* options, char* name, int name_len, int32_t* plan);
 /* Diagnostics: the FP64 FMA rate (TFLOP/s) the device sustains right now with `waves_per_simd` (1 .. 8) wavefronts on every SIMD — about
  * `ms` milliseconds of a pure stream of independent v_fma_f64, event-timed on the context's stream.  The measured ceiling of any FP64
  * vector kernel on this box at that occupancy (the 78.6 TFLOP/s vendor figure assumes one FMA per SIMD every 4 cycles at 2.4 GHz).

@@ -930,6 +930,35 @@ int pioran_entry_route(const char* entry, int32_t R, int32_t J, int32_t n_one_ro
     return plan.rc;
 }
 
+int pioran_step_route(const char* family, int32_t R, int32_t standard_rows, int32_t n_complex, int64_t B, int shared_table, int32_t npd_rows,
+                      int per_draw_tables, const char* options, char* name, int name_len, int32_t* plan)
+{
+    if (!family || R < 1 || standard_rows < 0 || standard_rows > 2 || n_complex < 0 || B < 1 || npd_rows < 0 || !name || name_len < 1) return PIORAN_ERR_ARG;
+    ScanOptions opt{};
+    if (const int rc = parse_options(options, opt)) return rc;
+    int32_t fields[8] = {};
+    int rc = PIORAN_OK;
+    if (!std::strcmp(family, "scan")) {
+        const ScanPlan sp = scan_plan({R, standard_rows, n_complex, B, shared_table != 0, npd_rows, &opt});
+        scan_plan_name(sp, name, (size_t)name_len);
+        const int32_t f[8] = {sp.config, sp.form, sp.shared_tab, sp.mixed, sp.ycol, sp.npb, pioran_scan_kernel_exists(sp), sp.config < 0 ? 0 : kScanConfigs[sp.config].capacity()};
+        std::memcpy(fields, f, sizeof(f));
+        rc = sp.config < 0 ? PIORAN_ERR_UNSUPPORTED : PIORAN_OK;
+    } else {
+        static const char* const modes[4] = {"value", "store", "simulate", "gradient"};
+        int m = 0;
+        while (m < 4 && std::strcmp(family, modes[m])) ++m;
+        if (m == 4) return PIORAN_ERR_ARG;
+        const WidePlan wp = wide_plan((WideMode)m, R, npd_rows, per_draw_tables != 0, &opt);
+        wide_plan_name(wp, (WideMode)m, name, (size_t)name_len);
+        const int32_t f[8] = {wp.rpl, wp.lean, wp.ycol, wp.lean_adjoint};
+        std::memcpy(fields, f, sizeof(f));
+        rc = wp.rc;
+    }
+    if (plan) std::memcpy(plan, fields, sizeof(fields));
+    return rc;
+}
+
 extern "C" {
 
 const char* pioran_strerror(int code)
@@ -2816,7 +2845,7 @@ int pioran_psd_check_summary(pioran_ctx* ctx, int64_t B, int model, int64_t n_co
 const char* pioran_celerite_config_name(int64_t R)
 {
     if (R < 0) return g_last_kernel;                 // kernel family of the calling thread's last launch: block, block+pd, wide, scan, fallback
-    if (R <= 0) return pioran_scan_config_name(0);   // what the calling thread's last throughput-layout launch ran on
+    if (R <= 0) return pioran_scan_config_name(0);   // what the calling thread's last step-by-step launch (throughput or latency layout) ran on
     if (R > pioran_wide_supported_rows()) return "fallback";
     if (R > pioran_scan_supported_rows()) return "wide";   // 80 .. 143 rows: the lean latency kernel (80 with a shared table and a large batch: the scan)
     return pioran_scan_config_name((int)R);

@@ -31,10 +31,13 @@
 // celerite_adjoint_kernel below, which walks the recurrence backwards and returns the gradient of log L.
 #include "common.h"
 #include "device_util.h"
+#include "route.h"
 
+#include <array>
 #include <cmath>
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 
 // Diagnostic hooks: compiled out in the product; tools/wide_probe.hip defines them to s_memtime accumulators.
 #ifndef PIORAN_WSTAMP
@@ -98,8 +101,6 @@ __device__ __forceinline__ void describe_slots(const ScanParams& p, int64_t b, i
         }
     }
 }
-
-constexpr int kWideMaxRecord = 512;   // staged doubles per step: two per thread
 
 // MODE 0: log-likelihood.  MODE 1: the same, and the factor goes to HBM (W_n, D_n, forward-solved z_n per step) for the
 // backward sweep of the prediction path (celerite_predict.hip).  MODE 2: simulation — the extra row carries
@@ -1488,66 +1489,46 @@ int pioran_wide_supported_rows_grad() { return 143; }
 // Batches up to this size take the latency layout (at most one workgroup per CU on the chip's 256 CUs).
 int64_t pioran_wide_max_batch() { return 256; }
 
+// The kernels by rows per lane: one table per kernel template and mode, over the rows per lane that template is built for.  The plan (route.h wide_plan)
+// says which template and which entry a launch runs.
+using WideKernel = void (*)(ScanParams);
+template <int MODE> struct Wide { template <int RPL> static constexpr WideKernel kernel = celerite_wide_kernel<RPL, MODE>; };
+template <bool YC, int MODE> struct Wide2 { template <int RPL> static constexpr WideKernel kernel = celerite_wide2_kernel<RPL, YC, MODE>; };
+struct Replay { template <int RPL> static constexpr WideKernel kernel = celerite_replay_kernel<RPL>; };
+struct Adjoint { template <int RPL> static constexpr WideKernel kernel = celerite_adjoint_kernel<RPL>; };
+struct Adjoint2 { template <int RPL> static constexpr WideKernel kernel = celerite_adjoint2_kernel<RPL>; };
+
+template <class K, int FIRST, int... I>
+constexpr std::array<WideKernel, sizeof...(I)> kernel_table(std::integer_sequence<int, I...>) { return {K::template kernel<FIRST + I>...}; }
+
+// K's kernel for `rpl` rows per lane, FIRST <= rpl <= LAST (nullptr outside)
+template <class K, int FIRST, int LAST>
+static WideKernel kernel_at(int rpl)
+{
+    static constexpr auto table = kernel_table<K, FIRST>(std::make_integer_sequence<int, LAST - FIRST + 1>{});
+    return rpl >= FIRST && rpl <= LAST ? table[rpl - FIRST] : nullptr;
+}
+
+// the forward kernel of a plan: celerite_wide_kernel up to 6 rows per lane (95 rows); the lean one for the value at every size (y as a vector: 48 ..
+// 128 rows), for the gradient from 4 rows per lane on, for store and simulate from 5
+template <int MODE>
+static WideKernel forward_kernel(const WidePlan& plan)
+{
+    constexpr int first_lean = MODE == 0 ? 1 : (MODE == 3 ? 4 : 5);
+    if constexpr (MODE == 0)
+        if (plan.ycol) return kernel_at<Wide2<true, 0>, 3, 8>(plan.rpl);
+    return plan.lean ? kernel_at<Wide2<false, MODE>, first_lean, 9>(plan.rpl) : kernel_at<Wide<MODE>, 1, 6>(plan.rpl);
+}
+
 template <int MODE>
 static int launch_wide_mode(const ScanParams& p, hipStream_t stream)
 {
-    if (!p.tab || p.R > 143 || p.B <= 0 || p.B > 0x7fffffffLL) return PIORAN_ERR_UNSUPPORTED;
-    const dim3 grid((unsigned)p.B), block(256);
-    if constexpr (MODE == 0) {
-        // the lean form: from 48 rows on (tools/sweep_wide.py, N = 8192: R = 48 6.0 -> 5.7 ms, 80 9.1 -> 7.5, 94 9.4 -> 7.6; below
-        // that the register copies of celerite_wide_kernel are still cheaper: R = 40 4.8 vs 5.1 ms), or on request
-        const bool lean = (p.opt && p.opt->wide2) || (p.R >= 48 && !(p.opt && p.opt->no_wide2));
-        if (lean || p.R > 95 || p.tab_draw_stride != 0) {
-            if (p.R % 16 == 0 && p.R >= 48 && p.npd_rows == 0) {   // exactly 16 RPL rows: y as a vector, one row per lane less
-                switch (p.R / 16) {
-                case 3: hipLaunchKernelGGL((celerite_wide2_kernel<3, true>), grid, block, 0, stream, p); break;
-                case 4: hipLaunchKernelGGL((celerite_wide2_kernel<4, true>), grid, block, 0, stream, p); break;
-                case 5: hipLaunchKernelGGL((celerite_wide2_kernel<5, true>), grid, block, 0, stream, p); break;
-                case 6: hipLaunchKernelGGL((celerite_wide2_kernel<6, true>), grid, block, 0, stream, p); break;
-                case 7: hipLaunchKernelGGL((celerite_wide2_kernel<7, true>), grid, block, 0, stream, p); break;
-                default: hipLaunchKernelGGL((celerite_wide2_kernel<8, true>), grid, block, 0, stream, p); break;
-                }
-                return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;
-            }
-            switch ((p.R + 1 + 15) / 16) {
-            case 1: hipLaunchKernelGGL(celerite_wide2_kernel<1>, grid, block, 0, stream, p); break;
-            case 2: hipLaunchKernelGGL(celerite_wide2_kernel<2>, grid, block, 0, stream, p); break;
-            case 3: hipLaunchKernelGGL(celerite_wide2_kernel<3>, grid, block, 0, stream, p); break;
-            case 4: hipLaunchKernelGGL(celerite_wide2_kernel<4>, grid, block, 0, stream, p); break;
-            case 5: hipLaunchKernelGGL(celerite_wide2_kernel<5>, grid, block, 0, stream, p); break;
-            case 6: hipLaunchKernelGGL(celerite_wide2_kernel<6>, grid, block, 0, stream, p); break;
-            case 7: hipLaunchKernelGGL(celerite_wide2_kernel<7>, grid, block, 0, stream, p); break;
-            case 8: hipLaunchKernelGGL(celerite_wide2_kernel<8>, grid, block, 0, stream, p); break;
-            default: hipLaunchKernelGGL(celerite_wide2_kernel<9>, grid, block, 0, stream, p); break;
-            }
-            return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;
-        }
-    }
-    if constexpr (MODE == 1 || MODE == 2) {
-        // store / simulate on the lean kernel: 96 .. 143 rows (round 4), and from 64 rows on (where the windowed kernels end) unless `no_wide2`
-        if (p.tab_draw_stride == 0 && p.npd_rows == 0 && (p.R > 95 || (p.R >= 64 && !(p.opt && p.opt->no_wide2)))) {
-            switch ((p.R + 1 + 15) / 16) {
-            case 5: hipLaunchKernelGGL((celerite_wide2_kernel<5, false, MODE>), grid, block, 0, stream, p); break;
-            case 6: hipLaunchKernelGGL((celerite_wide2_kernel<6, false, MODE>), grid, block, 0, stream, p); break;
-            case 7: hipLaunchKernelGGL((celerite_wide2_kernel<7, false, MODE>), grid, block, 0, stream, p); break;
-            case 8: hipLaunchKernelGGL((celerite_wide2_kernel<8, false, MODE>), grid, block, 0, stream, p); break;
-            default: hipLaunchKernelGGL((celerite_wide2_kernel<9, false, MODE>), grid, block, 0, stream, p); break;
-            }
-            return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;
-        }
-    }
-    if (p.tab_draw_stride != 0) return PIORAN_ERR_UNSUPPORTED;   // per-draw tables: celerite_wide2_kernel (log-likelihood) only
-    if (3 * (p.R + 2) + 2 + 3 * p.npd_rows > kWideMaxRecord) return PIORAN_ERR_UNSUPPORTED;   // staged record too long
-    if (p.R <= 15) hipLaunchKernelGGL((celerite_wide_kernel<1, MODE>), grid, block, 0, stream, p);
-    else if (p.R <= 31) hipLaunchKernelGGL((celerite_wide_kernel<2, MODE>), grid, block, 0, stream, p);
-    else if (p.R <= 47) hipLaunchKernelGGL((celerite_wide_kernel<3, MODE>), grid, block, 0, stream, p);
-    else if (p.R <= 63) hipLaunchKernelGGL((celerite_wide_kernel<4, MODE>), grid, block, 0, stream, p);
-    else if (p.R <= 79) hipLaunchKernelGGL((celerite_wide_kernel<5, MODE>), grid, block, 0, stream, p);
-    else if (p.R <= 95) {
-        hipLaunchKernelGGL((celerite_wide_kernel<6, MODE>), grid, block, 0, stream, p);
-    } else {
-        return PIORAN_ERR_UNSUPPORTED;   // 96 .. 143 rows: celerite_wide2_kernel above (log-likelihood only)
-    }
+    if (!p.tab || p.B <= 0 || p.B > 0x7fffffffLL) return PIORAN_ERR_UNSUPPORTED;
+    const WidePlan plan = wide_plan((WideMode)MODE, p.R, p.npd_rows, p.tab_draw_stride != 0, p.opt);
+    const WideKernel kernel = plan.rc == PIORAN_OK ? forward_kernel<MODE>(plan) : nullptr;
+    if (!kernel) return PIORAN_ERR_UNSUPPORTED;
+    pioran_note_wide_launch(plan, (WideMode)MODE);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)p.B), dim3(256), 0, stream, p);
     return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;
 }
 
@@ -1593,10 +1574,14 @@ size_t pioran_grad_workspace_doubles(int64_t B, int64_t N, int32_t R)
 int pioran_launch_scan_wide_grad(ScanParams p, double* work, double* grad_a, double* grad_b, double* grad_c, double* grad_d,
                                  double* grad_nu, double* grad_mu, hipStream_t stream, hipStream_t aux, hipEvent_t* ev)
 {
-    if (!p.tab || p.R > 143 || p.npd_rows || p.B <= 0 || p.B > 0x7fffffffLL || !grad_a || !grad_b) return PIORAN_ERR_UNSUPPORTED;
-    const int rpl = rpl_of(p.R), ns = 16 * rpl;
+    if (!p.tab || p.B <= 0 || p.B > 0x7fffffffLL || !grad_a || !grad_b) return PIORAN_ERR_UNSUPPORTED;
+    const WidePlan plan = wide_plan(WideMode::gradient, p.R, p.npd_rows, false, p.opt);
+    if (plan.rc != PIORAN_OK) return plan.rc;
+    const int rpl = plan.rpl, ns = 16 * rpl;
+    const WideKernel forward = forward_kernel<3>(plan), replay = kernel_at<Replay, 1, 9>(rpl);
+    const WideKernel adjoint = plan.lean_adjoint ? kernel_at<Adjoint2, 1, 9>(rpl) : kernel_at<Adjoint, 1, 9>(rpl);
+    if (!forward || !replay || !adjoint) return PIORAN_ERR_UNSUPPORTED;
     p.exp = p.opt ? p.opt->exp : 0;
-    if (3 * (p.R + 2) + 2 + 3 * p.npd_rows + ns + 1 > (rpl >= 7 ? 768 : kWideMaxRecord)) return PIORAN_ERR_UNSUPPORTED;
     const size_t sp = (size_t)((rpl * rpl + 1) & ~1), nstate = (size_t)(rpl * rpl + 3 * rpl + 4);
     const int K = grad_ckpt_every(p.N);
     const size_t nck = (size_t)((p.N - 1) / K + 1), B = (size_t)p.B, BN = B * (size_t)p.N;
@@ -1613,61 +1598,37 @@ int pioran_launch_scan_wide_grad(ScanParams p, double* work, double* grad_a, dou
     p.g_c = p.g_d + B * ns;
     p.g_scal = p.g_c + B * ns;
     const dim3 grid((unsigned)p.B), block(256);
-    auto run = [&](auto Rc) {
-        constexpr int RPL = decltype(Rc)::value;
-        // the lean reverse pass (celerite_adjoint2_kernel): always from 7 rows per lane on; below, by option (wide2 = 1: on, no_wide2: off)
-        const bool lean = RPL >= 7 || (RPL >= 4 && !(p.opt && p.opt->no_wide2)) || (p.opt && p.opt->wide2);
-        if constexpr (RPL >= 7) {
-            hipLaunchKernelGGL((celerite_wide2_kernel<RPL, false, 3>), grid, block, 0, stream, p);
-        } else if constexpr (RPL >= 4) {   // (64 .. 95 rows: the lean forward kernel is the faster one, 9.0 against 13.1 ms at 80 rows)
-            if (lean) hipLaunchKernelGGL((celerite_wide2_kernel<RPL, false, 3>), grid, block, 0, stream, p);
-            else hipLaunchKernelGGL((celerite_wide_kernel<RPL, 3>), grid, block, 0, stream, p);
-        } else {
-            hipLaunchKernelGGL((celerite_wide_kernel<RPL, 3>), grid, block, 0, stream, p);
-        }
-        // reverse pass, last segment first; segment k holds steps k K + 1 .. min((k + 1) K, N - 1); the first segment's
-        // adjoint launch also takes step 0
-        const int64_t nseg = (p.N - 1 + K - 1) / K;
-        ScanParams q = p;
-        q.seg_first = 1;
-        if (nseg == 0) {                               // N = 1
-            q.seg_n0 = 0; q.seg_hi = 0; q.seg_lo = 0;
-            if (lean) hipLaunchKernelGGL(celerite_adjoint2_kernel<RPL>, grid, block, 0, stream, q);
-            else hipLaunchKernelGGL(celerite_adjoint_kernel<RPL>, grid, block, 0, stream, q);
-        }
-        // events: ev[0] forward done; ev[1 + (k & 1)] replay of segment k done; ev[3 + (k & 1)] adjoint of segment k done
-        hipStream_t rs = aux ? aux : stream;
+    pioran_note_wide_launch(plan, WideMode::gradient);
+    hipLaunchKernelGGL(forward, grid, block, 0, stream, p);
+    // reverse pass, last segment first; segment k holds steps k K + 1 .. min((k + 1) K, N - 1); the first segment's
+    // adjoint launch also takes step 0
+    const int64_t nseg = (p.N - 1 + K - 1) / K;
+    ScanParams q = p;
+    q.seg_first = 1;
+    if (nseg == 0) {                               // N = 1
+        q.seg_n0 = 0; q.seg_hi = 0; q.seg_lo = 0;
+        hipLaunchKernelGGL(adjoint, grid, block, 0, stream, q);
+    }
+    // events: ev[0] forward done; ev[1 + (k & 1)] replay of segment k done; ev[3 + (k & 1)] adjoint of segment k done
+    hipStream_t rs = aux ? aux : stream;
+    if (aux) {
+        (void)hipEventRecord(ev[0], stream);
+        (void)hipStreamWaitEvent(aux, ev[0], 0);
+    }
+    for (int64_t k = nseg - 1; k >= 0; --k) {
+        q.seg_n0 = k * K;
+        q.seg_hi = (k + 1) * K < p.N - 1 ? (k + 1) * K : p.N - 1;
+        q.seg_lo = k == 0 ? 0 : q.seg_n0 + 1;
+        q.st_s = p.st_s + (size_t)(k & 1) * seg_doubles;
+        if (aux && k + 2 <= nseg - 1) (void)hipStreamWaitEvent(aux, ev[3 + (k & 1)], 0);   // its buffer was read by segment k + 2
+        hipLaunchKernelGGL(replay, grid, block, 0, rs, q);
         if (aux) {
-            (void)hipEventRecord(ev[0], stream);
-            (void)hipStreamWaitEvent(aux, ev[0], 0);
+            (void)hipEventRecord(ev[1 + (k & 1)], aux);
+            (void)hipStreamWaitEvent(stream, ev[1 + (k & 1)], 0);
         }
-        for (int64_t k = nseg - 1; k >= 0; --k) {
-            q.seg_n0 = k * K;
-            q.seg_hi = (k + 1) * K < p.N - 1 ? (k + 1) * K : p.N - 1;
-            q.seg_lo = k == 0 ? 0 : q.seg_n0 + 1;
-            q.st_s = p.st_s + (size_t)(k & 1) * seg_doubles;
-            if (aux && k + 2 <= nseg - 1) (void)hipStreamWaitEvent(aux, ev[3 + (k & 1)], 0);   // its buffer was read by segment k + 2
-            hipLaunchKernelGGL(celerite_replay_kernel<RPL>, grid, block, 0, rs, q);
-            if (aux) {
-                (void)hipEventRecord(ev[1 + (k & 1)], aux);
-                (void)hipStreamWaitEvent(stream, ev[1 + (k & 1)], 0);
-            }
-            if (lean) hipLaunchKernelGGL(celerite_adjoint2_kernel<RPL>, grid, block, 0, stream, q);
-            else hipLaunchKernelGGL(celerite_adjoint_kernel<RPL>, grid, block, 0, stream, q);
-            if (aux) (void)hipEventRecord(ev[3 + (k & 1)], stream);
-            q.seg_first = 0;
-        }
-    };
-    switch (rpl) {
-    case 1: run(ic<1>{}); break;
-    case 2: run(ic<2>{}); break;
-    case 3: run(ic<3>{}); break;
-    case 4: run(ic<4>{}); break;
-    case 5: run(ic<5>{}); break;
-    case 6: run(ic<6>{}); break;    // 80 .. 95 rows (SHO-40, the dense configuration's model): round 3
-    case 7: run(ic<7>{}); break;    // 96 .. 143 rows (the reference grid's j = 64 is 128): round 4
-    case 8: run(ic<8>{}); break;
-    default: run(ic<9>{}); break;
+        hipLaunchKernelGGL(adjoint, grid, block, 0, stream, q);
+        if (aux) (void)hipEventRecord(ev[3 + (k & 1)], stream);
+        q.seg_first = 0;
     }
     hipLaunchKernelGGL(grad_finish_kernel, grid, block, 0, stream, p, ns, grad_a, grad_b, grad_c, grad_d, grad_nu, grad_mu);
     return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;

@@ -2,9 +2,13 @@
 // runtime call, no context, no data set.  capi.hip fills the query once per launch, asks the rules in the ladder's order (time-parallel, tile,
 // windowed, remainder split, scan / latency layout, fallback) and does the rest: tables, workspaces, streams, the launches.  Draws with (c, d) of
 // their own are planned before the ladder: mixed_plan where only a few terms differ between the draws, perdraw_form where the caller says all do.
-// The other batched entries (prediction, gradient, simulation, posterior draws) have one rule, entry_plan, at the end.
+// The other batched entries (prediction, gradient, simulation, posterior draws) have one rule, entry_plan.
+// One level down, the step-by-step families name the kernel instantiation a launch runs by the same kind of rule, at the end: scan_plan for the
+// throughput layout (celerite_scan.hip), wide_plan for the latency layout (celerite_wide.hip).  Those files look the plan's kernel up in a table
+// and launch it; they read no selection option themselves.  pioran_step_route names both plans without a GPU.
 #pragma once
 #include "common.h"
+#include "scan_configs.h"
 
 #include <functional>
 
@@ -87,3 +91,58 @@ EntryPlan entry_plan(Entry entry, int32_t R, int32_t J, int32_t npd_terms, int64
 // what pioran_celerite_config_name(-1) reports after the public entry's call with every resource granted (pioran_entry_route): the batch form's plan,
 // or — per_draw and the batch form refuses — the plan of the one-draw shared calls the entry falls back to.  rc PIORAN_ERR_ARG: no such entry
 EntryPlan entry_route(const char* entry, int32_t R, int32_t J, int64_t B, bool per_draw, int grad_flags, const ScanOptions& o);
+
+// ---- the step-by-step kernels' instantiations ----------------------------------------------------------------------------------------------------
+
+// A configuration of the throughput layout (scan_configs.h has the list)
+struct ScanConfig {
+    const char* name;
+    int rpl, cbr, nsrc, minw;
+    bool paired;
+    int npb;
+    bool ycol, autopick, preferred;
+    // real rows it holds: one slot carries y (unless ycol); a paired config with an odd block keeps one single slot per block
+    constexpr int capacity() const
+    {
+        const int rb = rpl * nsrc;
+        if (ycol) return cbr * (paired ? (rb & ~1) : rb);
+        return paired ? cbr * (rb & ~1) - ((rb & 1) ? 0 : 1) : rpl * cbr * nsrc - 1;
+    }
+};
+extern const ScanConfig kScanConfigs[kNumScanConfigs];
+
+// What the throughput layout's choice reads of a launch (ScanParams: R, standard_rows, n_complex, B, tab != nullptr, npd_rows, opt)
+struct ScanQuery {
+    int32_t R, standard_rows, n_complex;
+    int64_t B;
+    bool shared_tab;
+    int32_t npd_rows;
+    const ScanOptions* opt;   // nullptr: defaults
+};
+// The instantiation a launch runs: celerite_scan_kernel<rpl, cbr, nsrc, shared_tab, minw, paired, mixed, npb, form == 2, ycol, form == 3> of
+// configuration `config` (-1: none holds the rows — the launch is refused)
+struct ScanPlan {
+    int config = -1;
+    int form = 0;          // steps of the recurrence per pass over T: 1, 2 or 3
+    bool shared_tab = false, mixed = false, ycol = false;   // mixed: per-draw rows beside the shared table
+    int npb = 0;
+    const char* name() const { return config < 0 ? "none" : kScanConfigs[config].name; }
+};
+ScanPlan scan_plan(const ScanQuery& q);
+// what pioran_celerite_config_name(0) reports after the plan's launch: the configuration's name, "+win3" on the three-step form
+void scan_plan_name(const ScanPlan& plan, char* buf, size_t len);
+bool pioran_scan_kernel_exists(const ScanPlan& plan);   // celerite_scan.hip: its table holds a kernel for the plan
+
+// The latency layout: rows per lane; the forward kernel celerite_wide_kernel or the lean celerite_wide2_kernel, that one in its y-as-a-vector shape
+// or not; gradient: the reverse pass on celerite_adjoint_kernel or the lean celerite_adjoint2_kernel
+enum class WideMode { value, store, simulate, gradient };
+constexpr int kWideMaxRecord = 512;   // staged doubles per step of celerite_wide_kernel: two per thread
+struct WidePlan {
+    int rc = PIORAN_ERR_UNSUPPORTED;
+    int rpl = 0;
+    bool lean = false, ycol = false, lean_adjoint = false;
+};
+WidePlan wide_plan(WideMode mode, int32_t R, int32_t npd_rows, bool per_draw_tables, const ScanOptions* opt);
+// its name to pioran_celerite_config_name(0): "wide_rpl3", "wide2_rpl4", "wide2_rpl4_y"; gradient: "+adjoint" / "+adjoint2" behind the forward kernel's
+void wide_plan_name(const WidePlan& plan, WideMode mode, char* buf, size_t len);
+void pioran_note_wide_launch(const WidePlan& plan, WideMode mode);   // celerite_scan.hip pioran_scan_config_name(0): the thread's last launch was this one

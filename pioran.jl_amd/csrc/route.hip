@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 
 // The automatic choice between the windowed form with one draw per wavefront ("tile", 1) and the rest (0: step-by-step throughput layouts / the
@@ -410,4 +411,139 @@ EntryPlan entry_route(const char* entry, int32_t R, int32_t J, int64_t B, bool p
         B = 1;   // draw by draw (capi.hip each_draw)
     }
     return entry_plan((Entry)e, R, J, 0, B, false, grad_flags, o);
+}
+
+// ---- the step-by-step kernels' instantiations (route.h scan_plan, wide_plan) ----------------------------------------------------------------------
+
+#define PIORAN_SCAN_DESC(NAME, RPL, CBR, NSRC, MINW, PAIRED, NPB, YCOL, AUTOPICK, PREFERRED) {#NAME, RPL, CBR, NSRC, MINW, PAIRED, NPB, YCOL, AUTOPICK, PREFERRED},
+const ScanConfig kScanConfigs[kNumScanConfigs] = {PIORAN_SCAN_CONFIGS(PIORAN_SCAN_DESC)};
+#undef PIORAN_SCAN_DESC
+
+static const ScanOptions kDefaultOptions{};
+
+// y-as-a-vector shapes exist in the two-step form for launches without per-draw rows only
+static bool ycol_usable(const ScanConfig& c, const ScanQuery& q, const ScanOptions& o)
+{
+    if (!c.ycol) return true;
+    // (per-draw (c, d) launches evaluate the transcendentals in the kernel: at four rows per lane the two-step form then spills —
+    // 19.5 k instead of 42.8 k evaluations per second at j = 32 — so those keep the 80-row step-by-step shape)
+    return q.shared_tab && q.npd_rows == 0 && !o.no_win2;
+}
+
+// does the block layout of `c` hold this row structure?  (shared table, no per-draw rows)
+static bool blocked_fits(const ScanConfig& c, const ScanQuery& q)
+{
+    if (c.npb == 0) return true;
+    const int rb = c.rpl * c.nsrc, nsb = rb - 1 - 2 * c.npb;
+    return q.standard_rows == 2 && q.shared_tab && q.npd_rows == 0 && q.n_complex == c.npb * c.cbr && q.R - 2 * q.n_complex <= nsb * c.cbr;
+}
+
+// The configuration: the one "scan_config" names, where it holds the launch; else the block layout that fits the row structure; else the first
+// preferred one with room for the rows — or, on the standard row map, its paired variant
+static int scan_pick(const ScanQuery& q, const ScanOptions& o)
+{
+    const bool standard_rows = q.standard_rows == 1;
+    if (o.scan_config[0]) {
+        for (int i = 0; i < kNumScanConfigs; ++i) {
+            const ScanConfig& c = kScanConfigs[i];
+            if (!std::strcmp(o.scan_config, c.name) && c.capacity() >= q.R && (!c.paired || standard_rows) && blocked_fits(c, q) && ycol_usable(c, q, o))
+                return i;
+        }
+    }
+    if (!o.no_paired) {
+        for (int i = 0; i < kNumScanConfigs; ++i)
+            if (kScanConfigs[i].npb > 0 && kScanConfigs[i].autopick && blocked_fits(kScanConfigs[i], q)) return i;
+    }
+    int best = -1;
+    for (int i = 0; i < kNumScanConfigs && best < 0; ++i) {
+        const ScanConfig& c = kScanConfigs[i];
+        if (c.preferred && c.autopick && c.capacity() >= q.R && ycol_usable(c, q, o)) best = i;
+    }
+    if (standard_rows && !o.no_paired) {
+        // a paired variant of the same shape (or the smallest paired one that fits) wins when the row map allows it
+        for (int i = 0; i < kNumScanConfigs; ++i) {
+            const ScanConfig& c = kScanConfigs[i];
+            if (c.paired && c.npb == 0 && c.autopick && c.capacity() >= q.R && ycol_usable(c, q, o) &&
+                (best < 0 || c.rpl * c.cbr * c.nsrc <= kScanConfigs[best].rpl * kScanConfigs[best].cbr * kScanConfigs[best].nsrc))
+                return i;
+        }
+    }
+    return best;
+}
+
+ScanPlan scan_plan(const ScanQuery& q)
+{
+    const ScanOptions& o = q.opt ? *q.opt : kDefaultOptions;
+    ScanPlan plan;
+    plan.config = scan_pick(q, o);
+    if (plan.config < 0) return plan;
+    // Mid-size batches: up to 2048 draws the four-draws-per-wavefront shapes of this row range put at most one wavefront on
+    // half of the chip's 1024 SIMDs, and the launch takes as long as ONE wavefront needs for the series; two draws per
+    // wavefront (rpl2_cbr2_nsrc8: half the columns per lane) is then the faster walk (tools/sweep_midbatch.py, N = 1e4,
+    // R = 30: 4.2 instead of 5.3 ms for 768 .. 2048 draws; above 2048 draws the denser shape wins again: 5.3 vs 7.3 ms)
+    if (!o.scan_config[0] && q.B <= 2048 && q.R >= 24 && q.R <= 31 && kScanConfigs[plan.config].cbr == 1) plan.config = kScan_rpl2_cbr2_nsrc8;
+    const ScanConfig& c = kScanConfigs[plan.config];
+    plan.ycol = c.ycol;
+    plan.npb = c.npb;
+    plan.shared_tab = q.shared_tab;
+    plan.mixed = q.shared_tab && q.npd_rows > 0;   // (never with the y-as-a-vector shapes or the block layout: ycol_usable, blocked_fits)
+    // two-step form: faster wherever its working set fits the register file (tools/sweep_win2.py: RPL <= 3: +10 .. 24 %;
+    // RPL = 4: +4 .. 6 % with a few spilled registers); with RPL = 5 it loses 7 %, so there it runs only when forced
+    // (context option "win2")
+    plan.form = c.ycol || (c.rpl <= 4 && !o.no_win2) || o.win2 ? 2 : 1;
+    if (!c.ycol && c.npb == 0 && (c.rpl == 2 || c.rpl == 3)) {
+        // three-step form: measured faster where its row vectors fit the register file — two rows per lane from 13 source lanes on
+        // (R = 24 .. 31: 2 .. 6 % at B = 4096, tools/sweep_win3.py); with three rows per lane it spills (SHO-20: 18 % slower) and with
+        // one the extra row sums outweigh the saved scalings (10 .. 30 % slower): those run it only when the option asks
+        const bool auto3 = c.rpl == 2 && c.cbr == 1 && c.nsrc >= 13 && !(o.no_win3 || o.no_win2 || o.win2) && q.B > 2048;
+        if ((o.win3 || auto3) && q.shared_tab && q.npd_rows == 0) plan.form = 3;
+    }
+    return plan;
+}
+
+void scan_plan_name(const ScanPlan& plan, char* buf, size_t len) { std::snprintf(buf, len, "%s%s", plan.name(), plan.form == 3 ? "+win3" : ""); }
+
+// The latency layout's kernels (celerite_wide.hip), as they have been chosen since rounds 3 / 4 — the modes' rules differ, and each is kept as it is:
+//  value: the lean form from 48 rows on (tools/sweep_wide.py, N = 8192: R = 48 6.0 -> 5.7 ms, 80 9.1 -> 7.5, 94 9.4 -> 7.6; below that the register
+//   copies of celerite_wide_kernel are still cheaper: R = 40 4.8 vs 5.1 ms) unless `no_wide2`, on request (`wide2`), above 95 rows and with per-draw
+//   tables whatever the options say; in its y-as-a-vector shape at exactly 16 RPL rows, R % 16 == 0, from 48 rows on, without per-draw rows: one row
+//   per lane less;
+//  store / simulate: lean at 96 .. 143 rows (round 4), and from 64 rows on (where the windowed kernels end) unless `no_wide2` — only without per-draw
+//   tables and per-draw rows; `wide2` does NOT force the lean form here;
+//  gradient: the lean reverse pass (celerite_adjoint2_kernel) always from 7 rows per lane on, from 4 unless `no_wide2`, or on `wide2`; the lean FORWARD
+//   kernel only from 4 rows per lane, under the same condition (64 .. 95 rows: it is the faster one, 9.0 against 13.1 ms at 80 rows) — so `wide2` below
+//   4 rows per lane pairs celerite_wide_kernel with the lean reverse pass.
+// Refused: more than 143 rows; a step record longer than the kernels stage (kWideMaxRecord doubles; the gradient's, 768 from 7 rows per lane on); what
+// only the lean value kernel does — per-draw tables, more than 95 rows with per-draw rows — in another mode.
+WidePlan wide_plan(WideMode mode, int32_t R, int32_t npd_rows, bool per_draw_tables, const ScanOptions* opt)
+{
+    const ScanOptions& o = opt ? *opt : kDefaultOptions;
+    WidePlan plan;
+    if (R > 143) return plan;
+    plan.rpl = (R + 16) / 16;   // R + 1 slots, the y row's among them, 16 per row of the lanes
+    if (mode == WideMode::gradient) {
+        if (npd_rows != 0 || 3 * (R + 2) + 2 + 3 * npd_rows + 16 * plan.rpl + 1 > (plan.rpl >= 7 ? 768 : kWideMaxRecord)) return plan;
+        plan.lean_adjoint = plan.rpl >= 7 || (plan.rpl >= 4 && !o.no_wide2) || o.wide2;
+        plan.lean = plan.rpl >= 4 && plan.lean_adjoint;
+        plan.rc = PIORAN_OK;
+        return plan;
+    }
+    if (mode == WideMode::value) {
+        plan.lean = o.wide2 || (R >= 48 && !o.no_wide2) || R > 95 || per_draw_tables;
+        plan.ycol = plan.lean && R % 16 == 0 && R >= 48 && npd_rows == 0;
+        if (plan.ycol) plan.rpl = R / 16;
+    } else {
+        plan.lean = !per_draw_tables && npd_rows == 0 && (R > 95 || (R >= 64 && !o.no_wide2));
+    }
+    // celerite_wide_kernel: one shared table, up to 95 rows, the record staged in LDS
+    if (!plan.lean && (per_draw_tables || 3 * (R + 2) + 2 + 3 * npd_rows > kWideMaxRecord || R > 95)) return plan;
+    plan.rc = PIORAN_OK;
+    return plan;
+}
+
+void wide_plan_name(const WidePlan& plan, WideMode mode, char* buf, size_t len)
+{
+    if (plan.rc != PIORAN_OK) { std::snprintf(buf, len, "none"); return; }
+    std::snprintf(buf, len, "%s_rpl%d%s%s", plan.lean ? "wide2" : "wide", plan.rpl, plan.ycol ? "_y" : "",
+                  mode != WideMode::gradient ? "" : (plan.lean_adjoint ? "+adjoint2" : "+adjoint"));
 }

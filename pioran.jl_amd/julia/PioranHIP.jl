@@ -798,4 +798,24 @@ function predict_direct_hip(cov::SemiSeparable, τ::Vector{Float64}, t::Vector{F
     return with_covariance ? (μ, K) : μ
 end
 
+"""
+    step_route(family, R; standard_rows=0, n_complex=0, B=1, shared_table=true, npd_rows=0, per_draw_tables=false, options="")
+
+Diagnostics (no GPU needed): the kernel instantiation a step-by-step launch runs (`pioran_step_route`) — `family = "scan"` for the throughput
+layout, `"value"`, `"store"`, `"simulate"` or `"gradient"` for the latency layout's modes.  Returns `(name, plan)`: the name
+`pioran_celerite_config_name(0)` reports after such a launch (`nothing` where the family refuses) and the plan's eight integers
+(`include/pioran_hip.h`).
+"""
+function step_route(family::AbstractString, R::Integer; standard_rows::Integer=0, n_complex::Integer=0, B::Integer=1, shared_table::Bool=true,
+                    npd_rows::Integer=0, per_draw_tables::Bool=false, options::AbstractString="")
+    name = zeros(UInt8, 64)
+    plan = zeros(Int32, 8)
+    rc = ccall((:pioran_step_route, LIB), Cint,
+               (Cstring, Int32, Int32, Int32, Int64, Cint, Int32, Cint, Cstring, Ptr{UInt8}, Cint, Ptr{Int32}),
+               family, R, standard_rows, n_complex, B, shared_table, npd_rows, per_draw_tables, options, name, length(name), plan)
+    rc == -4 && return (nothing, plan)
+    check(rc)
+    return (GC.@preserve(name, unsafe_string(pointer(name))), plan)
+end
+
 end # module

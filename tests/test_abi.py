@@ -51,6 +51,8 @@ def test_argument_validation_without_gpu():
     assert L.pioran_celerite_logl_batch(None, 1, 1, None, None, None, None, 1, None, None, None, None, None, None) == -1
     assert L.pioran_celerite_logl_batch_dev(None, 1, None, None, None, None, None, None, None, None) == -1
     assert L.pioran_ctx_set_option(None, b"no_wide", b"1") == -1
+    assert L.pioran_step_route(None, 40, 1, 0, 1, 1, 0, 0, b"", ctypes.create_string_buffer(8), 8, None) == -1
+    assert L.pioran_step_route(b"scan", 40, 1, 0, 1, 1, 0, 0, b"", None, 0, None) == -1 and L.pioran_step_route(b"tile", 40, 1, 0, 1, 1, 0, 0, b"", ctypes.create_string_buffer(8), 8, None) == -1
     assert L.pioran_dense_nll_timed(None, 4, 1, None, None, None, None, None, None, None, None, None, None) == -1
 
 

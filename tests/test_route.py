@@ -1,9 +1,12 @@
 """CPU tests of the routing rules of the value path (csrc/route.hip) through pioran_value_route: the family the ladder of capi.hip's launch()
 takes when every resource is granted.  Routes the GPU tests already assert, transcribed; properties over a grid of ~89 000 queries; the
 time-parallel plans against the conditions pioran_launch_tp refuses on.  Likewise pioran_value_route_cd for draws with (c, d) of their own, and
-pioran_entry_route for the other batched entries (route.hip entry_plan) against the rules written out in entry_truth."""
+pioran_entry_route for the other batched entries (route.hip entry_plan) against the rules written out in entry_truth.  One level down,
+pioran_step_route (scan_plan, wide_plan: the kernel instantiation of a step-by-step launch) against the listing recorded before those rules
+existed, the names the GPU tests assert, and properties over the listing's grid."""
 import importlib.util
 import itertools
+import json
 from pathlib import Path
 
 import pytest
@@ -590,3 +593,149 @@ def test_entry_argument_validation():
     assert L.pioran_entry_route(b"grad", 40, 20, 0, 0, *args, None, name, 8, None, None) == -1
     assert L.pioran_entry_route(b"grad", 40, 20, 0, 8, *args, b"no_such_option=1", name, 8, None, None) == -1
     assert L.pioran_entry_route(b"grad", 40, 20, 0, 8, *args, None, None, 8, None, None) == -1
+
+
+# ---- the step-by-step kernels' instantiations: pioran_step_route (route.hip scan_plan, wide_plan) ---------------------------------------------------
+
+def _listing():
+    return json.loads((ROOT / "tests" / "golden" / "step_route_listing.json").read_text())
+
+
+def test_step_route_reproduces_the_listing_recorded_before_the_rules():
+    """tests/golden/step_route_listing.json: what the launch code of celerite_scan.hip / celerite_wide.hip chose before scan_plan / wide_plan existed
+    (tools/experiments/step_route_listing.py), over R = 1 .. 80 x row maps x batch classes x tables x options (scan) and R = 1 .. 144 x modes x
+    per-draw rows x per-draw tables x options (latency layout): the rules name the same instantiation for every entry."""
+    listing = _listing()
+    scan_keys, wide_keys = G.step_scan_keys(), G.step_wide_keys()
+    assert len(listing["scan"]) == len(scan_keys) and len(listing["wide"]) == len(wide_keys)
+    n = 0
+    for keys, held, answer, rows in ((scan_keys, listing["scan"], G.step_scan_answer, G.STEP_SCAN_ROWS),
+                                     (wide_keys, listing["wide"], G.step_wide_answer, G.STEP_WIDE_ROWS)):
+        for key in keys:
+            want = listing["answers"][held["|".join(map(str, key))]]
+            assert want[0][0] == rows[0] and want[-1][1] == rows[-1]
+            for first, last, a in want:
+                for R in range(first, last + 1):
+                    assert answer(key, R) == a, (key, R)
+                    n += 1
+    assert n == len(scan_keys) * 80 + len(wide_keys) * 144
+    # the DRWCelerite-20 shape is on the grid
+    assert G.step_n_complex(2, 60) == 20 and G.step_scan_answer((2, 2049, 1, 0, ""), 60)[0] == "rpl4_cbr4_nsrc4_b5a"
+
+
+# (rows, row map's kind, two-row terms first, B, options) -> what pioran_celerite_config_name(0) reports after the launch (a tuple: starts with;
+# "!...": does not start with), each from an assertion in the GPU suite; shared table, no per-draw rows
+STEP_PINNED = [
+    ((80, 1, 0, 300, ""), ("rpl5_cbr4_nsrc4",)),                # test_gpu_parity.py:451 (J = 40)
+    ((66, 1, 0, 290, ""), ("rpl5_cbr4_nsrc4",)),                # test_gpu_parity.py:451 (J = 33)
+    ((72, 1, 0, 301, ""), ("rpl5_cbr4_nsrc4",)),                # test_gpu_parity.py:451 (J = 36)
+    ((78, 1, 0, 280, ""), ("rpl5_cbr4_nsrc4",)),                # test_gpu_parity.py:451 (J = 39)
+    ((80, 1, 0, 7, ""), ("rpl5_cbr4_nsrc4",)),                  # test_gpu_parity.py:451 (J = 40, seven draws)
+    ((70, 2, 25, 300, ""), ("rpl5_cbr4_nsrc4",)),               # test_gpu_parity.py:451 (J = 45, 20 one-row terms)
+    ((78, 2, 28, 258, ""), ("rpl5_cbr4_nsrc4",)),               # test_gpu_parity.py:451 (J = 50, 22 one-row terms)
+    ((80, 2, 38, 259, ""), ("rpl5_cbr4_nsrc4",)),               # test_gpu_parity.py:451 (J = 42, 4 one-row terms)
+    ((76, 2, 32, 3, ""), ("rpl5_cbr4_nsrc4",)),                 # test_gpu_parity.py:451 (J = 44, 12 one-row terms)
+    ((30, 1, 0, 2100, ""), "rpl2_cbr1_nsrc16_p+win3"),          # test_gpu_parity.py:577
+    ((16, 1, 0, 45, ""), "rpl1_cbr1_nsrc16_yp"),                # test_gpu_parity.py:593 (J = 8)
+    ((32, 1, 0, 45, ""), "rpl2_cbr1_nsrc16_yp"),                # test_gpu_parity.py:593 (J = 16)
+    ((48, 1, 0, 45, ""), "rpl3_cbr2_nsrc8_yp"),                 # test_gpu_parity.py:593 (J = 24)
+    ((64, 1, 0, 70, ""), "rpl4_cbr4_nsrc4_yp"),                 # test_gpu_parity.py:622
+    ((64, 2, 30, 9, ""), "rpl4_cbr4_nsrc4_y"),                  # test_gpu_parity.py:639 (30 two-row + 4 one-row terms)
+    ((60, 2, 20, 300, ""), "rpl4_cbr4_nsrc4_b5a"),              # test_gpu_parity.py:774 (DRWCelerite-20)
+    ((36, 2, 12, 300, ""), "rpl3_cbr2_nsrc7"),                  # test_gpu_parity.py:774 (DRWCelerite-12)
+    ((60, 2, 20, 300, "no_paired=1"), "!rpl4_cbr4_nsrc4_b5"),   # test_gpu_parity.py:781
+    ((36, 2, 12, 300, "no_paired=1"), "!rpl4_cbr4_nsrc4_b5"),   # test_gpu_parity.py:781
+    ((40, 1, 0, 4096, ""), ("rpl",)),                           # test_gpu_configs.py:112 (SHO-20)
+    ((60, 2, 20, 4096, ""), ("rpl",)),                          # test_gpu_configs.py:112 (DRWCelerite-20)
+] + [((40, 1, 0, 21, f"scan_config={name}"), name)              # test_gpu_parity.py:808-813
+     for name in ("rpl3_cbr2_nsrc7_p", "rpl3_cbr2_nsrc8_p", "rpl3_cbr2_nsrc7", "rpl3_cbr2_nsrc8", "rpl3_cbr4_nsrc4", "rpl4_cbr4_nsrc4", "rpl5_cbr4_nsrc4",
+                  "rpl4_cbr4_nsrc4_p", "rpl5_cbr4_nsrc4_p")]
+
+
+@pytest.mark.parametrize("query,want", STEP_PINNED)
+def test_step_route_names_the_gpu_suite_asserts(query, want):
+    R, kind, nc, B, options = query
+    name, plan = G.step_route("scan", R, kind, nc, B, True, 0, False, options)
+    if isinstance(want, tuple):
+        assert name.startswith(want[0]), name
+    elif want.startswith("!"):
+        assert not name.startswith(want[1:]), name
+    else:
+        assert name == want
+    assert plan[6] == 1
+
+
+def test_config_name_of_a_row_count():
+    """pioran_celerite_config_name(R), R > 0: the configuration alone, with no launch behind it (tests/test_abi.py:40-43) — the rule asked for a
+    large batch without a table."""
+    L = pj._lib.lib()
+    assert L.pioran_celerite_config_name(40) == b"rpl3_cbr2_nsrc7_p"
+    assert L.pioran_celerite_config_name(60).startswith(b"rpl4_cbr4")
+    assert L.pioran_celerite_config_name(128) == b"wide" and L.pioran_celerite_config_name(80) == b"wide"
+    assert L.pioran_celerite_config_name(144) == b"fallback"
+    for R in range(1, 80):
+        name, plan = G.step_route("scan", R, 1 - R % 2, 0, 1 << 40, False)
+        assert L.pioran_celerite_config_name(R).decode() == name.split("+")[0]
+
+
+def test_step_route_properties_over_the_grid():
+    names = set()
+    for key in G.step_scan_keys():
+        kind, B, shared, npd, options = key
+        opt = dict(kv.split("=") for kv in options.split(";") if kv)
+        for R in G.STEP_SCAN_ROWS:
+            name, (config, form, shared_tab, mixed, ycol, npb, has_kernel, capacity) = G.step_route("scan", R, kind, G.step_n_complex(kind, R), B, shared, npd,
+                                                                                                  False, options)
+            if name is None:
+                # refused: only what no configuration holds — 80 rows without what the y-as-a-vector shapes need (a name that does not hold the
+                # launch leaves the automatic choice, so no refusal comes from it)
+                assert config == -1 and R == 80 and not (shared and npd == 0 and "no_win2" not in opt)
+                continue
+            base = name.split("+")[0]
+            names.add(base)
+            assert base == G.SCAN_CONFIG_NAMES[0] or base in G.SCAN_CONFIG_NAMES
+            assert has_kernel == 1                                       # celerite_scan.hip's table holds a kernel for every plan the rule returns
+            assert capacity >= R
+            rpl = int(base[3])
+            if base.endswith(("_p", "_yp")):                            # a paired configuration only on a standard row map
+                assert kind == 1
+            assert ycol == base.endswith(("_y", "_yp")) and (not ycol or (shared and npd == 0 and "no_win2" not in opt and form == 2))
+            assert (npb > 0) == base.endswith("_b5a") and (npb == 0 or (kind == 2 and shared and npd == 0 and form in (1, 2)))
+            assert name.endswith("+win3") == (form == 3) and (form != 3 or (shared and npd == 0 and rpl in (2, 3) and not ycol and npb == 0))
+            assert shared_tab == shared and mixed == (shared and npd > 0)
+            # a forbidding option is honoured; a forcing one too, where the form exists
+            if "no_win3" in opt or "no_win2" in opt or "win2" in opt:
+                assert form != 3
+            if "no_win2" in opt:
+                assert form == 1
+            if "win2" in opt:
+                assert form == 2
+            if "win3" in opt and shared and npd == 0 and rpl in (2, 3) and not ycol and npb == 0:
+                assert form == 3
+            if "no_paired" in opt:
+                assert not base.endswith(("_p", "_yp", "_b5a"))
+            if "scan_config" not in opt and base == "rpl2_cbr2_nsrc8":   # the mid-batch shape: up to 2048 draws of 24 .. 31 rows
+                assert B <= 2048 and 24 <= R <= 31
+            if "scan_config" in opt and base != opt["scan_config"]:      # the named configuration does not hold the launch: the automatic choice — but
+                # any name turns the mid-batch shape off, so the configuration is that of a batch above 2048 draws
+                assert base == G.step_route("scan", R, kind, G.step_n_complex(kind, R), 2049, shared, npd, False, "")[0].split("+")[0]
+    assert names == set(G.SCAN_CONFIG_NAMES)                             # every configuration of the list is reached
+    for key in G.step_wide_keys():
+        mode, npd, per_draw_tables, options = key
+        for R in G.STEP_WIDE_ROWS:
+            name, (rpl, lean, ycol, lean_adjoint, *_) = G.step_route(mode, R, 0, 0, 1, True, npd, per_draw_tables, options)
+            if name is None:
+                continue
+            assert R <= 143 and rpl == (R // 16 if ycol else R // 16 + 1)
+            assert not ycol or (mode == "value" and lean and R % 16 == 0 and npd == 0)
+            # celerite_wide_kernel: up to 95 rows of one shared table, the record staged in LDS (the gradient entry does not read per_draw_tables)
+            assert lean or (R <= 95 and (not per_draw_tables or mode == "gradient") and 3 * (R + 2) + 2 + 3 * npd <= 512)
+            assert not lean_adjoint or mode == "gradient"
+            if mode == "gradient":
+                assert npd == 0 and (not lean or lean_adjoint) and (rpl < 7 or lean)
+                if options == "no_wide2=1":
+                    assert lean == (rpl >= 7) == lean_adjoint
+            elif options == "no_wide2=1":
+                assert lean == (R > 95 or per_draw_tables)               # (store, simulate: per-draw tables are refused above)
+            if mode in ("store", "simulate"):
+                assert not per_draw_tables and (not lean or npd == 0) and (options != "wide2=1" or lean == (R >= 64 and npd == 0))

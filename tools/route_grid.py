@@ -10,13 +10,18 @@ arrays — a different segment count, mode or chunking changes bits, so two libr
 
 (--before-value-route[-cd]: the library is from before pioran_value_route[_cd] existed; the binding does not ask for the symbol.)
 
+`step_route` asks pioran_step_route, one level below the families: the kernel instantiation a throughput- or latency-layout launch runs;
+`step_points()` / `run_step_point` are the launches of tests/test_gpu_step_route.py, listed with `--steps`.
+
 `entry_points()` is the grid of tests/test_gpu_entry_route.py — posterior mean and variance, value and gradient, simulation, posterior draws —
 `run_entry_point` makes one call, `entry_route` asks pioran_entry_route.  `--entries [--save FILE.npz] [--against FILE.npz]` lists that grid
 instead: name, return code and a hash of the outputs per point; the gradient arrays are saved / compared with the saved ones
-(--before-entry-route: the library is from before pioran_entry_route existed).
+(--before-entry-route: the library is from before pioran_entry_route existed).  `--steps` lists step_points() the same way
+(--before-step-route: the library is from before pioran_step_route existed).
 """
 import ctypes
 import hashlib
+import itertools
 import sys
 from collections import namedtuple
 from pathlib import Path
@@ -220,6 +225,143 @@ def entry_route(entry, rows, J, n_one, B, per_draw=False, shift=False, want_c=Tr
     return (name.value.decode() if rc == 0 else None), cap.value, bool(shrink.value)
 
 
+def step_route(family, R, standard_rows=0, n_complex=0, B=1, shared=True, npd_rows=0, per_draw_tables=False, options=""):
+    """(name, plan) of pioran_step_route — the kernel instantiation of a step-by-step launch: family "scan" (throughput layout) or the latency
+    layout's "value", "store", "simulate", "gradient".  name: what pioran_celerite_config_name(0) reports after the launch, None where the family
+    refuses.  plan, scan: (configuration's index, steps per pass, shared table, per-draw rows, y as a vector, pairs per block, a kernel exists,
+    rows the configuration holds); latency: (rows per lane, lean forward kernel, y as a vector, lean reverse pass, 0 ...)."""
+    import pioran_jl_amd as pj
+    name = ctypes.create_string_buffer(64)
+    plan = (ctypes.c_int32 * 8)()
+    rc = pj._lib.lib().pioran_step_route(family.encode(), R, standard_rows, n_complex, B, int(shared), npd_rows, int(per_draw_tables), options.encode(),
+                                         name, len(name), plan)
+    if rc not in (0, -4):
+        raise ValueError(f"pioran_step_route: error {rc}")
+    return (name.value.decode() if rc == 0 else None), tuple(plan)
+
+
+# ---- one level below the families: the grid tests/golden/step_route_listing.json was recorded over, from the commit before scan_plan / wide_plan
+# existed (tools/experiments/step_route_listing.py), and tests/test_route.py holds pioran_step_route to ---------------------------------------------
+_SCAN_SHAPES = ((1, 1, 5), (1, 1, 9), (1, 1, 13), (1, 1, 16), (2, 1, 9), (2, 1, 11), (2, 1, 13), (2, 1, 15), (2, 1, 16), (3, 2, 6), (3, 2, 7), (3, 2, 8),
+                (4, 4, 4), (5, 4, 4))
+_SCAN_Y_SHAPES = ((1, 1, 16), (2, 1, 16), (3, 2, 8), (4, 4, 4), (5, 4, 4))
+SCAN_CONFIG_NAMES = tuple(f"rpl{r}_cbr{c}_nsrc{n}{sfx}" for shapes, sfxs in ((_SCAN_SHAPES, ("", "_p")), (_SCAN_Y_SHAPES, ("_y", "_yp")))
+                          for r, c, n in shapes for sfx in sfxs) + ("rpl4_cbr4_nsrc4_b5a", "rpl3_cbr4_nsrc4", "rpl2_cbr2_nsrc8")
+STEP_SCAN_ROWS = range(1, 81)
+STEP_SCAN_OPTIONS = ("", "no_win2=1", "win2=1", "win3=1", "no_win3=1", "no_paired=1") + tuple(f"scan_config={n}" for n in SCAN_CONFIG_NAMES)
+STEP_WIDE_ROWS = range(1, 145)
+STEP_WIDE_MODES = ("value", "store", "simulate", "gradient")
+
+
+def step_n_complex(kind, R):
+    """Two-row terms of the row map 'n_complex two-row terms, then one-row terms' (kind 2) of R rows: a third — 60 rows are DRWCelerite-20."""
+    return R // 3 if kind == 2 else 0
+
+
+def step_scan_keys():
+    """(row-map kind, B, shared table, per-draw rows, options): every R of STEP_SCAN_ROWS is asked under each."""
+    return list(itertools.product((0, 1, 2), (1, 2048, 2049), (1, 0), (0, 2), STEP_SCAN_OPTIONS))
+
+
+def step_wide_keys():
+    """(mode, per-draw rows, per-draw tables, options): every R of STEP_WIDE_ROWS is asked under each."""
+    return list(itertools.product(STEP_WIDE_MODES, (0, 2), (0, 1), ("", "wide2=1", "no_wide2=1")))
+
+
+def step_runs(answers):
+    """Runs of equal answers over consecutive rows: [[first row, last row, answer], ...] of a list of (row, answer)."""
+    runs = []
+    for R, a in answers:
+        if runs and runs[-1][2] == a and runs[-1][1] == R - 1:
+            runs[-1][1] = R
+        else:
+            runs.append([R, R, a])
+    return runs
+
+
+def step_scan_answer(key, R):
+    """What the listing holds per scan query: [name, steps per pass, shared table, per-draw rows, y as a vector, pairs per block], None: refused."""
+    kind, B, shared, npd, options = key
+    name, plan = step_route("scan", R, kind, step_n_complex(kind, R), B, shared, npd, False, options)
+    return None if name is None else [name, *plan[1:6]]
+
+
+def step_wide_answer(key, R):
+    """... per latency query: the kernels in launch order as [template, rows per lane, y as a vector, mode], None: refused."""
+    mode, npd, per_draw_tables, options = key
+    name, (rpl, lean, ycol, lean_adjoint, *_) = step_route(mode, R, 0, 0, 1, True, npd, per_draw_tables, options)
+    if name is None:
+        return None
+    m = STEP_WIDE_MODES.index(mode)
+    kernels = [["celerite_wide2_kernel" if lean else "celerite_wide_kernel", rpl, ycol, m]]
+    if mode == "gradient":
+        kernels.append(["celerite_adjoint2_kernel" if lean_adjoint else "celerite_adjoint_kernel", rpl, 0, 0])
+    return [name, kernels]
+
+
+# ---- the launches of tests/test_gpu_step_route.py: one on each side of every rule of scan_plan / wide_plan.  N = 37; the one-row terms are the LAST
+# ones (the row map "two-row terms, then one-row terms": an odd row count has one, the 60-row shape is DRWCelerite-20) ---------------------------------
+StepPoint = namedtuple("StepPoint", "family J n_one B options")
+STEP_N, STEP_M = 37, 5
+STEP_TO_SCAN = "no_tile=1;no_block=1;no_wide=1"
+STEP_SCAN_POINT_ROWS = (15, 16, 23, 24, 31, 32, 47, 48, 63, 64, 79, 80)
+
+
+def step_points():
+    def pt(family, rows, B, options):
+        return StepPoint(family, (rows + 1) // 2, rows % 2, B, options)
+    # the throughput layout: the batch classes where the rule reads B (the mid-batch shape and the three-step form: 24 .. 31 rows) and beside them
+    pts = [pt("scan", rows, B, STEP_TO_SCAN) for rows in STEP_SCAN_POINT_ROWS for B in ((5, 2048, 2049) if 23 <= rows <= 32 else (5,))]
+    pts.append(StepPoint("scan", 40, 20, 5, STEP_TO_SCAN))
+    # the latency layout at three draws: value, store (the prediction's factor), simulate, gradient, rows either side of 48, 64 and 96 ...
+    pts += [pt(mode, rows, 3, "no_tile=1;no_block=1") for mode in STEP_WIDE_MODES for rows in (47, 48, 63, 64, 95, 96)]
+    # ... and where only an option tells the sides apart
+    pts += [pt("value", 47, 3, "no_block=1;wide2=1"), pt("value", 48, 3, "no_block=1;no_wide2=1"), pt("simulate", 64, 3, "no_wide2=1"),
+            pt("gradient", 47, 3, "no_block=1;wide2=1"), pt("gradient", 95, 3, "no_wide2=1"), pt("gradient", 96, 3, "no_wide2=1")]
+    return pts
+
+
+def step_expected(pt):
+    """The name pioran_step_route gives the point's launch."""
+    rows = 2 * pt.J - pt.n_one
+    if pt.family == "scan":
+        return step_route("scan", rows, 2 if pt.n_one else 1, pt.J - pt.n_one, pt.B, True, 0, False, pt.options)[0]
+    return step_route(pt.family, rows, options=pt.options)[0]
+
+
+def run_step_point(ctx, pt):
+    """One call that reaches the point's launch: (family that ran, pioran_celerite_config_name(0) after it, the outputs that are one workgroup's
+    or one wavefront's sums — the gradient arrays are left out)."""
+    import pioran_jl_amd as pj
+    t, y, s2, A, Bc, C, Dd, mu, nu = inputs(Point(pt.J, 0, pt.B, STEP_N, ""))
+    if pt.n_one:
+        Bc[:, -pt.n_one:] = 0.0
+        Dd[-pt.n_one:] = 0.0
+    rng = np.random.default_rng([pt.J, pt.n_one, pt.B, STEP_N, 4])
+    opts = [kv.split("=") for kv in pt.options.split(";") if kv]
+    ds = pj.Dataset(t, y, s2, ctx)
+    try:
+        for k, v in opts:
+            ctx.set_option(k, v)
+        if pt.family in ("scan", "value"):
+            out, st = ds.logl_batch(A, Bc, C, Dd, mu=mu, nu=nu, return_status=True)
+            out = dict(logl=out, status=st)
+        elif pt.family == "store":
+            mean, st = ds.predict(A, Bc, C, Dd, rng.uniform(t[0] - 1, t[-1] + 1, STEP_M), mu=mu, nu=nu, return_status=True)
+            out = dict(mean=mean, status=st)
+        elif pt.family == "simulate":
+            out = dict(y=ctx.simulate(A, Bc, C, Dd, t, s2, rng.standard_normal((pt.B, STEP_N))))
+        else:
+            g = ds.logl_grad(A, Bc, C, Dd, mu=mu, nu=nu)
+            out = dict(logl=g["logl"], status=g["status"])
+        L = pj._lib.lib()
+        return L.pioran_celerite_config_name(-1).decode(), L.pioran_celerite_config_name(0).decode(), out
+    finally:
+        for k, _ in opts:
+            ctx.set_option(k, None)
+        ds.close()
+
+
 def expected(pt):
     """The family the rules name for a point of any of the three kinds."""
     if isinstance(pt, CdPoint):
@@ -332,10 +474,18 @@ def main():
         pj._lib.SIGNATURES.pop("pioran_value_route_cd", None)
     if "--before-entry-route" in sys.argv:
         pj._lib.SIGNATURES.pop("pioran_entry_route", None)
+    if "--before-step-route" in sys.argv:
+        pj._lib.SIGNATURES.pop("pioran_step_route", None)
     ctx = pj.Context(0)
     if "--entries" in sys.argv:
         arg = lambda flag: sys.argv[sys.argv.index(flag) + 1] if flag in sys.argv else None
         return run_entries(ctx, arg("--save"), arg("--against"))
+    if "--steps" in sys.argv:      # (the name of the instantiation is not listed: a library from before pioran_step_route names the scan's only)
+        for pt in step_points():
+            fam, _, out = run_step_point(ctx, pt)
+            digest = hashlib.sha256(b"".join(np.ascontiguousarray(v).tobytes() for _, v in sorted(out.items()))).hexdigest()[:16]
+            print(f"step {pt.family:8s} rows {2 * pt.J - pt.n_one:3d} J {pt.J:2d} B {pt.B:4d} N {STEP_N} [{pt.options}] {fam} {digest}", flush=True)
+        return
     for pt in points() + cd_points() + theta_points():
         fam, out, st = run_point(ctx, pt)
         digest = hashlib.sha256(out.tobytes() + st.tobytes()).hexdigest()[:16]
