@@ -53,14 +53,28 @@ constexpr int kTileWaves = 4;      // wavefronts (= draws) per workgroup
 template <int NB, bool CD = false>
 constexpr int tile_adj_waves() { return NB <= 3 ? 4 : (CD ? 2 : 3); }
 
+typedef __attribute__((address_space(3))) double lds_f64;
 template <int NB>
 struct TileWave {                  // LDS of one wavefront
     double scr[16 * 18];           // in turn: a block of M' for the transposing read-back; Sigma [j][n]; D_k (L^-1)_ik at [k * 18 + i], 1 / D_k at [k * 18 + 16]
     double2 albe[16 * NB];         // per row: u = al v + be x (:59-63)
     double ck[16 * NB + 16];       // the window's C_K per row, then sigma2 per step (staged from the record: read again and again by the update)
     double ys[16];                 // per-draw series (p.Y: the shifted log-flux models, docs/src/ultranest.md:199-205): y_n of the window's steps
-    double up[NB > 1 ? NB * (NB - 1) / 2 : 1][16 * 18];   // the strictly lower tiles of T once more, [row][column, stride 18]: read back transposed
-                                                          // they are the upper tiles as B operands
+    // The strictly lower tiles of T once more: read back transposed they are the upper tiles as B operands.  Up to three block columns (PERM, round 12) element
+    // (row, column) of tile u sits at (row & 3) S + (row >> 2) G + 18 u + column: a lane writes rows 4 g + q of every tile and reads row c16 of every tile, so
+    // its twelve writes lie within 3 G + 18 (NU - 1) doubles of its first and its twelve reads within 18 NU — inside the 2040 bytes that ds_read2_b64 / ds_write2_b64
+    // reach from ONE base register (as [tile][row][column, stride 18] the tiles are 2304 bytes apart, and every window paid ten v_add_u32 for rebased
+    // pointers).  G = 8 and S = 18 (mod 32) keep the banks of the stride-18 layout: across a half wavefront the transposed read starts at the sixteen
+    // distinct multiples of four dwords 36 (c16 & 3) + 16 (c16 >> 2) (mod 64), the write at 36 q + 2 c16 as before.  More block columns: [tile][row][column].
+    static constexpr int NU = NB > 1 ? NB * (NB - 1) / 2 : 1;
+    static constexpr bool PERM = NB <= 3;
+    static constexpr int G = (18 * NU + 23) / 32 * 32 + 8;              // >= 18 NU, = 8 (mod 32): 72 at three block columns
+    static constexpr int S = (3 * G + 18 * NU + 13) / 32 * 32 + 18;     // >= 3 G + 18 NU, = 18 (mod 32): 274
+    static constexpr int UPN = PERM ? 3 * S + 3 * G + 18 * NU : NU * 16 * 18;
+    static_assert(!PERM || 8 * (3 * G + 18 * (NU - 1)) <= 2040, "a lane's accesses of the tile copies must be within reach of one base register");
+    double up[UPN];
+    static constexpr int up_row(int row) { return PERM ? (row & 3) * S + (row >> 2) * G : 18 * row; }
+    static constexpr int up_at(int u, int row, int col) { return up_row(row) + (PERM ? 18 : 288) * u + col; }
 };
 
 // The contraction is a GEMM — out[draw][(window, pair)] = sum over (t, cos | sin) of coef[draw][(t, cos | sin)] E[(t, cos | sin)][(window, pair)],
@@ -75,6 +89,7 @@ struct TileWave {                  // LDS of one wavefront
 constexpr int kPairWin = 5;
 constexpr int kPairRow = 128 + 2;  // doubles per draw row of the scratch: the 16 rows of a 32-byte write then fall on different banks
 typedef double d2v __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) d2v lds_d2v;
 template <int JQ>
 __global__ void __launch_bounds__(256) tile_pairs_mfma_kernel(const ScanParams p, const double* __restrict__ btab, int64_t rsb, int64_t tsp, double* __restrict__ out)
 {
@@ -193,7 +208,6 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
     const int ry = R & 15;                         // ... its lane column
     const double mu = p.mu ? p.mu[b] : 0.0;
     const double nu = p.nu ? p.nu[b] : 1.0;
-    const bool has_nu = p.nu != nullptr;
     const double* __restrict__ Ab_ = p.A + b * J;
     const double* __restrict__ Bb_ = p.Bc + b * J;
     double suma = 0.0;  // :21
@@ -209,13 +223,25 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
         }
         sw.albe[r] = double2{a, bb};
     }
-    constexpr int NU = NB * (NB - 1) / 2;
-    for (int i = lane; i < (NU > 0 ? NU : 1) * 16 * 18; i += 64) (&sw.up[0][0])[i] = 0.0;
+    for (int i = lane; i < TileWave<NB>::UPN; i += 64) sw.up[i] = 0.0;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 
     constexpr int NT = NB * (NB + 1) / 2;          // T is symmetric: the tiles (I, Jc), I >= Jc, live in registers
     auto tix = [](int I, int Jc) constexpr { return I * (I + 1) / 2 + Jc; };
     auto uix = [](int I, int Jc) constexpr { return I * (I - 1) / 2 + Jc; };   // I > Jc: slot of the tile's LDS copy
+    // this lane's element of a tile's copy, for the transposed read and for the write: base registers of their own, so that every access of the window loop is
+    // base + immediate (formed from the wavefront's LDS base, the merged two-address forms reach 2040 bytes and pay a vector address sum per window beyond)
+    lds_f64* up_rd = (lds_f64*)(sw.up + TileWave<NB>::up_row(c16) + q);
+    lds_f64* up_wr = (lds_f64*)(sw.up + TileWave<NB>::up_row(q) + c16);
+    if constexpr (TileWave<NB>::PERM) asm volatile("" : "+v"(up_rd), "+v"(up_wr));
+    // ... and of the scratch: row-major (4 g + q, c16), transposed (c16, 4 ks + q), and row q alone
+    lds_f64* scr_rm = (lds_f64*)(sw.scr + q * 18 + c16);
+    lds_f64* scr_tr = (lds_f64*)(sw.scr + c16 * 18 + q);
+    lds_f64* scr_q = (lds_f64*)(sw.scr + q * 18);
+    if constexpr (TileWave<NB>::PERM) asm volatile("" : "+v"(scr_rm), "+v"(scr_tr), "+v"(scr_q));
+    lds_f64* ck_c = (lds_f64*)(sw.ck + c16);
+    lds_f64* ck_q = (lds_f64*)(sw.ck + q);
+    if constexpr (TileWave<NB>::PERM) asm volatile("" : "+v"(ck_c), "+v"(ck_q));
     d4 T[NT];
 #pragma unroll
     for (int i = 0; i < NT; ++i) T[i] = d4{0.0, 0.0, 0.0, 0.0};
@@ -364,7 +390,7 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
             for (int I = 0; I < Jc; ++I) {
                 double bt[4];
 #pragma unroll
-                for (int ks = 0; ks < 4; ++ks) bt[ks] = sw.up[uix(Jc, I)][c16 * 18 + 4 * ks + q];
+                for (int ks = 0; ks < 4; ++ks) bt[ks] = up_rd[TileWave<NB>::up_at(uix(Jc, I), 0, 4 * ks)];
 #pragma unroll
                 for (int ks = 0; ks < 4; ++ks) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Uf[I][ks], bt[ks], acc, 0, 0, 0);
             }
@@ -394,14 +420,14 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
             const bool gk = Jc < NB - 1 || KL > 0;      // block Jc of M' feeds G (KL = 0: the last block holds the y row alone)
             if (gk) {
 #pragma unroll
-                for (int g = 0; g < 4; ++g) sw.scr[(4 * g + q) * 18 + c16] = x[Jc][g];
+                for (int g = 0; g < 4; ++g) scr_rm[4 * g * 18] = x[Jc][g];
             }
             PIORAN_LDS_ORDER();
             double mb[4];   // M [row 16 Jc + 4 ks + q][step c16]
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks)
-                if (live_k(Jc, ks)) mb[ks] = sw.scr[c16 * 18 + 4 * ks + q];
-            const double ckc = sw.ck[16 * Jc + c16];
+                if (live_k(Jc, ks)) mb[ks] = scr_tr[4 * ks];
+            const double ckc = ck_c[16 * Jc];
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks)
@@ -452,13 +478,15 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
         // ---- Sigma = A - G, Sigma = L D L', L^-1 ----------------------------------------------------------------------------
         if constexpr (PRE) {
 #pragma unroll
-            for (int g = 0; g < 4; ++g) ckl[g] = sw.ck[16 * (NB - 1) + 4 * g + q];
+            for (int g = 0; g < 4; ++g) ckl[g] = ck_q[16 * (NB - 1) + 4 * g];
 #pragma unroll
-            for (int Jc = 0; Jc < NB; ++Jc) ckcl[Jc] = sw.ck[16 * Jc + c16];
+            for (int Jc = 0; Jc < NB; ++Jc) ckcl[Jc] = ck_c[16 * Jc];
         }
         {
-            const double s2n = sw.ck[16 * NB + c16];
-            double dg = suma + (has_nu ? nu * s2n : s2n);   // :92
+            const double s2n = ck_c[16 * NB];
+            double ns = nu * s2n;          // (without nu the factor is 1: the same bits as sigma2_n itself, and no select)
+            asm volatile("" : "+v"(ns));   // a product and a sum, as the reference rounds them: not one fused operation
+            double dg = suma + ns;         // :92
             // padded steps of the last, ragged window: D = 1.  The wave-uniform test of the fix-up of V^' above and a lane mask formed before the loop (round 10; as a
             // per-lane test of the step in EVERY window: a 64-bit vector compare, an exec mask and a branch around the diagonal.  As a branch under k == k_ragged the
             // compiler peels the loop and the headline instantiation spills two scalar registers)
@@ -485,9 +513,9 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
         __builtin_amdgcn_s_setprio(0);
         PIORAN_TSTAMP(5);
         if (q == 0) {   // lane n holds column n of L^-1 (scaled by D_n) in m[j], j > n, D_n in m[n]; the rest of m is left-over Sigma (masked below)
-            double2* dst = reinterpret_cast<double2*>(sw.scr + c16 * 18);
+            lds_d2v* dst = reinterpret_cast<lds_d2v*>(scr_tr);      // (q == 0: row c16 of the scratch)
 #pragma unroll
-            for (int j = 0; j < 16; j += 2) dst[j / 2] = double2{m[j], m[j + 1]};
+            for (int j = 0; j < 16; j += 2) dst[j / 2] = d2v{m[j], m[j + 1]};
         }
         PIORAN_LDS_ORDER();
         double li[4], idv[4];
@@ -498,19 +526,19 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
         const double dj = sw.scr[c16 * 18 + c16];              // D_n sits on the diagonal; this lane follows step c16 of every window
         double lv[4];
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) lv[ks] = sw.scr[(4 * ks + q) * 18 + c16];
+        for (int ks = 0; ks < 4; ++ks) lv[ks] = scr_rm[4 * ks * 18];
         if constexpr (PRE) {
 #pragma unroll
             for (int I = 0; I < NB - 1; ++I)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) cku[I][g] = sw.ck[16 * I + 4 * g + q];
+                for (int g = 0; g < 4; ++g) cku[I][g] = ck_q[16 * I + 4 * g];
         }
         if (more) fetch_u(k + 1, 0);
         const double rj = recip_f64(dj);
-        if (q == 0) sw.scr[c16 * 18 + 16] = rj;
+        if (q == 0) scr_tr[16] = rj;
         PIORAN_LDS_ORDER();
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) idv[ks] = sw.scr[(4 * ks + q) * 18 + 16];
+        for (int ks = 0; ks < 4; ++ks) idv[ks] = scr_q[4 * ks * 18 + 16];
         nonpd |= !(dj > 0.0);
         Pm *= (k == 0 && c16 == 0) ? dj : fabs(dj);    // log(D[1]) :126, log(abs(D[n])) :140
         int ex;
@@ -550,11 +578,11 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
 #pragma unroll
             for (int I = 0; I < NB; ++I) {
 #pragma unroll
-                for (int g = 0; g < 4; ++g) ckrow[I][g] = sw.ck[16 * I + 4 * g + q];
-                ckcol[I] = sw.ck[16 * I + c16];
+                for (int g = 0; g < 4; ++g) ckrow[I][g] = ck_q[16 * I + 4 * g];
+                ckcol[I] = ck_c[16 * I];
             }
         }
-        [[maybe_unused]] auto ck_row = [&](int I, int g) __attribute__((always_inline)) -> double { if constexpr (CKP) return ckrow[I][g]; else return sw.ck[16 * I + 4 * g + q]; };
+        [[maybe_unused]] auto ck_row = [&](int I, int g) __attribute__((always_inline)) -> double { if constexpr (CKP) return ckrow[I][g]; else return ck_q[16 * I + 4 * g]; };
         // ---- T <- (C_K C_K') o T + Y^ D^-1 Y^', lower tiles, one block column at a time; the off-diagonal ones are copied to LDS for the
         //      next window's M'; U~ of the next window is formed on the way ------------------------------------------------------
 #pragma unroll
@@ -565,7 +593,7 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
             }
             double ysc[4];
             [[maybe_unused]] double ckc = 0.0;
-            if constexpr (CKP) ckc = ckcol[Jc]; else if constexpr (!PRE) ckc = sw.ck[16 * Jc + c16];
+            if constexpr (CKP) ckc = ckcol[Jc]; else if constexpr (!PRE) ckc = ck_c[16 * Jc];
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 ysc[g] = yt[Jc][g] * idv[g];
@@ -582,7 +610,7 @@ __global__ void __launch_bounds__(64 * kTileWaves, NB <= 4 ? 2 : 1) celerite_til
                 for (int ks = 0; ks < 4; ++ks) T[tix(I, Jc)] = __builtin_amdgcn_mfma_f64_16x16x4f64(yt[I][ks], ysc[ks], T[tix(I, Jc)], 0, 0, 0);
                 if (Jc < I) {
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) sw.up[uix(I, Jc)][(4 * g + q) * 18 + c16] = T[tix(I, Jc)][g];
+                    for (int g = 0; g < 4; ++g) up_wr[TileWave<NB>::up_at(uix(I, Jc), 4 * g, 0)] = T[tix(I, Jc)][g];
                 }
             }
             __builtin_amdgcn_sched_barrier(0);

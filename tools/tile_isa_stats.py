@@ -1,12 +1,30 @@
 #!/usr/bin/env python3
 """Static counts of the window loop of the celerite_tile_kernel instantiations (reads a `hipcc -S --cuda-device-only` listing of celerite_tile.hip made
 with build.py's flags).  usage: tile_isa_stats.py tile.s [NB KL ST SER] ...   (no selection: every instantiation)
-tests/test_tile_isa.py imports kernel_stats()."""
+literal_address_adds: the loop's v_add_u32 of a literal and a register the loop never writes (an LDS address a base register could hold).
+tests/test_tile_isa.py and tests/test_gpu_tile_table_products.py import kernel_stats()."""
 import re
 import sys
 from collections import Counter
 
 NAME = re.compile(r'^(_ZN12_GLOBAL__N_120celerite_tile_kernelILi(\d+)ELi(\d+)ELb([01])ELb([01])EEEv10ScanParamsPKdS\d+_):', re.M)
+
+
+LIT_ADD = re.compile(r'^v_add_u32_e32 v\d+, (?:0x[0-9a-f]+|\d+), v(\d+)$')
+
+
+def _written_vgprs(line: str) -> set:
+    """VGPR numbers an instruction line writes: its first operand (v7 or v[4:7]); stores, compares into SGPRs and s_* write none (the DPP updates
+    of the inline assembly write their first operand too)."""
+    parts = line.split(None, 1)
+    if len(parts) < 2 or parts[0].startswith(('s_', 'ds_write', 'buffer_store', 'global_store', ';')):
+        return set()
+    mm = re.match(r'v(\d+)\b|v\[(\d+):(\d+)\]', parts[1])
+    if not mm:
+        return set()
+    if mm.group(1):
+        return {int(mm.group(1))}
+    return set(range(int(mm.group(2)), int(mm.group(3)) + 1))
 
 
 def _meta(listing: str, name: str) -> dict:
@@ -38,15 +56,23 @@ def kernel_stats(listing: str) -> dict:
             if mm and labels.get(mm.group(1), idx) < idx:
                 loops.append((idx - labels[mm.group(1)], labels[mm.group(1)], idx))
         c = Counter()
+        lit_adds = 0
         if loops:
             _, a, b = max(loops)
+            written = set()
             for l in body[a:b + 1]:
                 l = l.strip()
                 if not l or l.startswith(('.', ';')) or l.endswith(':'):
                     continue
                 c[l.split()[0]] += 1
+                written.update(_written_vgprs(l))
+            # address sums that a base register could hold: v_add_u32 of a literal and a register the loop never writes
+            for l in body[a:b + 1]:
+                mm = LIT_ADD.match(l.strip())
+                if mm and int(mm.group(1)) not in written:
+                    lit_adds += 1
         key = (int(m.group(2)), int(m.group(3)), bool(int(m.group(4))), bool(int(m.group(5))))
-        out[key] = {"loop": c, "meta": _meta(listing, name)}
+        out[key] = {"loop": c, "meta": _meta(listing, name), "literal_address_adds": lit_adds}
     return out
 
 
@@ -56,7 +82,7 @@ def summary(st: dict) -> str:
     lanes = c['v_readlane_b32'] + c['v_writelane_b32']
     return (f"loop={sum(c.values())} v_*={valu} mfma={c['v_mfma_f64_16x16x4_f64']} lane_moves={lanes} v_cndmask={c['v_cndmask_b32_e32'] + c['v_cndmask_b32_e64']} "
             f"v_mov_b64={c['v_mov_b64_e32']} branches={sum(v for k, v in c.items() if k.startswith(('s_cbranch', 's_branch')))} vgpr={md.get('vgpr_count')} "
-            f"agpr={md.get('agpr_count')} sgpr_spill={md.get('sgpr_spill_count')} vgpr_spill={md.get('vgpr_spill_count')} scratch={md.get('private_segment_fixed_size')}")
+            f"literal_address_adds={st.get('literal_address_adds')} agpr={md.get('agpr_count')} sgpr_spill={md.get('sgpr_spill_count')} vgpr_spill={md.get('vgpr_spill_count')} scratch={md.get('private_segment_fixed_size')}")
 
 
 if __name__ == "__main__":
