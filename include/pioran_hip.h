@@ -442,7 +442,7 @@ int pioran_celerite_rand_posterior_summary(pioran_ds* ds, int64_t B, int64_t J, 
  * are not affected, and no output depends on which other outputs are requested or on how the call is chunked.
  *   theta [B][P], norm [B], freq [F] positive and finite (any order), psd / psd_approx / residuals / ratios [B][F] each or NULL,
  *   amplitudes [B][J] or NULL, integ [B] or NULL, status [B] or NULL.
- * Out of scope: QPO features, PowerLaw, and the CARMA variant plot_psd_ppc_CARMA.
+ * Out of scope: QPO features and PowerLaw.  (The CARMA variant plot_psd_ppc_CARMA: pioran_carma_psd_batch / pioran_carma_psd_summary, below.)
  * pioran_psd_check_batch uploads, runs chunk by chunk under "workspace_limit_mb" and downloads, and blocks; pioran_psd_check_batch_dev takes
  * device pointers for every array and is asynchronous on the context's stream (a call with another grid than the previous one waits for the stream first).
  * pioran_psd_check_summary keeps the four arrays in buffers of the context (pioran_ctx_trim releases them; PIORAN_ERR_ALLOC where they do not fit
@@ -471,6 +471,65 @@ int pioran_psd_check_summary(pioran_ctx* ctx, int64_t B, int model, int64_t n_co
                              double f_min, double f_max, double S_low, double S_high, const double* theta, const double* norm,
                              int64_t F, const double* freq, int normalise, int times_f, int64_t Q, const double* probs,
                              double* quant, double* mean, double* meta, int32_t* status, int32_t* kept);
+/* ---- CARMA(p, q) models from their sampled parameters (src/CARMA.jl, docs/src/carma.md, log_likelihood(::CARMA, ...) src/celerite_solver.jl:272-282,
+ * plot_psd_ppc_CARMA src/plots_diagnostics.jl:832-936) -----------------------------------------------------------------------------------------
+ * Orders 1 <= p <= 16, 0 <= q <= p (the constructor's rule, src/CARMA.jl:28-36; outside: PIORAN_ERR_UNSUPPORTED); J = (p + 1) / 2 celerite terms, for
+ * odd p the last one real (b = d = 0).  Two input forms:
+ *   form 0, quad: qa [B][p], qb [B][q] (NULL for q = 0), the quadratic factors the reference's models sample.  r_alpha = quad2roots(qa) (:201-223) and
+ *           beta = roots2coeffs(quad2roots(qb)), formed as the product of the real factors x^2 + qb[k+1] x + qb[k] (x + qb[q-1] for odd q): ascending, monic;
+ *   form 1, roots: r_alpha [B][p][2] (re, im), beta [B][q + 1], what CARMA(...) holds and plot_psd_ppc_CARMA receives.
+ * norm [B]; is_integrated_power as in CARMA(...).  tools/carma_proto.py is the definition, operation by operation.
+ * A draw is REJECTED when a parameter (norm included) is not finite (flag 1); in quad form, when a pair of qa or qb has b^2 - 4c >= 0 — not a conjugate
+ * pair, which CARMA_celerite_coefs assumes — (flag 2); when a root has real part >= 0 (flag 3; quad form: of either polynomial, roots form: of r_alpha);
+ * or when bounds are given (f_lo = f_hi = 0: none) and check_roots_bounds (src/utils.jl:187-192) fails on r_alpha or, in quad form, on the moving-average
+ * roots, as both models of docs/src/carma.md do (flag 4).  The first reason in this order is the flag; 0 = accepted.  Rejected draws never disturb others.
+ *
+ * pioran_carma_coefs_batch: CARMA_celerite_coefs (:98-143) -> A, Bc, C, Dd [B][J], flags [B] or NULL.  A rejected draw gets (1, 0, 1, 0) in every term.
+ * pioran_carma_vjp_batch (quad form): cotangents ga, gb, gc, gd [B][J] of the coefficients -> grad_qa [B][p], grad_qb [B][q] (NULL for q = 0),
+ *   grad_norm [B]; the Jacobian applied direction by direction with forward duals, forward quantities recomputed.  Rejected draws (flags 1-3; the entry
+ *   takes no bounds) get exact zeros; a zero cotangent gives exact zeros.
+ * pioran_carma_psd_batch: evaluate(::CARMA, f) (:150-172) -> psd [B][F] = 2 |beta(iw) / alpha(iw)|^2 norm / CARMA_normalisation(r_alpha, beta), or
+ *   4 |.|^2 norm without is_integrated_power; times_f != 0: multiplied by freq_f (plot_f_P).  status [B] or NULL: 3, with NaN in the draw's row, for a
+ *   rejected draw.  freq [F] positive and finite.  Chunk by chunk under "workspace_limit_mb": no limit on B or F.
+ * pioran_carma_psd_summary: the same array kept on the device and reduced per frequency over the draws with status 0 by the kernel of
+ *   pioran_quantiles_batch_dev: quant [Q][F], kept (or NULL) = the number of such draws.  B > 4096: PIORAN_ERR_UNSUPPORTED, before any GPU call.
+ * All four take host pointers and block.  PIORAN_ERR_ARG, before any GPU call: NULL ctx or a NULL required array, B / F / Q < 1, form not 0 or 1,
+ * bounds that are not finite or not 0 <= f_lo < f_hi (or both 0), a freq that is not positive and finite, a prob outside [0, 1].
+ * Timing tools: context option "carma_events" records the event slots 4 | 5 around the kernel(s) of a call (the PSD forms: of its first chunk). */
+int pioran_carma_coefs_batch(pioran_ctx* ctx, int64_t B, int p, int q, int form, const double* qa_or_roots, const double* qb_or_beta,
+                             const double* norm, int is_integrated_power, double f_lo, double f_hi, double* A, double* Bc, double* C, double* Dd,
+                             int32_t* flags);
+int pioran_carma_vjp_batch(pioran_ctx* ctx, int64_t B, int p, int q, const double* qa, const double* qb, const double* norm,
+                           int is_integrated_power, const double* ga, const double* gb, const double* gc, const double* gd, double* grad_qa,
+                           double* grad_qb, double* grad_norm);
+int pioran_carma_psd_batch(pioran_ctx* ctx, int64_t B, int p, int q, int form, const double* qa_or_roots, const double* qb_or_beta,
+                           const double* norm, int is_integrated_power, double f_lo, double f_hi, int64_t F, const double* freq, int times_f,
+                           double* psd, int32_t* status);
+int pioran_carma_psd_summary(pioran_ctx* ctx, int64_t B, int p, int q, int form, const double* qa_or_roots, const double* qb_or_beta,
+                             const double* norm, int is_integrated_power, double f_lo, double f_hi, int64_t F, const double* freq, int times_f,
+                             int64_t Q, const double* probs, double* quant, int32_t* status, int32_t* kept);
+/* (qa, qb, norm) -> log L in one call (quad form): pioran_carma_coefs_batch's kernel writes the batch's coefficients where the value bodies read a
+ * batch's draws, and the call goes on as pioran_celerite_logl_batch (shift: pioran_celerite_logl_batch_shift) with cd_shared = 0 goes on from there —
+ * the same routing, decided from the flags and (b, c, d) the host fetches (one draw, or the same (c, d) in every draw: the shared table; mixed mode
+ * where its plan takes the batch; else the per-draw-(c, d) body of pioran_celerite_logl_batch_dev_cd), the same kernels, the same bits.
+ * mu, nu, shift [B] or NULL; A_out .. Dd_out [B][J] or NULL: the coefficients.
+ * status: as the existing entries (0, 1, 2) plus 3 = rejected by the root checks (above, with the bounds): out = -inf, as the reference's models do with
+ * @addlogprob! -Inf; the draw ran on benign coefficients and never disturbs its neighbours.  No other entry of this library returns status 3.
+ *
+ * pioran_logpdf_batch_carma_grad: ... and the gradient w.r.t. the sampled parameters: grad_qa [B][p], grad_qb [B][q] (NULL for q = 0), grad_norm [B];
+ * each of grad_nu, grad_mu, grad_shift [B] is NULL exactly when its input is; grad_a, grad_b, grad_c, grad_d [B][J]: the intermediates, all or none.
+ * The coefficients come from the same kernel; the reverse mode is that of pioran_celerite_logl_grad[_shift] with cd_shared = 0 and grad_c / grad_d on
+ * these coefficients, with its routing — all draws in one launch of the windowed reverse mode where the shape fits it, one draw as a shared-table call —
+ * and pioran_carma_vjp_batch's kernel chains (grad_a .. grad_d) back.  The coefficients and their gradients pass through host memory between the three
+ * steps ([B][4 J] doubles each way).  With shift the per-draw reverse mode has no shifted form and the call goes draw by draw, as the existing entry
+ * does: a shifted form of the per-draw reverse mode is out of scope.  A rejected draw has status 3, out = -inf and exactly 0.0 in every gradient row. */
+int pioran_logpdf_batch_carma(pioran_ds* ds, int64_t B, int p, int q, const double* qa, const double* qb, const double* norm,
+                              int is_integrated_power, double f_lo, double f_hi, const double* mu, const double* nu, const double* shift,
+                              double* out, int32_t* status, double* A_out, double* Bc_out, double* C_out, double* Dd_out);
+int pioran_logpdf_batch_carma_grad(pioran_ds* ds, int64_t B, int p, int q, const double* qa, const double* qb, const double* norm,
+                                   int is_integrated_power, double f_lo, double f_hi, const double* mu, const double* nu, const double* shift,
+                                   double* out, int32_t* status, double* grad_qa, double* grad_qb, double* grad_norm, double* grad_nu,
+                                   double* grad_mu, double* grad_shift, double* grad_a, double* grad_b, double* grad_c, double* grad_d);
 /* Name of the kernel configuration a large batch with R active rows (all terms with both rows when R is even) runs on;
  * R == 0: the kernel instantiation the calling thread's last step-by-step launch (throughput or latency layout) actually ran on, as
  * pioran_step_route names it; R < 0: the kernel FAMILY of the

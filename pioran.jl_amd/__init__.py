@@ -6,7 +6,9 @@ from . import _lib, farm  # noqa: F401
 from .gp import (Context, CustomMean, Dataset, Farm, FiniteScalableGP, PosteriorGP, ScalableGP, cov, default_context,
                  log_likelihood, log_likelihood_direct, logl, logpdf, logpdf_batch, lombscargle, lsp_ppc, lsp_ppc_frequencies, mean, posterior, ppc_t_pred, ppc_timeseries, ppc_timeseries_summary, predict, predict_cov, predict_direct,
                  predict_var, quantiles, rand, rand_posterior, simulate, std, var)
-from .gp import posterior_predict_checks, psd_ppc, run_diagnostics, sample_approx_model
+from .gp import posterior_predict_checks, psd_ppc, psd_ppc_carma, run_diagnostics, sample_approx_model
+from .carma import (CARMA_normalisation, check_conjugate_pair, check_order_imag_roots, check_roots_bounds, evaluate, quad2roots, roots2coeffs,
+                    sample_quad)
 from .kernels import (CARMA, Celerite, Exp, ScaledKernel, SemiSeparable, SHO, SumOfCelerite, SumOfSemiSeparable,
                       SumOfTerms, celerite_coefs)
 from .psd import (QPO, DoubleBendingPowerLaw, SingleBendingPowerLaw, approx, approx_batch, approx_batch_vjp, approximated_psd, build_approx,

@@ -70,6 +70,17 @@ SIGNATURES = {
                                    [i64, c_void_p, ctypes.c_int, ctypes.c_int] + [c_void_p] * 7),
     "pioran_psd_check_summary": (ctypes.c_int, [c_void_p, i64, ctypes.c_int, i64, ctypes.c_int, ctypes.c_int] + [ctypes.c_double] * 4 + [c_void_p] * 2 +
                                  [i64, c_void_p, ctypes.c_int, ctypes.c_int, i64] + [c_void_p] * 6),
+    "pioran_carma_coefs_batch": (ctypes.c_int, [c_void_p, i64, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [c_void_p] * 3 +
+                                 [ctypes.c_int, ctypes.c_double, ctypes.c_double] + [c_void_p] * 5),
+    "pioran_carma_vjp_batch": (ctypes.c_int, [c_void_p, i64, ctypes.c_int, ctypes.c_int] + [c_void_p] * 3 + [ctypes.c_int] + [c_void_p] * 7),
+    "pioran_carma_psd_batch": (ctypes.c_int, [c_void_p, i64, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [c_void_p] * 3 +
+                               [ctypes.c_int, ctypes.c_double, ctypes.c_double, i64, c_void_p, ctypes.c_int] + [c_void_p] * 2),
+    "pioran_carma_psd_summary": (ctypes.c_int, [c_void_p, i64, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [c_void_p] * 3 +
+                                 [ctypes.c_int, ctypes.c_double, ctypes.c_double, i64, c_void_p, ctypes.c_int, i64] + [c_void_p] * 4),
+    "pioran_logpdf_batch_carma": (ctypes.c_int, [c_void_p, i64, ctypes.c_int, ctypes.c_int] + [c_void_p] * 3 +
+                                  [ctypes.c_int, ctypes.c_double, ctypes.c_double] + [c_void_p] * 9),
+    "pioran_logpdf_batch_carma_grad": (ctypes.c_int, [c_void_p, i64, ctypes.c_int, ctypes.c_int] + [c_void_p] * 3 +
+                                       [ctypes.c_int, ctypes.c_double, ctypes.c_double] + [c_void_p] * 15),
     "pioran_celerite_config_name": (ctypes.c_char_p, [i64]),
     "pioran_ctx_fp64_probe": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_double, ctypes.POINTER(ctypes.c_double)]),
     "pioran_tile_choice": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),

@@ -55,6 +55,9 @@ struct pioran_ctx {
     // PSD check (psd_check.hip): the grid's sp | LU | piv, the host forms' theta | norm | freq, a chunk's amp | integ | pf0 | status, a chunk's
     // (the summary: the batch's) arrays psd | psd_approx | residuals | ratios, the summary's transposed copies | partials, its small inputs and results
     Buf bpcgrid, bpcin, bpcdraw, bpcout, bpcT, bpcq;
+    // CARMA entries (carma.hip): the batch's sampled parameters in1 | in2 | norm | flags, and what the kernels leave beside the coefficients (which
+    // land where the value and gradient bodies read them, bA .. bD): the reverse mode's results, the PSD's per-draw roots | beta | factor | status
+    Buf bcarma, bcarmaout;
     std::vector<double> pcgrid_host;   // what bpcgrid is filled from: the device form returns before the copy has run
     double pcgrid_key[6] = {};         // ... and the (J, basis, f_min, f_max, S_low, S_high) it was built for
     // scalar entry point: the last series' time stamps stay resident (samplers call logl with the same t)
@@ -863,6 +866,7 @@ int set_option(ScanOptions& o, const char* key, const char* value)
     else if (!std::strcmp(key, "rp_events")) o.rp_events = on ? 1 : 0;
     else if (!std::strcmp(key, "theta_events")) o.theta_events = on ? 1 : 0;
     else if (!std::strcmp(key, "pc_events")) o.pc_events = on ? 1 : 0;
+    else if (!std::strcmp(key, "carma_events")) o.carma_events = on ? 1 : 0;
     else if (!std::strcmp(key, "wide2")) o.wide2 = on;
     else if (!std::strcmp(key, "no_wide2")) o.no_wide2 = on;
     else return PIORAN_ERR_ARG;
@@ -1060,7 +1064,7 @@ int pioran_ctx_destroy(pioran_ctx* ctx)
     pioran_ctx::Buf* bufs[] = {&ctx->bA, &ctx->bB, &ctx->bC, &ctx->bD, &ctx->bmu, &ctx->bnu, &ctx->bY,
                                &ctx->bS2, &ctx->bout, &ctx->bst, &ctx->bscratch, &ctx->bK, &ctx->bwork, &ctx->bshift, &ctx->bgtab, &ctx->bq, &ctx->bpair, &ctx->btp, &ctx->btprow, &ctx->brqd, &ctx->brqn, &ctx->breps, &ctx->brqT, &ctx->brstores, &ctx->brxi, &ctx->brf, &ctx->brsout, &ctx->brsst, &ctx->brmaps,
                                &ctx->brY, &ctx->brS2, &ctx->brshift, &ctx->brres, &ctx->brst, &ctx->bqX, &ctx->bqst, &ctx->bqin, &ctx->bqidx, &ctx->bqout,
-                               &ctx->bthin, &ctx->bthout, &ctx->bpcgrid, &ctx->bpcin, &ctx->bpcdraw, &ctx->bpcout, &ctx->bpcT, &ctx->bpcq};
+                               &ctx->bthin, &ctx->bthout, &ctx->bpcgrid, &ctx->bpcin, &ctx->bpcdraw, &ctx->bpcout, &ctx->bpcT, &ctx->bpcq, &ctx->bcarma, &ctx->bcarmaout};
     for (auto* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto& e : ctx->ev)
@@ -1087,7 +1091,7 @@ int pioran_ctx_trim(pioran_ctx* ctx)
                                &ctx->bS2, &ctx->bout, &ctx->bst, &ctx->bscratch, &ctx->bK, &ctx->bwork, &ctx->bshift, &ctx->bgtab, &ctx->bq, &ctx->bpair, &ctx->btp, &ctx->btprow,
                                &ctx->blstab, &ctx->blsaux, &ctx->brqd, &ctx->brqn, &ctx->breps, &ctx->brqT, &ctx->brstores, &ctx->brxi, &ctx->brf, &ctx->brsout, &ctx->brsst, &ctx->brmaps,
                                &ctx->brY, &ctx->brS2, &ctx->brshift, &ctx->brres, &ctx->brst, &ctx->bqX, &ctx->bqst, &ctx->bqin, &ctx->bqidx, &ctx->bqout,
-                               &ctx->bthin, &ctx->bthout, &ctx->bpcgrid, &ctx->bpcin, &ctx->bpcdraw, &ctx->bpcout, &ctx->bpcT, &ctx->bpcq};
+                               &ctx->bthin, &ctx->bthout, &ctx->bpcgrid, &ctx->bpcin, &ctx->bpcdraw, &ctx->bpcout, &ctx->bpcT, &ctx->bpcq, &ctx->bcarma, &ctx->bcarmaout};
     for (auto* b : bufs) {
         if (b->p) (void)hipFree(b->p);
         b->p = nullptr;
@@ -2838,6 +2842,349 @@ int pioran_psd_check_summary(pioran_ctx* ctx, int64_t B, int model, int64_t n_co
     if (mean && (rc = download(ctx, mean, dq + o_mean, 4 * (size_t)F * sizeof(double)))) return rc;
     if (status && (rc = download(ctx, status, dr.status, (size_t)B * sizeof(int32_t)))) return rc;
     if (kept && (rc = download(ctx, kept, dkept, sizeof(int32_t)))) return rc;
+    SYNC(ctx);
+    return PIORAN_OK;
+}
+
+// ---- CARMA(p, q) models from their sampled parameters (carma.hip) ---------------------------------------------------------------------------
+static const char* const kCarmaCoefsName = "carma (sampled parameters to coefficients)";
+static const char* const kCarmaVjpName = "carma (reverse mode of the coefficients)";
+static const char* const kCarmaPsdName = "carma (power spectral density)";
+
+// The batch's inputs on the device (bcarma): in1 [B][n1] | in2 [B][n2] | norm [B] | flags [B] (int32) — form 0: qa, qb (n1 = p, n2 = q), form 1: roots,
+// beta (n1 = 2 p, n2 = q + 1)
+struct CarmaDraws {
+    int p = 0, q = 0, J = 0, form = 0, integrated = 0, n1 = 0, n2 = 0;
+    double f_lo = 0.0, f_hi = 0.0;
+    const double *in1 = nullptr, *in2 = nullptr, *norm = nullptr;
+    int32_t* flags = nullptr;
+};
+
+// what every CARMA entry can see without looking at an array: NULL or inconsistent arguments first, then the orders
+static int carma_refuse(const void* handle, int64_t B, int p, int q, int form, const void* in1, const void* in2, const void* norm, double f_lo, double f_hi)
+{
+    if (!handle || B < 1 || !in1 || !norm || form < 0 || form > 1) return PIORAN_ERR_ARG;
+    if (!std::isfinite(f_lo) || !std::isfinite(f_hi) || f_lo < 0.0 || f_hi < f_lo || (f_hi > 0.0 && !(f_lo < f_hi))) return PIORAN_ERR_ARG;
+    if (p < 1 || p > pioran_carma_max_order() || q < 0 || q > p) return PIORAN_ERR_UNSUPPORTED;
+    if (!in2 && !(form == 0 && q == 0)) return PIORAN_ERR_ARG;
+    return PIORAN_OK;
+}
+
+static int stage_carma(pioran_ctx* ctx, int64_t B, int p, int q, int form, const double* in1, const double* in2, const double* norm, int integrated,
+                       double f_lo, double f_hi, CarmaDraws& cd)
+{
+    cd.p = p; cd.q = q; cd.J = (p + 1) / 2; cd.form = form; cd.integrated = integrated != 0; cd.f_lo = f_lo; cd.f_hi = f_hi;
+    cd.n1 = form == 0 ? p : 2 * p; cd.n2 = form == 0 ? q : q + 1;
+    const size_t b1 = (size_t)B * cd.n1, b2 = (size_t)B * cd.n2;
+    int rc;
+    if ((rc = ensure(ctx, ctx->bcarma, (b1 + b2 + (size_t)B + ((size_t)B + 1) / 2) * sizeof(double)))) return rc;
+    double* dev = (double*)ctx->bcarma.p;
+    if ((rc = upload_to(ctx, dev, in1, b1 * sizeof(double)))) return rc;
+    if (b2 && (rc = upload_to(ctx, dev + b1, in2, b2 * sizeof(double)))) return rc;
+    if ((rc = upload_to(ctx, dev + b1 + b2, norm, (size_t)B * sizeof(double)))) return rc;
+    cd.in1 = dev; cd.in2 = b2 ? dev + b1 : nullptr; cd.norm = dev + b1 + b2; cd.flags = (int32_t*)(dev + b1 + b2 + B);
+    return PIORAN_OK;
+}
+
+// carma_coefs_kernel on the staged batch: (a, b, c, d) [B][J] into bA .. bD, where the value and gradient bodies read a batch's coefficients
+static int carma_coefs_to_draws(pioran_ctx* ctx, int64_t B, const CarmaDraws& cd, bool timed)
+{
+    int rc;
+    const size_t bj = (size_t)B * (size_t)cd.J * sizeof(double);
+    if ((rc = ensure_each(ctx, {{&ctx->bA, bj}, {&ctx->bB, bj}, {&ctx->bC, bj}, {&ctx->bD, bj}}))) return rc;
+    g_last_kernel = kCarmaCoefsName;
+    if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
+    if ((rc = pioran_launch_carma_coefs(B, cd.p, cd.q, cd.form, cd.in1, cd.in2, cd.norm, cd.integrated, cd.f_lo, cd.f_hi, (double*)ctx->bA.p,
+                                        (double*)ctx->bB.p, (double*)ctx->bC.p, (double*)ctx->bD.p, cd.flags, ctx->stream))) {
+        if (rc == PIORAN_ERR_HIP) ctx->last_err = "carma coefficient launch failed";
+        return rc;
+    }
+    if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
+    return PIORAN_OK;
+}
+
+int pioran_carma_coefs_batch(pioran_ctx* ctx, int64_t B, int p, int q, int form, const double* qa_or_roots, const double* qb_or_beta, const double* norm,
+                             int is_integrated_power, double f_lo, double f_hi, double* A, double* Bc, double* C, double* Dd, int32_t* flags)
+{
+    if (const int rc = carma_refuse(ctx, B, p, q, form, qa_or_roots, qb_or_beta, norm, f_lo, f_hi)) return rc;
+    if (!A || !Bc || !C || !Dd) return PIORAN_ERR_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    PendingGuard guard(ctx);
+    CarmaDraws cd;
+    int rc;
+    if ((rc = stage_carma(ctx, B, p, q, form, qa_or_roots, qb_or_beta, norm, is_integrated_power, f_lo, f_hi, cd))) return rc;
+    if ((rc = carma_coefs_to_draws(ctx, B, cd, ctx->opt.carma_events != 0))) return rc;
+    const size_t bj = (size_t)B * (size_t)cd.J * sizeof(double);
+    if ((rc = download(ctx, A, ctx->bA.p, bj))) return rc;
+    if ((rc = download(ctx, Bc, ctx->bB.p, bj))) return rc;
+    if ((rc = download(ctx, C, ctx->bC.p, bj))) return rc;
+    if ((rc = download(ctx, Dd, ctx->bD.p, bj))) return rc;
+    if (flags && (rc = download(ctx, flags, cd.flags, (size_t)B * sizeof(int32_t)))) return rc;
+    SYNC(ctx);
+    return PIORAN_OK;
+}
+
+// (ga, gb, gc, gd) [B][J] of the caller through carma_vjp_kernel on the staged batch (quad form) to the caller's grad_qa [B][p], grad_qb [B][q] (may be
+// NULL for q = 0), grad_norm [B]
+static int carma_vjp_from_host(pioran_ctx* ctx, int64_t B, const CarmaDraws& cd, const double* ga, const double* gb, const double* gc, const double* gd,
+                               double* grad_qa, double* grad_qb, double* grad_norm, bool timed)
+{
+    int rc;
+    const size_t bj = (size_t)B * (size_t)cd.J, np = (size_t)B * cd.p, nq = (size_t)B * cd.q;
+    if ((rc = ensure(ctx, ctx->bK, 4 * bj * sizeof(double)))) return rc;
+    if ((rc = ensure(ctx, ctx->bcarmaout, (np + nq + (size_t)B) * sizeof(double)))) return rc;
+    double* dg = (double*)ctx->bK.p;
+    const double* host[4] = {ga, gb, gc, gd};
+    for (int k = 0; k < 4; ++k)
+        if ((rc = upload_to(ctx, dg + k * bj, host[k], bj * sizeof(double)))) return rc;
+    double* dqa = (double*)ctx->bcarmaout.p;
+    g_last_kernel = kCarmaVjpName;
+    if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
+    if ((rc = pioran_launch_carma_vjp(B, cd.p, cd.q, cd.in1, cd.in2, cd.norm, cd.integrated, cd.f_lo, cd.f_hi, dg, dg + bj, dg + 2 * bj, dg + 3 * bj, dqa,
+                                      dqa + np, dqa + np + nq, ctx->stream))) {
+        if (rc == PIORAN_ERR_HIP) ctx->last_err = "carma reverse-mode launch failed";
+        return rc;
+    }
+    if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
+    if ((rc = download(ctx, grad_qa, dqa, np * sizeof(double)))) return rc;
+    if (nq && grad_qb && (rc = download(ctx, grad_qb, dqa + np, nq * sizeof(double)))) return rc;
+    return download(ctx, grad_norm, dqa + np + nq, (size_t)B * sizeof(double));
+}
+
+int pioran_carma_vjp_batch(pioran_ctx* ctx, int64_t B, int p, int q, const double* qa, const double* qb, const double* norm, int is_integrated_power,
+                           const double* ga, const double* gb, const double* gc, const double* gd, double* grad_qa, double* grad_qb, double* grad_norm)
+{
+    if (const int rc = carma_refuse(ctx, B, p, q, 0, qa, qb, norm, 0.0, 0.0)) return rc;
+    if (!ga || !gb || !gc || !gd || !grad_qa || !grad_norm || (q > 0 && !grad_qb)) return PIORAN_ERR_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    PendingGuard guard(ctx);
+    CarmaDraws cd;
+    int rc;
+    if ((rc = stage_carma(ctx, B, p, q, 0, qa, qb, norm, is_integrated_power, 0.0, 0.0, cd))) return rc;
+    if ((rc = carma_vjp_from_host(ctx, B, cd, ga, gb, gc, gd, grad_qa, grad_qb, grad_norm, ctx->opt.carma_events != 0))) return rc;
+    SYNC(ctx);
+    return PIORAN_OK;
+}
+
+// the frequencies of a PSD call onto the device, behind the per-draw workspace in bcarmaout: roots [B][p][2] | beta [B][q + 1] | factor [B] | freq [F] |
+// status [B] (int32)
+struct CarmaPsdWork { double *roots, *betas, *scale, *freq; int32_t* status; };
+static int carma_psd_stage(pioran_ctx* ctx, int64_t B, const CarmaDraws& cd, int64_t F, const double* freq, CarmaPsdWork& w)
+{
+    const size_t nr = (size_t)B * 2 * cd.p, nb = (size_t)B * (cd.q + 1);
+    int rc;
+    if ((rc = ensure(ctx, ctx->bcarmaout, (nr + nb + (size_t)B + (size_t)F + ((size_t)B + 1) / 2) * sizeof(double)))) return rc;
+    double* dev = (double*)ctx->bcarmaout.p;
+    w = {dev, dev + nr, dev + nr + nb, dev + nr + nb + B, (int32_t*)(dev + nr + nb + B + F)};
+    return upload_to(ctx, w.freq, freq, (size_t)F * sizeof(double));
+}
+
+static int carma_psd_refuse(int64_t F, const double* freq, const void* any_output)
+{
+    if (!freq || !any_output || F < 1) return PIORAN_ERR_ARG;
+    for (int64_t f = 0; f < F; ++f)
+        if (!(std::isfinite(freq[f]) && freq[f] > 0.0)) return PIORAN_ERR_ARG;
+    return PIORAN_OK;
+}
+
+// draws [b0, b0 + nb) of the staged batch through the two PSD kernels into psd [nb][F]
+static int carma_psd_chunk(pioran_ctx* ctx, const CarmaDraws& cd, const CarmaPsdWork& w, int64_t b0, int64_t nb, int64_t F, int times_f, double* psd, bool timed)
+{
+    g_last_kernel = kCarmaPsdName;
+    if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
+    const int rc = pioran_launch_carma_psd(nb, cd.p, cd.q, cd.form, cd.in1 + b0 * cd.n1, cd.in2 ? cd.in2 + b0 * cd.n2 : nullptr, cd.norm + b0, cd.integrated,
+                                           cd.f_lo, cd.f_hi, F, w.freq, times_f != 0, w.roots + b0 * 2 * cd.p, w.betas + b0 * (cd.q + 1), w.scale + b0, psd,
+                                           w.status + b0, ctx->stream);
+    if (rc == PIORAN_ERR_HIP) ctx->last_err = "carma psd launch failed";
+    if (rc) return rc;
+    if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
+    return PIORAN_OK;
+}
+
+int pioran_carma_psd_batch(pioran_ctx* ctx, int64_t B, int p, int q, int form, const double* qa_or_roots, const double* qb_or_beta, const double* norm,
+                           int is_integrated_power, double f_lo, double f_hi, int64_t F, const double* freq, int times_f, double* psd, int32_t* status)
+{
+    if (const int rc = carma_refuse(ctx, B, p, q, form, qa_or_roots, qb_or_beta, norm, f_lo, f_hi)) return rc;
+    if (const int rc = carma_psd_refuse(F, freq, psd)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    PendingGuard guard(ctx);
+    CarmaDraws cd;
+    CarmaPsdWork w;
+    int rc;
+    if ((rc = stage_carma(ctx, B, p, q, form, qa_or_roots, qb_or_beta, norm, is_integrated_power, f_lo, f_hi, cd))) return rc;
+    if ((rc = carma_psd_stage(ctx, B, cd, F, freq, w))) return rc;
+    // the array of a chunk of draws, chunk by chunk under the workspace budget, as the PSD check's host form goes
+    auto out_bytes = [&](int64_t nb) { return (size_t)nb * (size_t)F * sizeof(double); };
+    int64_t chunk = B;
+    if ((rc = size_chunk(ctx, chunk, {&ctx->bpcout}, out_bytes, [&](int64_t nb) { return ensure(ctx, ctx->bpcout, out_bytes(nb)); }))) return rc;
+    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+        const int64_t nb = std::min(B - b0, chunk);
+        if ((rc = carma_psd_chunk(ctx, cd, w, b0, nb, F, times_f, (double*)ctx->bpcout.p, ctx->opt.carma_events != 0 && b0 == 0))) return rc;
+        if ((rc = download(ctx, psd + b0 * F, ctx->bpcout.p, out_bytes(nb)))) return rc;
+        if (status && (rc = download(ctx, status + b0, w.status + b0, (size_t)nb * sizeof(int32_t)))) return rc;
+        SYNC(ctx);   // the chunk's buffer is reused by the next
+    }
+    return PIORAN_OK;
+}
+
+int pioran_carma_psd_summary(pioran_ctx* ctx, int64_t B, int p, int q, int form, const double* qa_or_roots, const double* qb_or_beta, const double* norm,
+                             int is_integrated_power, double f_lo, double f_hi, int64_t F, const double* freq, int times_f, int64_t Q, const double* probs,
+                             double* quant, int32_t* status, int32_t* kept)
+{
+    if (const int rc = carma_refuse(ctx, B, p, q, form, qa_or_roots, qb_or_beta, norm, f_lo, f_hi)) return rc;
+    if (const int rc = carma_psd_refuse(F, freq, quant)) return rc;
+    if (!probs || Q < 1) return PIORAN_ERR_ARG;
+    for (int64_t k = 0; k < Q; ++k)
+        if (!(probs[k] >= 0.0 && probs[k] <= 1.0)) return PIORAN_ERR_ARG;   // NaN included
+    if (B > pioran_quantiles_max_draws()) return PIORAN_ERR_UNSUPPORTED;    // the draws of a frequency are sorted inside one workgroup's LDS
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    PendingGuard guard(ctx);
+    const size_t x_bytes = (size_t)B * (size_t)F * sizeof(double);
+    if (!ws_fits(ctx, ctx->bpcout, x_bytes)) { ctx->last_err = "the array does not fit the context's workspace budget"; return PIORAN_ERR_ALLOC; }
+    CarmaDraws cd;
+    CarmaPsdWork w;
+    int rc;
+    if ((rc = stage_carma(ctx, B, p, q, form, qa_or_roots, qb_or_beta, norm, is_integrated_power, f_lo, f_hi, cd))) return rc;
+    if ((rc = carma_psd_stage(ctx, B, cd, F, freq, w))) return rc;
+    // bpcq = probs [Q] | quant [Q][F] | kept
+    const size_t o_quant = (size_t)Q, o_kept = o_quant + (size_t)Q * F;
+    if ((rc = ensure_each(ctx, {{&ctx->bpcout, x_bytes}, {&ctx->bpcq, (o_kept + 1) * sizeof(double)}}))) return rc;
+    double* dq = (double*)ctx->bpcq.p;
+    if ((rc = upload_to(ctx, dq, probs, (size_t)Q * sizeof(double)))) return rc;
+    if ((rc = carma_psd_chunk(ctx, cd, w, 0, B, F, times_f, (double*)ctx->bpcout.p, ctx->opt.carma_events != 0))) return rc;
+    // per frequency, over the draws with status 0: the reduction of pioran_quantiles_batch_dev on the [B][F] array
+    int32_t* dkept = (int32_t*)(dq + o_kept);
+    if ((rc = pioran_launch_quantiles(B, F, F, (const double*)ctx->bpcout.p, w.status, nullptr, F, nullptr, nullptr, nullptr, Q, dq, dq + o_quant, nullptr, dkept,
+                                      ctx->stream)))
+        return rc;
+    if ((rc = download(ctx, quant, dq + o_quant, (size_t)Q * F * sizeof(double)))) return rc;
+    if (status && (rc = download(ctx, status, w.status, (size_t)B * sizeof(int32_t)))) return rc;
+    if (kept && (rc = download(ctx, kept, dkept, sizeof(int32_t)))) return rc;
+    SYNC(ctx);
+    return PIORAN_OK;
+}
+
+// The coefficients of the staged batch made on the device (bA .. bD), and what the host needs of them to route the call as the host-pointer entries
+// route per-draw (c, d): the flags and (b, c, d) — with `a` too for the callers that go on from host arrays
+static int carma_coefs_fetch(pioran_ctx* ctx, int64_t B, const CarmaDraws& cd, std::vector<double>* hA, std::vector<double>& hB, std::vector<double>& hC,
+                             std::vector<double>& hD, std::vector<int32_t>& hflags)
+{
+    int rc;
+    if ((rc = carma_coefs_to_draws(ctx, B, cd, false))) return rc;
+    const size_t bj = (size_t)B * (size_t)cd.J;
+    hB.resize(bj); hC.resize(bj); hD.resize(bj); hflags.resize((size_t)B);
+    if (hA) { hA->resize(bj); if ((rc = download(ctx, hA->data(), ctx->bA.p, bj * sizeof(double)))) return rc; }
+    if ((rc = download(ctx, hB.data(), ctx->bB.p, bj * sizeof(double)))) return rc;
+    if ((rc = download(ctx, hC.data(), ctx->bC.p, bj * sizeof(double)))) return rc;
+    if ((rc = download(ctx, hD.data(), ctx->bD.p, bj * sizeof(double)))) return rc;
+    if ((rc = download(ctx, hflags.data(), cd.flags, (size_t)B * sizeof(int32_t)))) return rc;
+    SYNC(ctx);
+    return PIORAN_OK;
+}
+
+int pioran_logpdf_batch_carma(pioran_ds* ds, int64_t B, int p, int q, const double* qa, const double* qb, const double* norm, int is_integrated_power,
+                              double f_lo, double f_hi, const double* mu, const double* nu, const double* shift, double* out, int32_t* status,
+                              double* A_out, double* Bc_out, double* C_out, double* Dd_out)
+{
+    if (const int rc = carma_refuse(ds, B, p, q, 0, qa, qb, norm, f_lo, f_hi)) return rc;
+    if (!out) return PIORAN_ERR_ARG;
+    pioran_ctx* ctx = ds->ctx;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    PendingGuard guard(ctx);
+    CarmaDraws cd;
+    int rc;
+    if ((rc = stage_carma(ctx, B, p, q, 0, qa, qb, norm, is_integrated_power, f_lo, f_hi, cd))) return rc;
+    std::vector<double> hB, hC, hD;
+    std::vector<int32_t> hflags;
+    if ((rc = carma_coefs_fetch(ctx, B, cd, nullptr, hB, hC, hD, hflags))) return rc;
+    const int64_t J = cd.J;
+    const size_t bj = (size_t)B * (size_t)J * sizeof(double), bn = (size_t)B * (size_t)ds->N * sizeof(double);
+    if (mu && (rc = upload(ctx, ctx->bmu, mu, B * sizeof(double)))) return rc;
+    if (nu && (rc = upload(ctx, ctx->bnu, nu, B * sizeof(double)))) return rc;
+    const double *dY = nullptr, *dS2 = nullptr;
+    if (shift) {   // the transformed series of the whole batch, as pioran_celerite_logl_batch_shift builds them
+        if ((rc = ensure(ctx, ctx->bY, bn))) return rc;
+        if ((rc = ensure(ctx, ctx->bS2, bn))) return rc;
+        if ((rc = upload(ctx, ctx->bshift, shift, B * sizeof(double)))) return rc;
+        if ((rc = pioran_launch_shift_transform(ds->N, B, ds->y, ds->s2, (const double*)ctx->bshift.p, (double*)ctx->bY.p, (double*)ctx->bS2.p, ctx->stream)))
+            return rc;
+        dY = (const double*)ctx->bY.p; dS2 = (const double*)ctx->bS2.p;
+    }
+    const DrawChunk dev{(const double*)ctx->bA.p, (const double*)ctx->bB.p, (const double*)ctx->bC.p, (const double*)ctx->bD.p,
+                        mu ? (const double*)ctx->bmu.p : nullptr, nu ? (const double*)ctx->bnu.p : nullptr, dY, dS2};
+    // from here on the routing of batch_host_impl with cd_shared = 0, the draws already on the device: one draw, or the same (c, d) in every draw, is the
+    // shared case; else mixed mode where its plan takes the batch; else the per-draw-(c, d) body
+    bool same = true;
+    for (int64_t b = 1; b < B && same; ++b)
+        same = !std::memcmp(hC.data() + b * J, hC.data(), (size_t)J * sizeof(double)) && !std::memcmp(hD.data() + b * J, hD.data(), (size_t)J * sizeof(double));
+    bool done = false;
+    if (!same && !ctx->opt.no_mixed) {
+        const MixedSource src{dev, true, false};
+        rc = mixed_core(ds, B, J, classify_terms(B, J, hB.data(), hC.data(), hD.data(), true), hC.data(), hD.data(), src, out, status);
+        if (rc < 0) return rc;
+        done = rc == 1;
+    }
+    if (!done) {
+        if (same && (rc = prepare_shared(ds, B, J, hB.data(), hC.data(), hD.data()))) return rc;
+        if ((rc = ensure_results(ctx, B))) return rc;
+        rc = same ? batch_dev_impl(ds, ds->host, B, dev.A, dev.Bc, dev.mu, dev.nu, dY, dS2, (double*)ctx->bout.p, (int32_t*)ctx->bst.p)
+                  : pioran_celerite_logl_batch_dev_cd(ds, B, J, dev.A, dev.Bc, dev.C, dev.D, dev.mu, dev.nu, dY, dS2, (double*)ctx->bout.p, (int32_t*)ctx->bst.p);
+        if (rc) return rc;
+        if ((rc = download_results(ctx, out, status, 0, B))) return rc;
+    }
+    if (A_out && (rc = download(ctx, A_out, ctx->bA.p, bj))) return rc;
+    if (Bc_out && (rc = download(ctx, Bc_out, ctx->bB.p, bj))) return rc;
+    if (C_out && (rc = download(ctx, C_out, ctx->bC.p, bj))) return rc;
+    if (Dd_out && (rc = download(ctx, Dd_out, ctx->bD.p, bj))) return rc;
+    SYNC(ctx);
+    for (int64_t b = 0; b < B; ++b)   // a rejected draw ran on benign coefficients: its results are overwritten
+        if (hflags[(size_t)b]) { out[b] = -INFINITY; if (status) status[b] = 3; }
+    return PIORAN_OK;
+}
+
+int pioran_logpdf_batch_carma_grad(pioran_ds* ds, int64_t B, int p, int q, const double* qa, const double* qb, const double* norm, int is_integrated_power,
+                                   double f_lo, double f_hi, const double* mu, const double* nu, const double* shift, double* out, int32_t* status,
+                                   double* grad_qa, double* grad_qb, double* grad_norm, double* grad_nu, double* grad_mu, double* grad_shift, double* grad_a,
+                                   double* grad_b, double* grad_c, double* grad_d)
+{
+    if (const int rc = carma_refuse(ds, B, p, q, 0, qa, qb, norm, f_lo, f_hi)) return rc;
+    if (!out || !grad_qa || !grad_norm || (q > 0 && !grad_qb)) return PIORAN_ERR_ARG;
+    if ((nu == nullptr) != (grad_nu == nullptr) || (mu == nullptr) != (grad_mu == nullptr) || (shift == nullptr) != (grad_shift == nullptr)) return PIORAN_ERR_ARG;
+    const int n_inter = (grad_a != nullptr) + (grad_b != nullptr) + (grad_c != nullptr) + (grad_d != nullptr);
+    if (n_inter != 0 && n_inter != 4) return PIORAN_ERR_ARG;
+    pioran_ctx* ctx = ds->ctx;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    CarmaDraws cd;
+    int rc;
+    std::vector<double> hA, hB, hC, hD;
+    std::vector<int32_t> hflags;
+    {
+        PendingGuard guard(ctx);
+        if ((rc = stage_carma(ctx, B, p, q, 0, qa, qb, norm, is_integrated_power, f_lo, f_hi, cd))) return rc;
+        if ((rc = carma_coefs_fetch(ctx, B, cd, &hA, hB, hC, hD, hflags))) return rc;
+    }
+    // the reverse mode of the host-pointer gradient entries on these coefficients, (c, d) per draw: their routing (all draws in one launch of the windowed
+    // reverse mode where the shape fits it; one draw, and every draw of a shifted call, as a batch of its own) and their kernels
+    const int64_t J = cd.J;
+    const size_t bj = (size_t)B * (size_t)J;
+    std::vector<double> inter;
+    double *ga = grad_a, *gb = grad_b, *gc = grad_c, *gd = grad_d;
+    if (!n_inter) { inter.resize(4 * bj); ga = inter.data(); gb = ga + bj; gc = gb + bj; gd = gc + bj; }
+    std::vector<int32_t> st((size_t)B, 0);
+    if ((rc = logl_grad_impl(ds, B, J, hA.data(), hB.data(), hC.data(), hD.data(), 0, mu, nu, shift, out, st.data(), {ga, gb, gc, gd, grad_nu, grad_mu, nullptr, nullptr},
+                             grad_shift)))
+        return rc;
+    for (int64_t b = 0; b < B; ++b) {   // a rejected draw ran on benign coefficients: log L = -inf, status 3, exact zeros in every gradient row
+        if (!hflags[(size_t)b]) continue;
+        out[b] = -INFINITY; st[(size_t)b] = 3;
+        for (double* g : {ga, gb, gc, gd}) std::fill(g + b * J, g + (b + 1) * J, 0.0);
+        if (grad_nu) grad_nu[b] = 0.0;
+        if (grad_mu) grad_mu[b] = 0.0;
+        if (grad_shift) grad_shift[b] = 0.0;
+    }
+    if (status) std::memcpy(status, st.data(), (size_t)B * sizeof(int32_t));
+    PendingGuard guard(ctx);
+    if ((rc = carma_vjp_from_host(ctx, B, cd, ga, gb, gc, gd, grad_qa, grad_qb, grad_norm, false))) return rc;
     SYNC(ctx);
     return PIORAN_OK;
 }

@@ -59,6 +59,8 @@ struct ScanOptions {
                           // 4 .. 7 (before approx_kernel | after it | before approx_vjp_kernel | after it)
     int pc_events = 0;    // PSD check (capi.hip psd_check_chunk), timing tools ONLY: 1 = a call's first chunk records the context's event slots
                           // 4 .. 6 (before psd_check_draw_kernel | after it | after psd_check_eval_kernel)
+    int carma_events = 0; // CARMA entries (capi.hip pioran_carma_*_batch), timing tools ONLY: 1 = a call records the context's event slots 4 | 5 around its
+                          // kernel (the PSD form: its first chunk's two kernels)
 };
 
 struct ScanParams {
@@ -297,6 +299,19 @@ int pioran_launch_approx(int64_t B, int model, int P, int J, int basis, int inte
 int pioran_launch_approx_vjp(int64_t B, int model, int P, int J, int basis, const double* sp, const double* w /*pioran_approx_weights_host*/,
                              const double* LU, const int32_t* piv, const double* theta, const double* norm, const double* ga, const double* gb,
                              double* scratch, double* gtheta, double* gnorm, hipStream_t stream);
+// carma.hip: CARMA(p, q) models — sampled parameters (form 0: quadratic factors qa [B][p], qb [B][q]; form 1: roots [B][p][2], beta [B][q + 1]) ->
+// celerite coefficients [B][(p + 1) / 2] and a per-draw flag (0, or the reason the draw is rejected), the reverse mode (quad form), the PSD [B][F]
+int pioran_carma_max_order();
+int pioran_launch_carma_coefs(int64_t B, int p, int q, int form, const double* in1, const double* in2, const double* norm, int integrated, double f_lo,
+                              double f_hi /*both 0: no bounds*/, double* A, double* Bc, double* C, double* D, int32_t* flags /*or nullptr*/,
+                              hipStream_t stream);
+int pioran_launch_carma_vjp(int64_t B, int p, int q, const double* qa, const double* qb, const double* norm, int integrated, double f_lo, double f_hi,
+                            const double* ga, const double* gb, const double* gc, const double* gd, double* gqa, double* gqb, double* gnorm,
+                            hipStream_t stream);
+// roots [B][p][2], betas [B][q + 1], scale [B]: workspace the per-draw kernel leaves for the frequency kernel; status [B]: 0, or 3 with a NaN row
+int pioran_launch_carma_psd(int64_t B, int p, int q, int form, const double* in1, const double* in2, const double* norm, int integrated, double f_lo,
+                            double f_hi, int64_t F, const double* freq, int times_f, double* roots, double* betas, double* scale, double* psd,
+                            int32_t* status, hipStream_t stream);
 // table.hip (diagnostics)
 int pioran_launch_fma_stream(int blocks, int iters, double* scratch, double* flop, hipStream_t stream);
 // dense.hip

@@ -1,7 +1,7 @@
 // The PSD model against its basis-function approximation for a batch of draws: what sample_approx_model (src/plots_diagnostics.jl:195-213), the
 // prior check run_diagnostics (:232-240) and the posterior check plot_psd_ppc (:371-487) evaluate draw by draw on the host.  The definition,
-// operation by operation, is tools/psd_check_proto.py.  Continuum models only (the two bending power laws of psd_device.h); QPO features, PowerLaw
-// and the CARMA variant plot_psd_ppc_CARMA are not covered.
+// operation by operation, is tools/psd_check_proto.py.  Continuum models only (the two bending power laws of psd_device.h); QPO features and PowerLaw
+// are not covered.  (plot_psd_ppc_CARMA: carma.hip.)
 //
 //   psd_check_draw_kernel   one thread per draw, as approx_kernel: amplitudes amp = B^-1 p (the first half of approx_kernel, the same device code:
 //       psd_device.h), the normalising integral of get_norm_psd, the model at the first frequency passed, and the draw's status.

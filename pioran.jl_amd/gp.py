@@ -44,6 +44,31 @@ def _theta_args(model, theta, norm, basis_function):
     return mid, 0 if basis_function == "SHO" else 1, theta, _f64(np.broadcast_to(norm, (theta.shape[0],)))
 
 
+def _carma_args(p, q, qa, qb, norm, r_alpha, beta):
+    """(p, q, form, in1, in2, norm (B,)) of the CARMA entries: form 0 with qa (B, p), qb (B, q) (None for q = 0), or form 1 with the roots as
+    (B, p, 2) = (re, im) and beta (B, q + 1)."""
+    p, q = int(p), int(q)
+    if r_alpha is None:
+        if qa is None:
+            raise ValueError("give the quadratic factors (qa, qb) or the roots and coefficients (r_alpha, beta)")
+        in1 = _f64(np.atleast_2d(qa))
+        B = in1.shape[0]
+        in2 = np.zeros((B, 0)) if qb is None else _f64(np.asarray(qb, dtype=np.float64).reshape(B, -1))
+        if in1.shape[1] != p or in2.shape[1] != q:
+            raise ValueError("qa must be (B, p) and qb (B, q)")
+        form, in2 = 0, (in2 if q else None)
+    else:
+        r = np.atleast_2d(np.asarray(r_alpha, dtype=complex))
+        B = r.shape[0]
+        in2 = _f64(np.atleast_2d(beta))
+        if r.shape[1] != p:
+            raise ValueError("The length of the roots of the autoregressive polynomial must be equal to the order of the autoregressive polynomial")
+        if in2.shape != (B, q + 1):
+            raise ValueError("The length of the moving average coefficients must be equal to q + 1")
+        form, in1 = 1, _f64(np.stack([r.real, r.imag], axis=-1))
+    return p, q, form, in1, in2, _f64(np.broadcast_to(norm, (B,)))
+
+
 class Context:
     """One GPU + one HIP stream (pioran_ctx).  One per host thread / rank."""
 
@@ -284,6 +309,64 @@ class Context:
                                                        int(bool(normalise)), int(bool(times_f)), Q, _ptr(probs), _ptr(out["quant"]), _ptr(out.get("mean")),
                                                        _ptr(out.get("meta")), _ptr(out["status"]), ctypes.cast(ctypes.byref(kept), ctypes.c_void_p)),
                    self._h)
+        out["kept"] = kept.value
+        return out
+
+    # -- CARMA(p, q) models from their sampled parameters ---------------------------------------
+    def carma_coefs(self, p, q, qa=None, qb=None, norm=1.0, *, r_alpha=None, beta=None, is_integrated_power=True, bounds=None, return_flags=False):
+        """CARMA_celerite_coefs for B draws on the device (pioran_carma_coefs_batch).  Quad form: qa (B, p), qb (B, q), the quadratic factors the
+        reference's models sample (r_alpha = quad2roots(qa), beta = roots2coeffs(quad2roots(qb))); roots form: r_alpha (B, p) complex, beta (B, q + 1).
+        norm: scalar or (B,); bounds: (f_lo, f_hi) of check_roots_bounds, or None.  Returns A, Bc, C, Dd (B, J), J = (p + 1) // 2, and with
+        return_flags the per-draw flag: 0, or why the draw is rejected (1 non-finite parameter, 2 a pair that is not a conjugate pair, 3 a root
+        with real part >= 0, 4 outside the bounds); a rejected draw has (1, 0, 1, 0) in every term."""
+        p, q, form, in1, in2, norm = _carma_args(p, q, qa, qb, norm, r_alpha, beta)
+        B, J = in1.shape[0], (p + 1) // 2
+        f_lo, f_hi = (0.0, 0.0) if bounds is None else map(float, bounds)
+        A, Bc, C, Dd = (np.empty((B, J)) for _ in range(4))
+        flags = np.zeros(B, dtype=np.int32)
+        _lib.check(_lib.lib().pioran_carma_coefs_batch(self._h, B, p, q, form, _ptr(in1), _ptr(in2), _ptr(norm), int(bool(is_integrated_power)), f_lo,
+                                                       f_hi, _ptr(A), _ptr(Bc), _ptr(C), _ptr(Dd), _ptr(flags)), self._h)
+        return (A, Bc, C, Dd, flags) if return_flags else (A, Bc, C, Dd)
+
+    def carma_vjp(self, p, q, qa, qb, norm, grad_a, grad_b, grad_c, grad_d, *, is_integrated_power=True):
+        """Chain rule through quad2roots and CARMA_celerite_coefs on the device (pioran_carma_vjp_batch): dL/da, dL/db, dL/dc, dL/dd (B, J) ->
+        dL/dqa (B, p), dL/dqb (B, q), dL/dnorm (B,).  Rejected draws get exact zeros."""
+        p, q, _, qa, qb, norm = _carma_args(p, q, qa, qb, norm, None, None)
+        B, J = qa.shape[0], (p + 1) // 2
+        g = [_f64(x) for x in (grad_a, grad_b, grad_c, grad_d)]
+        if any(x.shape != (B, J) for x in g):
+            raise ValueError("grad_a, grad_b, grad_c, grad_d must be (B, J)")
+        gqa, gqb, gnorm = np.empty((B, p)), np.empty((B, q)), np.empty(B)
+        _lib.check(_lib.lib().pioran_carma_vjp_batch(self._h, B, p, q, _ptr(qa), _ptr(qb), _ptr(norm), int(bool(is_integrated_power)), *map(_ptr, g),
+                                                     _ptr(gqa), _ptr(gqb) if q else None, _ptr(gnorm)), self._h)
+        return gqa, gqb, gnorm
+
+    def carma_psd(self, p, q, freq, qa=None, qb=None, norm=1.0, *, r_alpha=None, beta=None, is_integrated_power=True, bounds=None, times_f=False,
+                  return_status=False):
+        """evaluate(::CARMA, f) for B draws at the frequencies freq (F,): (B, F) (pioran_carma_psd_batch).  The draws as in carma_coefs; times_f:
+        multiplied by the frequency (plot_f_P).  status (B,): 3, with NaN in the draw's row, for a rejected draw."""
+        p, q, form, in1, in2, norm = _carma_args(p, q, qa, qb, norm, r_alpha, beta)
+        freq = _f64(freq).reshape(-1)
+        B, F = in1.shape[0], len(freq)
+        f_lo, f_hi = (0.0, 0.0) if bounds is None else map(float, bounds)
+        psd, st = np.empty((B, F)), np.zeros(B, dtype=np.int32)
+        _lib.check(_lib.lib().pioran_carma_psd_batch(self._h, B, p, q, form, _ptr(in1), _ptr(in2), _ptr(norm), int(bool(is_integrated_power)), f_lo, f_hi,
+                                                     F, _ptr(freq), int(bool(times_f)), _ptr(psd), _ptr(st)), self._h)
+        return (psd, st) if return_status else psd
+
+    def carma_psd_summary(self, p, q, freq, qa=None, qb=None, norm=1.0, *, r_alpha=None, beta=None, is_integrated_power=True, bounds=None,
+                          times_f=False, probs=PPC_QUANTILES):
+        """carma_psd with its array kept on the device and reduced there (pioran_carma_psd_summary): a dict with quant (Q, F), the quantiles per
+        frequency over the draws with status 0, status (B,) and kept.  At most 4096 draws (the quantile kernel's limit)."""
+        p, q, form, in1, in2, norm = _carma_args(p, q, qa, qb, norm, r_alpha, beta)
+        freq, probs = _f64(freq).reshape(-1), _f64(probs).reshape(-1)
+        B, F, Q = in1.shape[0], len(freq), len(probs)
+        f_lo, f_hi = (0.0, 0.0) if bounds is None else map(float, bounds)
+        out = dict(quant=np.empty((Q, F)), status=np.zeros(B, dtype=np.int32))
+        kept = ctypes.c_int32(-1)
+        _lib.check(_lib.lib().pioran_carma_psd_summary(self._h, B, p, q, form, _ptr(in1), _ptr(in2), _ptr(norm), int(bool(is_integrated_power)), f_lo,
+                                                       f_hi, F, _ptr(freq), int(bool(times_f)), Q, _ptr(probs), _ptr(out["quant"]), _ptr(out["status"]),
+                                                       ctypes.cast(ctypes.byref(kept), ctypes.c_void_p)), self._h)
         out["kept"] = kept.value
         return out
 
@@ -672,6 +755,46 @@ class Dataset:
         if return_coefs:
             res = res + (Ao, Bo)
         return res if len(res) > 1 else res[0]
+
+    def logpdf_carma(self, p, q, qa, qb, norm, *, is_integrated_power=True, bounds=None, mu=None, nu=None, shift=None, return_status=False,
+                     return_coefs=False):
+        """(qa, qb, norm) -> log L in one call for the CARMA(p, q) models of docs/src/carma.md (pioran_logpdf_batch_carma): quad2roots,
+        CARMA_celerite_coefs and the root checks run on the device in front of the per-draw-(c, d) value path.  qa (B, p), qb (B, q); norm scalar
+        or (B,); bounds = (f_lo, f_hi) of the models' root checks or None; mu, nu, shift as in logl_batch.  A rejected draw has log L = -inf and
+        status 3 (what the models do with @addlogprob! -Inf).  return_coefs: also A, Bc, C, Dd (B, J)."""
+        p, q, _, qa, qb, norm = _carma_args(p, q, qa, qb, norm, None, None)
+        B, J = qa.shape[0], (p + 1) // 2
+        mu, nu, shift = (None if v is None else _f64(np.broadcast_to(v, (B,))) for v in (mu, nu, shift))
+        f_lo, f_hi = (0.0, 0.0) if bounds is None else map(float, bounds)
+        out, st = np.empty(B), np.zeros(B, dtype=np.int32)
+        co = [np.empty((B, J)) if return_coefs else None for _ in range(4)]
+        _lib.check(_lib.lib().pioran_logpdf_batch_carma(self._h, B, p, q, _ptr(qa), _ptr(qb), _ptr(norm), int(bool(is_integrated_power)), f_lo, f_hi,
+                                                        _ptr(mu), _ptr(nu), _ptr(shift), _ptr(out), _ptr(st), *map(_ptr, co)), self.ctx._h)
+        res = (out, st) if return_status else (out,)
+        if return_coefs:
+            res = res + tuple(co)
+        return res if len(res) > 1 else res[0]
+
+    def logpdf_carma_grad(self, p, q, qa, qb, norm, *, is_integrated_power=True, bounds=None, mu=None, nu=None, shift=None, return_coef_grads=False):
+        """log L and its gradient with respect to the SAMPLED parameters of the CARMA models (pioran_logpdf_batch_carma_grad): the coefficients, the
+        reverse mode with grad_c / grad_d and the chain back through CARMA_celerite_coefs and quad2roots.  Returns a dict: logl, status,
+        grad_qa (B, p), grad_qb (B, q), grad_norm (B,), grad_nu, grad_mu, grad_shift (None where the input is None) and, with return_coef_grads, the
+        intermediates grad_a, grad_b, grad_c, grad_d (B, J).  A rejected draw: status 3, logl = -inf, exact zeros in every gradient row."""
+        p, q, _, qa, qb, norm = _carma_args(p, q, qa, qb, norm, None, None)
+        B, J = qa.shape[0], (p + 1) // 2
+        mu, nu, shift = (None if v is None else _f64(np.broadcast_to(v, (B,))) for v in (mu, nu, shift))
+        f_lo, f_hi = (0.0, 0.0) if bounds is None else map(float, bounds)
+        out, st = np.empty(B), np.zeros(B, dtype=np.int32)
+        gqa, gqb, gnorm = np.empty((B, p)), np.empty((B, q)), np.empty(B)
+        gnu, gmu, gsh = (None if v is None else np.empty(B) for v in (nu, mu, shift))
+        co = [np.empty((B, J)) if return_coef_grads else None for _ in range(4)]
+        _lib.check(_lib.lib().pioran_logpdf_batch_carma_grad(self._h, B, p, q, _ptr(qa), _ptr(qb), _ptr(norm), int(bool(is_integrated_power)), f_lo,
+                                                             f_hi, _ptr(mu), _ptr(nu), _ptr(shift), _ptr(out), _ptr(st), _ptr(gqa), _ptr(gqb) if q else None,
+                                                             _ptr(gnorm), _ptr(gnu), _ptr(gmu), _ptr(gsh), *map(_ptr, co)), self.ctx._h)
+        res = {"logl": out, "status": st, "grad_qa": gqa, "grad_qb": gqb, "grad_norm": gnorm, "grad_nu": gnu, "grad_mu": gmu, "grad_shift": gsh}
+        if return_coef_grads:
+            res.update(zip(("grad_a", "grad_b", "grad_c", "grad_d"), co))
+        return res
 
     def logl_batch_shift_dev(self, B, dA, dBc, dmu=0, dnu=0, dshift=0, dout=0, dstatus=0):
         """Device-pointer asynchronous variant of the shifted-log-flux batch; (c, d) from prepare()."""
@@ -1195,6 +1318,41 @@ def psd_ppc(samples_psd, samples_norm, samples_nu, t, y, yerr, model, S_low=20.0
         q_approx, _, _ = _quantiles_host(r["psd_approx"], PPC_QUANTILES, r["status"])
     return dict(f=f, psd_quantiles=q_psd, psd_approx_quantiles=q_approx, mean_noise_level=mean_noise_level, median_noise_level=median_noise_level,
                 f_min=f_min, f_max=f_max, kept=kept)
+
+
+def psd_ppc_carma(samples_r_alpha, samples_beta, samples_norm, samples_nu, t, y, yerr, p, q, plot_f_P=False, n_frequencies=1000,
+                  with_log_transform=False, ctx: Context | None = None):
+    """plot_psd_ppc_CARMA(samples_r_alpha, samples_beta, samples_norm, samples_nu, t, y, yerr, p, q; ...) of src/plots_diagnostics.jl:832-936 as
+    numbers.  samples_r_alpha (B, p) complex, samples_beta (B, q + 1), one posterior sample per row.  Returns a dict with f (F,), the reference's
+    grid exp.(range(log(f_min / 10), log(10 f_max))) around the observed window f_min = 1 / T, f_max = 1 / (2 min dt); psd_quantiles (5, F) at
+    PPC_QUANTILES of evaluate(CARMA(p, q, r_alpha, beta, norm), f), multiplied by f with plot_f_P; mean_noise_level, median_noise_level (host
+    scalars; multiply by f yourself with plot_f_P as the reference's lines do); f_min, f_max of the grid; kept.
+    Up to 4096 samples: one device call (Context.carma_psd_summary); with more, the array comes from Context.carma_psd chunk by chunk and is
+    reduced on the host with the definition of tools/quantiles_proto.py."""
+    r = np.asarray(samples_r_alpha, dtype=complex)
+    be = np.asarray(samples_beta, dtype=np.float64)
+    r, be = (r.reshape(1, -1) if r.ndim == 1 else r), (be.reshape(1, -1) if be.ndim == 1 else be)
+    if p != r.shape[1]:
+        raise ValueError(f"p={p} is not equal to the number of columns in samples_rα={r.shape[1]}")
+    if q + 1 != be.shape[1]:
+        raise ValueError(f"q+1={q + 1} is not equal to the number of columns in samples_β={be.shape[1]}")
+    t, y, yerr = _f64(t).reshape(-1), _f64(y).reshape(-1), _f64(yerr).reshape(-1)
+    dt = np.diff(t)
+    f_min, f_max = 1.0 / (t[-1] - t[0]) / 10.0, 1.0 / np.min(dt) / 2.0 * 10.0
+    f = np.exp(np.linspace(np.log(f_min), np.log(f_max), int(n_frequencies)))
+    sq_err = (yerr / y) ** 2 if with_log_transform else yerr ** 2
+    nu = _f64(samples_nu).reshape(-1)
+    mean_noise_level = 2.0 * np.mean(nu) * np.mean(sq_err) * np.mean(dt)
+    median_noise_level = 2.0 * np.median(nu) * np.median(sq_err) * np.median(dt)
+    norm = _f64(samples_norm).reshape(-1)
+    ctx = ctx or default_context()
+    if r.shape[0] <= _MAX_SUMMARY:
+        s = ctx.carma_psd_summary(p, q, f, r_alpha=r, beta=be, norm=norm, times_f=plot_f_P)
+        q_psd, kept = s["quant"], s["kept"]
+    else:
+        psd, st = ctx.carma_psd(p, q, f, r_alpha=r, beta=be, norm=norm, times_f=plot_f_P, return_status=True)
+        q_psd, _, kept = _quantiles_host(psd, PPC_QUANTILES, st)
+    return dict(f=f, psd_quantiles=q_psd, mean_noise_level=mean_noise_level, median_noise_level=median_noise_level, f_min=f_min, f_max=f_max, kept=kept)
 
 
 def posterior_predict_checks(rng, samples_psd, samples_norm, samples_nu, samples_mu, samples_c, t, y, yerr, model, with_log_transform=False,

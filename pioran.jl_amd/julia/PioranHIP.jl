@@ -11,6 +11,7 @@
 module PioranHIP
 
 using LinearAlgebra
+using Statistics
 using Pioran
 import Pioran: log_likelihood, SumOfCelerite, SemiSeparable, CARMA, celerite_coefs
 import ChainRulesCore
@@ -318,6 +319,188 @@ function approx_vjp_batch(model::Symbol, θ::Matrix{Float64}, norm::Vector{Float
                     grad_a, grad_b, gθ, gn))
     end
     return gθ, gn
+end
+
+# ---- CARMA(p, q) models from their sampled parameters (src/CARMA.jl, docs/src/carma.md) ---------------------------------------------------
+# Quad form: qa `p × nbatch`, qb `q × nbatch`, the quadratic factors the models sample (rα = quad2roots(qa), β = roots2coeffs(quad2roots(qb)));
+# roots form: rα `p × nbatch` ComplexF64, β `(q + 1) × nbatch`.  bounds = (f_lo, f_hi) of check_roots_bounds, or nothing.
+_carma_bounds(bounds) = bounds === nothing ? (0.0, 0.0) : (Float64(bounds[1]), Float64(bounds[2]))
+_carma_form(in1::Matrix{Float64}) = Cint(0)
+_carma_form(in1::Matrix{ComplexF64}) = Cint(1)
+function _carma_sizes(p::Integer, q::Integer, in1::Matrix, in2::Matrix{Float64}, norm::Vector{Float64})
+    form = _carma_form(in1)
+    size(in1, 1) == p || error("the first array must have p = $p rows")
+    size(in2, 1) == (form == 0 ? q : q + 1) || error("the second array must have $(form == 0 ? q : q + 1) rows")
+    nb = size(in1, 2)
+    (size(in2, 2) == nb && length(norm) == nb) || error("one column and one norm per draw")
+    return form, nb
+end
+
+"""
+    carma_coefs_batch(p, q, qa, qb, norm; is_integrated_power, bounds, ctx)          (quad form)
+    carma_coefs_batch(p, q, rα, β, norm; ...)                                        (roots form)
+
+`CARMA_celerite_coefs` for a batch on the GPU: `(a, b, c, d)` `J × nbatch`, `J = (p + 1) ÷ 2`, and `flags` (0, or why a draw is rejected: 1 non-finite,
+2 not a conjugate pair, 3 a root with real part ≥ 0, 4 outside the bounds; such a draw has (1, 0, 1, 0) in every term).
+"""
+function carma_coefs_batch(p::Integer, q::Integer, in1::Matrix, in2::Matrix{Float64}, norm::Vector{Float64}; is_integrated_power::Bool = true,
+                           bounds = nothing, ctx = default_context())
+    form, nb = _carma_sizes(p, q, in1, in2, norm)
+    J = (p + 1) ÷ 2
+    f_lo, f_hi = _carma_bounds(bounds)
+    a, b, c, d = (Matrix{Float64}(undef, J, nb) for _ in 1:4)
+    flags = Vector{Int32}(undef, nb)
+    GC.@preserve in1 in2 norm a b c d flags begin
+        check(ccall((:pioran_carma_coefs_batch, LIB), Cint,
+                    (Ptr{Cvoid}, Int64, Cint, Cint, Cint, Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Cdouble, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}),
+                    ctx.h, nb, p, q, form, pointer(in1), q == 0 && form == 0 ? C_NULL : pointer(in2), norm, is_integrated_power ? 1 : 0, f_lo, f_hi,
+                    a, b, c, d, flags))
+    end
+    return a, b, c, d, flags
+end
+
+"""
+    carma_vjp_batch(p, q, qa, qb, norm, grad_a, grad_b, grad_c, grad_d; is_integrated_power, ctx)
+
+The reverse mode of quad2roots and `CARMA_celerite_coefs` on the GPU — what an `rrule` returns for the cotangents of the coefficients
+(`J × nbatch` each): `(grad_qa, grad_qb, grad_norm)`.  Rejected draws get exact zeros.
+"""
+function carma_vjp_batch(p::Integer, q::Integer, qa::Matrix{Float64}, qb::Matrix{Float64}, norm::Vector{Float64}, grad_a::Matrix{Float64},
+                         grad_b::Matrix{Float64}, grad_c::Matrix{Float64}, grad_d::Matrix{Float64}; is_integrated_power::Bool = true,
+                         ctx = default_context())
+    _, nb = _carma_sizes(p, q, qa, qb, norm)
+    all(size(g) == ((p + 1) ÷ 2, nb) for g in (grad_a, grad_b, grad_c, grad_d)) || error("the cotangents must be J × nbatch")
+    gqa = Matrix{Float64}(undef, p, nb); gqb = Matrix{Float64}(undef, q, nb); gn = Vector{Float64}(undef, nb)
+    GC.@preserve qa qb norm grad_a grad_b grad_c grad_d gqa gqb gn begin
+        check(ccall((:pioran_carma_vjp_batch, LIB), Cint,
+                    (Ptr{Cvoid}, Int64, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    ctx.h, nb, p, q, qa, q == 0 ? C_NULL : pointer(qb), norm, is_integrated_power ? 1 : 0, grad_a, grad_b, grad_c, grad_d, gqa,
+                    q == 0 ? C_NULL : pointer(gqb), gn))
+    end
+    return gqa, gqb, gn
+end
+
+"""
+    carma_psd_batch(p, q, in1, in2, norm, f; is_integrated_power, bounds, times_f, ctx)
+
+`evaluate(::CARMA, f)` for a batch on the GPU: `(psd, status)` with `psd` `length(f) × nbatch`; status 3, and NaN in the column, for a rejected draw.
+"""
+function carma_psd_batch(p::Integer, q::Integer, in1::Matrix, in2::Matrix{Float64}, norm::Vector{Float64}, f::Vector{Float64};
+                         is_integrated_power::Bool = true, bounds = nothing, times_f::Bool = false, ctx = default_context())
+    form, nb = _carma_sizes(p, q, in1, in2, norm)
+    f_lo, f_hi = _carma_bounds(bounds)
+    psd = Matrix{Float64}(undef, length(f), nb); status = Vector{Int32}(undef, nb)
+    GC.@preserve in1 in2 norm f psd status begin
+        check(ccall((:pioran_carma_psd_batch, LIB), Cint,
+                    (Ptr{Cvoid}, Int64, Cint, Cint, Cint, Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Cdouble, Int64, Ptr{Cdouble}, Cint,
+                     Ptr{Cdouble}, Ptr{Int32}),
+                    ctx.h, nb, p, q, form, pointer(in1), q == 0 && form == 0 ? C_NULL : pointer(in2), norm, is_integrated_power ? 1 : 0, f_lo, f_hi,
+                    length(f), f, times_f ? 1 : 0, psd, status))
+    end
+    return psd, status
+end
+
+"""
+    carma_psd_summary(p, q, in1, in2, norm, f, probs = PPC_QUANTILES; ...)
+
+`carma_psd_batch` with the array left on the device and reduced there: `(quant, status, kept)`, `quant` `length(f) × length(probs)` over the draws with
+status 0 — the quantiles `plot_psd_ppc_CARMA` draws (src/plots_diagnostics.jl:832-936).  At most 4096 draws.
+"""
+function carma_psd_summary(p::Integer, q::Integer, in1::Matrix, in2::Matrix{Float64}, norm::Vector{Float64}, f::Vector{Float64},
+                           probs::Vector{Float64} = PPC_QUANTILES; is_integrated_power::Bool = true, bounds = nothing, times_f::Bool = false,
+                           ctx = default_context())
+    form, nb = _carma_sizes(p, q, in1, in2, norm)
+    f_lo, f_hi = _carma_bounds(bounds)
+    quant = Matrix{Float64}(undef, length(f), length(probs)); status = Vector{Int32}(undef, nb); kept = Ref{Int32}(-1)
+    GC.@preserve in1 in2 norm f probs quant status begin
+        check(ccall((:pioran_carma_psd_summary, LIB), Cint,
+                    (Ptr{Cvoid}, Int64, Cint, Cint, Cint, Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Cdouble, Int64, Ptr{Cdouble}, Cint, Int64,
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ref{Int32}),
+                    ctx.h, nb, p, q, form, pointer(in1), q == 0 && form == 0 ? C_NULL : pointer(in2), norm, is_integrated_power ? 1 : 0, f_lo, f_hi,
+                    length(f), f, times_f ? 1 : 0, length(probs), probs, quant, status, kept))
+    end
+    return quant, status, Int(kept[])
+end
+
+"""
+    psd_ppc_carma(samples_rα, samples_β, samples_norm, samples_ν, t, y, yerr, p, q; plot_f_P, n_frequencies, with_log_transform)
+
+`plot_psd_ppc_CARMA` (src/plots_diagnostics.jl:832-936) as numbers, the samples one per ROW as the reference takes them: the grid, the five quantiles of
+the PSD per frequency and the two noise levels.
+"""
+function psd_ppc_carma(samples_rα::Matrix, samples_β::Matrix{Float64}, samples_norm::Vector{Float64}, samples_ν::Vector{Float64}, t::Vector{Float64},
+                       y::Vector{Float64}, yerr::Vector{Float64}, p::Integer, q::Integer; plot_f_P::Bool = false, n_frequencies::Integer = 1000,
+                       with_log_transform::Bool = false, ctx = default_context())
+    p == size(samples_rα, 2) || error("p=$(p) is not equal to the number of columns in samples_rα=$(size(samples_rα, 2))")
+    q + 1 == size(samples_β, 2) || error("q+1=$(q + 1) is not equal to the number of columns in samples_β=$(size(samples_β, 2))")
+    dt = diff(t)
+    f_min = 1 / (t[end] - t[1]) / 10
+    f_max = 1 / minimum(dt) / 2.0 * 10
+    f = collect(exp.(range(log(f_min), log(f_max), length = n_frequencies)))
+    sq_err = with_log_transform ? (yerr ./ y) .^ 2 : yerr .^ 2
+    mean_noise_level = 2 * mean(samples_ν) * mean(sq_err) * mean(dt)
+    median_noise_level = 2 * median(samples_ν) * median(sq_err) * median(dt)
+    rα = Matrix{ComplexF64}(permutedims(samples_rα)); β = Matrix{Float64}(permutedims(samples_β))
+    quant, status, kept = carma_psd_summary(p, q, rα, β, samples_norm, f; times_f = plot_f_P, ctx = ctx)
+    return (f = f, psd_quantiles = quant, mean_noise_level = mean_noise_level, median_noise_level = median_noise_level, f_min = f_min, f_max = f_max,
+            kept = kept)
+end
+
+"""
+    logpdf_batch_carma(ds, p, q, qa, qb, norm; is_integrated_power, bounds, μ, ν, shift)
+
+(qa, qb, norm) -> log L in one call for the CARMA models of docs/src/carma.md: the whole body of a vectorised likelihood.  `(out, status)`; a draw the
+root checks reject has `out = -Inf` and status 3 (the models' `@addlogprob! -Inf`).
+"""
+function logpdf_batch_carma(ds::Dataset, p::Integer, q::Integer, qa::Matrix{Float64}, qb::Matrix{Float64}, norm::Vector{Float64};
+                            is_integrated_power::Bool = true, bounds = nothing, μ::Union{Nothing, Vector{Float64}} = nothing,
+                            ν::Union{Nothing, Vector{Float64}} = nothing, shift::Union{Nothing, Vector{Float64}} = nothing)
+    _, nb = _carma_sizes(p, q, qa, qb, norm)
+    f_lo, f_hi = _carma_bounds(bounds)
+    out = Vector{Float64}(undef, nb); status = zeros(Int32, nb)
+    pt(x) = x === nothing ? Ptr{Cdouble}(C_NULL) : pointer(x)
+    GC.@preserve qa qb norm μ ν shift out status begin
+        check(ccall((:pioran_logpdf_batch_carma, LIB), Cint,
+                    (Ptr{Cvoid}, Int64, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Cdouble, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    ds.h, nb, p, q, qa, q == 0 ? C_NULL : pointer(qb), norm, is_integrated_power ? 1 : 0, f_lo, f_hi, pt(μ), pt(ν), pt(shift), out,
+                    status, C_NULL, C_NULL, C_NULL, C_NULL))
+    end
+    return out, status
+end
+
+"""
+    logpdf_carma_grad_batch(ds, p, q, qa, qb, norm; is_integrated_power, bounds, μ, ν, shift, coef_grads)
+
+Value and gradient with respect to the sampled parameters of the CARMA models — what NUTS needs: `grad_qa` (`p × nbatch`), `grad_qb` (`q × nbatch`),
+`grad_norm`, `grad_ν`, `grad_μ`, `grad_shift` (each `nothing` when its input is); `coef_grads = true` also returns `grad_a .. grad_d` (`J × nbatch`).
+A rejected draw has status 3, `logl = -Inf` and zeros in every gradient column.
+"""
+function logpdf_carma_grad_batch(ds::Dataset, p::Integer, q::Integer, qa::Matrix{Float64}, qb::Matrix{Float64}, norm::Vector{Float64};
+                                 is_integrated_power::Bool = true, bounds = nothing, μ::Union{Nothing, Vector{Float64}} = nothing,
+                                 ν::Union{Nothing, Vector{Float64}} = nothing, shift::Union{Nothing, Vector{Float64}} = nothing,
+                                 coef_grads::Bool = false)
+    _, nb = _carma_sizes(p, q, qa, qb, norm)
+    J = (p + 1) ÷ 2
+    f_lo, f_hi = _carma_bounds(bounds)
+    out = Vector{Float64}(undef, nb); status = zeros(Int32, nb)
+    gqa = Matrix{Float64}(undef, p, nb); gqb = Matrix{Float64}(undef, q, nb); gn = Vector{Float64}(undef, nb)
+    like(x) = x === nothing ? nothing : Vector{Float64}(undef, nb)
+    gν = like(ν); gμ = like(μ); gs = like(shift)
+    ga, gb, gc, gd = (coef_grads ? Matrix{Float64}(undef, J, nb) : nothing for _ in 1:4)
+    pt(x) = x === nothing ? Ptr{Cdouble}(C_NULL) : pointer(x)
+    GC.@preserve qa qb norm μ ν shift out status gqa gqb gn gν gμ gs ga gb gc gd begin
+        check(ccall((:pioran_logpdf_batch_carma_grad, LIB), Cint,
+                    (Ptr{Cvoid}, Int64, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Cdouble, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    ds.h, nb, p, q, qa, q == 0 ? C_NULL : pointer(qb), norm, is_integrated_power ? 1 : 0, f_lo, f_hi, pt(μ), pt(ν), pt(shift), out,
+                    status, gqa, q == 0 ? C_NULL : pointer(gqb), gn, pt(gν), pt(gμ), pt(gs), pt(ga), pt(gb), pt(gc), pt(gd)))
+    end
+    return (logl = out, status = status, grad_qa = gqa, grad_qb = gqb, grad_norm = gn, grad_ν = gν, grad_μ = gμ, grad_shift = gs, grad_a = ga,
+            grad_b = gb, grad_c = gc, grad_d = gd)
 end
 
 # ---- in-process farm: ONE Julia process driving several GPUs (no Distributed/MPI launcher needed) ----------------------

@@ -202,6 +202,11 @@ class CARMA(SemiSeparable):
     def scaled(self, number):
         return CARMA(self.p, self.q, self.r_alpha, self.beta, self.norm * number, self.is_integrated_power)
 
+    def evaluate(self, f):
+        """evaluate(model::CARMA, f): the power spectral density at the frequencies f   src/CARMA.jl:150-172."""
+        from .carma import evaluate
+        return evaluate(self, f)
+
 
 def celerite_coefs(cov: SemiSeparable):
     return cov.celerite_coefs()
