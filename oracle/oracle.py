@@ -389,6 +389,44 @@ def predict_mean_truth(a, b, c, d, tau, t, y, s2, dtype=np.longdouble):
     return kern(tau[:, None] - t[None, :]) @ z
 
 
+def dense_nll_truth(a, b, c, d, t, y, s2, dtype=np.longdouble):
+    """Truth for log_likelihood_direct (src/direct_solver.jl:6-21), the positive NLL sum log L_nn + z'z / 2 + N log(2 pi) / 2 with K = L L' by
+    _truth_cholesky (t in any order) and z = L^-1 y by forward substitution, in `dtype`.  Shares nothing with LAPACK or the C restatement.
+    Returns (nll, scale): scale is the sum of the absolute values of the 2 N + 1 terms, sum |log L_nn| + z'z / 2 + N log(2 pi) / 2, the
+    natural scale of the sum (as scale_mu is in logl_grad_truth).  Raises LinAlgError naming the 0-based row of the first non-positive pivot."""
+    a, b, c, d, t, y, s2 = _truth_inputs(dtype, a, b, c, d, t, y, s2)
+    N = len(t)
+    L = _truth_cholesky(a, b, c, d, t, s2, dtype)
+    z = np.zeros(N, dtype=dtype)
+    for n in range(N):
+        z[n] = (y[n] - L[n, :n] @ z[:n]) / L[n, n]
+    ld = np.log(np.diag(L))
+    q2 = (z * z).sum() / 2
+    const = N * np.log(8 * np.arctan(dtype(1))) / 2
+    return ld.sum() + q2 + const, np.abs(ld).sum() + q2 + const
+
+
+def predict_cov_truth(a, b, c, d, tau, t, s2, dtype=np.longdouble):
+    """Truth for predict_cov (src/direct_solver.jl:28-69): the full posterior covariance K(tau, tau) - w'w, w = L^-1 K(t, tau), dense in `dtype`
+    (_truth_cholesky; every evaluation time gets a triangular solve of its own, as in predict_var_truth).  K(tau, tau) is evaluated on the lower
+    triangle and mirrored and w'w is one product of w with itself, so the result is symmetric by construction; its diagonal is
+    predict_var_truth to rounding (k(0) in place of K(tau_m, tau_m)).  Raises LinAlgError when K is not positive definite.  Returns (M, M)."""
+    a, b, c, d, tau, t, s2 = _truth_inputs(dtype, a, b, c, d, tau, t, s2)
+    kern = _truth_kernel(a, b, c, d)
+    N, M = len(t), len(tau)
+    L = _truth_cholesky(a, b, c, d, t, s2, dtype)
+    Ks = kern(tau[:, None] - t[None, :])
+    w = np.zeros((M, N), dtype=dtype)               # row m: L^-1 k*(tau_m)
+    for n in range(N):
+        w[:, n] = (Ks[:, n] - w[:, :n] @ L[n, :n]) / L[n, n]
+    Ktt = np.zeros((M, M), dtype=dtype)
+    i, j = np.tril_indices(M)
+    Ktt[i, j] = kern(tau[i] - tau[j])
+    Ktt[j, i] = Ktt[i, j]
+    G = w @ w.T
+    return Ktt - (G + G.T) / 2
+
+
 def sim_truth(a, b, c, d, t, s2, q, dtype=np.longdouble):
     """Truth for a realisation from the normals q: C q with C the Cholesky factor (positive diagonal) of K = k(|t_i - t_j|) + diag(s2), dense
     in `dtype` (_truth_cholesky).  C = L D^1/2 of the celerite factorisation K = L D L', so this is what `sim` (src/celerite_solver.jl:515-549)
