@@ -300,7 +300,7 @@ int pioran_celerite_logl_grad_shift(pioran_ds* ds, int64_t B, int64_t J, const d
  *   h_j = kappa_j (ga_j + gb_j)   |   kappa_j (ga_j + ga_{J+j} + sqrt3 gb_j),      grad_norm = h'x / I,
  *   xbar = (norm / I) h - (norm / I^2) (h'x) w,   pbar = B^-T xbar (transposed solve on the same LU),
  *   grad_theta_k = sum_j pbar_j p_j (dlog P(f_j)/dtheta_k - dlog P(f_0)/dtheta_k).
- * PSD features (QPO) are out of scope: there is no mixed shared / per-draw reverse mode to chain through, and n_qpo is not a parameter here.
+ * Continuum + QPO features: pioran_logpdf_batch_theta_qpo_grad below.
  * NULL ds / theta / norm / out / grad_theta / grad_norm, model outside 0 .. 1, basis outside 0 .. 1: PIORAN_ERR_ARG before any GPU call.
  * Host pointers, blocking. */
 int pioran_logpdf_batch_theta_grad(pioran_ds* ds, int64_t B, int model, int64_t n_components, int basis, int is_integrated_power,
@@ -314,6 +314,45 @@ int pioran_logpdf_batch_theta_grad(pioran_ds* ds, int64_t B, int model, int64_t 
 int pioran_approx_vjp_batch(pioran_ctx* ctx, int64_t B, int model, int64_t n_components, int basis, int is_integrated_power,
                             double f_min, double f_max, double S_low, double S_high, const double* theta, const double* norm,
                             const double* grad_a, const double* grad_b, double* grad_theta, double* grad_norm);
+/* The reverse mode of approx WITH QPO features (approx_qpo_vjp_kernel, csrc/approx.hip; no data set): 1 <= n_qpo <= 8 features (S0, f0, Q) per draw,
+ * qpo [B][n_qpo][3] as in pioran_logpdf_batch_theta; cotangents grad_a, grad_b, grad_c, grad_d [B][Jt], Jt = J + n_qpo (J as above), of the coefficients
+ * approx returns -- of grad_c, grad_d only the feature columns are read, the continuum's (c, d) are the grid's -- ->
+ *   grad_theta [B][P],  grad_norm [B],  grad_qpo [B][n_qpo][3] = d/d(S0, f0, Q).
+ * With p0 = P(f_0; theta), x, w, h, kappa as above, and per feature w0 = 2 pi f0, De = sqrt(4 Q^2 - 1), al = S0 w0 Q / 4:
+ *   forward   fa = al / p0, fb = fa / De, c = w0 / (2 Q), d = c De;   I = w'x + [integrated] sum_q (fa_q Ia_q + fb_q Ib_q), Ia, Ib the two brackets of
+ *             integral_celerite between f_min and f_max;   a_j = kappa_j x_j norm / I,  A_q = 2 fa_q norm / I,  B_q = 2 fb_q norm / I,  C_q = c_q,  D_q = d_q
+ *   reverse   s = norm / I,  T = h'x + sum_q 2 (ga_q fa_q + gb_q fb_q),  grad_norm = T / I,  Ibar = -s T / I,  xbar = s h + Ibar w,  pbar = B^-T xbar,
+ *             fabar = 2 s ga_q + [i] Ibar Ia,  fbbar = 2 s gb_q + [i] Ibar Ib,  cbar = gc_q + [i] Ibar (fa dIa/dc + fb dIb/dc),  dbar likewise in d,
+ *             fabar += fbbar / De,  Debar = dbar c - fbbar fb / De,  cbar += dbar De,  albar = fabar / p0,
+ *             grad_S0 = albar w0 Q / 4,  grad_f0 = 2 pi (albar S0 Q / 4 + cbar / (2 Q)),  grad_Q = albar S0 w0 / 4 - cbar c / Q + Debar 4 Q / De,
+ *             grad_theta_k = sum_j pbar_j p_j (dlog P(f_j)/dtheta_k - dlog P(f_0)/dtheta_k) - (sum_q fabar_q fa_q) dlog P(f_0)/dtheta_k.
+ * In the variance form ([i] = 0) the features do not enter I but are still scaled by norm / I.  2 <= n_components <= 256.  NULL ctx or pointer, model or
+ * basis out of range, n_qpo outside 1 .. 8 (n_qpo = 0: pioran_approx_vjp_batch): PIORAN_ERR_ARG before any GPU call.  Host pointers, blocking. */
+int pioran_approx_qpo_vjp_batch(pioran_ctx* ctx, int64_t B, int model, int64_t n_components, int basis, int is_integrated_power,
+                                double f_min, double f_max, double S_low, double S_high, const double* theta, const double* norm,
+                                int64_t n_qpo, const double* qpo, const double* grad_a, const double* grad_b, const double* grad_c,
+                                const double* grad_d, double* grad_theta, double* grad_norm, double* grad_qpo);
+/* log L and its gradient with respect to the SAMPLED parameters of a continuum + QPO model in one call: pioran_logpdf_batch_theta's arguments with
+ * 1 <= n_qpo <= 8 (n_qpo = 0 is PIORAN_ERR_ARG: pioran_logpdf_batch_theta_grad serves it), and out of it grad_theta [B][P], grad_norm [B],
+ * grad_qpo [B][n_qpo][3], grad_nu, grad_mu, grad_shift [B] (each NULL exactly when its input is NULL) and, all eight or none, the coefficients
+ * coef_a .. coef_d and their gradients grad_a .. grad_d [B][Jt], for checking.
+ * Three steps, as pioran_logpdf_batch_carma_grad: approx_kernel makes the coefficients on the device; they come to the host, where the continuum columns
+ * of (c, d) are filled with the grid's values, and go through pioran_celerite_logl_grad[_shift] with (c, d) per draw (cd_shared = 0) -- its routing (the
+ * windowed reverse mode with one pair of tables per draw up to 63 rows, each draw a batch of its own step by step up to 143 and for every shifted call),
+ * its kernels, its out and status on the same numbers --; approx_qpo_vjp_kernel chains (grad_a .. grad_d) back on the device.  The coefficients and their
+ * gradients cross PCIe between the steps ([B][Jt] x 4 doubles each way): accepted, these models run at a handful to a few hundred chains.  Every draw
+ * has its own tables; there is no mixed shared / per-draw reverse mode.
+ * A draw the reference could not evaluate -- a non-finite theta, norm or feature, f0 <= 0, Q <= 1/2 (a DomainError in convert_feature) -- runs on benign
+ * parameters and returns out = -inf, status 3 and exact zeros in every gradient row (its coef_* rows are the benign coefficients).
+ * NULL ds / theta / norm / qpo / out / grad_theta / grad_norm / grad_qpo, model or basis outside 0 .. 1, n_components outside 2 .. 256, n_qpo outside
+ * 1 .. 8, a gradient whose null-ness differs from its input's, some but not all of the eight [B][Jt] arrays: PIORAN_ERR_ARG; more than 143 rows
+ * (2 n_components (SHO) or 3 n_components (DRWCelerite), + 2 n_qpo): PIORAN_ERR_UNSUPPORTED; both before any GPU call.  Host pointers, blocking. */
+int pioran_logpdf_batch_theta_qpo_grad(pioran_ds* ds, int64_t B, int model, int64_t n_components, int basis, int is_integrated_power,
+                                       double f_min, double f_max, double S_low, double S_high, const double* theta, const double* norm,
+                                       const double* mu, const double* nu, const double* shift, int64_t n_qpo, const double* qpo, double* out,
+                                       int32_t* status, double* grad_theta, double* grad_norm, double* grad_qpo, double* grad_nu, double* grad_mu,
+                                       double* grad_shift, double* coef_a, double* coef_b, double* coef_c, double* coef_d, double* grad_a,
+                                       double* grad_b, double* grad_c, double* grad_d);
 /* simulate (src/celerite_solver.jl:497-513 -> sim :515-549; rand(f(t, sigma2)) of src/scalable_GP.jl:137-146):
  * realisations y_b = L_b D_b^(1/2) q_b of the GP with kernel (a_b, b_b, c, d) + diag(sigma2) at the times t, from
  * caller-supplied standard-normal draws q [B][N] (the reference draws them with its rng, :528).  y_out [B][N].

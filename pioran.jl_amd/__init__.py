@@ -11,7 +11,7 @@ from .carma import (CARMA_normalisation, check_conjugate_pair, check_order_imag_
                     sample_quad)
 from .kernels import (CARMA, Celerite, Exp, ScaledKernel, SemiSeparable, SHO, SumOfCelerite, SumOfSemiSeparable,
                       SumOfTerms, celerite_coefs)
-from .psd import (QPO, DoubleBendingPowerLaw, SingleBendingPowerLaw, approx, approx_batch, approx_batch_vjp, approximated_psd, build_approx,
-                  convert_feature, get_approx_coefficients, get_norm_psd, psd_decomp, separate_psd)
+from .psd import (QPO, DoubleBendingPowerLaw, SingleBendingPowerLaw, approx, approx_batch, approx_batch_qpo, approx_batch_qpo_vjp, approx_batch_vjp, approximated_psd,
+                  build_approx, convert_feature, get_approx_coefficients, get_norm_psd, psd_decomp, separate_psd)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -56,6 +56,10 @@ SIGNATURES = {
     "pioran_logpdf_batch_theta_grad": (ctypes.c_int, [c_void_p, i64, ctypes.c_int, i64, ctypes.c_int, ctypes.c_int] + [ctypes.c_double] * 4 +
                                        [c_void_p] * 14),
     "pioran_approx_vjp_batch": (ctypes.c_int, [c_void_p, i64, ctypes.c_int, i64, ctypes.c_int, ctypes.c_int] + [ctypes.c_double] * 4 + [c_void_p] * 6),
+    "pioran_approx_qpo_vjp_batch": (ctypes.c_int, [c_void_p, i64, ctypes.c_int, i64, ctypes.c_int, ctypes.c_int] + [ctypes.c_double] * 4 + [c_void_p] * 2 +
+                                    [i64] + [c_void_p] * 8),
+    "pioran_logpdf_batch_theta_qpo_grad": (ctypes.c_int, [c_void_p, i64, ctypes.c_int, i64, ctypes.c_int, ctypes.c_int] + [ctypes.c_double] * 4 +
+                                           [c_void_p] * 5 + [i64] + [c_void_p] * 17),
     "pioran_celerite_rand_posterior": (ctypes.c_int, [c_void_p, i64, i64] + [c_void_p] * 4 + [ctypes.c_int] + [c_void_p] * 3 + [i64] + [c_void_p] * 6),
     "pioran_celerite_simulate": (ctypes.c_int, [c_void_p, i64, i64, i64] + [c_void_p] * 4 + [ctypes.c_int] + [c_void_p] * 4),
     "pioran_lombscargle_batch": (ctypes.c_int, [c_void_p, i64, i64, i64] + [c_void_p] * 4 + [ctypes.c_int, ctypes.c_int, c_void_p, c_void_p]),

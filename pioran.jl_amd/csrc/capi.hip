@@ -344,6 +344,8 @@ struct ThetaDraws {
     const double *sp = nullptr, *w = nullptr, *LU = nullptr, *theta = nullptr, *norm = nullptr;
     const int32_t* piv = nullptr;
     double *grad_theta = nullptr, *grad_norm = nullptr;          // the caller's: [B][P], [B]
+    int n_qpo = 0;                                               // QPO features per draw (the entries that chain through approx_qpo_vjp_kernel) ...
+    const double* qpo = nullptr;                                 // ... and their (S0, f0, Q) [B][n_qpo][3] on the device, behind norm
     std::vector<double> grid, c, d;                              // host: sp | w | LU | piv (what `sp` .. `piv` hold), the shared (c, d) of the celerite terms
     std::vector<int32_t> real;                                   // ... and which of them keep their cos row only
     int64_t terms() const { return basis == 0 ? J : 2 * (int64_t)J; }
@@ -351,7 +353,7 @@ struct ThetaDraws {
 
 // The grid of approx and the batch's theta [B][P], norm [B] onto the device.  `td` keeps the host copies until the call's last synchronisation.
 int stage_theta(pioran_ctx* ctx, int64_t B, int model, int64_t J, int basis, int integrated, double f_min, double f_max, double S_low, double S_high,
-                const double* theta, const double* norm, ThetaDraws& td)
+                const double* theta, const double* norm, ThetaDraws& td, int64_t n_qpo = 0, const double* qpo = nullptr)
 {
     std::vector<double> sp, w, LU;
     std::vector<int32_t> piv;
@@ -365,20 +367,23 @@ int stage_theta(pioran_ctx* ctx, int64_t B, int model, int64_t J, int basis, int
     std::memcpy(td.grid.data() + nJ, w.data(), nJ * sizeof(double));
     std::memcpy(td.grid.data() + 2 * nJ, LU.data(), nJ * nJ * sizeof(double));
     std::memcpy(td.grid.data() + 2 * nJ + nJ * nJ, piv.data(), nJ * sizeof(int32_t));
-    if ((rc = ensure(ctx, ctx->bthin, (ngrid + nth + (size_t)B) * sizeof(double)))) return rc;
+    const size_t nq = (size_t)B * 3 * (size_t)n_qpo;
+    if ((rc = ensure(ctx, ctx->bthin, (ngrid + nth + (size_t)B + nq) * sizeof(double)))) return rc;
     double* dev = (double*)ctx->bthin.p;
     if ((rc = upload_to(ctx, dev, td.grid.data(), ngrid * sizeof(double)))) return rc;
     if ((rc = upload_to(ctx, dev + ngrid, theta, nth * sizeof(double)))) return rc;
     if ((rc = upload_to(ctx, dev + ngrid + nth, norm, (size_t)B * sizeof(double)))) return rc;
+    if (nq && (rc = upload_to(ctx, dev + ngrid + nth + B, qpo, nq * sizeof(double)))) return rc;
+    td.n_qpo = (int)n_qpo; td.qpo = nq ? dev + ngrid + nth + B : nullptr;
     td.sp = dev; td.w = dev + nJ; td.LU = dev + 2 * nJ; td.piv = (const int32_t*)(dev + 2 * nJ + nJ * nJ);
     td.theta = dev + ngrid; td.norm = dev + ngrid + nth;
     return PIORAN_OK;
 }
 
-// a chunk's grad_theta [nb][P] | grad_norm [nb] | the reverse kernel's scratch [2 J][nb] in bthout
+// a chunk's grad_theta [nb][P] | grad_norm [nb] | the reverse kernel's scratch [2 J][nb] | with features, grad_qpo [nb][n_qpo][3] in bthout
 int ensure_theta_grads(pioran_ctx* ctx, const ThetaDraws& td, int64_t nb)
 {
-    return ensure(ctx, ctx->bthout, (size_t)nb * (size_t)(td.P + 1 + 2 * td.J) * sizeof(double));
+    return ensure(ctx, ctx->bthout, (size_t)nb * (size_t)(td.P + 1 + 2 * td.J + 3 * td.n_qpo) * sizeof(double));
 }
 
 // (ga, gb) [nb][terms] of draws [b0, b0 + nb), on the device, through the reverse mode of approx to the caller's grad_theta, grad_norm
@@ -2044,6 +2049,157 @@ int pioran_approx_vjp_batch(pioran_ctx* ctx, int64_t B, int model, int64_t n_com
     if ((rc = ensure_theta_grads(ctx, td, B))) return rc;
     if ((rc = theta_grads(ctx, td, 0, B, dga, dga + bj))) return rc;
     SYNC(ctx);
+    return PIORAN_OK;
+}
+
+// ---- continuum + QPO features from their sampled parameters: the gradient (approx.hip approx_qpo_vjp_kernel) ----------------------------------
+static const char* const kApproxQpoVjpName = "approx with features (reverse mode of the coefficients)";
+
+// what both entries can see without looking at an array
+static int qpo_refuse(const void* handle, int64_t B, int model, int64_t n_components, int basis, const void* theta, const void* norm, int64_t n_qpo,
+                      const void* qpo)
+{
+    if (!handle || B < 1 || !theta || !norm || model < 0 || model > 1 || basis < 0 || basis > 1) return PIORAN_ERR_ARG;
+    if (n_components < 2 || n_components > 256 || n_qpo < 1 || n_qpo > 8 || !qpo) return PIORAN_ERR_ARG;
+    return PIORAN_OK;
+}
+
+// (ga, gb, gc, gd) [B][Jt] of the caller through approx_qpo_vjp_kernel on the staged batch to the caller's grad_theta [B][P], grad_norm [B],
+// grad_qpo [B][n_qpo][3].  bthout: grad_theta | grad_norm | scratch [2 J][B] | grad_qpo
+static int qpo_vjp_from_host(pioran_ctx* ctx, int64_t B, const ThetaDraws& td, const double* ga, const double* gb, const double* gc, const double* gd,
+                             double* grad_theta, double* grad_norm, double* grad_qpo)
+{
+    int rc;
+    const size_t bj = (size_t)B * (size_t)(td.terms() + td.n_qpo), nth = (size_t)B * td.P, nq = (size_t)B * 3 * (size_t)td.n_qpo;
+    if ((rc = ensure(ctx, ctx->bK, 4 * bj * sizeof(double)))) return rc;
+    if ((rc = ensure_theta_grads(ctx, td, B))) return rc;
+    double* dg = (double*)ctx->bK.p;
+    const double* host[4] = {ga, gb, gc, gd};
+    for (int k = 0; k < 4; ++k)
+        if ((rc = upload_to(ctx, dg + k * bj, host[k], bj * sizeof(double)))) return rc;
+    double* gth = (double*)ctx->bthout.p; double* gn = gth + nth; double* scratch = gn + B; double* gq = scratch + 2 * (size_t)td.J * (size_t)B;
+    const bool timed = ctx->opt.theta_events != 0;
+    g_last_kernel = kApproxQpoVjpName;
+    if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
+    if ((rc = pioran_launch_approx_qpo_vjp(B, td.model, td.P, td.J, td.basis, td.integrated, td.f_min, td.f_max, td.sp, td.w, td.LU, td.piv, td.theta, td.norm,
+                                           td.n_qpo, td.qpo, dg, dg + bj, dg + 2 * bj, dg + 3 * bj, scratch, gth, gn, gq, ctx->stream))) {
+        if (rc == PIORAN_ERR_HIP) ctx->last_err = "approx reverse-mode launch failed";
+        return rc;
+    }
+    if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
+    if ((rc = download(ctx, grad_theta, gth, nth * sizeof(double)))) return rc;
+    if ((rc = download(ctx, grad_norm, gn, (size_t)B * sizeof(double)))) return rc;
+    return download(ctx, grad_qpo, gq, nq * sizeof(double));
+}
+
+int pioran_approx_qpo_vjp_batch(pioran_ctx* ctx, int64_t B, int model, int64_t n_components, int basis, int is_integrated_power, double f_min, double f_max,
+                                double S_low, double S_high, const double* theta, const double* norm, int64_t n_qpo, const double* qpo,
+                                const double* grad_a, const double* grad_b, const double* grad_c, const double* grad_d, double* grad_theta,
+                                double* grad_norm, double* grad_qpo)
+{
+    if (const int rc = qpo_refuse(ctx, B, model, n_components, basis, theta, norm, n_qpo, qpo)) return rc;
+    if (!grad_a || !grad_b || !grad_c || !grad_d || !grad_theta || !grad_norm || !grad_qpo) return PIORAN_ERR_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    PendingGuard pending_guard(ctx);
+    ThetaDraws td;
+    int rc = stage_theta(ctx, B, model, n_components, basis, is_integrated_power != 0, f_min, f_max, S_low, S_high, theta, norm, td, n_qpo, qpo);
+    if (rc) return rc;
+    if ((rc = qpo_vjp_from_host(ctx, B, td, grad_a, grad_b, grad_c, grad_d, grad_theta, grad_norm, grad_qpo))) return rc;
+    SYNC(ctx);
+    return PIORAN_OK;
+}
+
+int pioran_logpdf_batch_theta_qpo_grad(pioran_ds* ds, int64_t B, int model, int64_t n_components, int basis, int is_integrated_power, double f_min,
+                                       double f_max, double S_low, double S_high, const double* theta, const double* norm, const double* mu,
+                                       const double* nu, const double* shift, int64_t n_qpo, const double* qpo, double* out, int32_t* status,
+                                       double* grad_theta, double* grad_norm, double* grad_qpo, double* grad_nu, double* grad_mu, double* grad_shift,
+                                       double* coef_a, double* coef_b, double* coef_c, double* coef_d, double* grad_a, double* grad_b, double* grad_c,
+                                       double* grad_d)
+{
+    if (const int rc = qpo_refuse(ds, B, model, n_components, basis, theta, norm, n_qpo, qpo)) return rc;
+    if (!out || !grad_theta || !grad_norm || !grad_qpo) return PIORAN_ERR_ARG;
+    if ((nu == nullptr) != (grad_nu == nullptr) || (mu == nullptr) != (grad_mu == nullptr) || (shift == nullptr) != (grad_shift == nullptr)) return PIORAN_ERR_ARG;
+    const int n_inter = (coef_a != nullptr) + (coef_b != nullptr) + (coef_c != nullptr) + (coef_d != nullptr) + (grad_a != nullptr) + (grad_b != nullptr) +
+                        (grad_c != nullptr) + (grad_d != nullptr);
+    if (n_inter != 0 && n_inter != 8) return PIORAN_ERR_ARG;
+    const int P = model == 0 ? 3 : 5;
+    const int64_t J = n_components, Jc = basis == 0 ? J : 2 * J, Jt = Jc + n_qpo;
+    // rows of the celerite state: two per SHO term and per feature, three per DRWCelerite pair (its second term keeps the cos row only)
+    if ((basis == 0 ? 2 * J : 3 * J) + 2 * n_qpo > pioran_wide_supported_rows()) return PIORAN_ERR_UNSUPPORTED;
+    // a draw the reference could not evaluate (non-finite theta, norm or feature; f0 <= 0; Q <= 1/2: DomainError of convert_feature) runs on benign
+    // parameters and is overwritten afterwards
+    std::vector<double> th(theta, theta + B * P), nm(norm, norm + B), qp(qpo, qpo + B * n_qpo * 3);
+    std::vector<char> bad((size_t)B, 0);
+    const double f_mid = std::sqrt(f_min * f_max);
+    for (int64_t b = 0; b < B; ++b) {
+        bool ok = std::isfinite(nm[b]);
+        for (int k = 0; k < P; ++k) ok = ok && std::isfinite(th[b * P + k]);
+        for (int64_t q = 0; q < n_qpo; ++q) {
+            const double* f = &qp[(b * n_qpo + q) * 3];
+            ok = ok && std::isfinite(f[0]) && std::isfinite(f[1]) && std::isfinite(f[2]) && f[1] > 0.0 && f[2] > 0.5;
+        }
+        if (ok) continue;
+        bad[(size_t)b] = 1;
+        const double benign[5] = {1.0, f_mid, 3.0, f_max, 4.0};
+        std::copy(benign, benign + P, th.begin() + b * P);
+        nm[b] = 1.0;
+        for (int64_t q = 0; q < n_qpo; ++q) { double* f = &qp[(b * n_qpo + q) * 3]; f[0] = 1.0; f[1] = f_mid; f[2] = 2.0; }
+    }
+    pioran_ctx* ctx = ds->ctx;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ThetaDraws td;
+    int rc;
+    const size_t bj = (size_t)B * (size_t)Jt;
+    std::vector<double> hA(bj), hB(bj), hC(bj), hD(bj);
+    {   // approx_kernel on the staged batch: (a, b) and the features' (c, d) [B][Jt] into bA .. bD, and from there to the host
+        PendingGuard guard(ctx);
+        if ((rc = stage_theta(ctx, B, model, J, basis, is_integrated_power != 0, f_min, f_max, S_low, S_high, th.data(), nm.data(), td, n_qpo, qp.data())))
+            return rc;
+        const size_t bytes = bj * sizeof(double);
+        if ((rc = ensure_each(ctx, {{&ctx->bA, bytes}, {&ctx->bB, bytes}, {&ctx->bC, bytes}, {&ctx->bD, bytes}}))) return rc;
+        if ((rc = pioran_launch_approx(B, td.model, td.P, td.J, td.basis, td.integrated, td.f_min, td.f_max, td.sp, td.LU, td.piv, td.theta, td.norm, td.n_qpo,
+                                       td.qpo, (double*)ctx->bA.p, (double*)ctx->bB.p, (double*)ctx->bC.p, (double*)ctx->bD.p, ctx->stream)))
+            return rc;
+        if ((rc = download(ctx, hA.data(), ctx->bA.p, bytes))) return rc;
+        if ((rc = download(ctx, hB.data(), ctx->bB.p, bytes))) return rc;
+        if ((rc = download(ctx, hC.data(), ctx->bC.p, bytes))) return rc;
+        if ((rc = download(ctx, hD.data(), ctx->bD.p, bytes))) return rc;
+        SYNC(ctx);
+    }
+    for (int64_t b = 0; b < B; ++b) {   // the continuum's (c, d) are the grid's: approx_kernel writes the features' columns only
+        std::copy(td.c.begin(), td.c.end(), hC.begin() + b * Jt);
+        std::copy(td.d.begin(), td.d.end(), hD.begin() + b * Jt);
+    }
+    // the reverse mode of the host-pointer gradient entries on these coefficients, (c, d) per draw: their routing and their kernels
+    std::vector<double> inter;
+    double *ga = grad_a, *gb = grad_b, *gc = grad_c, *gd = grad_d;
+    if (!n_inter) { inter.resize(4 * bj); ga = inter.data(); gb = ga + bj; gc = gb + bj; gd = gc + bj; }
+    std::vector<int32_t> st((size_t)B, 0);
+    if ((rc = logl_grad_impl(ds, B, Jt, hA.data(), hB.data(), hC.data(), hD.data(), 0, mu, nu, shift, out, st.data(),
+                             {ga, gb, gc, gd, grad_nu, grad_mu, nullptr, nullptr}, grad_shift)))
+        return rc;
+    for (int64_t b = 0; b < B; ++b) {   // a rejected draw: log L = -inf, status 3, exact zeros in every gradient row
+        if (!bad[(size_t)b]) continue;
+        out[b] = -INFINITY; st[(size_t)b] = 3;
+        for (double* g : {ga, gb, gc, gd}) std::fill(g + b * Jt, g + (b + 1) * Jt, 0.0);
+        if (grad_nu) grad_nu[b] = 0.0;
+        if (grad_mu) grad_mu[b] = 0.0;
+        if (grad_shift) grad_shift[b] = 0.0;
+    }
+    if (status) std::memcpy(status, st.data(), (size_t)B * sizeof(int32_t));
+    if (n_inter) {
+        std::copy(hA.begin(), hA.end(), coef_a); std::copy(hB.begin(), hB.end(), coef_b);
+        std::copy(hC.begin(), hC.end(), coef_c); std::copy(hD.begin(), hD.end(), coef_d);
+    }
+    PendingGuard guard(ctx);
+    if ((rc = qpo_vjp_from_host(ctx, B, td, ga, gb, gc, gd, grad_theta, grad_norm, grad_qpo))) return rc;
+    SYNC(ctx);
+    for (int64_t b = 0; b < B; ++b) {   // (the chain of zero cotangents is zero up to its sign)
+        if (!bad[(size_t)b]) continue;
+        std::fill(grad_theta + b * P, grad_theta + (b + 1) * P, 0.0);
+        grad_norm[b] = 0.0;
+        std::fill(grad_qpo + b * n_qpo * 3, grad_qpo + (b + 1) * n_qpo * 3, 0.0);
+    }
     return PIORAN_OK;
 }
 

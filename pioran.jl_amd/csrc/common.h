@@ -56,7 +56,8 @@ struct ScanOptions {
     int rp_events = 0;    // posterior draws (capi.hip rand_posterior_batch), timing tools ONLY: 1 = the steps of a call's first chunk record the context's event
                           // slots 4 .. 9 (before the gather | after it | after the simulation | the residual | the prediction | the combination)
     int theta_events = 0; // theta gradient (capi.hip logl_grad_batch fed by approx), timing tools ONLY: 1 = a call's first chunk records the context's event slots
-                          // 4 .. 7 (before approx_kernel | after it | before approx_vjp_kernel | after it)
+                          // 4 .. 7 (before approx_kernel | after it | before approx_vjp_kernel | after it); the entries with QPO features
+                          // (capi.hip qpo_vjp_from_host) record 6 | 7 around approx_qpo_vjp_kernel alone
     int pc_events = 0;    // PSD check (capi.hip psd_check_chunk), timing tools ONLY: 1 = a call's first chunk records the context's event slots
                           // 4 .. 6 (before psd_check_draw_kernel | after it | after psd_check_eval_kernel)
     int carma_events = 0; // CARMA entries (capi.hip pioran_carma_*_batch), timing tools ONLY: 1 = a call records the context's event slots 4 | 5 around its
@@ -299,6 +300,12 @@ int pioran_launch_approx(int64_t B, int model, int P, int J, int basis, int inte
 int pioran_launch_approx_vjp(int64_t B, int model, int P, int J, int basis, const double* sp, const double* w /*pioran_approx_weights_host*/,
                              const double* LU, const int32_t* piv, const double* theta, const double* norm, const double* ga, const double* gb,
                              double* scratch, double* gtheta, double* gnorm, hipStream_t stream);
+// reverse mode of approx with 1 <= n_qpo <= 8 features: ga, gb, gc, gd [B][Jt] (Jt = J | 2 J, + n_qpo; of gc, gd the feature columns are read) ->
+// gtheta [B][P], gnorm [B], gqpo [B][n_qpo][3] = d/d(S0, f0, Q); scratch: 2 J B doubles
+int pioran_launch_approx_qpo_vjp(int64_t B, int model, int P, int J, int basis, int integrated, double f_min, double f_max, const double* sp,
+                                 const double* w /*pioran_approx_weights_host*/, const double* LU, const int32_t* piv, const double* theta,
+                                 const double* norm, int n_qpo, const double* qpo /*[B][n_qpo][3]*/, const double* ga, const double* gb,
+                                 const double* gc, const double* gd, double* scratch, double* gtheta, double* gnorm, double* gqpo, hipStream_t stream);
 // carma.hip: CARMA(p, q) models — sampled parameters (form 0: quadratic factors qa [B][p], qb [B][q]; form 1: roots [B][p][2], beta [B][q + 1]) ->
 // celerite coefficients [B][(p + 1) / 2] and a per-draw flag (0, or the reason the draw is rejected), the reverse mode (quad form), the PSD [B][F]
 int pioran_carma_max_order();

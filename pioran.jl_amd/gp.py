@@ -172,6 +172,24 @@ class Context:
                                                       _ptr(grad_b), _ptr(gth), _ptr(gnorm)), self._h)
         return gth, gnorm
 
+    def approx_qpo_vjp(self, model, theta, norm, qpo, grad_a, grad_b, grad_c, grad_d, f_min, f_max, n_components=20, S_low=20.0, S_high=20.0, *,
+                       is_integrated_power=True, basis_function="SHO"):
+        """Chain rule through `approx` with QPO features on the device (pioran_approx_qpo_vjp_batch): dL/da, dL/db, dL/dc, dL/dd (B, Jt),
+        Jt = J + n_qpo -> dL/dtheta (B, P), dL/dnorm (B,), dL/dqpo (B, n_qpo, 3) = d/d(S0, f0, Q).  qpo: (B, n_qpo, 3) or (B, 3), 1 <= n_qpo <= 8;
+        of grad_c, grad_d only the feature columns are read (the continuum's c, d are the grid's).  The rest as in approx_vjp."""
+        mid, basis, theta, norm = _theta_args(model, theta, norm, basis_function)
+        B, P = theta.shape
+        qpo = _f64(np.asarray(qpo, dtype=np.float64).reshape(B, -1, 3))
+        n_qpo = qpo.shape[1]
+        g = [_f64(v) for v in (grad_a, grad_b, grad_c, grad_d)]
+        if any(v.shape != (B, n_components * (1 + basis) + n_qpo) for v in g):
+            raise ValueError("grad_a, grad_b, grad_c, grad_d must be (B, J + n_qpo)")
+        gth, gnorm, gq = np.empty((B, P)), np.empty(B), np.empty((B, n_qpo, 3))
+        _lib.check(_lib.lib().pioran_approx_qpo_vjp_batch(self._h, B, mid, int(n_components), basis, int(bool(is_integrated_power)), float(f_min),
+                                                          float(f_max), float(S_low), float(S_high), _ptr(theta), _ptr(norm), n_qpo, _ptr(qpo),
+                                                          *map(_ptr, g), _ptr(gth), _ptr(gnorm), _ptr(gq)), self._h)
+        return gth, gnorm, gq
+
     # -- batched Lomb-Scargle periodogram ------------------------------------------------------
     def lombscargle(self, t, Y, yerr, freq, fit_mean=True, center_data=True, return_status=False):
         """Generalised Lomb-Scargle power (standard normalisation) of the B series Y (B, N) sampled at t (N,) at the frequencies freq (F,)
@@ -662,18 +680,25 @@ class Dataset:
 
     def logpdf_theta_grad(self, model, theta, norm, f_min, f_max, n_components=20, S_low=20.0, S_high=20.0, *,
                           is_integrated_power=True, basis_function="SHO", mu=None, nu=None, shift=None, approx_on="host",
-                          return_coef_grads=False):
+                          return_coef_grads=False, qpo=None):
         """log L and its gradient with respect to the SAMPLED parameters of the reference's models
         (README.md:38-71: theta = PSD parameters, norm = variance, nu, mu): the device gradient w.r.t. (a, b, nu, mu)
         chained through `approx` on the host (approx_batch_vjp) or, approx_on="device", in one device call
         (pioran_logpdf_batch_theta_grad: approx and its reverse mode run either side of the same reverse-mode kernels).
         Returns a dict: logl, status, grad_theta (B, P), grad_norm, grad_nu, grad_mu (B,) and, with return_coef_grads,
-        the intermediate grad_a, grad_b (B, J)."""
+        the intermediate grad_a, grad_b (B, J).
+        qpo: (B, n_qpo, 3) or (B, 3) = (S0, f0, Q) of QPO features added to the continuum, as in logpdf_theta: the dict also holds
+        grad_qpo (B, n_qpo, 3) and, with return_coef_grads, coef_a .. coef_d and grad_a .. grad_d (B, J + n_qpo); every draw has its own (c, d)
+        (pioran_logpdf_batch_theta_qpo_grad on the device, approx_batch_qpo[_vjp] around logl_grad on the host).  On the device a draw the
+        reference could not evaluate (non-finite parameters, f0 <= 0, Q <= 1/2) has status 3, logl = -inf and zeros in every gradient row."""
+        if approx_on not in ("host", "device"):
+            raise ValueError('approx_on must be "host" or "device"')
+        if qpo is not None:
+            return self._logpdf_theta_qpo_grad(model, theta, norm, qpo, f_min, f_max, n_components, S_low, S_high, is_integrated_power,
+                                               basis_function, mu, nu, shift, approx_on, return_coef_grads)
         if approx_on == "device":
             return self._logpdf_theta_grad_device(model, theta, norm, f_min, f_max, n_components, S_low, S_high, is_integrated_power,
                                                   basis_function, mu, nu, shift, return_coef_grads)
-        if approx_on != "host":
-            raise ValueError('approx_on must be "host" or "device"')
         from .psd import approx_batch, approx_batch_vjp
         theta = np.atleast_2d(_f64(theta))
         A, Bc, C, Dd = approx_batch(model, theta, f_min, f_max, n_components, norm, S_low, S_high,
@@ -706,6 +731,41 @@ class Dataset:
         res = {"logl": out, "status": st, "grad_theta": gth, "grad_norm": gnorm, "grad_nu": gnu, "grad_mu": gmu, "grad_shift": gsh}
         if return_coef_grads:
             res["grad_a"], res["grad_b"] = ga, gb
+        return res
+
+    def _logpdf_theta_qpo_grad(self, model, theta, norm, qpo, f_min, f_max, n_components, S_low, S_high, is_integrated_power, basis_function,
+                               mu, nu, shift, approx_on, return_coef_grads):
+        mid, basis, theta, norm = _theta_args(model, theta, norm, basis_function)
+        B, P = theta.shape
+        qpo = _f64(np.asarray(qpo, dtype=np.float64).reshape(B, -1, 3))
+        n_qpo = qpo.shape[1]
+        names = ("coef_a", "coef_b", "coef_c", "coef_d", "grad_a", "grad_b", "grad_c", "grad_d")
+        if approx_on == "host":
+            from .psd import approx_batch_qpo, approx_batch_qpo_vjp
+            kw = dict(is_integrated_power=is_integrated_power, basis_function=basis_function)
+            co = approx_batch_qpo(model, theta, qpo, f_min, f_max, n_components, norm, S_low, S_high, **kw)
+            g = self.logl_grad(*co, mu=mu, nu=nu, shift=shift, cd_grad=True)
+            gr = [g[k] for k in names[4:]]
+            gth, gnorm, gq = approx_batch_qpo_vjp(model, theta, qpo, f_min, f_max, n_components, norm, *gr, S_low, S_high, **kw)
+            res = {"logl": g["logl"], "status": g["status"], "grad_theta": gth, "grad_norm": gnorm, "grad_qpo": gq,
+                   "grad_nu": g["grad_nu"] if nu is not None else None, "grad_mu": g["grad_mu"] if mu is not None else None,
+                   "grad_shift": g.get("grad_shift")}
+            if return_coef_grads:
+                res.update(zip(names, [*co, *gr]))
+            return res
+        mu, nu, shift = (None if v is None else _f64(np.broadcast_to(v, (B,))) for v in (mu, nu, shift))
+        out, st = np.empty(B), np.zeros(B, dtype=np.int32)
+        gth, gnorm, gq = np.empty((B, P)), np.empty(B), np.empty((B, n_qpo, 3))
+        gnu, gmu, gsh = (None if v is None else np.empty(B) for v in (nu, mu, shift))
+        Jt = n_components * (1 + basis) + n_qpo
+        co = [np.empty((B, Jt)) if return_coef_grads else None for _ in names]
+        _lib.check(_lib.lib().pioran_logpdf_batch_theta_qpo_grad(
+            self._h, B, mid, int(n_components), basis, int(bool(is_integrated_power)), float(f_min), float(f_max), float(S_low), float(S_high),
+            _ptr(theta), _ptr(norm), _ptr(mu), _ptr(nu), _ptr(shift), n_qpo, _ptr(qpo), _ptr(out), _ptr(st), _ptr(gth), _ptr(gnorm), _ptr(gq),
+            _ptr(gnu), _ptr(gmu), _ptr(gsh), *map(_ptr, co)), self.ctx._h)
+        res = {"logl": out, "status": st, "grad_theta": gth, "grad_norm": gnorm, "grad_qpo": gq, "grad_nu": gnu, "grad_mu": gmu, "grad_shift": gsh}
+        if return_coef_grads:
+            res.update(zip(names, co))
         return res
 
     def logl_batch_dev(self, B, dA, dBc, dmu=0, dnu=0, dY=0, dS2=0, dout=0, dstatus=0):

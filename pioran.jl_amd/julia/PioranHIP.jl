@@ -266,7 +266,7 @@ end
 
 Value and gradient with respect to the sampled parameters in one device call: `approx`, the reverse mode of the likelihood and the
 reverse mode of `approx` all run on the GPU; `θ` (`P × nbatch`), `norm`, `μ`, `ν`, `shift` go in and `grad_θ` (`P × nbatch`),
-`grad_norm`, `grad_ν`, `grad_μ`, `grad_shift` (each `nothing` when its input is) come out.  Continuum models only (no QPO features).
+`grad_norm`, `grad_ν`, `grad_μ`, `grad_shift` (each `nothing` when its input is) come out.  Continuum models; with QPO features: `logpdf_theta_qpo_grad_batch`.
 `coef_grads = true` also returns the intermediate `grad_a`, `grad_b` (`J × nbatch`).
 """
 function logpdf_theta_grad_batch(ds::Dataset, model::Symbol, θ::Matrix{Float64}, norm::Vector{Float64}, f_min::Real, f_max::Real,
@@ -319,6 +319,76 @@ function approx_vjp_batch(model::Symbol, θ::Matrix{Float64}, norm::Vector{Float
                     grad_a, grad_b, gθ, gn))
     end
     return gθ, gn
+end
+
+"""
+    logpdf_theta_qpo_grad_batch(ds, model, θ, norm, qpo, f_min, f_max, n_components; basis, μ, ν, shift, coef_grads, ...)
+
+Value and gradient with respect to the sampled parameters of a continuum + QPO model in one call: `qpo` is `3 × n_qpo × nbatch`
+(S₀, f₀, Q), `1 ≤ n_qpo ≤ 8`; besides `logpdf_theta_grad_batch`'s results `grad_qpo` (`3 × n_qpo × nbatch`) comes out.  Every draw
+has its own (c, d): the reverse mode is `logl_grad`'s for per-draw tables.  A draw the reference could not evaluate (non-finite
+parameters, f₀ ≤ 0, Q ≤ 1/2) has status 3, `logl = -Inf` and zero gradients.  `coef_grads = true` also returns the coefficients
+`coef_a … coef_d` and their gradients `grad_a … grad_d` (`Jt × nbatch`, `Jt = J + n_qpo`).
+"""
+function logpdf_theta_qpo_grad_batch(ds::Dataset, model::Symbol, θ::Matrix{Float64}, norm::Vector{Float64}, qpo::Array{Float64, 3},
+                                     f_min::Real, f_max::Real, n_components::Integer; basis::String = "SHO",
+                                     is_integrated_power::Bool = true, S_low::Real = 20.0, S_high::Real = 20.0,
+                                     μ::Union{Nothing, Vector{Float64}} = nothing, ν::Union{Nothing, Vector{Float64}} = nothing,
+                                     shift::Union{Nothing, Vector{Float64}} = nothing, coef_grads::Bool = false)
+    m = model === :SingleBendingPowerLaw ? 0 : model === :DoubleBendingPowerLaw ? 1 : error("model $model not supported on the device")
+    bs = basis == "SHO" ? 0 : basis == "DRWCelerite" ? 1 : error("basis $basis not supported on the device")
+    size(θ, 1) == (m == 0 ? 3 : 5) || error("θ must be $(m == 0 ? 3 : 5) × nbatch")
+    nb = size(θ, 2)
+    size(qpo, 1) == 3 && size(qpo, 3) == nb || error("qpo must be 3 × n_qpo × nbatch")
+    nq = size(qpo, 2)
+    Jt = (bs == 0 ? 1 : 2) * n_components + nq
+    out = Vector{Float64}(undef, nb); status = zeros(Int32, nb)
+    gθ = Matrix{Float64}(undef, size(θ, 1), nb); gn = Vector{Float64}(undef, nb); gq = Array{Float64, 3}(undef, 3, nq, nb)
+    like(x) = x === nothing ? nothing : Vector{Float64}(undef, nb)
+    gν = like(ν); gμ = like(μ); gs = like(shift)
+    co = [coef_grads ? Matrix{Float64}(undef, Jt, nb) : nothing for _ in 1:8]
+    p(x) = x === nothing ? Ptr{Cdouble}(C_NULL) : pointer(x)
+    GC.@preserve θ norm qpo μ ν shift out status gθ gn gq gν gμ gs co begin
+        check(ccall((:pioran_logpdf_batch_theta_qpo_grad, LIB), Cint,
+                    (Ptr{Cvoid}, Int64, Cint, Int64, Cint, Cint, Cdouble, Cdouble, Cdouble, Cdouble, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    ds.h, nb, m, n_components, bs, is_integrated_power ? 1 : 0, f_min, f_max, S_low, S_high, θ, norm,
+                    p(μ), p(ν), p(shift), nq, qpo, out, status, gθ, gn, gq, p(gν), p(gμ), p(gs),
+                    p(co[1]), p(co[2]), p(co[3]), p(co[4]), p(co[5]), p(co[6]), p(co[7]), p(co[8])))
+    end
+    return (logl = out, status = status, grad_θ = gθ, grad_norm = gn, grad_qpo = gq, grad_ν = gν, grad_μ = gμ, grad_shift = gs,
+            coef_a = co[1], coef_b = co[2], coef_c = co[3], coef_d = co[4], grad_a = co[5], grad_b = co[6], grad_c = co[7], grad_d = co[8])
+end
+
+"""
+    approx_qpo_vjp_batch(model, θ, norm, qpo, grad_a, grad_b, grad_c, grad_d, f_min, f_max, n_components; basis, ctx, ...)
+
+The reverse mode of `approx` with QPO features alone, on the GPU: cotangents `grad_a … grad_d` (`Jt × nbatch`; of `grad_c`, `grad_d`
+only the feature rows are read) of the celerite coefficients → `(grad_θ, grad_norm, grad_qpo)`.
+"""
+function approx_qpo_vjp_batch(model::Symbol, θ::Matrix{Float64}, norm::Vector{Float64}, qpo::Array{Float64, 3}, grad_a::Matrix{Float64},
+                              grad_b::Matrix{Float64}, grad_c::Matrix{Float64}, grad_d::Matrix{Float64}, f_min::Real, f_max::Real,
+                              n_components::Integer; basis::String = "SHO", is_integrated_power::Bool = true, S_low::Real = 20.0,
+                              S_high::Real = 20.0, ctx = default_context())
+    m = model === :SingleBendingPowerLaw ? 0 : model === :DoubleBendingPowerLaw ? 1 : error("model $model not supported on the device")
+    bs = basis == "SHO" ? 0 : basis == "DRWCelerite" ? 1 : error("basis $basis not supported on the device")
+    size(θ, 1) == (m == 0 ? 3 : 5) || error("θ must be $(m == 0 ? 3 : 5) × nbatch")
+    nb = size(θ, 2)
+    size(qpo, 1) == 3 && size(qpo, 3) == nb || error("qpo must be 3 × n_qpo × nbatch")
+    nq = size(qpo, 2)
+    size(grad_a) == size(grad_b) == size(grad_c) == size(grad_d) == ((bs == 0 ? 1 : 2) * n_components + nq, nb) ||
+        error("grad_a … grad_d must be (J + n_qpo) × nbatch")
+    gθ = Matrix{Float64}(undef, size(θ, 1), nb); gn = Vector{Float64}(undef, nb); gq = Array{Float64, 3}(undef, 3, nq, nb)
+    GC.@preserve θ norm qpo grad_a grad_b grad_c grad_d gθ gn gq begin
+        check(ccall((:pioran_approx_qpo_vjp_batch, LIB), Cint,
+                    (Ptr{Cvoid}, Int64, Cint, Int64, Cint, Cint, Cdouble, Cdouble, Cdouble, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Int64,
+                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    ctx.h, nb, m, n_components, bs, is_integrated_power ? 1 : 0, f_min, f_max, S_low, S_high, θ, norm, nq, qpo,
+                    grad_a, grad_b, grad_c, grad_d, gθ, gn, gq))
+    end
+    return gθ, gn, gq
 end
 
 # ---- CARMA(p, q) models from their sampled parameters (src/CARMA.jl, docs/src/carma.md) ---------------------------------------------------

@@ -259,6 +259,89 @@ def approx_batch_vjp(model, theta, f_min, f_max, n_components, norm, grad_a, gra
     return gth, gnorm
 
 
+def _integral_celerite_analytic(a, b, c, d, x):
+    """_integral_celerite for arguments that may be complex: with Re c > 0, atan2(c, u) = pi / 2 - atan(u / c), which is analytic in (c, u)"""
+    up, um = d + 2 * math.pi * x, d - 2 * math.pi * x
+    return (2 * a * (np.arctan(up / c) - np.arctan(um / c)) + b * np.log((c ** 2 + up ** 2) / (c ** 2 + um ** 2))) / (2 * math.pi)
+
+
+def approx_batch_qpo(model, theta, qpo, f_min, f_max, n_components=20, norm=1.0, S_low=20.0, S_high=20.0, *,
+                     is_integrated_power=True, basis_function="SHO"):
+    """Vectorised `approx` for continuum + QPO models (src/psd.jl:214-289 with features :15-27, 228-241, 254-261) over B rows.
+
+    model, theta, norm as in approx_batch; qpo: (B, n_qpo, 3) or (B, 3) = (S0, f0, Q) per feature.  Returns A, Bc, C, Dd of shape (B, Jt),
+    Jt = J + n_qpo: the continuum's terms (their c, d repeated in every row) followed by one term (2a, 2b, c, d) per feature.
+    Every operation is analytic in theta, norm and qpo, so complex arguments pass through (approx_batch_qpo_vjp's complex step)."""
+    theta = np.atleast_2d(np.asarray(theta))
+    B = theta.shape[0]
+    qpo = np.asarray(qpo).reshape(B, -1, 3)
+    cplx = np.iscomplexobj(theta) or np.iscomplexobj(norm) or np.iscomplexobj(qpo)
+    dt = complex if cplx else float
+    theta, qpo = theta.astype(dt), qpo.astype(dt)
+    norm = np.broadcast_to(np.asarray(norm, dt), (B,))
+    sp, Bm = build_approx(n_components, f_min / S_low, f_max * S_high, basis_function)
+    psd = _eval_model_batch(model, theta, sp)
+    p0 = psd[:, :1]
+    amplitudes = np.ascontiguousarray(np.linalg.solve(Bm, (psd / p0).T).T)
+    S0, f0, Q = qpo[:, :, 0], qpo[:, :, 1], qpo[:, :, 2]
+    delta = np.sqrt(4 * Q ** 2 - 1)            # convert_feature
+    w0 = 2 * math.pi * f0
+    fa = S0 * w0 * Q / 4 / p0
+    fb = fa / delta
+    fc = w0 / Q / 2
+    fd = fc * delta
+    integ = get_norm_psd(amplitudes, sp, f_min, f_max, basis_function, is_integrated_power)
+    if is_integrated_power:
+        prim = _integral_celerite_analytic if cplx else _integral_celerite
+        integ = integ + np.sum(prim(fa, fb, fc, fd, f_max) - prim(fa, fb, fc, fd, f_min), axis=1)
+    scale = (norm / integ)[:, None]
+    amplitudes = amplitudes * scale
+    ones = np.ones((B, 1))
+    if basis_function == "SHO":
+        a = amplitudes * sp * math.pi / math.sqrt(2)
+        c = math.sqrt(2) * math.pi * sp
+        aa, bb, cc, dd = a, a, c, c
+    else:
+        a = amplitudes * sp * math.pi / 3
+        c = math.pi * sp
+        aa, bb = np.concatenate([a, a], axis=1), np.concatenate([math.sqrt(3) * a, np.zeros_like(a)], axis=1)
+        cc, dd = np.concatenate([c, 2 * c]), np.concatenate([math.sqrt(3) * c, np.zeros(n_components)])
+    return (np.concatenate([aa, 2 * fa * scale], axis=1), np.concatenate([bb, 2 * fb * scale], axis=1),
+            np.concatenate([ones * cc, fc], axis=1), np.concatenate([ones * dd, fd], axis=1))
+
+
+def approx_batch_qpo_vjp(model, theta, qpo, f_min, f_max, n_components, norm, grad_a, grad_b, grad_c, grad_d, S_low=20.0, S_high=20.0, *,
+                         is_integrated_power=True, basis_function="SHO", h=1e-30):
+    """Chain rule through `approx` with QPO features: given dL/da, dL/db, dL/dc, dL/dd (B, Jt) returns dL/dtheta (B, P), dL/dnorm (B,) and
+    dL/dqpo (B, n_qpo, 3) = d/d(S0, f0, Q), by one complex step per parameter through approx_batch_qpo (the twin of approx_batch_vjp)."""
+    theta = np.atleast_2d(np.asarray(theta, float))
+    B, P = theta.shape
+    qpo = np.asarray(qpo, float).reshape(B, -1, 3)
+    norm = np.broadcast_to(np.asarray(norm, float), (B,))
+    if model not in (SingleBendingPowerLaw, DoubleBendingPowerLaw):
+        raise ValueError("approx_batch_qpo_vjp supports SingleBendingPowerLaw and DoubleBendingPowerLaw")
+    g = (grad_a, grad_b, grad_c, grad_d)
+    kw = dict(is_integrated_power=is_integrated_power, basis_function=basis_function)
+
+    def directional(th, qp):
+        out = approx_batch_qpo(model, th, qp, f_min, f_max, n_components, norm, S_low, S_high, **kw)
+        return sum((gk * ok.imag).sum(axis=1) for gk, ok in zip(g, out)) / h
+
+    gth, gq = np.empty((B, P)), np.empty(qpo.shape)
+    for k in range(P):
+        th = theta.astype(complex)
+        th[:, k] += 1j * h
+        gth[:, k] = directional(th, qpo)
+    for q in range(qpo.shape[1]):
+        for k in range(3):
+            qp = qpo.astype(complex)
+            qp[:, q, k] += 1j * h
+            gq[:, q, k] = directional(theta, qp)
+    A, Bc, _, _ = approx_batch_qpo(model, theta, qpo, f_min, f_max, n_components, norm, S_low, S_high, **kw)
+    gnorm = (grad_a * A + grad_b * Bc).sum(axis=1) / norm      # (a, b) are proportional to norm
+    return gth, gnorm, gq
+
+
 def _eval_model_batch(model, theta, sp):
     f = sp[None, :]
     if model is SingleBendingPowerLaw:
