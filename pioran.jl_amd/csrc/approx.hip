@@ -376,6 +376,7 @@ void pioran_approx_weights_host(int basis, int integrated, double f_min, double 
     for (size_t j = 0; j < sp.size(); ++j) {
         const double c = sp[j];
         if (!integrated) { w[j] = basis == 0 ? c * M_PI / s2 : c * 2.0 * M_PI / 3.0; continue; }
+        if (c <= 0.5 * f_min) { w[j] = psd_band_tail(c, f_min, f_max, basis == 0 ? 4 : 6); continue; }   // far below the band: no cancellation
         auto sho = [&](double f) {
             const double ph = (f * f + s2 * c * f + c * c) / (f * f - s2 * c * f + c * c);
             return c / (4.0 * s2) * (std::log(ph) + 2.0 * std::atan2(c * s2 * f, c * c - f * f));

@@ -45,8 +45,28 @@ __device__ __forceinline__ void psd_lu_solve(int J, const double* __restrict__ L
     }
 }
 
+// The band integral of one basis function per unit amplitude, int_{f_min}^{f_max} df / (1 + (f / c)^p) (p = 4 SHO, 6 DRWCelerite), for a term far
+// below the band, c <= f_min / 2.  There the closed forms below give it as the difference of two primitives of size c that agree to
+// (c / f_min)^(p - 1) — seven digits at c = f_min / 20, p = 6 — so it is summed instead as the series in t = c / f, which has no cancellation:
+//   c sum_k (-1)^k (th^n_k - tl^n_k) / n_k,   n_k = p (k + 1) - 1,   th = c / f_min <= 1/2,   tl = c / f_max;   16 terms: th^(16 p) < 1e-19.
+// pioran_approx_weights_host (approx.hip) and the host mirror (psd.py _band_tail) form the same sum.
+#define PIORAN_PSD_TAIL_TERMS 16
+__host__ __device__ inline double psd_band_tail(double c, double f_min, double f_max, int p)
+{
+    const double th = c / f_min, tl = c / f_max;
+    double thp = th * th, tlp = tl * tl;
+    thp = p == 4 ? thp * thp : thp * thp * thp;
+    tlp = p == 4 ? tlp * tlp : tlp * tlp * tlp;
+    double uh = thp / th, ul = tlp / tl, sum = 0.0, sign = 1.0;
+    for (int k = 0; k < PIORAN_PSD_TAIL_TERMS; ++k) {
+        sum += sign * (uh - ul) / (double)(p * (k + 1) - 1);
+        uh *= thp; ul *= tlp; sign = -sign;
+    }
+    return c * sum;
+}
+
 // get_norm_psd over the amplitudes of the continuum (src/psd.jl:375-395): the analytic integral over [f_min, f_max] (integral_sho :301-305,
-// integral_drwcelerite :318-324) or the variance form
+// integral_drwcelerite :318-324; terms with c <= f_min / 2 by psd_band_tail) or the variance form
 __device__ __forceinline__ double psd_norm_integral(int J, int basis, int integrated, double f_min, double f_max, const double* __restrict__ sp,
                                                     const double* x, int64_t stride)
 {
@@ -55,10 +75,11 @@ __device__ __forceinline__ double psd_norm_integral(int J, int basis, int integr
         for (int j = 0; j < J; ++j) acc += x[(int64_t)j * stride] * sp[j];
         return basis == 0 ? acc * M_PI / 1.4142135623730951 : acc * 2.0 * M_PI / 3.0;
     }
-    double hi = 0.0, lo = 0.0;
+    double hi = 0.0, lo = 0.0, tail = 0.0;      // tail: the terms far below the band (psd_band_tail)
     if (basis == 0) {            // integral_sho :301-305
         const double s2 = 1.4142135623730951;
         for (int j = 0; j < J; ++j) {
+            if (sp[j] <= 0.5 * f_min) { tail = fma(x[(int64_t)j * stride], psd_band_tail(sp[j], f_min, f_max, 4), tail); continue; }
             const double c = sp[j], nrm = c * x[(int64_t)j * stride] / (4.0 * s2);
             const double ph = (f_max * f_max + s2 * c * f_max + c * c) / (f_max * f_max - s2 * c * f_max + c * c);
             const double pl = (f_min * f_min + s2 * c * f_min + c * c) / (f_min * f_min - s2 * c * f_min + c * c);
@@ -68,6 +89,7 @@ __device__ __forceinline__ double psd_norm_integral(int J, int basis, int integr
     } else {                     // integral_drwcelerite :318-324
         const double s3 = 1.7320508075688772;
         for (int j = 0; j < J; ++j) {
+            if (sp[j] <= 0.5 * f_min) { tail = fma(x[(int64_t)j * stride], psd_band_tail(sp[j], f_min, f_max, 6), tail); continue; }
             const double c = sp[j], nrm = x[(int64_t)j * stride] * c / 3.0;
             const double ph = (f_max * f_max + s3 * c * f_max + c * c) / (f_max * f_max - s3 * c * f_max + c * c);
             const double pl = (f_min * f_min + s3 * c * f_min + c * c) / (f_min * f_min - s3 * c * f_min + c * c);
@@ -75,7 +97,7 @@ __device__ __forceinline__ double psd_norm_integral(int J, int basis, int integr
             lo += nrm * (atan(f_min / c) + 0.5 * atan2(f_min * f_min - c * c, c * f_min) + s3 / 4.0 * log(pl));
         }
     }
-    return hi - lo;
+    return (hi - lo) + tail;
 }
 
 }  // namespace

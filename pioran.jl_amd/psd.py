@@ -153,11 +153,32 @@ def _integral_celerite(a, b, c, d, x):
             + b * np.log(num / den)) / (2 * math.pi)
 
 
+TAIL_TERMS = 16
+
+
+def _band_tail(c, f_min, f_max, power):
+    """int_{f_min}^{f_max} df / (1 + (f / c)^power) of the basis functions far below the band (c <= f_min / 2), where the difference of the two
+    primitives above cancels (c / f_min)^(power - 1) of its digits: the series in t = c / f instead, c sum_k (-1)^k (th^n - tl^n) / n with
+    n = power (k + 1) - 1, th = c / f_min, tl = c / f_max (csrc/psd_device.h psd_band_tail forms the same sum)."""
+    th, tl = c / f_min, c / f_max
+    thp, tlp = th ** power, tl ** power
+    uh, ul, total, sign = thp / th, tlp / tl, 0.0, 1.0
+    for k in range(TAIL_TERMS):
+        total = total + sign * (uh - ul) / (power * (k + 1) - 1)
+        uh, ul, sign = uh * thp, ul * tlp, -sign
+    return c * total
+
+
 def get_norm_psd(amplitudes, spectral_points, f_min, f_max, basis_function, is_integrated_power, cov_features=None):
-    """src/psd.jl:375-395."""
+    """src/psd.jl:375-395; the terms with spectral point <= f_min / 2 through _band_tail."""
     if is_integrated_power:
         fn = _integral_sho if basis_function == "SHO" else _integral_drwcelerite
-        integ = fn(amplitudes, spectral_points, f_max) - fn(amplitudes, spectral_points, f_min)
+        far = spectral_points <= 0.5 * f_min
+        inband = np.where(far, 0.0, amplitudes)
+        integ = fn(inband, spectral_points, f_max) - fn(inband, spectral_points, f_min)
+        if far.any():
+            w = _band_tail(spectral_points[far], f_min, f_max, 4 if basis_function == "SHO" else 6)
+            integ = integ + np.sum(np.asarray(amplitudes)[..., far] * w, axis=-1)
         if cov_features is not None:
             for a, b, c, d in np.asarray(cov_features).T:
                 integ = integ + _integral_celerite(a, b, c, d, f_max) - _integral_celerite(a, b, c, d, f_min)

@@ -57,7 +57,17 @@ def weights(sp, basis, integrated, f_min, f_max):
         def prim(f):
             ph = (f * f + s3 * c * f + c * c) / (f * f - s3 * c * f + c * c)
             return c / 3 * (np.arctan(f / c) + 0.5 * np.arctan2(f * f - c * c, c * f) + s3 / 4 * np.log(ph))
-    return prim(f_max) - prim(f_min)
+    w = prim(f_max) - prim(f_min)
+    far = c <= 0.5 * f_min          # far below the band the two primitives cancel: the series of psd_device.h psd_band_tail (16 terms)
+    p = 4 if basis == 0 else 6
+    th, tl = c[far] / f_min, c[far] / f_max
+    thp, tlp = th ** p, tl ** p
+    uh, ul, total, sign = thp / th, tlp / tl, 0.0, 1.0
+    for k in range(16):
+        total = total + sign * (uh - ul) / (p * (k + 1) - 1)
+        uh, ul, sign = uh * thp, ul * tlp, -sign
+    w[far] = c[far] * total
+    return w
 
 
 def dlog_psd(model, theta, f):
@@ -83,6 +93,51 @@ def dlog_psd(model, theta, f):
     return val, np.stack(d, axis=-1)
 
 
+def lu_factor(Bm):
+    """(LU, piv) with P B = L U by partial pivoting, pioran_approx_setup_host's loop"""
+    LU = Bm.copy()
+    J = len(LU)
+    piv = np.zeros(J, dtype=np.int64)
+    for k in range(J):
+        p = k + int(np.argmax(np.abs(LU[k:, k])))
+        piv[k] = p
+        if p != k:
+            LU[[k, p]] = LU[[p, k]]
+        LU[k + 1:, k] /= LU[k, k]
+        LU[k + 1:, k + 1:] -= np.outer(LU[k + 1:, k], LU[k, k + 1:])
+    return LU, piv
+
+
+def lu_solve(LU, piv, rhs):
+    """B^-1 rhs for rhs [B][J] through the factors, in the kernel's order (psd_lu_solve): interchanges, unit lower, upper"""
+    x = np.array(rhs, float).T.copy()
+    J = len(piv)
+    for j in range(J):
+        if piv[j] != j:
+            x[[j, piv[j]]] = x[[piv[j], j]]
+    for i in range(1, J):
+        x[i] = x[i] - LU[i, :i] @ x[:i]
+    for i in range(J - 1, -1, -1):
+        x[i] = (x[i] - LU[i, i + 1:] @ x[i + 1:]) / LU[i, i]
+    return x.T
+
+
+def lu_solve_transposed(LU, piv, rhs):
+    """B^-T rhs for rhs [B][J] through the same factors (psd_lu_solve_transposed): U' forward, L' backward, the interchanges undone in reverse
+    order.  numpy's solve on B' factorises B' anew, with other pivots: on the sparse grids its result is as good in norm but loses the small
+    components that the pullback multiplies with large p_j (draws with alpha1 < 0), 8e-11 S_k at DRWCelerite J = 3 where the kernel has 1e-15."""
+    x = np.array(rhs, float).T.copy()
+    J = len(piv)
+    for i in range(J):
+        x[i] = (x[i] - LU[:i, i] @ x[:i]) / LU[i, i]
+    for i in range(J - 2, -1, -1):
+        x[i] = x[i] - LU[i + 1:, i] @ x[i + 1:]
+    for j in range(J - 1, -1, -1):
+        if piv[j] != j:
+            x[[j, piv[j]]] = x[[piv[j], j]]
+    return x.T
+
+
 def approx_vjp(model, theta, norm, grad_a, grad_b, f_min, f_max, n_components=20, S_low=20.0, S_high=20.0, *, is_integrated_power=True,
                basis=0, mistake=None):
     """(grad_theta [B][P], grad_norm [B]) from grad_a, grad_b [B][J] (J = n_components, or 2 n_components for basis 1)"""
@@ -97,7 +152,8 @@ def approx_vjp(model, theta, norm, grad_a, grad_b, f_min, f_max, n_components=20
     w = weights(sp, basis, is_integrated_power, f_min, f_max)
     P, dl = dlog_psd(model, theta, sp)                 # [B][J], [B][J][P]
     p = P / P[:, :1]
-    x = np.linalg.solve(Bm, p.T).T                     # [B][J]
+    LU, piv = lu_factor(Bm)
+    x = lu_solve(LU, piv, p)                           # [B][J]
     if basis == 0:
         h = sp * math.pi / math.sqrt(2) * (ga + gb)
     else:
@@ -108,7 +164,7 @@ def approx_vjp(model, theta, norm, grad_a, grad_b, f_min, f_max, n_components=20
     xbar = (norm / I)[:, None] * h
     if mistake != "no_w":
         xbar = xbar - (norm / I ** 2 * hx)[:, None] * w[None, :]
-    pbar = np.linalg.solve(Bm if mistake == "no_transpose" else Bm.T, xbar.T).T
+    pbar = lu_solve(LU, piv, xbar) if mistake == "no_transpose" else lu_solve_transposed(LU, piv, xbar)
     dd = dl if mistake == "no_f0" else dl - dl[:, :1, :]
     return np.einsum("bj,bj,bjk->bk", pbar, p, dd), hx / I
 
