@@ -583,6 +583,13 @@ const char* pioran_celerite_config_name(int64_t R);
  * returns -1 where the choice depends on it), no_split != 0: option "no_split".  The thresholds come from one sweep (profiles/r05_tile_batch_sweep.txt);
  * tests/test_host.py holds this function against that file, tools/retune_thresholds.py prints both side by side. */
 int pioran_tile_choice(int32_t R, int64_t B, int64_t pass, int no_split);
+/* Diagnostics (no GPU needed): the slot of the pair workspace that workgroup `id` (in launch order, 0 .. nchunk * ndb - 1) of the tile family's
+ * pre-pass fills: *chunk of the nchunk chunks of windows, *draw_block of the ndb blocks of 64 draws.  A bijection.  Workgroups go to the eight XCDs
+ * in turn; on the whole eights of chunks, which come first, chunk = id (mod 8) — one L2 reads one eighth of the pair table — and the draw blocks go
+ * in groups of four, the workgroups of one chunk and group on ids 8 apart; the nchunk mod 8 last chunks follow on adjacent ids, in the same groups.
+ * The kernel calls the same function (csrc/common.h tile_pairs_slot);
+ * tests/test_tile_pairs_map_host.py holds it.  PIORAN_ERR_ARG: a count below 1, an id outside the range, a NULL output. */
+int pioran_tile_pairs_slot(int64_t id, int64_t nchunk, int64_t ndb, int64_t* chunk, int64_t* draw_block);
 /* Diagnostics (no GPU needed): the kernel family a log-likelihood launch takes — shared (c, d) of J terms, n_one_row_terms of them with one row
  * (R = 2 J - n_one_row_terms active rows), B draws of N time stamps, per_draw_series != 0: (y, sigma2) per draw — when every resource it asks
  * for is granted: the table fits, the workspace is within the budget, the time-parallel family's repair pass is available.  `name` receives one of

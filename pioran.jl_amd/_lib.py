@@ -88,6 +88,7 @@ SIGNATURES = {
     "pioran_celerite_config_name": (ctypes.c_char_p, [i64]),
     "pioran_ctx_fp64_probe": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_double, ctypes.POINTER(ctypes.c_double)]),
     "pioran_tile_choice": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
+    "pioran_tile_pairs_slot": (ctypes.c_int, [i64, i64, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
     "pioran_value_route": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, i64, i64, ctypes.c_int, i64, ctypes.c_char_p,
                                           ctypes.c_char_p, ctypes.c_int, c_int32_p]),
     "pioran_value_route_cd": (ctypes.c_int, [ctypes.c_int32] * 3 + [i64, i64, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int,

@@ -882,6 +882,15 @@ int set_option(ScanOptions& o, const char* key, const char* value)
 
 int pioran_tile_choice(int32_t R, int64_t B, int64_t pass, int no_split) { return tile_choice(R, B, pass, no_split); }
 
+int pioran_tile_pairs_slot(int64_t id, int64_t nchunk, int64_t ndb, int64_t* chunk, int64_t* draw_block)
+{
+    if (nchunk < 1 || ndb < 1 || id < 0 || nchunk > INT64_MAX / ndb || id >= nchunk * ndb || !chunk || !draw_block) return PIORAN_ERR_ARG;
+    const PairsSlot s = tile_pairs_slot(id, nchunk, ndb);
+    *chunk = s.chunk;
+    *draw_block = s.db;
+    return PIORAN_OK;
+}
+
 // "key=value;key=value" into a set of options
 static int parse_options(const char* options, ScanOptions& opt)
 {

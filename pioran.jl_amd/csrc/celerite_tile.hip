@@ -22,8 +22,8 @@
 // vector instructions, against ~1300 SIMD cycles of the register-resident step-by-step scan (celerite_scan.hip), whose every FMA is
 // a vector instruction.
 // The window's own covariance block A (kappa on the 120 pairs of the window: a contraction of the pair table E with the draw's
-// (a, b)) does not depend on the state: tile_pairs_mfma_kernel forms it for every (draw, window) of the launch beforehand — E in
-// registers, 32 draws per workgroup — into a workspace of 1 KB per draw and window that the factorisation reads one window ahead
+// (a, b)) does not depend on the state: tile_pairs_mfma_kernel forms it for every (draw, window) of the launch beforehand — a matrix
+// product, 64 draws and five windows per workgroup, E read from L2 — into a workspace of 1 KB per draw and window that the factorisation reads one window ahead
 // (first version: the contraction inside the window loop, 40 .. 80 dependent reads of E from L2 per window: a third of the time).
 // Restrictions: shared (c, d) without per-draw rows; 1 .. 95 active rows; the series shared or per draw (Y, S2: the shifted log-flux models).
 // Everything else stays on the other kernels.
@@ -87,6 +87,7 @@ struct TileWave {                  // LDS of one wavefront
 // 32-byte stride in each of sixteen rows, and no line whole).  The scratch (66 560 bytes per workgroup) holds two workgroups on a CU.  JQ = ceil(J / 4), compile-time.
 // (Vector forms of round 5, removed in round 6: 0.93 ms per 4096 draws at 20 terms with the table in registers, 1.97 ms at 40 terms with the coefficients in LDS.)
 constexpr int kPairWin = 5;
+constexpr int64_t kPairMaxGroups = (1 << 24) - 1;   // workgroups of 256 threads in a launch: it stays within 2^32 threads
 constexpr int kPairRow = 128 + 2;  // doubles per draw row of the scratch: the 16 rows of a 32-byte write then fall on different banks
 typedef double d2v __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) d2v lds_d2v;
@@ -96,8 +97,17 @@ __global__ void __launch_bounds__(256) tile_pairs_mfma_kernel(const ScanParams p
     const int J = p.J;
     const int64_t NW = (p.N + KW - 1) / KW;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, li = lane & 15, lk = lane >> 4;
-    const int64_t b0 = ((int64_t)blockIdx.y * 4 + w) * 16;
-    if (b0 >= p.B) return;                         // (no workgroup-level synchronisation in this kernel)
+    // The scratch belongs to this wavefront alone: the LDS executes a wavefront's operations in order, so between its writes and its read-back only the
+    // compiler's order has to be kept (PIORAN_LDS_ORDER) — no barrier, no counter wait beyond the one the read's own result needs.
+    __shared__ __attribute__((aligned(16))) double scr_[4][16 * kPairRow];
+    // A workgroup fills one slot of the workspace — 64 draws x kPairWin windows — and its linear id names the slot (tile_pairs_slot, common.h: the kPairGroup
+    // workgroups that read one chunk of E run side by side behind one L2).  The grid is one-dimensional and holds every id up to kPairMaxGroups; a launch
+    // with more slots folds them onto it.
+    const int64_t nchunk = (NW + kPairWin - 1) / kPairWin, ndb = (p.B + 63) / 64;
+    for (int64_t id = blockIdx.x; id < nchunk * ndb; id += gridDim.x) {
+    const PairsSlot slot = tile_pairs_slot(id, nchunk, ndb);
+    const int64_t b0 = (slot.db * 4 + w) * 16;
+    if (b0 >= p.B) continue;                       // (no workgroup-level synchronisation in this kernel)
     const int64_t draw = b0 + li < p.B ? b0 + li : p.B - 1;
     // The PAIRS are the rows of the product (table entries as A operands), the draws its columns (coefficients as B operands), and row r of a tile is
     // pair 4 (r & 3) + (r >> 2): result register g of lane (lk, li) is then pair 4 lk + g of draw li — four ADJACENT pairs, 32 contiguous bytes of
@@ -112,10 +122,7 @@ __global__ void __launch_bounds__(256) tile_pairs_mfma_kernel(const ScanParams p
         bop[q] = t < J ? p.Bc[draw * J + t] : 0.0;
         toff[q] = (t < J ? t : J - 1) * 128 + 4 * (li & 3) + (li >> 2);
     }
-    const int64_t k0 = (int64_t)blockIdx.x * kPairWin, k1 = k0 + kPairWin < NW ? k0 + kPairWin : NW;
-    // The scratch belongs to this wavefront alone: the LDS executes a wavefront's operations in order, so between its writes and its read-back only the
-    // compiler's order has to be kept (PIORAN_LDS_ORDER) — no barrier, no counter wait beyond the one the read's own result needs.
-    __shared__ __attribute__((aligned(16))) double scr_[4][16 * kPairRow];
+    const int64_t k0 = slot.chunk * kPairWin, k1 = k0 + kPairWin < NW ? k0 + kPairWin : NW;
     double* wr = scr_[w] + li * kPairRow + 4 * lk;       // write: draw row li, pairs 4 lk .. 4 lk + 3 of the tile
     const double* rd = scr_[w] + 2 * lane;               // read-back i: draw row i, pairs 2 lane, 2 lane + 1 of the window
     double* orow = out + b0 * NW * 128 + 2 * lane;       // ... and that row's place in the workspace; row b0 + i exists only if b0 + i < B
@@ -125,8 +132,12 @@ __global__ void __launch_bounds__(256) tile_pairs_mfma_kernel(const ScanParams p
 #pragma unroll
         for (int q = 0; q < JQ; ++q) e[q] = E[toff[q] + 16 * pt];
     };
+    // The workgroups of a chunk start together and run at one speed.  Walking the tiles in the same order they ask the L2 for the same lines at the same
+    // moment, all but the first while the line is still on its way, and the kernel takes 1.4 to 1.6 times as long (docs/EXPERIMENTS.md section 40).  So
+    // draw block i of a group walks a window's eight tiles from tile 2 i on, round the window: the scratch takes the tiles in any order.
+    const int rot = 2 * (int)(slot.db & (kPairGroup - 1));
     double2 e[JQ];
-    load_e(e, k0, 0);
+    load_e(e, k0, rot);
     for (int64_t k = k0; k < k1; ++k) {
 #pragma unroll 2
         for (int pt = 0; pt < 8; ++pt) {
@@ -138,10 +149,10 @@ __global__ void __launch_bounds__(256) tile_pairs_mfma_kernel(const ScanParams p
             }
             {   // the next tile's fragments (the last tile of the last window fetches itself again: nothing past the table is read)
                 const bool last = pt == 7 && k + 1 == k1;
-                load_e(e, pt == 7 && !last ? k + 1 : k, last ? 7 : (pt + 1) & 7);
+                load_e(e, pt == 7 && !last ? k + 1 : k, ((last ? 7 : (pt + 1) & 7) + rot) & 7);
             }
-            *reinterpret_cast<d2v*>(wr + 16 * pt) = d2v{acc[0], acc[1]};
-            *reinterpret_cast<d2v*>(wr + 16 * pt + 2) = d2v{acc[2], acc[3]};
+            *reinterpret_cast<d2v*>(wr + 16 * ((pt + rot) & 7)) = d2v{acc[0], acc[1]};
+            *reinterpret_cast<d2v*>(wr + 16 * ((pt + rot) & 7) + 2) = d2v{acc[2], acc[3]};
         }
         PIORAN_LDS_ORDER();
 #pragma unroll
@@ -149,10 +160,12 @@ __global__ void __launch_bounds__(256) tile_pairs_mfma_kernel(const ScanParams p
 #pragma unroll
             for (int i = i0; i < i0 + 4; ++i) {
                 const d2v v = *reinterpret_cast<const d2v*>(rd + i * kPairRow);
-                if (b0 + i < p.B) *reinterpret_cast<d2v*>(orow + i * rstep + k * 128) = v;
+                // (non-temporal: nobody reads the row before the main kernel does, and the lines of E that the chunk's other workgroups are about to ask for stay)
+                if (b0 + i < p.B) __builtin_nontemporal_store(v, reinterpret_cast<d2v*>(orow + i * rstep + k * 128));
             }
             PIORAN_LDS_ORDER();
         }
+    }
     }
 }
 
@@ -160,8 +173,9 @@ template <typename... Args>
 static inline bool launch_pairs_mfma(const ScanParams& p, hipStream_t stream, Args... args)
 {
     const int64_t NW = (p.N + KW - 1) / KW;
-    if ((p.B + 63) / 64 > 65535 || p.J > kTileMaxTerms) return false;       // (more than 4 M draws per launch / 64 terms: the callers chunk / refuse)
-    const dim3 gr((unsigned)((NW + kPairWin - 1) / kPairWin), (unsigned)((p.B + 63) / 64));
+    if (p.J > kTileMaxTerms) return false;                                   // (more than 64 terms: the callers refuse)
+    const int64_t nid = (NW + kPairWin - 1) / kPairWin * ((p.B + 63) / 64);
+    const dim3 gr((unsigned)(nid < kPairMaxGroups ? nid : kPairMaxGroups));
     const int jq = (p.J + 3) / 4;
     if (jq <= 5) hipLaunchKernelGGL(tile_pairs_mfma_kernel<5>, gr, dim3(256), 0, stream, p, args...);
     else if (jq <= 10) hipLaunchKernelGGL(tile_pairs_mfma_kernel<10>, gr, dim3(256), 0, stream, p, args...);

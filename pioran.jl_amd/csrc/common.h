@@ -191,6 +191,27 @@ int pioran_tile_fits(int32_t R, int32_t J);
 int64_t pioran_tile_pass_draws(int32_t R, int cus);
 size_t pioran_tile_workspace_doubles(int64_t B, int64_t N);
 int pioran_launch_scan_tile(const ScanParams& p, const double* btab, double* work, hipStream_t stream);
+// ... its pair pre-pass (tile_pairs_mfma_kernel): the slot of the workspace that the workgroup with linear id `id` (0 .. nchunk ndb - 1) of the launch fills —
+// chunk `chunk` of the windows (of nchunk) for block `db` of 64 draws (of ndb).  A pure function and a bijection, the kernel's own decode;
+// pioran_tile_pairs_slot exports it.  Workgroups start in the order of their ids and go to the eight XCDs (one L2 each) in turn, so ids equal modulo 8
+// share an L2 and ids 8 apart are neighbours in its launch order.  First the whole eights of chunks, 8 (nchunk / 8) ndb ids: chunk = id (mod 8) — an
+// XCD reads an eighth of the pair table and nothing else of it — and the ids = x (mod 8) take the draw blocks in groups of kPairGroup = 4 (the last
+// group: what is left), a group after the other, inside a group chunk after chunk, draw block fastest: the workgroups that read one chunk of the table
+// are ids 8 apart, run together behind one L2, and the chunk is fetched from beyond it once per group at the most, not once per draw block.  Then the
+// nchunk mod 8 chunks that are left, which have no residue of their own: the same groups, draw block fastest on adjacent ids (nothing shared).  The
+// groups are as short as four because the stores want the workgroups in flight on few draw rows (docs/EXPERIMENTS.md section 40).
+constexpr int kPairGroup = 4;
+struct PairsSlot { int64_t chunk, db; };
+__host__ __device__ inline PairsSlot tile_pairs_slot(int64_t id, int64_t nchunk, int64_t ndb)
+{
+    const int64_t n8 = nchunk >> 3, whole = 8 * n8 * ndb;             // whole eights of chunks, and their ids
+    const bool tail = id >= whole;
+    const int64_t s = tail ? id - whole : id >> 3;                     // the place among the ids of one residue / of the chunks left over
+    const int64_t per = tail ? nchunk - 8 * n8 : n8;                   // chunks that one group of draw blocks meets there
+    const int64_t g = s / (kPairGroup * per), r = s - g * kPairGroup * per;
+    const int64_t G = ndb - g * kPairGroup < kPairGroup ? ndb - g * kPairGroup : kPairGroup;   // draw blocks of this group
+    return {tail ? 8 * n8 + r / G : (r / G) * 8 + (id & 7), g * kPairGroup + r % G};
+}
 // ... its reverse mode: log L and d/d(a, b, mu, nu), one draw per wavefront (1 .. 63 rows; shared (c, d) and series)
 int pioran_tile_grad_supported_rows();
 // celerite_tp.hip: time-parallel evaluation for a handful of draws (state-space form, associative filter elements; round 5)
