@@ -156,6 +156,14 @@ int ensure(pioran_ctx* ctx, pioran_ctx::Buf& b, size_t bytes)
     return PIORAN_OK;
 }
 
+struct BufNeed { pioran_ctx::Buf* b; size_t bytes; };
+int ensure_each(pioran_ctx* ctx, std::initializer_list<BufNeed> needs)
+{
+    for (const BufNeed& n : needs)
+        if (int rc = ensure(ctx, *n.b, n.bytes)) return rc;
+    return PIORAN_OK;
+}
+
 // stream synchronisation + delivery of the results staged in pinned memory + reset of the staging allocator
 int ctx_sync(pioran_ctx* ctx)
 {
@@ -398,21 +406,23 @@ int theta_grads(pioran_ctx* ctx, const ThetaDraws& td, int64_t b0, int64_t nb, c
 }
 
 // Where a chunk's draws come from: draws [b0, b0 + nb) of the caller's host arrays `in` (upload_draws; per_draw: with their (c, d)), or, `td`,
-// approx_kernel's coefficients of the sampled parameters, written into the staging buffers upload_draws would have filled (mu, nu: the caller's, `in`'s)
+// approx_kernel's coefficients of the sampled parameters, written into the staging buffers upload_draws would have filled (mu, nu: the caller's, `in`'s).
+// J counts the features' terms where `td` has any: their (a, b) are the last columns of the rows, and their (c, d) land in the same columns of bC / bD.
 int stage_draws(pioran_ctx* ctx, int64_t J, int64_t b0, int64_t nb, const DrawChunk& in, bool per_draw, const ThetaDraws* td, DrawChunk& m)
 {
     if (!td) return upload_draws(ctx, J, b0, nb, in.A, in.Bc, per_draw ? in.C : nullptr, in.D, in.mu, in.nu, m);
     int rc;
     const size_t bj = (size_t)nb * (size_t)J * sizeof(double);
-    if ((rc = ensure(ctx, ctx->bA, bj))) return rc;
-    if ((rc = ensure(ctx, ctx->bB, bj))) return rc;
+    if ((rc = ensure_each(ctx, {{&ctx->bA, bj}, {&ctx->bB, bj}, {&ctx->bC, td->n_qpo ? bj : 0}, {&ctx->bD, td->n_qpo ? bj : 0}}))) return rc;
     if (in.mu && (rc = upload(ctx, ctx->bmu, in.mu + b0, nb * sizeof(double)))) return rc;
     if (in.nu && (rc = upload(ctx, ctx->bnu, in.nu + b0, nb * sizeof(double)))) return rc;
     m = DrawChunk{};
     m.A = (const double*)ctx->bA.p; m.Bc = (const double*)ctx->bB.p;
+    if (td->n_qpo) { m.C = (const double*)ctx->bC.p; m.D = (const double*)ctx->bD.p; }
     m.mu = in.mu ? (const double*)ctx->bmu.p : nullptr; m.nu = in.nu ? (const double*)ctx->bnu.p : nullptr;
     return pioran_launch_approx(nb, td->model, td->P, td->J, td->basis, td->integrated, td->f_min, td->f_max, td->sp, td->LU, td->piv,
-                                td->theta + b0 * td->P, td->norm + b0, 0, nullptr, (double*)ctx->bA.p, (double*)ctx->bB.p, nullptr, nullptr, ctx->stream);
+                                td->theta + b0 * td->P, td->norm + b0, td->n_qpo, at(td->qpo, b0 * 3 * td->n_qpo), (double*)ctx->bA.p, (double*)ctx->bB.p,
+                                (double*)m.C, (double*)m.D, ctx->stream);
 }
 
 // log L and status of n draws land in bout / bst ...
@@ -487,14 +497,6 @@ int size_chunk(pioran_ctx* ctx, int64_t& chunk, BufList held, Need need, EnsureA
     }
 }
 
-struct BufNeed { pioran_ctx::Buf* b; size_t bytes; };
-int ensure_each(pioran_ctx* ctx, std::initializer_list<BufNeed> needs)
-{
-    for (const BufNeed& n : needs)
-        if (int rc = ensure(ctx, *n.b, n.bytes)) return rc;
-    return PIORAN_OK;
-}
-
 // second stream + events of the gradient's reverse pass and of the remainder launch (split_dispatch): created on first use
 int ensure_aux(pioran_ctx* ctx)
 {
@@ -567,6 +569,33 @@ int set_rowmap(pioran_ds* ds, PrepState& s, const std::vector<int32_t>& rm)
 }
 
 thread_local const char* g_last_kernel = "none";   // which kernel family the calling thread's last launch ran on (diagnostics)
+
+// A launch of the sampled-parameter kernels (approx with features, carma.hip): the family's name for the diagnostics, the launch between the events
+// ev0, ev0 + 1 where the call is timed, and the entry's text for a launch the runtime refused
+template <class Launch>
+int timed_launch(pioran_ctx* ctx, const char* name, int ev0, bool timed, const char* err_text, Launch launch)
+{
+    g_last_kernel = name;
+    if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[ev0], ctx->stream));
+    if (const int rc = launch()) {
+        if (rc == PIORAN_ERR_HIP) ctx->last_err = err_text;
+        return rc;
+    }
+    if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[ev0 + 1], ctx->stream));
+    return PIORAN_OK;
+}
+
+// The caller's cotangent arrays, n doubles each, one behind the other in bK (where the gradient entries keep a chunk's: grad_chunk); dev: the first
+int upload_cotangents(pioran_ctx* ctx, std::initializer_list<const double*> host, size_t n, double*& dev)
+{
+    int rc;
+    if ((rc = ensure(ctx, ctx->bK, host.size() * n * sizeof(double)))) return rc;
+    dev = (double*)ctx->bK.p;
+    size_t k = 0;
+    for (const double* h : host)
+        if ((rc = upload_to(ctx, dev + k++ * n, h, n * sizeof(double)))) return rc;
+    return PIORAN_OK;
+}
 
 // ---- the value path: which family takes a launch is route.hip's to say; here the family's table, workspace, second stream are acquired and it is launched ----
 // The prepared state whose shared table a launch reads, if it is one without per-draw terms.  What else a family needs of it is a second test at its
@@ -1440,13 +1469,61 @@ static int mixed_core(pioran_ds* ds, int64_t B, int64_t J, const std::vector<int
     return 1;
 }
 
-static int batch_host_mixed(pioran_ds* ds, int64_t B, int64_t J, const double* A, const double* Bc, const double* C,
-                            const double* Dd, const double* mu, const double* nu, const double* Y, const double* S2,
-                            bool series_on_device, double* out, int32_t* status)
+// kind[J] of a batch whose host arrays hold a (c, d) row per draw.  One draw, or the same rows in every draw: that IS the shared case (table built once,
+// windowed kernel for small batches), no term is per-draw.  Else the terms that differ are; under "no_mixed" all of them, unlooked at (mixed_plan
+// declines the batch whatever they are: this saves classify_terms' pass over it).
+static std::vector<int32_t> draw_layout(const ScanOptions& opt, int64_t B, int64_t J, const double* Bc, const double* C, const double* Dd)
 {
-    if (ds->ctx->opt.no_mixed) return 0;   // (mixed_plan says so too: this saves classify_terms' pass over the batch)
-    const MixedSource src{{A, Bc, C, Dd, mu, nu, Y, S2}, false, series_on_device};
-    return mixed_core(ds, B, J, classify_terms(B, J, Bc, C, Dd, true), C, Dd, src, out, status);   // row 0 of C, Dd: the shared values
+    bool same = true;
+    for (int64_t b = 1; b < B && same; ++b)
+        same = !std::memcmp(C + b * J, C, (size_t)J * sizeof(double)) && !std::memcmp(Dd + b * J, Dd, (size_t)J * sizeof(double));
+    if (!same && opt.no_mixed) return std::vector<int32_t>((size_t)J, 2);
+    return classify_terms(B, J, Bc, C, Dd, !same);
+}
+
+// The transformed series of the shifted log-flux models, all B draws' (dshift: their shifts, on the device), in bY / bS2: where the value bodies read a
+// batch's per-draw series
+static int stage_shift_dev(pioran_ds* ds, int64_t B, const double* dshift)
+{
+    pioran_ctx* ctx = ds->ctx;
+    const size_t bn = (size_t)B * (size_t)ds->N * sizeof(double);
+    int rc;
+    if ((rc = ensure_each(ctx, {{&ctx->bY, bn}, {&ctx->bS2, bn}}))) return rc;
+    return pioran_launch_shift_transform(ds->N, B, ds->y, ds->s2, dshift, (double*)ctx->bY.p, (double*)ctx->bS2.p, ctx->stream);
+}
+
+// ... from the caller's shifts
+static int stage_shift(pioran_ds* ds, int64_t B, const double* shift)
+{
+    const int rc = upload(ds->ctx, ds->ctx->bshift, shift, B * sizeof(double));
+    return rc ? rc : stage_shift_dev(ds, B, (const double*)ds->ctx->bshift.p);
+}
+
+// The value of a batch from the host's view of its terms: kind[J] as mixed_core reads it, (C0, D0) [J] the values of the terms that are not per-draw.
+// No per-draw term: the shared table.  Else mixed mode where its plan takes the batch, else every term from the draws' own (c, d) — which a caller
+// whose shared terms have no per-draw copy does not have (must_run: PIORAN_ERR_UNSUPPORTED then).  Results go to the caller's host arrays; the last
+// copies are queued, not waited for.
+static int value_from_draws(pioran_ds* ds, int64_t B, int64_t J, const MixedSource& src, const std::vector<int32_t>& kind, const double* C0, const double* D0,
+                            bool must_run, double* out, int32_t* status)
+{
+    pioran_ctx* ctx = ds->ctx;
+    const bool shared = std::find(kind.begin(), kind.end(), 2) == kind.end();
+    int rc;
+    if (shared) {
+        if ((rc = prepare_state(ds, ds->host, J, C0, D0, kind.data()))) return rc;
+    } else {
+        if ((rc = mixed_core(ds, B, J, kind, C0, D0, src, out, status, must_run))) return rc < 0 ? rc : PIORAN_OK;
+        if (must_run) return PIORAN_ERR_UNSUPPORTED;   // too many rows for the register-resident kernels
+    }
+    MixedSource whole = src;
+    if (shared) whole.draws.C = whole.draws.D = nullptr;   // (host arrays: the table has them, they do not go up)
+    DrawChunk m{};
+    if ((rc = mixed_chunk(ds, J, whole, 0, B, m))) return rc;
+    if ((rc = ensure_results(ctx, B))) return rc;
+    double* const dout = (double*)ctx->bout.p; int32_t* const dst = (int32_t*)ctx->bst.p;
+    rc = shared ? batch_dev_impl(ds, ds->host, B, m.A, m.Bc, m.mu, m.nu, m.Y, m.S2, dout, dst)
+                : pioran_celerite_logl_batch_dev_cd(ds, B, J, m.A, m.Bc, m.C, m.D, m.mu, m.nu, m.Y, m.S2, dout, dst);
+    return rc ? rc : download_results(ctx, out, status, 0, B);
 }
 
 // host-pointer batch; series_on_device: ctx->bY / ctx->bS2 already hold the per-draw series (shift transform)
@@ -1462,18 +1539,8 @@ static int batch_host_impl(pioran_ds* ds, int64_t B, int64_t J, const double* A,
     const size_t bj = (size_t)B * (size_t)J * sizeof(double);
     const size_t bn = (size_t)B * (size_t)ds->N * sizeof(double);
     int rc;
-    if (!cd_shared) {   // one draw, or the same (c, d) in every draw: that IS the shared case (table built once, windowed kernel for small batches)
-        bool same = true;
-        for (int64_t b = 1; b < B && same; ++b)
-            same = !std::memcmp(C + b * J, C, (size_t)J * sizeof(double)) && !std::memcmp(Dd + b * J, Dd, (size_t)J * sizeof(double));
-        if (same) cd_shared = 1;
-    }
-    if (!cd_shared && B > 1) {
-        rc = batch_host_mixed(ds, B, J, A, Bc, C, Dd, mu, nu, Y, S2, series_on_device, out, status);
-        if (rc < 0) return rc;
-        if (rc == 1) return PIORAN_OK;
-    }
-    if (cd_shared && (rc = prepare_shared(ds, B, J, Bc, C, Dd))) return rc;
+    const std::vector<int32_t> kind = cd_shared ? classify_terms(B, J, Bc, C, Dd, false) : draw_layout(ctx->opt, B, J, Bc, C, Dd);
+    cd_shared = std::find(kind.begin(), kind.end(), 2) == kind.end();
     // Small calls with shared (c, d) — the scalar drop-in, a few walkers (late round 4): the kernels read the coefficients straight from
     // pinned host memory (each value once) and write log L / status straight into it, so the call issues no copy command for them; a
     // per-draw series, which the kernels stream step by step, still goes to HBM, (y | sigma2) in ONE copy.  Scalar call, N = 32: 44 -> 3x us.
@@ -1481,7 +1548,9 @@ static int batch_host_impl(pioran_ds* ds, int64_t B, int64_t J, const double* A,
     const size_t zc_all = zc_in + B * sizeof(double) + ((B * sizeof(int32_t) + 7) & ~size_t(7));
     const size_t zc_pad = (zc_all + 255) & ~size_t(255);
     const bool y_staged = Y && zc_pad + 2 * bn <= kPinMaxRequest;      // (ONE reservation: a second one could drain or move the staging area)
-    char* zc = (cd_shared && zc_all <= (size_t(16) << 10) && !(ctx->opt.exp & 64)) ? (char*)pin_reserve(ctx, zc_pad + (y_staged ? 2 * bn : 0)) : nullptr;
+    const bool zc_wanted = cd_shared && zc_all <= (size_t(16) << 10) && !(ctx->opt.exp & 64);
+    if (zc_wanted && (rc = prepare_state(ds, ds->host, J, C, Dd, kind.data()))) return rc;
+    char* zc = zc_wanted ? (char*)pin_reserve(ctx, zc_pad + (y_staged ? 2 * bn : 0)) : nullptr;
     if (zc) {
         const double *dA = (const double*)zc, *dB = dA + B * J, *dmu = nullptr, *dnu = nullptr;
         char* q = zc + 2 * bj;
@@ -1511,21 +1580,8 @@ static int batch_host_impl(pioran_ds* ds, int64_t B, int64_t J, const double* A,
         SYNC(ctx);
         return PIORAN_OK;
     }
-    DrawChunk m;
-    if ((rc = upload_draws(ctx, J, 0, B, A, Bc, cd_shared ? nullptr : C, Dd, mu, nu, m))) return rc;
-    if (Y) {
-        if ((rc = upload(ctx, ctx->bY, Y, bn))) return rc;
-        if ((rc = upload(ctx, ctx->bS2, S2, bn))) return rc;
-    }
-    if ((rc = ensure_results(ctx, B))) return rc;
-    const double* dY = (Y || series_on_device) ? (const double*)ctx->bY.p : nullptr;
-    const double* dS2 = (Y || series_on_device) ? (const double*)ctx->bS2.p : nullptr;
-    if (cd_shared)
-        rc = batch_dev_impl(ds, ds->host, B, m.A, m.Bc, m.mu, m.nu, dY, dS2, (double*)ctx->bout.p, (int32_t*)ctx->bst.p);
-    else
-        rc = pioran_celerite_logl_batch_dev_cd(ds, B, J, m.A, m.Bc, m.C, m.D, m.mu, m.nu, dY, dS2, (double*)ctx->bout.p, (int32_t*)ctx->bst.p);
-    if (rc) return rc;
-    if ((rc = download_results(ctx, out, status, 0, B))) return rc;
+    const MixedSource src{{A, Bc, C, Dd, mu, nu, Y, S2}, false, series_on_device};
+    if ((rc = value_from_draws(ds, B, J, src, kind, C, Dd, false, out, status))) return rc;   // row 0 of C, Dd: the shared values
     SYNC(ctx);
     return PIORAN_OK;
 }
@@ -1537,28 +1593,15 @@ int pioran_celerite_logl_batch(pioran_ds* ds, int64_t B, int64_t J, const double
     return batch_host_impl(ds, B, J, A, Bc, C, Dd, cd_shared, mu, nu, Y, S2, false, out, status);
 }
 
-static int batch_shift_dev_impl(pioran_ds* ds, const PrepState& s, int64_t B, const double* dA, const double* dBc, const double* dmu,
-                                const double* dnu, const double* dshift, double* dout, int32_t* dstatus)
-{
-    if (!ds || B < 1 || !dA || !dBc || !dshift || !dout) return PIORAN_ERR_ARG;
-    if (!s.prepared) return PIORAN_ERR_ARG;
-    pioran_ctx* ctx = ds->ctx;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t bn = (size_t)B * (size_t)ds->N * sizeof(double);
-    int rc;
-    if ((rc = ensure(ctx, ctx->bY, bn))) return rc;
-    if ((rc = ensure(ctx, ctx->bS2, bn))) return rc;
-    rc = pioran_launch_shift_transform(ds->N, B, ds->y, ds->s2, dshift, (double*)ctx->bY.p, (double*)ctx->bS2.p, ctx->stream);
-    if (rc) return rc;
-    return batch_dev_impl(ds, s, B, dA, dBc, dmu, dnu, (const double*)ctx->bY.p, (const double*)ctx->bS2.p,
-                                          dout, dstatus);
-}
-
 int pioran_celerite_logl_batch_shift_dev(pioran_ds* ds, int64_t B, const double* dA, const double* dBc, const double* dmu,
                                          const double* dnu, const double* dshift, double* dout, int32_t* dstatus)
 {
-    if (!ds) return PIORAN_ERR_ARG;
-    return batch_shift_dev_impl(ds, ds->user, B, dA, dBc, dmu, dnu, dshift, dout, dstatus);
+    if (!ds || B < 1 || !dA || !dBc || !dshift || !dout) return PIORAN_ERR_ARG;
+    if (!ds->user.prepared) return PIORAN_ERR_ARG;
+    pioran_ctx* ctx = ds->ctx;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (const int rc = stage_shift_dev(ds, B, dshift)) return rc;
+    return batch_dev_impl(ds, ds->user, B, dA, dBc, dmu, dnu, (const double*)ctx->bY.p, (const double*)ctx->bS2.p, dout, dstatus);
 }
 
 int pioran_celerite_logl_batch_shift(pioran_ds* ds, int64_t B, int64_t J, const double* A, const double* Bc,
@@ -1568,14 +1611,7 @@ int pioran_celerite_logl_batch_shift(pioran_ds* ds, int64_t B, int64_t J, const 
     if (!ds || B < 1 || J < 1 || !A || !Bc || !C || !Dd || !shift || !out) return PIORAN_ERR_ARG;
     pioran_ctx* ctx = ds->ctx;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    int rc;
-    const size_t bn = (size_t)B * (size_t)ds->N * sizeof(double);
-    if ((rc = ensure(ctx, ctx->bY, bn))) return rc;
-    if ((rc = ensure(ctx, ctx->bS2, bn))) return rc;
-    if ((rc = upload(ctx, ctx->bshift, shift, B * sizeof(double)))) return rc;
-    rc = pioran_launch_shift_transform(ds->N, B, ds->y, ds->s2, (const double*)ctx->bshift.p, (double*)ctx->bY.p,
-                                       (double*)ctx->bS2.p, ctx->stream);
-    if (rc) return rc;
+    if (const int rc = stage_shift(ds, B, shift)) return rc;
     return batch_host_impl(ds, B, J, A, Bc, C, Dd, cd_shared, mu, nu, nullptr, nullptr, /*series_on_device=*/true, out,
                            status);
 }
@@ -1590,86 +1626,24 @@ int pioran_logpdf_batch_theta(pioran_ds* ds, int64_t B, int model, int64_t n_com
     pioran_ctx* ctx = ds->ctx;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     PendingGuard pending_guard(ctx);
-    const int P = model == 0 ? 3 : 5;
-    const int64_t J = n_components, Jc = basis == 0 ? J : 2 * J, Jt = Jc + n_qpo;
-    std::vector<double> sp, LU, c, d;
-    std::vector<int32_t> piv, real;
-    int rc = pioran_approx_setup_host(J, basis, f_min, f_max, S_low, S_high, sp, LU, piv, c, d, real);
+    ThetaDraws td;
+    int rc = stage_theta(ctx, B, model, n_components, basis, is_integrated_power, f_min, f_max, S_low, S_high, theta, norm, td, n_qpo, qpo);
     if (rc) return rc;
-    // staging: [sp J | LU J*J | piv (as int32, J)] in bwork; theta in bC / norm in bD without QPO features (both free when
-    // (c, d) are shared); with features bC / bD receive the per-draw (c, d) of the feature terms and theta, norm, qpo ride in bwork
-    const size_t nd = (size_t)J + (size_t)J * J + (size_t)J;
-    const size_t nextra = n_qpo ? (size_t)B * (P + 1 + 3 * n_qpo) : 0;
-    if ((rc = ensure(ctx, ctx->bwork, (nd + nextra) * sizeof(double)))) return rc;
-    double* dsp = (double*)ctx->bwork.p;
-    double* dLU = dsp + J;
-    int32_t* dpiv = (int32_t*)(dLU + J * J);
-    HIPCHK(ctx, hipMemcpyAsync(dsp, sp.data(), J * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(dLU, LU.data(), J * J * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(dpiv, piv.data(), J * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    const size_t bj = (size_t)B * (size_t)Jt * sizeof(double);
-    if ((rc = ensure(ctx, ctx->bA, bj))) return rc;
-    if ((rc = ensure(ctx, ctx->bB, bj))) return rc;
-    const double *dtheta, *dnorm, *dqpo = nullptr;
-    double *dCq = nullptr, *dDq = nullptr;
-    if (n_qpo) {
-        double* ex = dsp + nd;
-        HIPCHK(ctx, hipMemcpyAsync(ex, theta, (size_t)B * P * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(ex + (size_t)B * P, norm, (size_t)B * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(ex + (size_t)B * (P + 1), qpo, (size_t)B * 3 * n_qpo * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        dtheta = ex; dnorm = ex + (size_t)B * P; dqpo = ex + (size_t)B * (P + 1);
-        if ((rc = ensure(ctx, ctx->bC, bj))) return rc;
-        if ((rc = ensure(ctx, ctx->bD, bj))) return rc;
-        dCq = (double*)ctx->bC.p; dDq = (double*)ctx->bD.p;
-    } else {
-        if ((rc = upload(ctx, ctx->bC, theta, (size_t)B * P * sizeof(double)))) return rc;
-        if ((rc = upload(ctx, ctx->bD, norm, (size_t)B * sizeof(double)))) return rc;
-        dtheta = (const double*)ctx->bC.p; dnorm = (const double*)ctx->bD.p;
-    }
-    rc = pioran_launch_approx(B, model, P, (int)J, basis, is_integrated_power, f_min, f_max, dsp, dLU, dpiv, dtheta, dnorm,
-                              (int)n_qpo, dqpo, (double*)ctx->bA.p, (double*)ctx->bB.p, dCq, dDq, ctx->stream);
-    if (rc) return rc;
-    SYNC(ctx);   // sp/LU/piv host vectors go out of scope below
-    if (mu && (rc = upload(ctx, ctx->bmu, mu, B * sizeof(double)))) return rc;
-    if (nu && (rc = upload(ctx, ctx->bnu, nu, B * sizeof(double)))) return rc;
-    const double* dmu = mu ? (const double*)ctx->bmu.p : nullptr;
-    const double* dnu = nu ? (const double*)ctx->bnu.p : nullptr;
-    const size_t bn = (size_t)B * (size_t)ds->N * sizeof(double);
+    const int64_t Jc = td.terms(), Jt = Jc + n_qpo;
+    MixedSource src{{}, true, false};
+    if ((rc = stage_draws(ctx, Jt, 0, B, {nullptr, nullptr, nullptr, nullptr, mu, nu, nullptr, nullptr}, false, &td, src.draws))) return rc;
     if (shift) {
-        if ((rc = upload(ctx, ctx->bshift, shift, B * sizeof(double)))) return rc;
-        if (n_qpo) {   // transformed series of the whole batch, chunks of the mixed core read their slices
-            if ((rc = ensure(ctx, ctx->bY, bn))) return rc;
-            if ((rc = ensure(ctx, ctx->bS2, bn))) return rc;
-            if ((rc = pioran_launch_shift_transform(ds->N, B, ds->y, ds->s2, (const double*)ctx->bshift.p, (double*)ctx->bY.p,
-                                                    (double*)ctx->bS2.p, ctx->stream))) return rc;
-        }
+        if ((rc = stage_shift(ds, B, shift))) return rc;
+        src.draws.Y = (const double*)ctx->bY.p; src.draws.S2 = (const double*)ctx->bS2.p;
     }
-    if (n_qpo) {
-        // continuum terms from the shared table, the feature terms (per-draw c, d) from the per-draw block: mixed mode
-        std::vector<int32_t> kind((size_t)Jt, 0);
-        std::vector<double> c0((size_t)Jt, 0.0), d0((size_t)Jt, 0.0);
-        for (int64_t j = 0; j < Jc; ++j) { kind[j] = real[j] ? 1 : 0; c0[j] = c[j]; d0[j] = d[j]; }
-        for (int64_t q = 0; q < n_qpo; ++q) kind[Jc + q] = 2;
-        const bool series = shift != nullptr;   // (the transformed series of the whole batch: the chunks read their slices)
-        const MixedSource src{{(const double*)ctx->bA.p, (const double*)ctx->bB.p, dCq, dDq, dmu, dnu, series ? (const double*)ctx->bY.p : nullptr,
-                               series ? (const double*)ctx->bS2.p : nullptr}, true, false};
-        rc = mixed_core(ds, B, Jt, kind, c0.data(), d0.data(), src, out, status, /*must_run=*/true);
-        if (rc < 0) return rc;
-        if (rc == 0) return PIORAN_ERR_UNSUPPORTED;   // too many rows for the register-resident kernels
-    } else {
-        if ((rc = prepare_state(ds, ds->host, Jc, c.data(), d.data(), real.data()))) return rc;
-        if ((rc = ensure_results(ctx, B))) return rc;
-        if (shift)
-            rc = batch_shift_dev_impl(ds, ds->host, B, (const double*)ctx->bA.p, (const double*)ctx->bB.p, dmu, dnu,
-                                      (const double*)ctx->bshift.p, (double*)ctx->bout.p, (int32_t*)ctx->bst.p);
-        else
-            rc = batch_dev_impl(ds, ds->host, B, (const double*)ctx->bA.p, (const double*)ctx->bB.p, dmu, dnu, nullptr,
-                                nullptr, (double*)ctx->bout.p, (int32_t*)ctx->bst.p);
-        if (rc) return rc;
-        if ((rc = download_results(ctx, out, status, 0, B))) return rc;
-    }
-    if (A_out) if ((rc = download(ctx, A_out, ctx->bA.p, bj))) return rc;
-    if (Bc_out) if ((rc = download(ctx, Bc_out, ctx->bB.p, bj))) return rc;
+    // the continuum's terms are the grid's, shared by all draws; the features' (c, d) exist per draw only, and the continuum's per draw not at all
+    std::vector<int32_t> kind(td.real);
+    kind.resize((size_t)Jt, 2);
+    td.c.resize((size_t)Jt, 0.0); td.d.resize((size_t)Jt, 0.0);
+    if ((rc = value_from_draws(ds, B, Jt, src, kind, td.c.data(), td.d.data(), /*must_run=*/n_qpo > 0, out, status))) return rc;
+    const size_t bj = (size_t)B * (size_t)Jt * sizeof(double);
+    if (A_out && (rc = download(ctx, A_out, ctx->bA.p, bj))) return rc;
+    if (Bc_out && (rc = download(ctx, Bc_out, ctx->bB.p, bj))) return rc;
     SYNC(ctx);
     return PIORAN_OK;
 }
@@ -1997,6 +1971,35 @@ static int logl_grad_impl(pioran_ds* ds, int64_t B, int64_t J, const double* A, 
     });
 }
 
+// The gradient of a batch whose coefficients (hA .. hD [B][J], (c, d) per draw) were made on the device from sampled parameters and fetched (QPO features,
+// CARMA): the reverse mode of the host-pointer gradient entries on them, their routing and their kernels.  g = grad_a .. grad_d [B][J]: the caller's, or
+// all nullptr — they are then made to point into `inter`, for the model's own reverse-mode step to read.  A draw with rejected[b] != 0 ran on benign
+// coefficients: log L = -inf, status 3, exact zeros in every gradient row.
+static int grad_through_host_coefs(pioran_ds* ds, int64_t B, int64_t J, const double* hA, const double* hB, const double* hC, const double* hD,
+                                   const int32_t* rejected, const double* mu, const double* nu, const double* shift, double* out, int32_t* status,
+                                   double* grad_nu, double* grad_mu, double* grad_shift, double* (&g)[4], std::vector<double>& inter)
+{
+    const size_t bj = (size_t)B * (size_t)J;
+    if (!g[0]) {
+        inter.resize(4 * bj);
+        for (int k = 0; k < 4; ++k) g[k] = inter.data() + k * bj;
+    }
+    std::vector<int32_t> st((size_t)B, 0);
+    if (const int rc = logl_grad_impl(ds, B, J, hA, hB, hC, hD, 0, mu, nu, shift, out, st.data(), {g[0], g[1], g[2], g[3], grad_nu, grad_mu, nullptr, nullptr},
+                                      grad_shift))
+        return rc;
+    for (int64_t b = 0; b < B; ++b) {
+        if (!rejected[b]) continue;
+        out[b] = -INFINITY; st[(size_t)b] = 3;
+        for (double* gk : g) std::fill(gk + b * J, gk + (b + 1) * J, 0.0);
+        if (grad_nu) grad_nu[b] = 0.0;
+        if (grad_mu) grad_mu[b] = 0.0;
+        if (grad_shift) grad_shift[b] = 0.0;
+    }
+    if (status) std::memcpy(status, st.data(), (size_t)B * sizeof(int32_t));
+    return PIORAN_OK;
+}
+
 int pioran_celerite_logl_grad(pioran_ds* ds, int64_t B, int64_t J, const double* A, const double* Bc, const double* C,
                               const double* Dd, int cd_shared, const double* mu, const double* nu, double* out, int32_t* status,
                               double* grad_a, double* grad_b, double* grad_c, double* grad_d, double* grad_nu, double* grad_mu,
@@ -2051,10 +2054,8 @@ int pioran_approx_vjp_batch(pioran_ctx* ctx, int64_t B, int model, int64_t n_com
     td.grad_theta = grad_theta; td.grad_norm = grad_norm;
     // grad_a | grad_b of the batch where the gradient entries keep a chunk's (grad_chunk)
     const size_t bj = (size_t)B * (size_t)td.terms();
-    if ((rc = ensure(ctx, ctx->bK, 2 * bj * sizeof(double)))) return rc;
-    double* dga = (double*)ctx->bK.p;
-    if ((rc = upload_to(ctx, dga, grad_a, bj * sizeof(double)))) return rc;
-    if ((rc = upload_to(ctx, dga + bj, grad_b, bj * sizeof(double)))) return rc;
+    double* dga;
+    if ((rc = upload_cotangents(ctx, {grad_a, grad_b}, bj, dga))) return rc;
     if ((rc = ensure_theta_grads(ctx, td, B))) return rc;
     if ((rc = theta_grads(ctx, td, 0, B, dga, dga + bj))) return rc;
     SYNC(ctx);
@@ -2080,22 +2081,15 @@ static int qpo_vjp_from_host(pioran_ctx* ctx, int64_t B, const ThetaDraws& td, c
 {
     int rc;
     const size_t bj = (size_t)B * (size_t)(td.terms() + td.n_qpo), nth = (size_t)B * td.P, nq = (size_t)B * 3 * (size_t)td.n_qpo;
-    if ((rc = ensure(ctx, ctx->bK, 4 * bj * sizeof(double)))) return rc;
+    double* dg;
+    if ((rc = upload_cotangents(ctx, {ga, gb, gc, gd}, bj, dg))) return rc;
     if ((rc = ensure_theta_grads(ctx, td, B))) return rc;
-    double* dg = (double*)ctx->bK.p;
-    const double* host[4] = {ga, gb, gc, gd};
-    for (int k = 0; k < 4; ++k)
-        if ((rc = upload_to(ctx, dg + k * bj, host[k], bj * sizeof(double)))) return rc;
     double* gth = (double*)ctx->bthout.p; double* gn = gth + nth; double* scratch = gn + B; double* gq = scratch + 2 * (size_t)td.J * (size_t)B;
-    const bool timed = ctx->opt.theta_events != 0;
-    g_last_kernel = kApproxQpoVjpName;
-    if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
-    if ((rc = pioran_launch_approx_qpo_vjp(B, td.model, td.P, td.J, td.basis, td.integrated, td.f_min, td.f_max, td.sp, td.w, td.LU, td.piv, td.theta, td.norm,
-                                           td.n_qpo, td.qpo, dg, dg + bj, dg + 2 * bj, dg + 3 * bj, scratch, gth, gn, gq, ctx->stream))) {
-        if (rc == PIORAN_ERR_HIP) ctx->last_err = "approx reverse-mode launch failed";
+    if ((rc = timed_launch(ctx, kApproxQpoVjpName, 6, ctx->opt.theta_events != 0, "approx reverse-mode launch failed", [&] {
+            return pioran_launch_approx_qpo_vjp(B, td.model, td.P, td.J, td.basis, td.integrated, td.f_min, td.f_max, td.sp, td.w, td.LU, td.piv, td.theta,
+                                                td.norm, td.n_qpo, td.qpo, dg, dg + bj, dg + 2 * bj, dg + 3 * bj, scratch, gth, gn, gq, ctx->stream);
+        })))
         return rc;
-    }
-    if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
     if ((rc = download(ctx, grad_theta, gth, nth * sizeof(double)))) return rc;
     if ((rc = download(ctx, grad_norm, gn, (size_t)B * sizeof(double)))) return rc;
     return download(ctx, grad_qpo, gq, nq * sizeof(double));
@@ -2138,7 +2132,7 @@ int pioran_logpdf_batch_theta_qpo_grad(pioran_ds* ds, int64_t B, int model, int6
     // a draw the reference could not evaluate (non-finite theta, norm or feature; f0 <= 0; Q <= 1/2: DomainError of convert_feature) runs on benign
     // parameters and is overwritten afterwards
     std::vector<double> th(theta, theta + B * P), nm(norm, norm + B), qp(qpo, qpo + B * n_qpo * 3);
-    std::vector<char> bad((size_t)B, 0);
+    std::vector<int32_t> bad((size_t)B, 0);
     const double f_mid = std::sqrt(f_min * f_max);
     for (int64_t b = 0; b < B; ++b) {
         bool ok = std::isfinite(nm[b]);
@@ -2165,10 +2159,8 @@ int pioran_logpdf_batch_theta_qpo_grad(pioran_ds* ds, int64_t B, int model, int6
         if ((rc = stage_theta(ctx, B, model, J, basis, is_integrated_power != 0, f_min, f_max, S_low, S_high, th.data(), nm.data(), td, n_qpo, qp.data())))
             return rc;
         const size_t bytes = bj * sizeof(double);
-        if ((rc = ensure_each(ctx, {{&ctx->bA, bytes}, {&ctx->bB, bytes}, {&ctx->bC, bytes}, {&ctx->bD, bytes}}))) return rc;
-        if ((rc = pioran_launch_approx(B, td.model, td.P, td.J, td.basis, td.integrated, td.f_min, td.f_max, td.sp, td.LU, td.piv, td.theta, td.norm, td.n_qpo,
-                                       td.qpo, (double*)ctx->bA.p, (double*)ctx->bB.p, (double*)ctx->bC.p, (double*)ctx->bD.p, ctx->stream)))
-            return rc;
+        DrawChunk m;
+        if ((rc = stage_draws(ctx, Jt, 0, B, DrawChunk{}, false, &td, m))) return rc;
         if ((rc = download(ctx, hA.data(), ctx->bA.p, bytes))) return rc;
         if ((rc = download(ctx, hB.data(), ctx->bB.p, bytes))) return rc;
         if ((rc = download(ctx, hC.data(), ctx->bC.p, bytes))) return rc;
@@ -2179,29 +2171,17 @@ int pioran_logpdf_batch_theta_qpo_grad(pioran_ds* ds, int64_t B, int model, int6
         std::copy(td.c.begin(), td.c.end(), hC.begin() + b * Jt);
         std::copy(td.d.begin(), td.d.end(), hD.begin() + b * Jt);
     }
-    // the reverse mode of the host-pointer gradient entries on these coefficients, (c, d) per draw: their routing and their kernels
     std::vector<double> inter;
-    double *ga = grad_a, *gb = grad_b, *gc = grad_c, *gd = grad_d;
-    if (!n_inter) { inter.resize(4 * bj); ga = inter.data(); gb = ga + bj; gc = gb + bj; gd = gc + bj; }
-    std::vector<int32_t> st((size_t)B, 0);
-    if ((rc = logl_grad_impl(ds, B, Jt, hA.data(), hB.data(), hC.data(), hD.data(), 0, mu, nu, shift, out, st.data(),
-                             {ga, gb, gc, gd, grad_nu, grad_mu, nullptr, nullptr}, grad_shift)))
+    double* g[4] = {grad_a, grad_b, grad_c, grad_d};
+    if ((rc = grad_through_host_coefs(ds, B, Jt, hA.data(), hB.data(), hC.data(), hD.data(), bad.data(), mu, nu, shift, out, status, grad_nu, grad_mu, grad_shift,
+                                      g, inter)))
         return rc;
-    for (int64_t b = 0; b < B; ++b) {   // a rejected draw: log L = -inf, status 3, exact zeros in every gradient row
-        if (!bad[(size_t)b]) continue;
-        out[b] = -INFINITY; st[(size_t)b] = 3;
-        for (double* g : {ga, gb, gc, gd}) std::fill(g + b * Jt, g + (b + 1) * Jt, 0.0);
-        if (grad_nu) grad_nu[b] = 0.0;
-        if (grad_mu) grad_mu[b] = 0.0;
-        if (grad_shift) grad_shift[b] = 0.0;
-    }
-    if (status) std::memcpy(status, st.data(), (size_t)B * sizeof(int32_t));
     if (n_inter) {
         std::copy(hA.begin(), hA.end(), coef_a); std::copy(hB.begin(), hB.end(), coef_b);
         std::copy(hC.begin(), hC.end(), coef_c); std::copy(hD.begin(), hD.end(), coef_d);
     }
     PendingGuard guard(ctx);
-    if ((rc = qpo_vjp_from_host(ctx, B, td, ga, gb, gc, gd, grad_theta, grad_norm, grad_qpo))) return rc;
+    if ((rc = qpo_vjp_from_host(ctx, B, td, g[0], g[1], g[2], g[3], grad_theta, grad_norm, grad_qpo))) return rc;
     SYNC(ctx);
     for (int64_t b = 0; b < B; ++b) {   // (the chain of zero cotangents is zero up to its sign)
         if (!bad[(size_t)b]) continue;
@@ -3057,15 +3037,10 @@ static int carma_coefs_to_draws(pioran_ctx* ctx, int64_t B, const CarmaDraws& cd
     int rc;
     const size_t bj = (size_t)B * (size_t)cd.J * sizeof(double);
     if ((rc = ensure_each(ctx, {{&ctx->bA, bj}, {&ctx->bB, bj}, {&ctx->bC, bj}, {&ctx->bD, bj}}))) return rc;
-    g_last_kernel = kCarmaCoefsName;
-    if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
-    if ((rc = pioran_launch_carma_coefs(B, cd.p, cd.q, cd.form, cd.in1, cd.in2, cd.norm, cd.integrated, cd.f_lo, cd.f_hi, (double*)ctx->bA.p,
-                                        (double*)ctx->bB.p, (double*)ctx->bC.p, (double*)ctx->bD.p, cd.flags, ctx->stream))) {
-        if (rc == PIORAN_ERR_HIP) ctx->last_err = "carma coefficient launch failed";
-        return rc;
-    }
-    if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
-    return PIORAN_OK;
+    return timed_launch(ctx, kCarmaCoefsName, 4, timed, "carma coefficient launch failed", [&] {
+        return pioran_launch_carma_coefs(B, cd.p, cd.q, cd.form, cd.in1, cd.in2, cd.norm, cd.integrated, cd.f_lo, cd.f_hi, (double*)ctx->bA.p,
+                                         (double*)ctx->bB.p, (double*)ctx->bC.p, (double*)ctx->bD.p, cd.flags, ctx->stream);
+    });
 }
 
 int pioran_carma_coefs_batch(pioran_ctx* ctx, int64_t B, int p, int q, int form, const double* qa_or_roots, const double* qb_or_beta, const double* norm,
@@ -3096,21 +3071,15 @@ static int carma_vjp_from_host(pioran_ctx* ctx, int64_t B, const CarmaDraws& cd,
 {
     int rc;
     const size_t bj = (size_t)B * (size_t)cd.J, np = (size_t)B * cd.p, nq = (size_t)B * cd.q;
-    if ((rc = ensure(ctx, ctx->bK, 4 * bj * sizeof(double)))) return rc;
+    double* dg;
+    if ((rc = upload_cotangents(ctx, {ga, gb, gc, gd}, bj, dg))) return rc;
     if ((rc = ensure(ctx, ctx->bcarmaout, (np + nq + (size_t)B) * sizeof(double)))) return rc;
-    double* dg = (double*)ctx->bK.p;
-    const double* host[4] = {ga, gb, gc, gd};
-    for (int k = 0; k < 4; ++k)
-        if ((rc = upload_to(ctx, dg + k * bj, host[k], bj * sizeof(double)))) return rc;
     double* dqa = (double*)ctx->bcarmaout.p;
-    g_last_kernel = kCarmaVjpName;
-    if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
-    if ((rc = pioran_launch_carma_vjp(B, cd.p, cd.q, cd.in1, cd.in2, cd.norm, cd.integrated, cd.f_lo, cd.f_hi, dg, dg + bj, dg + 2 * bj, dg + 3 * bj, dqa,
-                                      dqa + np, dqa + np + nq, ctx->stream))) {
-        if (rc == PIORAN_ERR_HIP) ctx->last_err = "carma reverse-mode launch failed";
+    if ((rc = timed_launch(ctx, kCarmaVjpName, 4, timed, "carma reverse-mode launch failed", [&] {
+            return pioran_launch_carma_vjp(B, cd.p, cd.q, cd.in1, cd.in2, cd.norm, cd.integrated, cd.f_lo, cd.f_hi, dg, dg + bj, dg + 2 * bj, dg + 3 * bj, dqa,
+                                           dqa + np, dqa + np + nq, ctx->stream);
+        })))
         return rc;
-    }
-    if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
     if ((rc = download(ctx, grad_qa, dqa, np * sizeof(double)))) return rc;
     if (nq && grad_qb && (rc = download(ctx, grad_qb, dqa + np, nq * sizeof(double)))) return rc;
     return download(ctx, grad_norm, dqa + np + nq, (size_t)B * sizeof(double));
@@ -3155,15 +3124,10 @@ static int carma_psd_refuse(int64_t F, const double* freq, const void* any_outpu
 // draws [b0, b0 + nb) of the staged batch through the two PSD kernels into psd [nb][F]
 static int carma_psd_chunk(pioran_ctx* ctx, const CarmaDraws& cd, const CarmaPsdWork& w, int64_t b0, int64_t nb, int64_t F, int times_f, double* psd, bool timed)
 {
-    g_last_kernel = kCarmaPsdName;
-    if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
-    const int rc = pioran_launch_carma_psd(nb, cd.p, cd.q, cd.form, cd.in1 + b0 * cd.n1, cd.in2 ? cd.in2 + b0 * cd.n2 : nullptr, cd.norm + b0, cd.integrated,
-                                           cd.f_lo, cd.f_hi, F, w.freq, times_f != 0, w.roots + b0 * 2 * cd.p, w.betas + b0 * (cd.q + 1), w.scale + b0, psd,
-                                           w.status + b0, ctx->stream);
-    if (rc == PIORAN_ERR_HIP) ctx->last_err = "carma psd launch failed";
-    if (rc) return rc;
-    if (timed) HIPCHK(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
-    return PIORAN_OK;
+    return timed_launch(ctx, kCarmaPsdName, 4, timed, "carma psd launch failed", [&] {
+        return pioran_launch_carma_psd(nb, cd.p, cd.q, cd.form, cd.in1 + b0 * cd.n1, at(cd.in2, b0 * cd.n2), cd.norm + b0, cd.integrated, cd.f_lo, cd.f_hi, F,
+                                       w.freq, times_f != 0, w.roots + b0 * 2 * cd.p, w.betas + b0 * (cd.q + 1), w.scale + b0, psd, w.status + b0, ctx->stream);
+    });
 }
 
 int pioran_carma_psd_batch(pioran_ctx* ctx, int64_t B, int p, int q, int form, const double* qa_or_roots, const double* qb_or_beta, const double* norm,
@@ -3263,40 +3227,16 @@ int pioran_logpdf_batch_carma(pioran_ds* ds, int64_t B, int p, int q, const doub
     std::vector<int32_t> hflags;
     if ((rc = carma_coefs_fetch(ctx, B, cd, nullptr, hB, hC, hD, hflags))) return rc;
     const int64_t J = cd.J;
-    const size_t bj = (size_t)B * (size_t)J * sizeof(double), bn = (size_t)B * (size_t)ds->N * sizeof(double);
+    const size_t bj = (size_t)B * (size_t)J * sizeof(double);
     if (mu && (rc = upload(ctx, ctx->bmu, mu, B * sizeof(double)))) return rc;
     if (nu && (rc = upload(ctx, ctx->bnu, nu, B * sizeof(double)))) return rc;
-    const double *dY = nullptr, *dS2 = nullptr;
-    if (shift) {   // the transformed series of the whole batch, as pioran_celerite_logl_batch_shift builds them
-        if ((rc = ensure(ctx, ctx->bY, bn))) return rc;
-        if ((rc = ensure(ctx, ctx->bS2, bn))) return rc;
-        if ((rc = upload(ctx, ctx->bshift, shift, B * sizeof(double)))) return rc;
-        if ((rc = pioran_launch_shift_transform(ds->N, B, ds->y, ds->s2, (const double*)ctx->bshift.p, (double*)ctx->bY.p, (double*)ctx->bS2.p, ctx->stream)))
-            return rc;
-        dY = (const double*)ctx->bY.p; dS2 = (const double*)ctx->bS2.p;
-    }
-    const DrawChunk dev{(const double*)ctx->bA.p, (const double*)ctx->bB.p, (const double*)ctx->bC.p, (const double*)ctx->bD.p,
-                        mu ? (const double*)ctx->bmu.p : nullptr, nu ? (const double*)ctx->bnu.p : nullptr, dY, dS2};
-    // from here on the routing of batch_host_impl with cd_shared = 0, the draws already on the device: one draw, or the same (c, d) in every draw, is the
-    // shared case; else mixed mode where its plan takes the batch; else the per-draw-(c, d) body
-    bool same = true;
-    for (int64_t b = 1; b < B && same; ++b)
-        same = !std::memcmp(hC.data() + b * J, hC.data(), (size_t)J * sizeof(double)) && !std::memcmp(hD.data() + b * J, hD.data(), (size_t)J * sizeof(double));
-    bool done = false;
-    if (!same && !ctx->opt.no_mixed) {
-        const MixedSource src{dev, true, false};
-        rc = mixed_core(ds, B, J, classify_terms(B, J, hB.data(), hC.data(), hD.data(), true), hC.data(), hD.data(), src, out, status);
-        if (rc < 0) return rc;
-        done = rc == 1;
-    }
-    if (!done) {
-        if (same && (rc = prepare_shared(ds, B, J, hB.data(), hC.data(), hD.data()))) return rc;
-        if ((rc = ensure_results(ctx, B))) return rc;
-        rc = same ? batch_dev_impl(ds, ds->host, B, dev.A, dev.Bc, dev.mu, dev.nu, dY, dS2, (double*)ctx->bout.p, (int32_t*)ctx->bst.p)
-                  : pioran_celerite_logl_batch_dev_cd(ds, B, J, dev.A, dev.Bc, dev.C, dev.D, dev.mu, dev.nu, dY, dS2, (double*)ctx->bout.p, (int32_t*)ctx->bst.p);
-        if (rc) return rc;
-        if ((rc = download_results(ctx, out, status, 0, B))) return rc;
-    }
+    if (shift && (rc = stage_shift(ds, B, shift))) return rc;
+    const MixedSource src{{(const double*)ctx->bA.p, (const double*)ctx->bB.p, (const double*)ctx->bC.p, (const double*)ctx->bD.p,
+                           mu ? (const double*)ctx->bmu.p : nullptr, nu ? (const double*)ctx->bnu.p : nullptr,
+                           shift ? (const double*)ctx->bY.p : nullptr, shift ? (const double*)ctx->bS2.p : nullptr}, true, false};
+    // routed as the host-pointer entry routes a (c, d) row per draw
+    if ((rc = value_from_draws(ds, B, J, src, draw_layout(ctx->opt, B, J, hB.data(), hC.data(), hD.data()), hC.data(), hD.data(), false, out, status)))
+        return rc;
     if (A_out && (rc = download(ctx, A_out, ctx->bA.p, bj))) return rc;
     if (Bc_out && (rc = download(ctx, Bc_out, ctx->bB.p, bj))) return rc;
     if (C_out && (rc = download(ctx, C_out, ctx->bC.p, bj))) return rc;
@@ -3328,28 +3268,14 @@ int pioran_logpdf_batch_carma_grad(pioran_ds* ds, int64_t B, int p, int q, const
         if ((rc = stage_carma(ctx, B, p, q, 0, qa, qb, norm, is_integrated_power, f_lo, f_hi, cd))) return rc;
         if ((rc = carma_coefs_fetch(ctx, B, cd, &hA, hB, hC, hD, hflags))) return rc;
     }
-    // the reverse mode of the host-pointer gradient entries on these coefficients, (c, d) per draw: their routing (all draws in one launch of the windowed
-    // reverse mode where the shape fits it; one draw, and every draw of a shifted call, as a batch of its own) and their kernels
-    const int64_t J = cd.J;
-    const size_t bj = (size_t)B * (size_t)J;
+    // (all draws in one launch of the windowed reverse mode where the shape fits it; one draw, and every draw of a shifted call, as a batch of its own)
     std::vector<double> inter;
-    double *ga = grad_a, *gb = grad_b, *gc = grad_c, *gd = grad_d;
-    if (!n_inter) { inter.resize(4 * bj); ga = inter.data(); gb = ga + bj; gc = gb + bj; gd = gc + bj; }
-    std::vector<int32_t> st((size_t)B, 0);
-    if ((rc = logl_grad_impl(ds, B, J, hA.data(), hB.data(), hC.data(), hD.data(), 0, mu, nu, shift, out, st.data(), {ga, gb, gc, gd, grad_nu, grad_mu, nullptr, nullptr},
-                             grad_shift)))
+    double* g[4] = {grad_a, grad_b, grad_c, grad_d};
+    if ((rc = grad_through_host_coefs(ds, B, cd.J, hA.data(), hB.data(), hC.data(), hD.data(), hflags.data(), mu, nu, shift, out, status, grad_nu, grad_mu,
+                                      grad_shift, g, inter)))
         return rc;
-    for (int64_t b = 0; b < B; ++b) {   // a rejected draw ran on benign coefficients: log L = -inf, status 3, exact zeros in every gradient row
-        if (!hflags[(size_t)b]) continue;
-        out[b] = -INFINITY; st[(size_t)b] = 3;
-        for (double* g : {ga, gb, gc, gd}) std::fill(g + b * J, g + (b + 1) * J, 0.0);
-        if (grad_nu) grad_nu[b] = 0.0;
-        if (grad_mu) grad_mu[b] = 0.0;
-        if (grad_shift) grad_shift[b] = 0.0;
-    }
-    if (status) std::memcpy(status, st.data(), (size_t)B * sizeof(int32_t));
     PendingGuard guard(ctx);
-    if ((rc = carma_vjp_from_host(ctx, B, cd, ga, gb, gc, gd, grad_qa, grad_qb, grad_norm, false))) return rc;
+    if ((rc = carma_vjp_from_host(ctx, B, cd, g[0], g[1], g[2], g[3], grad_qa, grad_qb, grad_norm, false))) return rc;
     SYNC(ctx);
     return PIORAN_OK;
 }

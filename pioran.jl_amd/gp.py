@@ -783,21 +783,9 @@ class Dataset:
         model: SingleBendingPowerLaw / DoubleBendingPowerLaw (the class); theta: (B, 3 | 5); norm: scalar or (B,)
         — same meaning as the arguments of approx (src/psd.jl:214-289); mu, nu, shift as in logl_batch.
         qpo: (B, n_qpo, 3) or (B, 3) = (S0, f0, Q) of the QPO features added to the continuum (src/psd.jl:15-27, 228-241)."""
-        from .psd import DoubleBendingPowerLaw, SingleBendingPowerLaw
-        mid = {SingleBendingPowerLaw: 0, DoubleBendingPowerLaw: 1}.get(model)
-        if mid is None:
-            raise ValueError("model must be SingleBendingPowerLaw or DoubleBendingPowerLaw")
-        if basis_function not in ("SHO", "DRWCelerite"):
-            raise ValueError("Basis function" + basis_function + "not implemented")
-        theta = _f64(np.atleast_2d(theta))
-        B, P = theta.shape
-        if P != (3 if mid == 0 else 5):
-            raise ValueError("theta has the wrong number of columns for this model")
-        norm = _f64(np.broadcast_to(norm, (B,)))
-        mu = None if mu is None else _f64(np.broadcast_to(mu, (B,)))
-        nu = None if nu is None else _f64(np.broadcast_to(nu, (B,)))
-        shift = None if shift is None else _f64(np.broadcast_to(shift, (B,)))
-        basis = 0 if basis_function == "SHO" else 1
+        mid, basis, theta, norm = _theta_args(model, theta, norm, basis_function)
+        B = theta.shape[0]
+        mu, nu, shift = (None if v is None else _f64(np.broadcast_to(v, (B,))) for v in (mu, nu, shift))
         n_qpo = 0
         if qpo is not None:
             qpo = _f64(np.asarray(qpo, dtype=np.float64).reshape(B, -1, 3))

@@ -50,9 +50,16 @@ def test_time_parallel_thresholds(ctx):
 
 
 def test_draws_with_their_own_cd(ctx):
-    """Dataset.logl_batch with C, Dd per draw — all terms or a few of them differing (mixed mode) — and Dataset.logpdf_theta with QPO features, whose
-    mixed mode must run: the family pioran_value_route_cd names (route.hip mixed_plan, perdraw_form), at N = 130 (nine windows, the last ragged)."""
+    """Dataset.logl_batch with C, Dd per draw — all terms or a few of them differing (mixed mode) — Dataset.logpdf_theta with QPO features, whose
+    mixed mode must run, and Dataset.logpdf_carma, whose coefficients are made on the device: the family pioran_value_route_cd names (route.hip
+    mixed_plan, perdraw_form), at N = 130 (nine windows, the last ragged)."""
     seen = set()
+    for pt in G.carma_points():
+        got, out, st, (_, Bc, C, Dd) = G.run_carma_point(ctx, pt)
+        want = G.carma_expected(pt, Bc, C, Dd)
+        assert got == want, (pt, got, want)
+        assert np.isfinite(out).all() and (st == 0).all(), (pt, got)
+        seen.add(got)
     for pt in G.cd_points() + G.theta_points():
         want = G.expected(pt)
         got, out, st = G.run_point(ctx, pt)

@@ -2,8 +2,8 @@
 """The launches that cross every routing rule of the value path (csrc/route.hip), at the smallest shapes that still do.
 
 Importable: `points()` is the grid of tests/test_gpu_route.py, `run_point` makes one launch through the Python API, `value_route` asks
-pioran_value_route; `cd_points()` / `theta_points()` are the launches whose draws bring (c, d) of their own, `value_route_cd` asks
-pioran_value_route_cd.  As a program it runs the grid and prints, per point, the kernel family that ran and a hash of the log L and status
+pioran_value_route; `cd_points()` / `theta_points()` / `carma_points()` are the launches whose draws bring (c, d) of their own, `value_route_cd`
+asks pioran_value_route_cd.  As a program it runs the grid and prints, per point, the kernel family that ran and a hash of the log L and status
 arrays — a different segment count, mode or chunking changes bits, so two libraries with equal listings made equal plans:
 
     PIORAN_HIP_LIB=/path/to/other/libpioran_hip.so python tools/route_grid.py [--before-value-route] [--before-value-route-cd] > listing.txt
@@ -36,6 +36,8 @@ Point = namedtuple("Point", "J n_one B N options")
 CdPoint = namedtuple("CdPoint", "J npd B N options")
 # pioran_logpdf_batch_theta: n_qpo QPO features on a continuum of n_components SHO terms (mixed mode that must run)
 ThetaPoint = namedtuple("ThetaPoint", "n_components n_qpo B N")
+# pioran_logpdf_batch_carma: CARMA(p, q) from sampled parameters; which terms are per draw is read off the coefficients the call returns
+CarmaPoint = namedtuple("CarmaPoint", "p q B N options shift")
 
 
 def rows_of(pt):
@@ -105,6 +107,14 @@ def cd_points():
 
 def theta_points():
     return [ThetaPoint(5, n_qpo, 8, CD_N) for n_qpo in (1, 3)]
+
+
+def carma_points():
+    """One draw (the shared case); a few draws, also with mixed mode switched off and on per-draw series; more than one chunk; five roots; an even p
+    (no term with one row)."""
+    return [CarmaPoint(3, 2, 1, CD_N, "", False), CarmaPoint(3, 2, 7, CD_N, "", False), CarmaPoint(3, 2, 7, CD_N, "no_mixed=1", False),
+            CarmaPoint(3, 2, 7, CD_N, "", True), CarmaPoint(3, 2, 300, CD_N, "", False), CarmaPoint(5, 2, 16, CD_N, "", False),
+            CarmaPoint(4, 3, 5, CD_N, "", False)]
 
 
 # ---- the other batched entries (route.hip entry_plan).  N = 130: nine 16-step windows, the last ragged; M = 7 evaluation times, one on a data time.
@@ -416,6 +426,42 @@ def run_theta_point(ctx, pt):
         ds.close()
 
 
+def run_carma_point(ctx, pt):
+    """One call of Dataset.logpdf_carma under the point's options: (family that ran, log L, status, the coefficients A, Bc, C, Dd (B, J))."""
+    import pioran_jl_amd as pj
+    rng = np.random.default_rng([pt.p, pt.q, pt.B, pt.N, 5])
+    t = np.cumsum(rng.uniform(0.05, 2.0, pt.N))
+    y = np.exp(0.5 * rng.standard_normal(pt.N)) if pt.shift else rng.standard_normal(pt.N)     # a shifted call holds a positive series
+    s2 = rng.uniform(0.01, 0.1, pt.N)
+    bounds = 1 / (t[-1] - t[0]), 1 / np.min(np.diff(t)) / 2
+    quads = [pj.sample_quad(pt.p, pt.q, rng, *bounds) for _ in range(pt.B)]
+    qa, qb = np.array([x[0] for x in quads]), np.array([x[1] for x in quads])
+    shift = y.min() * np.linspace(0.1, 0.9, pt.B) if pt.shift else None
+    opts = [kv.split("=") for kv in pt.options.split(";") if kv]
+    ds = pj.Dataset(t, y, s2, ctx)
+    try:
+        for k, v in opts:
+            ctx.set_option(k, v)
+        out, st, *co = ds.logpdf_carma(pt.p, pt.q, qa, qb, rng.uniform(0.5, 2.0, pt.B), bounds=bounds, mu=rng.standard_normal(pt.B) * 0.1,
+                                       nu=rng.uniform(0.5, 2.0, pt.B), shift=shift, return_status=True, return_coefs=True)
+        return pj._lib.lib().pioran_celerite_config_name(-1).decode(), out, st, co
+    finally:
+        for k, _ in opts:
+            ctx.set_option(k, None)
+        ds.close()
+
+
+def carma_expected(pt, Bc, C, Dd):
+    """The family the rules name for a CarmaPoint whose call returned these coefficients: a term is per draw where its (c, d) differ between the
+    draws, and keeps one row where it is not and d = 0 and b = 0 in every draw.  No per-draw term is the shared case, pioran_value_route's."""
+    per_draw = (C != C[0]).any(axis=0) | (Dd != Dd[0]).any(axis=0)
+    one_row = ~per_draw & (Dd[0] == 0) & ~Bc.any(axis=0)
+    J, npd, n_one = len(per_draw), int(per_draw.sum()), int(one_row.sum())
+    if npd == 0:
+        return value_route(2 * J - n_one, J, n_one, pt.B, pt.N, per_draw_series=pt.shift, options=pt.options)[0]
+    return value_route_cd(J - npd - n_one, n_one, npd, pt.B, pt.N, per_draw_series=pt.shift, options=pt.options)[0]
+
+
 def run_point(ctx, pt):
     """One launch through Dataset.logl_batch under the point's options: (family that ran, log L, status)."""
     import pioran_jl_amd as pj
@@ -486,6 +532,10 @@ def main():
             digest = hashlib.sha256(b"".join(np.ascontiguousarray(v).tobytes() for _, v in sorted(out.items()))).hexdigest()[:16]
             print(f"step {pt.family:8s} rows {2 * pt.J - pt.n_one:3d} J {pt.J:2d} B {pt.B:4d} N {STEP_N} [{pt.options}] {fam} {digest}", flush=True)
         return
+    for pt in carma_points():
+        fam, out, st, _ = run_carma_point(ctx, pt)
+        digest = hashlib.sha256(out.tobytes() + st.tobytes()).hexdigest()[:16]
+        print(f"carma ({pt.p}, {pt.q}) B {pt.B:4d} N {pt.N:5d} shift {int(pt.shift)} [{pt.options}] {fam} {digest}", flush=True)
     for pt in points() + cd_points() + theta_points():
         fam, out, st = run_point(ctx, pt)
         digest = hashlib.sha256(out.tobytes() + st.tobytes()).hexdigest()[:16]
