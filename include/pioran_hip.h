@@ -571,7 +571,9 @@ int pioran_logpdf_batch_carma_grad(pioran_ds* ds, int64_t B, int p, int q, const
                                    double* grad_mu, double* grad_shift, double* grad_a, double* grad_b, double* grad_c, double* grad_d);
 /* Name of the kernel configuration a large batch with R active rows (all terms with both rows when R is even) runs on;
  * R == 0: the kernel instantiation the calling thread's last step-by-step launch (throughput or latency layout) actually ran on, as
- * pioran_step_route names it; R < 0: the kernel FAMILY of the
+ * pioran_step_route names it; R == -2: the kernel instantiation of the calling thread's last windowed, tile or time-parallel launch, as
+ * pioran_window_route names it ("none" before the first) — after a time-parallel call with a repair pass that is the windowed kernel's, which runs
+ * last; any other R < 0: the kernel FAMILY of the
  * calling thread's last launch — "tile" (windowed form, one draw per wavefront: large batches from 49 rows on and batch sizes between the
  * passes of the throughput layouts), "block" (windowed kernel), "block+pd" (with per-draw rows), "block (per-draw tables)", "wide"
  * (latency layout), "scan" (throughput layouts), "fallback", "block (windowed gradient[, per-draw tables])",
@@ -642,6 +644,30 @@ int pioran_entry_route(const char* entry, int32_t R, int32_t J, int32_t n_one_ro
  * unknown family.  tests/test_route.py holds the rules, tests/test_gpu_step_route.py the launches to them. */
 int pioran_step_route(const char* family, int32_t R, int32_t standard_rows, int32_t n_complex, int64_t B, int shared_table, int32_t npd_rows,
                       int per_draw_tables, const char* options, char* name, int name_len, int32_t* plan);
+/* Diagnostics (no GPU needed): the same for the windowed kernels (csrc/route.hip block_plan), their one-draw-per-wavefront form (tile_plan) and the
+ * time-parallel family (tp_step_plan).  `name` receives what pioran_celerite_config_name(-2) reports after that launch, in one-to-one correspondence with
+ * the template arguments of the kernels it runs, "none" where the launch is refused (PIORAN_ERR_UNSUPPORTED); plan, where not NULL, receives 12 integers.
+ * family = "block" (log-likelihood), "block_grad", "block_solve" (the prediction's K^-1 (y - mu)), "block_sim": R active rows, J terms, B draws,
+ * npd_rows per-draw rows (value only), want_cd != 0: the gradient with respect to c or d is asked for; options block_emode and exp are read.  Names:
+ * "block_nb<block columns>_e<0 the pair table in one LDS buffer, 1 in two, 2 in global memory>_pd<0 no per-draw rows, 1 a helper wavefront prepares
+ * them, 2 the chain wavefront>", the gradient "block_nb2_e0+adjoint[_cd]_<8 | 4 contraction threads per term>", "block_nb2_e0+backsolve",
+ * "block_nb2_e0+sim".  plan: {block columns, e, pd, stores (0 none, 1 gradient, 2 solve, 3 simulate), threads per workgroup, dynamic LDS bytes of the
+ * forward kernel, cd, contraction threads, 1 if celerite_block.hip holds the kernels, 0 ...}.
+ * family = "tile", "tile_grad": R, J, per_draw_series != 0: (y, sigma2) per draw (value only), want_cd.  Names: "tile_nb<block columns>_kl<live K-steps
+ * of four rows in the last row block>[_ser]"; "tile_nb<block columns>_kl4_st+adjoint[_cd]_w<draws per workgroup of the adjoint>".  plan: {block
+ * columns, kl, a series per draw, cd, draws per workgroup of the adjoint, threads per workgroup of the forward kernel, its dynamic LDS bytes, the
+ * adjoint's, 1 if celerite_tile.hip holds the kernels, 0 ...}.
+ * family = "tp": tp_rows padded state rows, tp_segments segments, tp_mode the boundary phase's mode (0 the walk, unchecked; 1 the scan, a verification
+ * launch and the walk for the draws that fail; 2 the scan, checked by the filter; 4 the walk, checked by the filter); options tp_scan_lean and
+ * tp_scan_waves are read.  Names: "tp_np<column pairs per wavefront>x<wavefronts of the element and filter kernels>" and the boundary phase,
+ * "+small<2 | 4>", "+wave<6 .. 16>", "+boundary_rt<tiles of 16 rows>" or "+combine[_lean]_rt<tiles>_w<wavefronts>", mode 1 also "+verify_wave<8 | 16>"
+ * or "+verify_boundary_rt<tiles>".  plan: {column pairs, wavefronts, boundary phase (1 small, 2 wave, 3 boundary, 4 the scan), its rows (small, wave) or
+ * tiles, lean, wavefronts per combination, dynamic LDS bytes of the boundary phase's kernel, verification (0 none, 2 wave, 3 boundary), its rows or
+ * tiles, its dynamic LDS bytes, 1 if the filter makes the check, 1 if celerite_tp.hip holds the kernels}.
+ * The arguments of the other families are not read.  options, name, PIORAN_ERR_ARG: as for pioran_value_route; also an unknown family.
+ * tests/test_route.py holds the rules to what the launch code chose before they existed, tests/test_gpu_window_route.py the launches to them. */
+int pioran_window_route(const char* family, int32_t R, int32_t J, int64_t B, int32_t npd_rows, int per_draw_series, int want_cd, int32_t tp_rows,
+                        int32_t tp_segments, int tp_mode, const char* options, char* name, int name_len, int32_t* plan);
 /* Diagnostics: the FP64 FMA rate (TFLOP/s) the device sustains right now with `waves_per_simd` (1 .. 8) wavefronts on every SIMD — about
  * `ms` milliseconds of a pure stream of independent v_fma_f64, event-timed on the context's stream.  The measured ceiling of any FP64
  * vector kernel on this box at that occupancy (the 78.6 TFLOP/s vendor figure assumes one FMA per SIMD every 4 cycles at 2.4 GHz).

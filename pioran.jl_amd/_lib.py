@@ -97,6 +97,8 @@ SIGNATURES = {
                                           ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int)]),
     "pioran_step_route": (ctypes.c_int, [ctypes.c_char_p] + [ctypes.c_int32] * 3 + [i64, ctypes.c_int, ctypes.c_int32, ctypes.c_int, ctypes.c_char_p,
                                          ctypes.c_char_p, ctypes.c_int, c_int32_p]),
+    "pioran_window_route": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int32, ctypes.c_int32, i64, ctypes.c_int32, ctypes.c_int, ctypes.c_int, ctypes.c_int32,
+                                           ctypes.c_int32, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, c_int32_p]),
     "pioran_farm_create": (ctypes.c_int, [ctypes.c_int, c_void_p, i64, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_void_p)]),
     "pioran_farm_destroy": (ctypes.c_int, [c_void_p]),
     "pioran_farm_size": (ctypes.c_int, [c_void_p]),

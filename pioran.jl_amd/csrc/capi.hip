@@ -1006,6 +1006,47 @@ int pioran_step_route(const char* family, int32_t R, int32_t standard_rows, int3
     return rc;
 }
 
+int pioran_window_route(const char* family, int32_t R, int32_t J, int64_t B, int32_t npd_rows, int per_draw_series, int want_cd, int32_t tp_rows,
+                        int32_t tp_segments, int tp_mode, const char* options, char* name, int name_len, int32_t* plan)
+{
+    if (!family || !name || name_len < 1) return PIORAN_ERR_ARG;
+    ScanOptions opt{};
+    if (const int rc = parse_options(options, opt)) return rc;
+    int32_t fields[12] = {};
+    int rc = PIORAN_OK;
+    static const char* const block_modes[4] = {"block", "block_grad", "block_solve", "block_sim"};
+    int m = 0;
+    while (m < 4 && std::strcmp(family, block_modes[m])) ++m;
+    if (m < 4) {
+        const BlockPlan bp = block_plan((BlockMode)m, R, J, B, npd_rows, want_cd != 0, &opt);
+        block_plan_name(bp, (BlockMode)m, name, (size_t)name_len);
+        const int32_t f[12] = {bp.NB, bp.emode, bp.pdm, bp.st, bp.threads, (int32_t)bp.lds, bp.cd, bp.tpt, pioran_block_kernel_exists(bp, (BlockMode)m)};
+        std::memcpy(fields, f, sizeof(f));
+        rc = bp.rc;
+    } else if (!std::strcmp(family, "tile") || !std::strcmp(family, "tile_grad")) {
+        const TileMode tm = family[4] ? TileMode::gradient : TileMode::value;
+        const TilePlan tp = tile_plan(tm, R, J, per_draw_series != 0, want_cd != 0);
+        tile_plan_name(tp, tm, name, (size_t)name_len);
+        const bool ok = tp.rc == PIORAN_OK;
+        const int32_t f[12] = {tp.NB, tp.KL, tp.SER, tp.cd, tp.adj_waves, ok ? 256 : 0, ok ? (int32_t)pioran_tile_lds_bytes(tp.NB) : 0,
+                               ok && tm == TileMode::gradient ? (int32_t)pioran_tile_adj_lds_bytes(tp.NB, tp.cd) : 0, pioran_tile_kernel_exists(tp, tm)};
+        std::memcpy(fields, f, sizeof(f));
+        rc = tp.rc;
+    } else if (!std::strcmp(family, "tp")) {
+        const TpStepPlan sp = tp_step_plan(tp_rows, tp_segments, tp_mode, &opt);
+        tp_step_plan_name(sp, name, (size_t)name_len);
+        const bool walk = sp.boundary == TpPhase::small || sp.boundary == TpPhase::wave;
+        const int32_t f[12] = {sp.NP, sp.NWV, (int32_t)sp.boundary, walk ? sp.rows : sp.rt, sp.lean, sp.tw, (int32_t)sp.lds, (int32_t)sp.verify,
+                               sp.verify == TpPhase::wave ? sp.verify_rows : sp.verify_rt, (int32_t)sp.verify_lds, sp.filter_disc, pioran_tp_kernel_exists(sp)};
+        std::memcpy(fields, f, sizeof(f));
+        rc = sp.rc;
+    } else {
+        return PIORAN_ERR_ARG;
+    }
+    if (plan) std::memcpy(plan, fields, sizeof(fields));
+    return rc;
+}
+
 extern "C" {
 
 const char* pioran_strerror(int code)
@@ -3282,6 +3323,7 @@ int pioran_logpdf_batch_carma_grad(pioran_ds* ds, int64_t B, int p, int q, const
 
 const char* pioran_celerite_config_name(int64_t R)
 {
+    if (R == -2) return pioran_window_last_name();   // the instantiation of the calling thread's last windowed, tile or time-parallel launch (pioran_window_route)
     if (R < 0) return g_last_kernel;                 // kernel family of the calling thread's last launch: block, block+pd, wide, scan, fallback
     if (R <= 0) return pioran_scan_config_name(0);   // what the calling thread's last step-by-step launch (throughput or latency layout) ran on
     if (R > pioran_wide_supported_rows()) return "fallback";

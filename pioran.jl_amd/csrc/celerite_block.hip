@@ -37,10 +37,14 @@
 // Numerical notes: the only division-like operation is 1 / D_n (v_rcp_f64 + two Newton steps, 1 ulp); a non-positive D_n is
 // carried on like the reference does (log|D_n|, :140; status 1), NaN / inf surface as status 2.
 #include "common.h"
+#include "lds_grant.h"
+#include "route.h"
 #include "window_common.h"
 
 #include <cmath>
+#include <array>
 #include <type_traits>
+#include <utility>
 
 // Diagnostic hooks: compiled out in the product; tools/block_probe.hip defines them to s_memtime accumulators.
 #ifndef PIORAN_ASTAMP
@@ -236,7 +240,6 @@ struct BlockSharedT {               // exchanges between the wavefronts of a wor
     double2 albe[NB > 4 ? 16 * NB : 64];   // per row: u = al v + be x
     double ys[2][32];               // per-draw series: (y_n, sigma2_n) of window k in ys[k & 1][0..15 | 16..31]
 };
-constexpr int kBlockMaxTerms = 64;
 
 // Per-draw rows (mixed mode: a few terms whose (c, d) differ per draw — QPO features on an approx continuum, src/psd.jl:254-261;
 // round 3).  The host puts those rows LAST (rows R - 2 npd .. R - 1, cos row then sin row of each term; capi.hip build_rowmap), the
@@ -245,7 +248,6 @@ constexpr int kBlockMaxTerms = 64;
 // pd_trig_kernel, so that the entries use the same rounded phases everywhere: see block_table_kernel) and the time stamps, both
 // staged by LDS DMA a window earlier: four exponentials per lane and window.  The readers of a record (load_u, load_vh, form_A)
 // take these rows' values from here instead of the tile.
-constexpr int kBlockMaxPdTerms = 2;
 struct BlockPd {
     double cv[2][2 * kBlockMaxPdTerms][16];   // [window parity][per-draw row][step]: C_n o v_n
     double cx[2][2 * kBlockMaxPdTerms][16];   //                                       C_n o x_n
@@ -1399,113 +1401,6 @@ __global__ void __launch_bounds__(256, 1) celerite_block_adjoint_kernel(const Sc
     }
 }
 
-constexpr size_t kBlockLdsMax = 160 * 1024;
-__host__ inline size_t block_lds_bytes(int NB, int J, int emode /*E buffers in LDS: 0 one, 1 two, 2 none*/, int npd = 0 /*per-draw terms*/)
-{
-    const size_t shared = NB == 1 ? sizeof(BlockSharedT<1>) : NB == 2 ? sizeof(BlockSharedT<2>) : NB == 3 ? sizeof(BlockSharedT<3>) : NB == 4 ? sizeof(BlockSharedT<4>)
-                          : NB == 5 ? sizeof(BlockSharedT<5>) : sizeof(BlockSharedT<6>);
-    return (size_t)(2 * block_tile_doubles(NB) + (emode == 2 ? 0 : emode == 1 ? 2 : 1) * 256 * J) * sizeof(double) + shared +
-           (npd > 0 ? sizeof(BlockPd) + (size_t)2 * npd * 128 * sizeof(double2) : 0);
-}
-
-template <int NB, int EM, int PDM = 0>
-int launch_block2(const ScanParams& p, const double* btab, hipStream_t stream)
-{
-    const size_t lds = block_lds_bytes(NB, p.J, EM, PDM ? p.npd_rows / 2 : 0);
-    // the attribute belongs to (function, device): one process may drive several devices (pioran_farm_*).  Racing threads at
-    // worst set it twice.
-    static size_t granted[64] = {};   // per template instance
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return PIORAN_ERR_HIP;
-    if (lds > granted[dev]) {
-        if (hipFuncSetAttribute((const void*)celerite_block_kernel<NB, EM, PDM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return PIORAN_ERR_HIP;
-        granted[dev] = lds;
-    }
-    hipLaunchKernelGGL((celerite_block_kernel<NB, EM, PDM>), dim3((unsigned)p.B), dim3(NB < 4 ? (PDM == 1 ? 320 : 256) : 512), lds, stream, p, btab);
-    return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;
-}
-
-template <int NB>
-int launch_block(const ScanParams& p, const double* btab, hipStream_t stream)
-{
-    if constexpr (NB >= 5) {   // 64 .. 95 rows (round 4): value only, no per-draw rows; the pair table in LDS where it fits, else from global memory
-        if (p.npd_rows > 0) return PIORAN_ERR_UNSUPPORTED;
-        if (block_lds_bytes(NB, p.J, 0) <= kBlockLdsMax) return launch_block2<NB, 0>(p, btab, stream);
-        if (block_lds_bytes(NB, p.J, 2) <= kBlockLdsMax) return launch_block2<NB, 2>(p, btab, stream);
-        return PIORAN_ERR_UNSUPPORTED;
-    } else {
-    // Where the pair table E lives (tools/sweep_block_emode.py, N = 1e4, late round 3): one LDS buffer is as fast as two or faster at
-    // every size measured (SHO-20, 256 draws: 1.92 vs 2.10 ms — the second buffer was worth its LDS in round 2, before the shared block
-    // shrank), so two buffers are an option only; above 256 draws what counts is whether TWO workgroups fit a CU — if they do not with E
-    // in LDS but do without, E is read from global memory (SHO-20, 512 draws: 2.68 instead of 3.75 ms).
-    if (p.npd_rows > 0) {   // per-draw rows
-        constexpr int PDH = NB < 4 ? 1 : 2;   // helper wavefront where the workgroup has room for one
-        const int npd = p.npd_rows / 2;
-        if constexpr (NB < 4) {
-            // above 256 draws: two workgroups of four wavefronts per CU (the chain wavefront prepares the per-draw rows, the shared
-            // terms' pair table comes from global memory) instead of one of five
-            const int pm = p.opt ? p.opt->block_emode : -1;
-            if ((pm == 2 || (pm < 0 && p.B > 256)) && 2 * block_lds_bytes(NB, p.J, 2, npd) <= kBlockLdsMax) return launch_block2<NB, 2, 2>(p, btab, stream);
-        }
-        if (p.B <= 256 && block_lds_bytes(NB, p.J, 1, npd) <= kBlockLdsMax) return launch_block2<NB, 1, PDH>(p, btab, stream);
-        if (block_lds_bytes(NB, p.J, 0, npd) <= kBlockLdsMax) return launch_block2<NB, 0, PDH>(p, btab, stream);
-        return PIORAN_ERR_UNSUPPORTED;
-    }
-    const int em = p.opt ? p.opt->block_emode : -1;   // diagnostics: force an E mode
-    if (em == 2 && NB < 4) return launch_block2<NB < 4 ? NB : 1, 2>(p, btab, stream);
-    if (em == 1 && block_lds_bytes(NB, p.J, 1) <= kBlockLdsMax) return launch_block2<NB, 1>(p, btab, stream);
-    if constexpr (NB < 4) {
-        if (em < 0 && p.B > 256 && 2 * block_lds_bytes(NB, p.J, 0) > kBlockLdsMax && 2 * block_lds_bytes(NB, p.J, 2) <= kBlockLdsMax)
-            return launch_block2<NB, 2>(p, btab, stream);
-    }
-    if (block_lds_bytes(NB, p.J, 0) <= kBlockLdsMax) return launch_block2<NB, 0>(p, btab, stream);
-    return PIORAN_ERR_UNSUPPORTED;
-    }
-}
-
-template <int NB>
-int launch_block_grad(const ScanParams& p, const double* btab, const double* gtab, double* ga, double* gb, double* gnu, double* gmu,
-                      double* gc, double* gd, hipStream_t stream)
-{
-    const size_t lds = block_lds_bytes(NB, p.J, 0);
-    if (lds > kBlockLdsMax) return PIORAN_ERR_UNSUPPORTED;
-    static size_t granted[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return PIORAN_ERR_HIP;
-    if (lds > granted[dev]) {
-        if (hipFuncSetAttribute((const void*)celerite_block_kernel<NB, 0, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return PIORAN_ERR_HIP;
-        granted[dev] = lds;
-    }
-    // more than 256 chains: the forward pass with two workgroups per CU (pair table from global memory, as the plain kernel does above 256
-    // draws); the reverse pass stays at one (its LDS holds two copies of a window's block)
-    bool fwd2 = false;
-    if constexpr (NB <= 3) {
-        const size_t lds2 = block_lds_bytes(NB, p.J, 2);
-        if (p.B > 256 && 2 * lds2 <= kBlockLdsMax && !(p.opt && (p.opt->exp & 16))) {
-            static size_t granted2[64] = {};
-            if (lds2 > granted2[dev]) {
-                if (hipFuncSetAttribute((const void*)celerite_block_kernel<NB, 2, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2) != hipSuccess)
-                    return PIORAN_ERR_HIP;
-                granted2[dev] = lds2;
-            }
-            hipLaunchKernelGGL((celerite_block_kernel<NB, 2, 0, 1>), dim3((unsigned)p.B), dim3(256), lds2, stream, p, btab);
-            fwd2 = true;
-        }
-    }
-    if (!fwd2) hipLaunchKernelGGL((celerite_block_kernel<NB, 0, 0, 1>), dim3((unsigned)p.B), dim3(NB < 4 ? 256 : 512), lds, stream, p, btab);
-    const bool cd = gc || gd;
-    if (p.J <= 32) {
-        if (cd) hipLaunchKernelGGL((celerite_block_adjoint_kernel<NB, true, 8>), dim3((unsigned)p.B), dim3(256), 0, stream, p, btab, gtab, ga, gb, gnu, gmu, gc, gd);
-        else hipLaunchKernelGGL((celerite_block_adjoint_kernel<NB, false, 8>), dim3((unsigned)p.B), dim3(256), 0, stream, p, btab, gtab, ga, gb, gnu, gmu, gc, gd);
-    } else {
-        if (cd) hipLaunchKernelGGL((celerite_block_adjoint_kernel<NB, true, 4>), dim3((unsigned)p.B), dim3(256), 0, stream, p, btab, gtab, ga, gb, gnu, gmu, gc, gd);
-        else hipLaunchKernelGGL((celerite_block_adjoint_kernel<NB, false, 4>), dim3((unsigned)p.B), dim3(256), 0, stream, p, btab, gtab, ga, gb, gnu, gmu, gc, gd);
-    }
-    return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;
-}
-
 // ---- z = K^-1 (y - mu) by block back-substitution (the prediction's first half; round 3) ---------------------------------------
 // The windowed factorisation is a block LDL' of the covariance with 16-step blocks: the block of L between a later window v and
 // window w is U~_v Phi Q_w' (Phi: the decay between the two windows), Q_w = Sigma_w^-1 X_w as left by the forward pass (ST).  Hence
@@ -1704,90 +1599,119 @@ __global__ void __launch_bounds__(64) celerite_block_sim_kernel(const ScanParams
     }
 }
 
-template <int NB>
-int launch_block_sim(const ScanParams& p, const double* btab, double* xi, hipStream_t stream)
+__host__ inline size_t block_lds_bytes(int NB, int J, int emode /*E buffers in LDS: 0 one, 1 two, 2 none*/, int npd = 0 /*per-draw terms*/)
 {
-    const size_t lds = block_lds_bytes(NB, p.J, 0);
-    if (lds > kBlockLdsMax) return PIORAN_ERR_UNSUPPORTED;
-    static size_t granted[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return PIORAN_ERR_HIP;
-    if (lds > granted[dev]) {
-        if (hipFuncSetAttribute((const void*)celerite_block_kernel<NB, 0, 0, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return PIORAN_ERR_HIP;
-        granted[dev] = lds;
-    }
-    const int64_t NW = (p.N + KW - 1) / KW;
-    hipLaunchKernelGGL((celerite_block_kernel<NB, 0, 0, 3>), dim3((unsigned)p.B), dim3(NB < 4 ? 256 : 512), lds, stream, p, btab);
-    hipLaunchKernelGGL((block_sim_xi_kernel<NB>), dim3((unsigned)((NW + 15) / 16), (unsigned)p.B), dim3(256), 0, stream, p, xi);
-    hipLaunchKernelGGL((celerite_block_sim_kernel<NB>), dim3((unsigned)p.B), dim3(64), 0, stream, p, btab, xi);
-    return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;
+    const size_t shared = NB == 1 ? sizeof(BlockSharedT<1>) : NB == 2 ? sizeof(BlockSharedT<2>) : NB == 3 ? sizeof(BlockSharedT<3>) : NB == 4 ? sizeof(BlockSharedT<4>)
+                          : NB == 5 ? sizeof(BlockSharedT<5>) : sizeof(BlockSharedT<6>);
+    return (size_t)(2 * block_tile_doubles(NB) + (emode == 2 ? 0 : emode == 1 ? 2 : 1) * 256 * J) * sizeof(double) + shared +
+           (npd > 0 ? sizeof(BlockPd) + (size_t)2 * npd * 128 * sizeof(double2) : 0);
 }
 
-template <int NB>
-int launch_block_solve(const ScanParams& p, const double* btab, const double* gtab, double* gy, hipStream_t stream)
+// The forward kernel of a BlockPlan (route.hip block_plan): the instantiations that exist, [NB - 1][emode][pdm][st].  Without stores: every E mode up to
+// three block columns, one or two LDS buffers at four, one or none at five and six; per-draw rows up to four block columns — with the helper wavefront
+// (pdm 1) up to three, on the chain wavefront (pdm 2) at four and, E from global memory, below.  With stores: E in one LDS buffer, up to four block
+// columns; the reverse mode's forward pass also with E from global memory up to three.
+using BlockKernel = void (*)(ScanParams, const double*);
+constexpr bool block_kernel_built(int NB, int EM, int PDM, int ST)
 {
-    const size_t lds = block_lds_bytes(NB, p.J, 0);
-    if (lds > kBlockLdsMax) return PIORAN_ERR_UNSUPPORTED;
-    static size_t granted[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return PIORAN_ERR_HIP;
-    if (lds > granted[dev]) {
-        if (hipFuncSetAttribute((const void*)celerite_block_kernel<NB, 0, 0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return PIORAN_ERR_HIP;
-        granted[dev] = lds;
-    }
-    hipLaunchKernelGGL((celerite_block_kernel<NB, 0, 0, 2>), dim3((unsigned)p.B), dim3(NB < 4 ? 256 : 512), lds, stream, p, btab);
-    hipLaunchKernelGGL((celerite_block_backsolve_kernel<NB>), dim3((unsigned)p.B), dim3(64), 0, stream, p, gtab, gy);
-    return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;
+    if (ST != 0) return PDM == 0 && NB <= 4 && (EM == 0 || (EM == 2 && ST == 1 && NB <= 3));
+    if (NB >= 5) return PDM == 0 && EM != 1;
+    if (NB == 4) return EM != 2 && PDM != 1;
+    return PDM == 0 || (PDM == 1 && EM != 2) || (PDM == 2 && EM == 2);
+}
+template <int NB, int EM, int PDM, int ST>
+constexpr BlockKernel block_kernel_or_null()
+{
+    if constexpr (block_kernel_built(NB, EM, PDM, ST)) return celerite_block_kernel<NB, EM, PDM, ST>;
+    else return nullptr;
+}
+template <int... I>
+constexpr std::array<BlockKernel, sizeof...(I)> block_kernel_table(std::integer_sequence<int, I...>)
+{
+    return {block_kernel_or_null<I / 36 + 1, I / 12 % 3, I / 4 % 3, I % 4>()...};
+}
+constexpr auto kBlockKernels = block_kernel_table(std::make_integer_sequence<int, 6 * 3 * 3 * 4>{});
+BlockKernel block_kernel(const BlockPlan& plan)
+{
+    if (plan.rc != PIORAN_OK || plan.NB < 1 || plan.NB > 6 || plan.emode < 0 || plan.emode > 2 || plan.pdm < 0 || plan.pdm > 2 || plan.st < 0 || plan.st > 3)
+        return nullptr;
+    return kBlockKernels[((plan.NB - 1) * 3 + plan.emode) * 12 + plan.pdm * 4 + plan.st];
+}
+
+// ... and what runs behind it, per block column (one to four): the reverse pass [d/d(c, d)][four contraction threads per term], the back-substitution,
+// the two simulation kernels
+using BlockAdjointKernel = void (*)(ScanParams, const double*, const double*, double*, double*, double*, double*, double*, double*);
+struct BlockBehind {
+    BlockAdjointKernel adjoint[2][2];
+    void (*backsolve)(ScanParams, const double*, double*);
+    void (*sim_xi)(ScanParams, double*);
+    void (*sim)(ScanParams, const double*, const double*);
+};
+template <int NB>
+constexpr BlockBehind block_behind()
+{
+    return {{{celerite_block_adjoint_kernel<NB, false, 8>, celerite_block_adjoint_kernel<NB, false, 4>},
+             {celerite_block_adjoint_kernel<NB, true, 8>, celerite_block_adjoint_kernel<NB, true, 4>}},
+            celerite_block_backsolve_kernel<NB>, block_sim_xi_kernel<NB>, celerite_block_sim_kernel<NB>};
+}
+constexpr BlockBehind kBlockBehind[4] = {block_behind<1>(), block_behind<2>(), block_behind<3>(), block_behind<4>()};
+
+// One body for the four launch entries: grant the LDS, launch the plan's forward kernel
+int launch_block_forward(const BlockPlan& plan, BlockMode mode, const ScanParams& p, const double* btab, hipStream_t stream)
+{
+    const BlockKernel kernel = block_kernel(plan);
+    if (!kernel) return PIORAN_ERR_UNSUPPORTED;
+    if (pioran_grant_lds((const void*)kernel, plan.lds) != PIORAN_OK) return PIORAN_ERR_HIP;
+    pioran_note_block_launch(plan, mode);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)p.B), dim3(plan.threads), plan.lds, stream, p, btab);
+    return PIORAN_OK;
 }
 
 }  // namespace
+
+size_t pioran_block_lds_bytes(int NB, int J, int emode, int npd_terms) { return block_lds_bytes(NB, J, emode, npd_terms); }
+bool pioran_block_kernel_exists(const BlockPlan& plan, BlockMode) { return block_kernel(plan) != nullptr; }   // (with stores: up to four block columns, all of kBlockBehind)
 
 // log L (p.out, p.status) and gy [B][N] = -K^-1 (y - mu): the windowed forward pass with its per-window stores (p.gw:
 // pioran_block_store_workspace_doubles(.., 2)) followed by the block back-substitution.  gtab: pioran_launch_block_gtab.
 int pioran_launch_block_solve(const ScanParams& p, const double* btab, const double* gtab, double* gy, hipStream_t stream)
 {
-    if (!btab || !gtab || !gy || !p.gw || p.npd_rows != 0 || p.B < 1 || p.N < 1 || !pioran_block_fits(p.R, p.J)) return PIORAN_ERR_UNSUPPORTED;
+    const BlockPlan plan = block_plan(BlockMode::solve, p.R, p.J, p.B, p.npd_rows, false, p.opt);
+    if (!btab || !gtab || !gy || !p.gw || p.B < 1 || p.N < 1 || plan.rc != PIORAN_OK) return PIORAN_ERR_UNSUPPORTED;
     if ((p.Y == nullptr) != (p.S2 == nullptr)) return PIORAN_ERR_ARG;
-    switch ((p.R + 1 + 15) / 16) {
-        case 1: return launch_block_solve<1>(p, btab, gtab, gy, stream);
-        case 2: return launch_block_solve<2>(p, btab, gtab, gy, stream);
-        case 3: return launch_block_solve<3>(p, btab, gtab, gy, stream);
-        case 4: return launch_block_solve<4>(p, btab, gtab, gy, stream);
-    }
-    return PIORAN_ERR_UNSUPPORTED;
+    if (const int rc = launch_block_forward(plan, BlockMode::solve, p, btab, stream)) return rc;
+    hipLaunchKernelGGL(kBlockBehind[plan.NB - 1].backsolve, dim3((unsigned)p.B), dim3(64), 0, stream, p, gtab, gy);
+    return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;
 }
 
 // GP realisations p.ysim [B][N] from the normals p.noise [B][N]: the windowed factorisation of the covariance (data set with y = 0;
 // p.gw: pioran_block_store_workspace_doubles(.., 3); xi: B N doubles of scratch), then the two simulation kernels above.
 int pioran_launch_block_sim(const ScanParams& p, const double* btab, double* xi, hipStream_t stream)
 {
-    if (!btab || !xi || !p.gw || !p.noise || !p.ysim || p.npd_rows != 0 || p.B < 1 || p.N < 1 || !pioran_block_fits(p.R, p.J)) return PIORAN_ERR_UNSUPPORTED;
-    switch ((p.R + 1 + 15) / 16) {
-        case 1: return launch_block_sim<1>(p, btab, xi, stream);
-        case 2: return launch_block_sim<2>(p, btab, xi, stream);
-        case 3: return launch_block_sim<3>(p, btab, xi, stream);
-        case 4: return launch_block_sim<4>(p, btab, xi, stream);
-    }
-    return PIORAN_ERR_UNSUPPORTED;
+    const BlockPlan plan = block_plan(BlockMode::simulate, p.R, p.J, p.B, p.npd_rows, false, p.opt);
+    if (!btab || !xi || !p.gw || !p.noise || !p.ysim || p.B < 1 || p.N < 1 || plan.rc != PIORAN_OK) return PIORAN_ERR_UNSUPPORTED;
+    if (const int rc = launch_block_forward(plan, BlockMode::simulate, p, btab, stream)) return rc;
+    const int64_t NW = (p.N + KW - 1) / KW;
+    hipLaunchKernelGGL(kBlockBehind[plan.NB - 1].sim_xi, dim3((unsigned)((NW + 15) / 16), (unsigned)p.B), dim3(256), 0, stream, p, xi);
+    hipLaunchKernelGGL(kBlockBehind[plan.NB - 1].sim, dim3((unsigned)p.B), dim3(64), 0, stream, p, btab, (const double*)xi);
+    return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;
 }
 
 // ---- windowed reverse mode: host side ----
 size_t pioran_block_grad_workspace_doubles(int64_t B, int64_t N, int32_t R)
 {
-    const int NB = (R + 1 + 15) / 16;
+    const int NB = block_columns(R);
     return (size_t)B * (size_t)((N + KW - 1) / KW) * (size_t)block_grad_ws_doubles(NB);
 }
 // p.gw of pioran_launch_block_solve (what = 2) / pioran_launch_block_sim (what = 3): the packed per-window stores
 size_t pioran_block_store_workspace_doubles(int64_t B, int64_t N, int32_t R, int what)
 {
-    const int NB = (R + 1 + 15) / 16;
+    const int NB = block_columns(R);
     return (size_t)B * (size_t)((N + KW - 1) / KW) * (size_t)block_ws_doubles(NB, what == 2 ? 2 : 3);
 }
 size_t pioran_block_gtab_doubles(int64_t N, int32_t R)
 {
-    const int NB = (R + 1 + 15) / 16;
+    const int NB = block_columns(R);
     return (size_t)((N + KW - 1) / KW) * (size_t)block_gtab_doubles(NB);
 }
 int pioran_launch_block_gtab(int64_t N, int32_t R, int32_t J, const int32_t* rowmap, const double* t, const double* c, const double* d,
@@ -1799,7 +1723,7 @@ int pioran_launch_block_gtab(int64_t N, int32_t R, int32_t J, const int32_t* row
 int pioran_launch_block_gtab_batch(int64_t N, int32_t R, int32_t J, int64_t nb, const int32_t* rowmap, const double* t, const double* C,
                                    const double* D, const double* s2, double* gtab, int64_t draw_stride, hipStream_t stream)
 {
-    const int NB = (R + 1 + 15) / 16;
+    const int NB = block_columns(R);
     const int64_t NW = (N + KW - 1) / KW;
     if (J < 1 || J > kBlockMaxTerms || NB > 4 || nb < 1 || nb > 65535 || NW > 0x7fffffffLL) return PIORAN_ERR_ARG;
     hipLaunchKernelGGL(block_gtable_window_kernel, dim3((unsigned)NW, (unsigned)nb), dim3(256), 0, stream, N, R, J, NB, rowmap, t, C, D, s2, gtab,
@@ -1812,15 +1736,13 @@ int pioran_launch_block_gtab_batch(int64_t N, int32_t R, int32_t J, int64_t nb, 
 int pioran_launch_block_grad(const ScanParams& p, const double* btab, const double* gtab, double* grad_a, double* grad_b, double* grad_nu,
                              double* grad_mu, double* grad_c, double* grad_d, hipStream_t stream)
 {
-    if (!btab || !gtab || !p.gw || p.npd_rows != 0 || p.B < 1 || p.N < 1 || !pioran_block_fits(p.R, p.J)) return PIORAN_ERR_UNSUPPORTED;
+    const BlockPlan plan = block_plan(BlockMode::gradient, p.R, p.J, p.B, p.npd_rows, grad_c || grad_d, p.opt);
+    if (!btab || !gtab || !p.gw || p.B < 1 || p.N < 1 || plan.rc != PIORAN_OK) return PIORAN_ERR_UNSUPPORTED;
     if ((p.Y == nullptr) != (p.S2 == nullptr)) return PIORAN_ERR_ARG;
-    switch ((p.R + 1 + 15) / 16) {
-        case 1: return launch_block_grad<1>(p, btab, gtab, grad_a, grad_b, grad_nu, grad_mu, grad_c, grad_d, stream);
-        case 2: return launch_block_grad<2>(p, btab, gtab, grad_a, grad_b, grad_nu, grad_mu, grad_c, grad_d, stream);
-        case 3: return launch_block_grad<3>(p, btab, gtab, grad_a, grad_b, grad_nu, grad_mu, grad_c, grad_d, stream);
-        case 4: return launch_block_grad<4>(p, btab, gtab, grad_a, grad_b, grad_nu, grad_mu, grad_c, grad_d, stream);
-    }
-    return PIORAN_ERR_UNSUPPORTED;
+    if (const int rc = launch_block_forward(plan, BlockMode::gradient, p, btab, stream)) return rc;
+    hipLaunchKernelGGL(kBlockBehind[plan.NB - 1].adjoint[plan.cd][plan.tpt == 4], dim3((unsigned)p.B), dim3(256), 0, stream, p, btab, gtab, grad_a, grad_b, grad_nu,
+                       grad_mu, grad_c, grad_d);
+    return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;
 }
 
 int pioran_block_supported_rows() { return 63; }
@@ -1828,13 +1750,13 @@ int pioran_block_supported_rows() { return 63; }
 // 0 when (R, J) does not fit the kernel's LDS budget
 size_t pioran_block_table_doubles(int64_t N, int32_t R, int32_t J)
 {
-    const int NB = (R + 1 + 15) / 16;
+    const int NB = block_columns(R);
     return (size_t)((N + KW - 1) / KW) * (size_t)block_rec_doubles(NB, J);
 }
 
 int pioran_block_fits(int32_t R, int32_t J)
 {
-    const int NB = (R + 1 + 15) / 16;
+    const int NB = block_columns(R);
     if (R < 1 || NB > 4 || J < 1 || J > kBlockMaxTerms) return 0;
     return block_lds_bytes(NB, J, 0) <= kBlockLdsMax;
 }
@@ -1842,7 +1764,7 @@ int pioran_block_fits(int32_t R, int32_t J)
 // ... the value-only kernel also runs five and six block columns (64 .. 95 rows)
 int pioran_block_fits_value(int32_t R, int32_t J)
 {
-    const int NB = (R + 1 + 15) / 16;
+    const int NB = block_columns(R);
     if (NB <= 4) return pioran_block_fits(R, J);
     if (NB > 6 || J < 1 || J > kBlockMaxTerms) return 0;
     return block_lds_bytes(NB, J, 0) <= kBlockLdsMax || block_lds_bytes(NB, J, 2) <= kBlockLdsMax;
@@ -1851,7 +1773,7 @@ int pioran_block_fits_value(int32_t R, int32_t J)
 // ... with `npd_terms` per-draw terms (their rows last)
 int pioran_block_fits_pd(int32_t R, int32_t J, int32_t npd_terms)
 {
-    const int NB = (R + 1 + 15) / 16;
+    const int NB = block_columns(R);
     if (R < 1 || NB > 4 || J < 1 || J > kBlockMaxTerms || npd_terms < 1 || npd_terms > kBlockMaxPdTerms || R < 2 * npd_terms) return 0;
     return block_lds_bytes(NB, J, 0, npd_terms) <= kBlockLdsMax;
 }
@@ -1898,7 +1820,7 @@ int pioran_launch_block_table(int64_t N, int32_t R, int32_t J, const int32_t* ro
 int pioran_launch_block_table_reference(int64_t N, int32_t R, int32_t J, const int32_t* rowmap, const double* t, const double* c,
                                         const double* d, const double* y, const double* s2, double* btab, hipStream_t stream)
 {
-    const int NB = (R + 1 + 15) / 16;
+    const int NB = block_columns(R);
     const int64_t total = (int64_t)pioran_block_table_doubles(N, R, J);
     hipLaunchKernelGGL(block_table_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, N, R, J, NB, rowmap, t, c, d, y,
                        s2, btab);
@@ -1909,7 +1831,7 @@ int pioran_launch_block_table_reference(int64_t N, int32_t R, int32_t J, const i
 int pioran_launch_block_table_batch(int64_t N, int32_t R, int32_t J, int64_t nb, const int32_t* rowmap, const double* t, const double* C,
                                     const double* D, const double* y, const double* s2, double* btab, int64_t draw_stride, hipStream_t stream)
 {
-    const int NB = (R + 1 + 15) / 16;
+    const int NB = block_columns(R);
     const int64_t NW = (N + KW - 1) / KW;
     if (J < 1 || J > kBlockMaxTerms || NB > 6 || nb < 1 || nb > 65535 || NW > 0x7fffffffLL) return PIORAN_ERR_ARG;
     hipLaunchKernelGGL(block_table_window_kernel, dim3((unsigned)NW, (unsigned)nb), dim3(256), 0, stream, N, R, J, NB, rowmap, t, C, D, y, s2,
@@ -1921,20 +1843,9 @@ int pioran_launch_block_table_batch(int64_t N, int32_t R, int32_t J, int64_t nb,
 // LAST rows of the row map) need p.pd_C ([B][J]) and p.pd_trig (pioran_launch_block_pd_trig), p.pd_npad
 int pioran_launch_scan_block(const ScanParams& p, const double* btab, hipStream_t stream)
 {
-    if (!btab || p.B < 1 || p.N < 1) return PIORAN_ERR_UNSUPPORTED;
-    if (p.npd_rows != 0) {
-        if ((p.npd_rows & 1) || !p.pd_C || !p.pd_trig || p.pd_npad < p.N || !pioran_block_fits_pd(p.R, p.J, p.npd_rows / 2)) return PIORAN_ERR_UNSUPPORTED;
-    } else if (!pioran_block_fits_value(p.R, p.J)) {
-        return PIORAN_ERR_UNSUPPORTED;
-    }
+    const BlockPlan plan = block_plan(BlockMode::value, p.R, p.J, p.B, p.npd_rows, false, p.opt);
+    if (!btab || p.B < 1 || p.N < 1 || plan.rc != PIORAN_OK || (p.npd_rows != 0 && (!p.pd_C || !p.pd_trig || p.pd_npad < p.N))) return PIORAN_ERR_UNSUPPORTED;
     if ((p.Y == nullptr) != (p.S2 == nullptr)) return PIORAN_ERR_ARG;
-    switch ((p.R + 1 + 15) / 16) {
-        case 1: return launch_block<1>(p, btab, stream);
-        case 2: return launch_block<2>(p, btab, stream);
-        case 3: return launch_block<3>(p, btab, stream);
-        case 4: return launch_block<4>(p, btab, stream);
-        case 5: return launch_block<5>(p, btab, stream);
-        case 6: return launch_block<6>(p, btab, stream);
-    }
-    return PIORAN_ERR_UNSUPPORTED;
+    if (const int rc = launch_block_forward(plan, BlockMode::value, p, btab, stream)) return rc;
+    return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;
 }

@@ -28,7 +28,12 @@
 // Restrictions: shared (c, d) without per-draw rows; 1 .. 95 active rows; the series shared or per draw (Y, S2: the shifted log-flux models).
 // Everything else stays on the other kernels.
 #include "common.h"
+#include "lds_grant.h"
+#include "route.h"
 #include "window_common.h"
+
+#include <array>
+#include <utility>
 
 // Diagnostic hooks: compiled out in the product; tools/tile_probe.hip defines them to s_memtime accumulators.
 #ifndef PIORAN_TSTAMP
@@ -44,14 +49,13 @@
 
 namespace {
 
-constexpr int kTileMaxTerms = 64;
 constexpr int kTileWaves = 4;      // wavefronts (= draws) per workgroup
 // ... of the reverse mode: T_k and T- of a draw are 45 KB (53 with d/d(c, d)) of LDS at four block columns — three draws fit a CU, not four
 // Between a wavefront's LDS writes and its own reads of the same addresses no counter wait is needed — the LDS executes a wavefront's instructions in order —
 // only the compiler has to keep the order (forward kernel: -0.3 % against a wait, same box):
 #define PIORAN_LDS_ORDER() asm volatile("" ::: "memory")
 template <int NB, bool CD = false>
-constexpr int tile_adj_waves() { return NB <= 3 ? 4 : (CD ? 2 : 3); }
+constexpr int tile_adj_waves() { return tile_adj_waves_of(NB, CD); }
 
 typedef __attribute__((address_space(3))) double lds_f64;
 template <int NB>
@@ -1572,94 +1576,70 @@ __global__ void __launch_bounds__(512) tile_pairs_grad_kernel(const ScanParams p
     }
 }
 
-template <int NB>
-constexpr size_t tile_lds_bytes() { return kTileWaves * sizeof(TileWave<NB>); }
-
+// The kernels of a TilePlan (route.hip tile_plan) and what a launch needs to know of their block columns.  Value: [NB - 1][KL][a series per draw] (no
+// live K-step in the last row block: only where there is a row block before it); gradient, up to four block columns: the forward pass with its stores
+// and the adjoint without and with d/d(c, d)
+using TileKernel = void (*)(ScanParams, const double*, const double*);
+using TileAdjointKernel = void (*)(ScanParams, const double*, const double*, double*, double*, double*, double*, double*, double*, double*);
 template <int NB, int KL, bool SER>
-int launch_tile(const ScanParams& p, const double* btab, double* pairs, hipStream_t stream)
+constexpr TileKernel tile_kernel_or_null()
 {
-    if ((p.R >> 4) != NB - 1) return PIORAN_ERR_UNSUPPORTED;   // the kernel's compile-time y block column
-    constexpr size_t lds = tile_lds_bytes<NB>();
-    static_assert(lds <= 160 * 1024, "one workgroup must fit a CU");
-    static bool granted[64] = {};   // (function, device): one process may drive several devices (pioran_farm_*); racing threads at worst set it twice
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return PIORAN_ERR_HIP;
-    if (!granted[dev]) {
-        if (hipFuncSetAttribute((const void*)celerite_tile_kernel<NB, KL, false, SER>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return PIORAN_ERR_HIP;
-        granted[dev] = true;
-    }
-    const int64_t groups = (p.B + kTileWaves - 1) / kTileWaves;
-    if (groups > 0x7fffffffLL) return PIORAN_ERR_UNSUPPORTED;
-    const int64_t NW = (p.N + KW - 1) / KW;
-    if (NW > 0x7fffffffLL) return PIORAN_ERR_UNSUPPORTED;
-    if (!launch_pairs_mfma(p, stream, btab, (int64_t)block_rec_doubles(NB, p.J), (int64_t)block_tile_doubles(NB), pairs)) return PIORAN_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL((celerite_tile_kernel<NB, KL, false, SER>), dim3((unsigned)groups), dim3(64 * kTileWaves), lds, stream, p, btab, (const double*)pairs);
-    return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;
+    if constexpr (KL > 0 || NB > 1) return celerite_tile_kernel<NB, KL, false, SER>;
+    else return nullptr;
 }
-
-// the kernel for R rows: NB = ceil((R + 1) / 16) block columns, KL = ceil((R - 16 (NB - 1)) / 4) live K-steps in the last row block (NB = 1: R >= 1, KL >= 1)
-template <int NB, bool SER>
-int launch_tile_rows(const ScanParams& p, const double* btab, double* pairs, hipStream_t stream)
+template <int... I>
+constexpr std::array<TileKernel, sizeof...(I)> tile_kernel_table(std::integer_sequence<int, I...>)
 {
-    switch ((p.R - 16 * (NB - 1) + 3) / 4) {
-        case 0: if constexpr (NB > 1) return launch_tile<NB, 0, SER>(p, btab, pairs, stream); break;
-        case 1: return launch_tile<NB, 1, SER>(p, btab, pairs, stream);
-        case 2: return launch_tile<NB, 2, SER>(p, btab, pairs, stream);
-        case 3: return launch_tile<NB, 3, SER>(p, btab, pairs, stream);
-        case 4: return launch_tile<NB, 4, SER>(p, btab, pairs, stream);
-    }
-    return PIORAN_ERR_UNSUPPORTED;
+    return {tile_kernel_or_null<I / 10 + 1, I / 2 % 5, I % 2 != 0>()...};
 }
-template <int NB>
-int launch_tile_rows(const ScanParams& p, const double* btab, double* pairs, hipStream_t stream)
+constexpr auto kTileKernels = tile_kernel_table(std::make_integer_sequence<int, 6 * 5 * 2>{});
+TileKernel tile_kernel(const TilePlan& plan)
 {
-    return p.Y ? launch_tile_rows<NB, true>(p, btab, pairs, stream) : launch_tile_rows<NB, false>(p, btab, pairs, stream);
+    if (plan.rc != PIORAN_OK || plan.NB < 1 || plan.NB > 6 || plan.KL < 0 || plan.KL > 4) return nullptr;
+    return kTileKernels[((plan.NB - 1) * 5 + plan.KL) * 2 + plan.SER];
 }
-
+struct TileGrad {
+    TileKernel forward;
+    TileAdjointKernel adjoint[2];
+    size_t adjoint_lds[2];
+};
 template <int NB>
-constexpr size_t tile_adj_lds_bytes() { return tile_adj_waves<NB>() * sizeof(TileAdjWave<NB>); }
-
-template <int NB>
-int launch_tile_grad(const ScanParams& p, const double* btab, const double* gtab, double* pairs, double* grad_a, double* grad_b, double* grad_nu,
-                     double* grad_mu, double* grad_c, double* grad_d, hipStream_t stream)
+constexpr TileGrad tile_grad()
 {
-    constexpr size_t lds_f = tile_lds_bytes<NB>(), lds_r = tile_adj_lds_bytes<NB>(), lds_rc = tile_adj_waves<NB, true>() * sizeof(TileAdjWave<NB, true>);
-    constexpr int AW = tile_adj_waves<NB>(), AWC = tile_adj_waves<NB, true>();
-    static_assert(lds_f <= 160 * 1024 && lds_r <= 160 * 1024 && lds_rc <= 160 * 1024, "one workgroup must fit a CU");
-    static bool granted[64] = {};
-    int dev = 0;
-    if ((p.R >> 4) != NB - 1) return PIORAN_ERR_UNSUPPORTED;   // the kernels' compile-time y block column
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return PIORAN_ERR_HIP;
-    const bool cd = grad_c && grad_d;
-    if ((grad_c != nullptr) != (grad_d != nullptr)) return PIORAN_ERR_ARG;
-    if (!granted[dev]) {
-        if (hipFuncSetAttribute((const void*)celerite_tile_kernel<NB, 4, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f) != hipSuccess) return PIORAN_ERR_HIP;
-        if (hipFuncSetAttribute((const void*)celerite_tile_adjoint_kernel<NB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r) != hipSuccess) return PIORAN_ERR_HIP;
-        if (hipFuncSetAttribute((const void*)celerite_tile_adjoint_kernel<NB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rc) != hipSuccess) return PIORAN_ERR_HIP;
-        granted[dev] = true;
-    }
-    const int64_t groups = (p.B + kTileWaves - 1) / kTileWaves;
-    const int64_t NW = (p.N + KW - 1) / KW;
+    return {celerite_tile_kernel<NB, 4, true, false>, {celerite_tile_adjoint_kernel<NB, false>, celerite_tile_adjoint_kernel<NB, true>},
+            {tile_adj_waves<NB, false>() * sizeof(TileAdjWave<NB, false>), tile_adj_waves<NB, true>() * sizeof(TileAdjWave<NB, true>)}};
+}
+constexpr TileGrad kTileGrad[4] = {tile_grad<1>(), tile_grad<2>(), tile_grad<3>(), tile_grad<4>()};
+constexpr size_t kTileLds[6] = {kTileWaves * sizeof(TileWave<1>), kTileWaves * sizeof(TileWave<2>), kTileWaves * sizeof(TileWave<3>),
+                                kTileWaves * sizeof(TileWave<4>), kTileWaves * sizeof(TileWave<5>), kTileWaves * sizeof(TileWave<6>)};
+constexpr bool tile_lds_fits()
+{
+    for (size_t lds : kTileLds) if (lds > 160 * 1024) return false;
+    for (const TileGrad& g : kTileGrad) if (g.adjoint_lds[0] > 160 * 1024 || g.adjoint_lds[1] > 160 * 1024) return false;
+    return true;
+}
+static_assert(tile_lds_fits(), "one workgroup must fit a CU");
+
+// The pair pre-pass and the plan's forward kernel (its LDS granted by the caller): what the value launch is, and the first half of the gradient's
+int launch_tile_forward(const TilePlan& plan, TileKernel kernel, const ScanParams& p, const double* btab, double* pairs, hipStream_t stream)
+{
+    const size_t lds = kTileLds[plan.NB - 1];
+    const int64_t groups = (p.B + kTileWaves - 1) / kTileWaves, NW = (p.N + KW - 1) / KW;
     if (groups > 0x7fffffffLL || NW > 0x7fffffffLL) return PIORAN_ERR_UNSUPPORTED;
-    const int64_t rsb = block_rec_doubles(NB, p.J), tsp = block_tile_doubles(NB);
-    if (!launch_pairs_mfma(p, stream, btab, rsb, tsp, pairs)) return PIORAN_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL((celerite_tile_kernel<NB, 4, true, false>), dim3((unsigned)groups), dim3(64 * kTileWaves), lds_f, stream, p, btab, (const double*)pairs);   // (all four K-steps: KL = 4)
-    const unsigned agroups = (unsigned)((p.B + AW - 1) / AW);
-    if (cd) {
-        hipLaunchKernelGGL((celerite_tile_adjoint_kernel<NB, true>), dim3((unsigned)((p.B + AWC - 1) / AWC)), dim3(64 * AWC), lds_rc, stream, p, btab, gtab, pairs, grad_a, grad_b,
-                           grad_nu, grad_mu, grad_c, grad_d);
-        hipLaunchKernelGGL(tile_pairs_grad_kernel<true>, dim3((unsigned)((p.B + 15) / 16)), dim3(512), 0, stream, p, btab, rsb, tsp, (const double*)pairs, grad_a, grad_b,
-                           grad_c, grad_d);
-    } else {
-        hipLaunchKernelGGL((celerite_tile_adjoint_kernel<NB, false>), dim3(agroups), dim3(64 * AW), lds_r, stream, p, btab, gtab, pairs, grad_a, grad_b,
-                           grad_nu, grad_mu, (double*)nullptr, (double*)nullptr);
-        hipLaunchKernelGGL(tile_pairs_grad_kernel<false>, dim3((unsigned)((p.B + 15) / 16)), dim3(512), 0, stream, p, btab, rsb, tsp, (const double*)pairs, grad_a, grad_b,
-                           (double*)nullptr, (double*)nullptr);
-    }
-    return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;
+    if (!launch_pairs_mfma(p, stream, btab, (int64_t)block_rec_doubles(plan.NB, p.J), (int64_t)block_tile_doubles(plan.NB), pairs)) return PIORAN_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)groups), dim3(64 * kTileWaves), lds, stream, p, btab, (const double*)pairs);
+    return PIORAN_OK;
 }
 
 }  // namespace
+
+size_t pioran_tile_lds_bytes(int NB) { return NB >= 1 && NB <= 6 ? kTileLds[NB - 1] : 0; }
+size_t pioran_tile_adj_lds_bytes(int NB, bool cd) { return NB >= 1 && NB <= 4 ? kTileGrad[NB - 1].adjoint_lds[cd] : 0; }
+bool pioran_tile_kernel_exists(const TilePlan& plan, TileMode mode)
+{
+    if (mode == TileMode::gradient) return plan.rc == PIORAN_OK && plan.NB >= 1 && plan.NB <= 4 && plan.KL == 4 && !plan.SER;
+    return tile_kernel(plan) != nullptr;
+}
 
 int pioran_tile_supported_rows() { return 95; }
 int pioran_tile_grad_supported_rows() { return 63; }   // four block columns (DRWCelerite-20 is 60 rows; there three draws per workgroup: tile_adj_waves)
@@ -1667,7 +1647,7 @@ int pioran_tile_grad_supported_rows() { return 63; }   // four block columns (DR
 // doubles of the state workspace of the reverse mode: the lower tiles of T at the start of every window, per draw
 size_t pioran_tile_grad_workspace_doubles(int64_t B, int64_t N, int32_t R)
 {
-    const int NB = (R + 1 + 15) / 16;
+    const int NB = block_columns(R);
     return (size_t)B * (size_t)((N + KW - 1) / KW) * (size_t)(NB * (NB + 1) / 2) * 256;
 }
 
@@ -1676,28 +1656,32 @@ size_t pioran_tile_grad_workspace_doubles(int64_t B, int64_t N, int32_t R)
 int pioran_launch_tile_grad(const ScanParams& p, const double* btab, const double* gtab, double* pairs, double* grad_a, double* grad_b, double* grad_nu,
                             double* grad_mu, double* grad_c, double* grad_d, hipStream_t stream)
 {
-    if (!btab || !gtab || !pairs || !p.gw || !grad_a || !grad_b || p.B < 1 || p.N < 1 || p.npd_rows != 0 || p.Y || p.S2 || p.J > kTileMaxTerms ||
-        p.R < 1 || p.R > pioran_tile_grad_supported_rows())
+    const TilePlan plan = tile_plan(TileMode::gradient, p.R, p.J, p.Y || p.S2, grad_c && grad_d);
+    if (!btab || !gtab || !pairs || !p.gw || !grad_a || !grad_b || p.B < 1 || p.N < 1 || p.npd_rows != 0 || !pioran_tile_kernel_exists(plan, TileMode::gradient))
         return PIORAN_ERR_UNSUPPORTED;
-    switch ((p.R + 1 + 15) / 16) {
-        case 1: return launch_tile_grad<1>(p, btab, gtab, pairs, grad_a, grad_b, grad_nu, grad_mu, grad_c, grad_d, stream);
-        case 2: return launch_tile_grad<2>(p, btab, gtab, pairs, grad_a, grad_b, grad_nu, grad_mu, grad_c, grad_d, stream);
-        case 3: return launch_tile_grad<3>(p, btab, gtab, pairs, grad_a, grad_b, grad_nu, grad_mu, grad_c, grad_d, stream);
-        case 4: return launch_tile_grad<4>(p, btab, gtab, pairs, grad_a, grad_b, grad_nu, grad_mu, grad_c, grad_d, stream);
-    }
-    return PIORAN_ERR_UNSUPPORTED;
+    if ((grad_c != nullptr) != (grad_d != nullptr)) return PIORAN_ERR_ARG;
+    const TileGrad& k = kTileGrad[plan.NB - 1];
+    if (pioran_grant_lds({{(const void*)k.forward, kTileLds[plan.NB - 1]}, {(const void*)k.adjoint[plan.cd], k.adjoint_lds[plan.cd]}}) != PIORAN_OK) return PIORAN_ERR_HIP;
+    if (const int rc = launch_tile_forward(plan, k.forward, p, btab, pairs, stream)) return rc;
+    pioran_note_tile_launch(plan, TileMode::gradient);
+    const int64_t rsb = block_rec_doubles(plan.NB, p.J), tsp = block_tile_doubles(plan.NB);
+    hipLaunchKernelGGL(k.adjoint[plan.cd], dim3((unsigned)((p.B + plan.adj_waves - 1) / plan.adj_waves)), dim3(64 * plan.adj_waves), k.adjoint_lds[plan.cd], stream, p, btab,
+                       gtab, pairs, grad_a, grad_b, grad_nu, grad_mu, grad_c, grad_d);
+    hipLaunchKernelGGL(plan.cd ? tile_pairs_grad_kernel<true> : tile_pairs_grad_kernel<false>, dim3((unsigned)((p.B + 15) / 16)), dim3(512), 0, stream, p, btab, rsb, tsp,
+                       (const double*)pairs, grad_a, grad_b, grad_c, grad_d);
+    return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;
 }
 
 int pioran_tile_fits(int32_t R, int32_t J)
 {
-    const int NB = (R + 1 + 15) / 16;
+    const int NB = block_columns(R);
     return R >= 1 && NB <= 6 && J >= 1 && J <= kTileMaxTerms;
 }
 
 // draws one full pass of the kernel holds on `cus` compute units
 int64_t pioran_tile_pass_draws(int32_t R, int cus)
 {
-    const int NB = (R + 1 + 15) / 16;
+    const int NB = block_columns(R);
     return (int64_t)cus * kTileWaves * (NB <= 4 ? 2 : 1);
 }
 
@@ -1709,15 +1693,12 @@ size_t pioran_tile_workspace_doubles(int64_t B, int64_t N) { return (size_t)B * 
 int pioran_launch_scan_tile(const ScanParams& p, const double* btab, double* work, hipStream_t stream)
 {
     if (!work) return PIORAN_ERR_ARG;
-    if (!btab || p.B < 1 || p.N < 1 || p.npd_rows != 0 || !pioran_tile_fits(p.R, p.J)) return PIORAN_ERR_UNSUPPORTED;
+    const TilePlan plan = tile_plan(TileMode::value, p.R, p.J, p.Y != nullptr, false);
+    const TileKernel kernel = tile_kernel(plan);
+    if (!btab || p.B < 1 || p.N < 1 || p.npd_rows != 0 || !kernel) return PIORAN_ERR_UNSUPPORTED;
     if ((p.Y == nullptr) != (p.S2 == nullptr)) return PIORAN_ERR_ARG;
-    switch ((p.R + 1 + 15) / 16) {
-        case 1: return launch_tile_rows<1>(p, btab, work, stream);
-        case 2: return launch_tile_rows<2>(p, btab, work, stream);
-        case 3: return launch_tile_rows<3>(p, btab, work, stream);
-        case 4: return launch_tile_rows<4>(p, btab, work, stream);
-        case 5: return launch_tile_rows<5>(p, btab, work, stream);
-        case 6: return launch_tile_rows<6>(p, btab, work, stream);
-    }
-    return PIORAN_ERR_UNSUPPORTED;
+    if (pioran_grant_lds((const void*)kernel, kTileLds[plan.NB - 1]) != PIORAN_OK) return PIORAN_ERR_HIP;
+    if (const int rc = launch_tile_forward(plan, kernel, p, btab, work, stream)) return rc;
+    pioran_note_tile_launch(plan, TileMode::value);
+    return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;
 }

@@ -28,6 +28,8 @@
 
 #include "common.h"
 #include "device_util.h"
+#include "lds_grant.h"
+#include "route.h"
 
 int pioran_tp_scan_rows(int RP);
 double pioran_tp_scan_tol(const ScanOptions* opt);
@@ -1071,7 +1073,7 @@ __global__ void __launch_bounds__(64 * TW) tp_combine_kernel(int RP, int nseg, i
 // memory straight into the matrix-core operands (32 KB each, L2-resident: they were written by the launch before), Z and M A_i stay where the elimination
 // left them — row l of X holds row mycol(l) of the solution — and are read through the inverse permutation `rowof`.  J_j is read as its transpose (it is
 // symmetric up to rounding) so that the lanes of a load run along a row.  Same three modes (prior / complete prefix / incomplete element) and the same
-// verification mode as tp_combine_kernel; tests hold the two against each other at 16 .. 48 rows (option tp_scan_lean).
+// verification mode as tp_combine_kernel; tests hold the two against each other at 16 .. 48 rows (the option that asks for it there: route.hip tp_step_plan).
 template <int RT, int TW>
 __global__ void __launch_bounds__(64 * TW) tp_combine_lean_kernel(int RP, int nseg, int J, int stride, const int32_t* __restrict__ row_term,
                                                               const int32_t* __restrict__ row_kind, const double* __restrict__ A_, const double* __restrict__ Bc_,
@@ -1593,139 +1595,54 @@ __global__ void __launch_bounds__(64) tp_boundary_wave_kernel(int nseg, int J, c
     }
 }
 
+// The kernels of a TpStepPlan (route.hip tp_step_plan).  Element and filter kernels, [NP - 1][four wavefronts]: one wavefront up to 12 state rows (two per
+// NP), four from 16 on (eight per NP)
+using TpElementKernel = decltype(&tp_element_kernel<1, 1>);
+using TpFilterKernel = decltype(&tp_filter_kernel<1, 1>);
+struct TpSegmentKernels { TpElementKernel element; TpFilterKernel filter; };
 template <int NP, int NWV>
-int tp_launch(const ScanParams& p, int RP, int nseg, int64_t L, const int32_t* row_term, const int32_t* row_kind, double* work, hipStream_t stream, int scan)
+constexpr TpSegmentKernels tp_segment_kernels() { return {tp_element_kernel<NP, NWV>, tp_filter_kernel<NP, NWV>}; }
+constexpr TpSegmentKernels kTpSegment[8][2] = {
+    {tp_segment_kernels<1, 1>(), {}},                           {tp_segment_kernels<2, 1>(), tp_segment_kernels<2, 4>()},
+    {tp_segment_kernels<3, 1>(), tp_segment_kernels<3, 4>()},   {tp_segment_kernels<4, 1>(), tp_segment_kernels<4, 4>()},
+    {tp_segment_kernels<5, 1>(), tp_segment_kernels<5, 4>()},   {tp_segment_kernels<6, 1>(), tp_segment_kernels<6, 4>()},
+    {{}, tp_segment_kernels<7, 4>()},                           {{}, tp_segment_kernels<8, 4>()}};
+// the boundary walk: two or four rows per thread of a wavefront's 64 draws; one wavefront per draw, 6 .. 16 rows; four wavefronts and 2 .. 4 tiles of 16 rows
+using TpSmallKernel = decltype(&tp_boundary_small_kernel<2>);
+using TpWalkKernel = decltype(&tp_boundary_wave_kernel<6>);
+constexpr TpSmallKernel kTpSmall[2] = {tp_boundary_small_kernel<2>, tp_boundary_small_kernel<4>};
+constexpr TpWalkKernel kTpWave[6] = {tp_boundary_wave_kernel<6>,  tp_boundary_wave_kernel<8>,  tp_boundary_wave_kernel<10>,
+                                     tp_boundary_wave_kernel<12>, tp_boundary_wave_kernel<14>, tp_boundary_wave_kernel<16>};
+constexpr decltype(&tp_boundary_kernel<4, 2>) kTpTiles[3] = {tp_boundary_kernel<4, 2>, tp_boundary_kernel<4, 3>, tp_boundary_kernel<4, 4>};
+// the scan's combination, [lean][tiles of rows - 1][eight wavefronts]: one tile runs on four wavefronts, four tiles fit the LDS in the lean form only
+using TpCombineKernel = decltype(&tp_combine_kernel<1, 4>);
+constexpr TpCombineKernel kTpCombine[2][4][2] = {
+    {{tp_combine_kernel<1, 4>, nullptr}, {tp_combine_kernel<2, 4>, tp_combine_kernel<2, 8>}, {tp_combine_kernel<3, 4>, tp_combine_kernel<3, 8>}, {nullptr, nullptr}},
+    {{tp_combine_lean_kernel<1, 4>, nullptr}, {tp_combine_lean_kernel<2, 4>, tp_combine_lean_kernel<2, 8>}, {tp_combine_lean_kernel<3, 4>, tp_combine_lean_kernel<3, 8>},
+     {tp_combine_lean_kernel<4, 4>, tp_combine_lean_kernel<4, 8>}}};
+
+bool tp_walk_exists(TpPhase phase, int rows, int rt)
 {
-    const int64_t B = p.B, N = p.N;
-    TpRec* rec = reinterpret_cast<TpRec*>(work);
-    TpStep* stp = reinterpret_cast<TpStep*>(work + (size_t)B * N * RP * 6);
-    double* sval = work + (size_t)B * N * RP * 6 + (size_t)B * N * 4;
-    double* elem = sval + (size_t)B * N;
-    double* elem2 = elem + (size_t)B * nseg * TP_ELEM_DOUBLES;       // the scan's two element buffers (its levels ping-pong; the raw elements stay for the check)
-    double* elem3 = elem2 + (size_t)B * nseg * TP_ELEM_DOUBLES;
-    double* bnd = elem3 + (size_t)B * nseg * TP_ELEM_DOUBLES;
-    double* part = bnd + (size_t)B * nseg * TP_BND_DOUBLES;
-    double* disc = part + (size_t)B * nseg * 4;                      // [B] per draw: the scan's check (product path: the estimate of log L's relative error; walk-repair mode: the state discrepancy)
-    if (hipMemsetAsync(bnd, 0, (size_t)B * nseg * TP_BND_DOUBLES * sizeof(double), stream) != hipSuccess) return PIORAN_ERR_HIP;
-    hipLaunchKernelGGL(tp_records_kernel, dim3((unsigned)N, (unsigned)B), dim3(64), 0, stream, N, RP, p.J, row_term, row_kind, p.t, p.y, p.s2, p.Y, p.S2, p.A,
-                       p.Bc, p.C, p.D, p.mu, p.nu, rec, stp);
-    if (nseg > 1)
-        hipLaunchKernelGGL((tp_element_kernel<NP, NWV>), dim3((unsigned)(nseg - 1), (unsigned)B), dim3(64 * NWV), 0, stream, N, RP, nseg, L, row_kind,
-                           (const TpRec*)rec, (const TpStep*)stp, elem);
-    const size_t r16 = (size_t)((RP + 15) / 16) * 16, lds2 = (r16 * (2 * r16 + 3) + 2 * r16 * (r16 + 1) + 192 + 1024) * sizeof(double);
-    static size_t granted[8][64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return PIORAN_ERR_HIP;
-    double* filter_disc = nullptr;
-    if (scan == 4) {
-        // the boundary WALK with the filter's check behind it (round 6, late): the walk's states are sequential, but a long segment's element is not better conditioned than
-        // a composite of the scan — on prior draws of DRWCelerite-10 the walk alone is off by up to 8e-7 (2e-6 at 32 segments) where the serial chain holds 4e-10
-        // (tools/tp_walk_accuracy.py) — so its draws are checked and repaired like the scan's
-        filter_disc = disc;
-        if (hipMemsetAsync(disc, 0, (size_t)B * sizeof(double), stream) != hipSuccess) return PIORAN_ERR_HIP;
-    }
-    if (scan && scan != 4 && nseg >= 2 && pioran_tp_scan_rows(RP)) {
-        // phase 2 as a scan: ceil(log2 nseg) launches of tp_combine_kernel, one workgroup per (draw, target)
-        const int rt = (RP + 15) / 16;
-        const bool lean = rt == 4 || (p.opt && p.opt->tp_scan_lean);          // (four tiles of rows: only the lean form fits the LDS)
-        const size_t r16s = (size_t)rt * 16;
-        // wavefronts per combination: eight from 17 rows on (three tiles of rows: nine product tiles and eight column tiles per elimination round — 48.9 -> 40.2 us;
-        // four tiles, lean: sixteen and twelve)
-        const int tw = rt >= 2 && !(p.opt && p.opt->tp_scan_waves == 4) ? 8 : 4;
-        const size_t ldsc = lean ? (r16s * (3 * r16s + 3) + r16s * (r16s + 1) + 7 * 64 + 32 + 256 * tw) * sizeof(double)
-                                 : (r16s * (3 * r16s + 3) + 4 * r16s * (r16s + 1) + 7 * 64 + 256 * tw) * sizeof(double);
-        const void* fnc = nullptr;
-#define TP_PICK(KERNEL) (rt == 1 ? (const void*)KERNEL<1, 4> : (rt == 2 ? (tw == 8 ? (const void*)KERNEL<2, 8> : (const void*)KERNEL<2, 4>) : (rt == 3 ? (tw == 8 ? (const void*)KERNEL<3, 8> : (const void*)KERNEL<3, 4>) : (tw == 8 ? (const void*)KERNEL<4, 8> : (const void*)KERNEL<4, 4>))))
-        if (lean) fnc = TP_PICK(tp_combine_lean_kernel);
-        else if (rt <= 3) fnc = rt == 1 ? (const void*)tp_combine_kernel<1, 4> : (rt == 2 ? (tw == 8 ? (const void*)tp_combine_kernel<2, 8> : (const void*)tp_combine_kernel<2, 4>) : (tw == 8 ? (const void*)tp_combine_kernel<3, 8> : (const void*)tp_combine_kernel<3, 4>));
-#undef TP_PICK
-        if (!fnc) return PIORAN_ERR_UNSUPPORTED;
-        static size_t granted_c[4][5][64] = {};
-        const int gi = (lean ? 2 : 0) + (tw == 8 ? 1 : 0);
-        if (ldsc > granted_c[gi][rt][dev]) {
-            if (hipFuncSetAttribute(fnc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsc) != hipSuccess) return PIORAN_ERR_HIP;
-            granted_c[gi][rt][dev] = ldsc;
-        }
-        const double tol = p.opt && p.opt->tp_scan_tol != 0.0 ? p.opt->tp_scan_tol : 1e-6;      // (walk-repair mode: of the verification launch's state discrepancy)
-        if (hipMemsetAsync(disc, 0, (size_t)B * sizeof(double), stream) != hipSuccess) return PIORAN_ERR_HIP;
-        auto combine = [&](const dim3& gr, int stride, const double* src, double* dst, double* dsc) {
-#define TP_COMBINE(KERNEL, WV) hipLaunchKernelGGL(KERNEL, gr, dim3(64 * WV), ldsc, stream, RP, nseg, p.J, stride, row_term, row_kind, p.A, p.Bc, src, dst, bnd, dsc)
-#define TP_COMBINE_RT(KERNEL, RR) do { if (tw == 8) TP_COMBINE((KERNEL<RR, 8>), 8); else TP_COMBINE((KERNEL<RR, 4>), 4); } while (0)
-            if (lean) {
-                if (rt == 1) TP_COMBINE((tp_combine_lean_kernel<1, 4>), 4); else if (rt == 2) TP_COMBINE_RT(tp_combine_lean_kernel, 2);
-                else if (rt == 3) TP_COMBINE_RT(tp_combine_lean_kernel, 3); else TP_COMBINE_RT(tp_combine_lean_kernel, 4);
-            } else {
-                if (rt == 1) TP_COMBINE((tp_combine_kernel<1, 4>), 4); else if (rt == 2) TP_COMBINE_RT(tp_combine_kernel, 2); else TP_COMBINE_RT(tp_combine_kernel, 3);
-            }
-#undef TP_COMBINE_RT
-#undef TP_COMBINE
-        };
-        const double* src = elem;
-        double* dst = elem2;
-        for (int stride = 1; stride < nseg; stride *= 2) {
-            combine(dim3((unsigned)(nseg - stride), (unsigned)B), stride, src, dst, nullptr);
-            src = dst;
-            dst = dst == elem2 ? elem3 : elem2;
-        }
-        // the check and what happens to the draws that fail it
-        if (scan == 2) {
-            // the caller repairs the draws that fail the check itself (capi.hip tp_dispatch: the serial-chain kernel with ScanParams::only_if), so the check can
-            // wait for the filter, which makes it on its way (tp_filter_kernel's `disc`) — no verification launch.  Otherwise: one boundary step per boundary
-            // from the scan's states, all at once (tp_combine_kernel's verify mode), and the walk for the draws that fail it, before the filter runs
-            filter_disc = disc;
-        } else if (RP <= 16) {
-            combine(dim3((unsigned)(nseg - 1), (unsigned)B), 1, elem, nullptr, disc);
-#define TP_WAVE_CASE(RR) case RR: hipLaunchKernelGGL((tp_boundary_wave_kernel<RR>), dim3((unsigned)B), dim3(64), 0, stream, nseg, p.J, row_term, row_kind, p.A, p.Bc, (const double*)elem, bnd, (const double*)disc, tol); break;
-            switch (RP) { TP_WAVE_CASE(8) TP_WAVE_CASE(16) default: return PIORAN_ERR_UNSUPPORTED; }
-#undef TP_WAVE_CASE
-        } else {
-            combine(dim3((unsigned)(nseg - 1), (unsigned)B), 1, elem, nullptr, disc);
-            const void* fn = rt == 2 ? (const void*)tp_boundary_kernel<4, 2> : (rt == 3 ? (const void*)tp_boundary_kernel<4, 3> : (const void*)tp_boundary_kernel<4, 4>);
-            if (lds2 > granted[rt][dev]) {
-                if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2) != hipSuccess) return PIORAN_ERR_HIP;
-                granted[rt][dev] = lds2;
-            }
-            if (rt == 2)
-                hipLaunchKernelGGL((tp_boundary_kernel<4, 2>), dim3((unsigned)B), dim3(256), lds2, stream, RP, nseg, p.J, row_term, row_kind, p.A, p.Bc, (const double*)elem, bnd, (const double*)disc, tol);
-            else if (rt == 3)
-                hipLaunchKernelGGL((tp_boundary_kernel<4, 3>), dim3((unsigned)B), dim3(256), lds2, stream, RP, nseg, p.J, row_term, row_kind, p.A, p.Bc, (const double*)elem, bnd, (const double*)disc, tol);
-            else
-                hipLaunchKernelGGL((tp_boundary_kernel<4, 4>), dim3((unsigned)B), dim3(256), lds2, stream, RP, nseg, p.J, row_term, row_kind, p.A, p.Bc, (const double*)elem, bnd, (const double*)disc, tol);
-        }
-    } else if (RP == 2)
-        hipLaunchKernelGGL((tp_boundary_small_kernel<2>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream, nseg, p.J, B, row_term, row_kind, p.A, p.Bc, (const double*)elem, bnd);
-    else if (RP == 4)
-        hipLaunchKernelGGL((tp_boundary_small_kernel<4>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream, nseg, p.J, B, row_term, row_kind, p.A, p.Bc, (const double*)elem, bnd);
-    else if (RP <= 16) {
-#define TP_WAVE_CASE(RR) case RR: hipLaunchKernelGGL((tp_boundary_wave_kernel<RR>), dim3((unsigned)B), dim3(64), 0, stream, nseg, p.J, row_term, row_kind, p.A, p.Bc, (const double*)elem, bnd, (const double*)nullptr, 0.0); break;
-        switch (RP) {
-            TP_WAVE_CASE(6) TP_WAVE_CASE(8) TP_WAVE_CASE(10) TP_WAVE_CASE(12) TP_WAVE_CASE(14) TP_WAVE_CASE(16)
-            default: return PIORAN_ERR_UNSUPPORTED;
-        }
-#undef TP_WAVE_CASE
-    } else {
-        // four wavefronts, RT = 2 .. 4 tiles of 16 rows (24 .. 64 state rows)
-        const int rt = (RP + 15) / 16;
-        const void* fn = rt == 2 ? (const void*)tp_boundary_kernel<4, 2> : (rt == 3 ? (const void*)tp_boundary_kernel<4, 3> : (const void*)tp_boundary_kernel<4, 4>);
-        if (lds2 > granted[rt][dev]) {
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2) != hipSuccess) return PIORAN_ERR_HIP;
-            granted[rt][dev] = lds2;
-        }
-        if (rt == 2)
-            hipLaunchKernelGGL((tp_boundary_kernel<4, 2>), dim3((unsigned)B), dim3(256), lds2, stream, RP, nseg, p.J, row_term, row_kind, p.A, p.Bc, (const double*)elem, bnd, (const double*)nullptr, 0.0);
-        else if (rt == 3)
-            hipLaunchKernelGGL((tp_boundary_kernel<4, 3>), dim3((unsigned)B), dim3(256), lds2, stream, RP, nseg, p.J, row_term, row_kind, p.A, p.Bc, (const double*)elem, bnd, (const double*)nullptr, 0.0);
-        else
-            hipLaunchKernelGGL((tp_boundary_kernel<4, 4>), dim3((unsigned)B), dim3(256), lds2, stream, RP, nseg, p.J, row_term, row_kind, p.A, p.Bc, (const double*)elem, bnd, (const double*)nullptr, 0.0);
-    }
-    const int check = p.opt ? p.opt->tp_check : 0;
-    hipLaunchKernelGGL((tp_filter_kernel<NP, NWV>), dim3((unsigned)nseg, (unsigned)B), dim3(64 * NWV), 0, stream, N, RP, nseg, L, row_kind,
-                       (const TpRec*)rec, (const TpStep*)stp, (const double*)bnd, part, sval, filter_disc, check);
-    hipLaunchKernelGGL(tp_finish_kernel, dim3((unsigned)B), dim3(64), 0, stream, N, nseg, B, (const double*)part, p.out, p.status, check != 1 ? filter_disc : (double*)nullptr, check);      // (tp_check = 2 / 3: the raw distance on the innovation scale / the estimate alone: tools)
-    return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;
+    if (phase == TpPhase::small) return rows == 2 || rows == 4;
+    if (phase == TpPhase::wave) return rows >= 6 && rows <= 16 && !(rows & 1);
+    return phase == TpPhase::tiles && rt >= 2 && rt <= 4;
+}
+TpCombineKernel tp_combine(const TpStepPlan& plan)
+{
+    return plan.rt >= 1 && plan.rt <= 4 && (plan.tw == 4 || plan.tw == 8) ? kTpCombine[plan.lean][plan.rt - 1][plan.tw == 8] : nullptr;
+}
+bool tp_kernels_exist(const TpStepPlan& plan)
+{
+    if (plan.rc != PIORAN_OK || plan.NP < 1 || plan.NP > 8 || (plan.NWV != 1 && plan.NWV != 4) || !kTpSegment[plan.NP - 1][plan.NWV == 4].filter) return false;
+    if (plan.boundary == TpPhase::scan)      // (its verification walks only the draws that failed: the one-wavefront walk at 8 or 16 rows, or the walk on tiles)
+        return tp_combine(plan) && (plan.verify == TpPhase::none || (plan.verify == TpPhase::wave && (plan.verify_rows == 8 || plan.verify_rows == 16)) ||
+                                    (plan.verify == TpPhase::tiles && tp_walk_exists(plan.verify, 0, plan.verify_rt)));
+    return tp_walk_exists(plan.boundary, plan.rows, plan.rt);
 }
 
 }  // namespace
+
+bool pioran_tp_kernel_exists(const TpStepPlan& plan) { return tp_kernels_exist(plan); }
 
 const double* pioran_tp_disc(const double* work, int64_t B, int64_t N, int RP, int nseg)
 {
@@ -1756,30 +1673,77 @@ size_t pioran_tp_workspace_doubles(int64_t B, int64_t N, int RP, int nseg)
 // (the last one shorter)
 int pioran_launch_tp(const ScanParams& p, int RP, int nseg, int64_t L, const int32_t* row_term, const int32_t* row_kind, double* work, hipStream_t stream, int scan)
 {
-    if (RP < 2 || RP > 64 || RP != pioran_tp_padded_rows(RP) || nseg < 1 || L < 2 || (int64_t)nseg * L < p.N || (int64_t)(nseg - 1) * L >= p.N || p.B < 1 ||
-        p.B > 65535 || p.N > 0x7fffffffLL)
+    const TpStepPlan plan = tp_step_plan(RP, nseg, scan, p.opt);
+    if (plan.rc != PIORAN_OK || L < 2 || (int64_t)nseg * L < p.N || (int64_t)(nseg - 1) * L >= p.N || p.B < 1 || p.B > 65535 || p.N > 0x7fffffffLL ||
+        !tp_kernels_exist(plan))
         return PIORAN_ERR_UNSUPPORTED;
-    if (RP <= 12) {
-        switch (RP / 2) {
-            case 1: return tp_launch<1, 1>(p, RP, nseg, L, row_term, row_kind, work, stream, scan);
-            case 2: return tp_launch<2, 1>(p, RP, nseg, L, row_term, row_kind, work, stream, scan);
-            case 3: return tp_launch<3, 1>(p, RP, nseg, L, row_term, row_kind, work, stream, scan);
-            case 4: return tp_launch<4, 1>(p, RP, nseg, L, row_term, row_kind, work, stream, scan);
-            case 5: return tp_launch<5, 1>(p, RP, nseg, L, row_term, row_kind, work, stream, scan);
-            case 6: return tp_launch<6, 1>(p, RP, nseg, L, row_term, row_kind, work, stream, scan);
-            case 7: return tp_launch<7, 1>(p, RP, nseg, L, row_term, row_kind, work, stream, scan);
-            case 8: return tp_launch<8, 1>(p, RP, nseg, L, row_term, row_kind, work, stream, scan);
+    const int64_t B = p.B, N = p.N;
+    TpRec* rec = reinterpret_cast<TpRec*>(work);
+    TpStep* stp = reinterpret_cast<TpStep*>(work + (size_t)B * N * RP * 6);
+    double* sval = work + (size_t)B * N * RP * 6 + (size_t)B * N * 4;
+    double* elem = sval + (size_t)B * N;
+    double* elem2 = elem + (size_t)B * nseg * TP_ELEM_DOUBLES;       // the scan's two element buffers (its levels ping-pong; the raw elements stay for the check)
+    double* elem3 = elem2 + (size_t)B * nseg * TP_ELEM_DOUBLES;
+    double* bnd = elem3 + (size_t)B * nseg * TP_ELEM_DOUBLES;
+    double* part = bnd + (size_t)B * nseg * TP_BND_DOUBLES;
+    double* disc = part + (size_t)B * nseg * 4;                      // [B] per draw: the scan's check (product path: the estimate of log L's relative error; walk-repair mode: the state discrepancy)
+    const TpSegmentKernels& seg = kTpSegment[plan.NP - 1][plan.NWV == 4];
+    // the dynamic LDS of the boundary phase's kernels, asked for in one call: the scan's combination, and the walk on tiles — alone or behind the verification
+    const LdsGrant combine{plan.boundary == TpPhase::scan ? (const void*)tp_combine(plan) : nullptr, plan.lds};
+    const LdsGrant tiles = plan.boundary == TpPhase::tiles ? LdsGrant{(const void*)kTpTiles[plan.rt - 2], plan.lds}
+                           : plan.verify == TpPhase::tiles ? LdsGrant{(const void*)kTpTiles[plan.verify_rt - 2], plan.verify_lds} : LdsGrant{nullptr, 0};
+    if ((combine.kernel || tiles.kernel) && pioran_grant_lds({combine, tiles}) != PIORAN_OK) return PIORAN_ERR_HIP;
+    pioran_note_tp_launch(plan);
+    if (hipMemsetAsync(bnd, 0, (size_t)B * nseg * TP_BND_DOUBLES * sizeof(double), stream) != hipSuccess) return PIORAN_ERR_HIP;
+    hipLaunchKernelGGL(tp_records_kernel, dim3((unsigned)N, (unsigned)B), dim3(64), 0, stream, N, RP, p.J, row_term, row_kind, p.t, p.y, p.s2, p.Y, p.S2, p.A,
+                       p.Bc, p.C, p.D, p.mu, p.nu, rec, stp);
+    if (nseg > 1)
+        hipLaunchKernelGGL(seg.element, dim3((unsigned)(nseg - 1), (unsigned)B), dim3(64 * plan.NWV), 0, stream, N, RP, nseg, L, row_kind, (const TpRec*)rec,
+                           (const TpStep*)stp, elem);
+    // the boundary walk, alone or behind the scan's check (dsc, tol: only the draws that failed it are walked)
+    auto walk = [&](TpPhase phase, int rows, int rt, size_t lds, const double* dsc, double tol) {
+        if (phase == TpPhase::small) {
+            hipLaunchKernelGGL(kTpSmall[rows / 2 - 1], dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream, nseg, p.J, B, row_term, row_kind, p.A, p.Bc, (const double*)elem, bnd);
+        } else if (phase == TpPhase::wave) {
+            hipLaunchKernelGGL(kTpWave[rows / 2 - 3], dim3((unsigned)B), dim3(64), 0, stream, nseg, p.J, row_term, row_kind, p.A, p.Bc, (const double*)elem, bnd, dsc, tol);
+        } else {
+            hipLaunchKernelGGL(kTpTiles[rt - 2], dim3((unsigned)B), dim3(256), lds, stream, RP, nseg, p.J, row_term, row_kind, p.A, p.Bc, (const double*)elem, bnd, dsc, tol);
         }
-        return PIORAN_ERR_UNSUPPORTED;
+    };
+    // (mode 4, the boundary WALK with the filter's check behind it (round 6, late): the walk's states are sequential, but a long segment's element is not better
+    // conditioned than a composite of the scan — on prior draws of DRWCelerite-10 the walk alone is off by up to 8e-7 (2e-6 at 32 segments) where the serial chain
+    // holds 4e-10 (tools/tp_walk_accuracy.py) — so its draws are checked and repaired like the scan's)
+    if (plan.filter_disc || plan.boundary == TpPhase::scan)
+        if (hipMemsetAsync(disc, 0, (size_t)B * sizeof(double), stream) != hipSuccess) return PIORAN_ERR_HIP;
+    if (plan.boundary == TpPhase::scan) {
+        // phase 2 as a scan: ceil(log2 nseg) launches of the combination, one workgroup per (draw, target)
+        const TpCombineKernel kernel = tp_combine(plan);
+        auto combine = [&](const dim3& gr, int stride, const double* src, double* dst, double* dsc) {
+            hipLaunchKernelGGL(kernel, gr, dim3(64 * plan.tw), plan.lds, stream, RP, nseg, p.J, stride, row_term, row_kind, p.A, p.Bc, src, dst, bnd, dsc);
+        };
+        const double* src = elem;
+        double* dst = elem2;
+        for (int stride = 1; stride < nseg; stride *= 2) {
+            combine(dim3((unsigned)(nseg - stride), (unsigned)B), stride, src, dst, nullptr);
+            src = dst;
+            dst = dst == elem2 ? elem3 : elem2;
+        }
+        // The check and what happens to the draws that fail it.  Mode 2: the caller repairs them itself (capi.hip tp_dispatch: the serial-chain kernel with
+        // ScanParams::only_if), so the check can wait for the filter, which makes it on its way (tp_filter_kernel's `disc`) — no verification launch.  Otherwise:
+        // one boundary step per boundary from the scan's states, all at once (the combination's verify mode), and the walk for the draws that fail it, before
+        // the filter runs
+        if (plan.verify != TpPhase::none) {
+            const double tol = p.opt && p.opt->tp_scan_tol != 0.0 ? p.opt->tp_scan_tol : 1e-6;      // (of the verification launch's state discrepancy)
+            combine(dim3((unsigned)(nseg - 1), (unsigned)B), 1, elem, nullptr, disc);
+            walk(plan.verify, plan.verify_rows, plan.verify_rt, plan.verify_lds, disc, tol);
+        }
+    } else {
+        walk(plan.boundary, plan.rows, plan.rt, plan.lds, nullptr, 0.0);
     }
-    switch (RP / 8) {
-        case 2: return tp_launch<2, 4>(p, RP, nseg, L, row_term, row_kind, work, stream, scan);
-        case 3: return tp_launch<3, 4>(p, RP, nseg, L, row_term, row_kind, work, stream, scan);
-        case 4: return tp_launch<4, 4>(p, RP, nseg, L, row_term, row_kind, work, stream, scan);
-        case 5: return tp_launch<5, 4>(p, RP, nseg, L, row_term, row_kind, work, stream, scan);
-        case 6: return tp_launch<6, 4>(p, RP, nseg, L, row_term, row_kind, work, stream, scan);
-        case 7: return tp_launch<7, 4>(p, RP, nseg, L, row_term, row_kind, work, stream, scan);
-        case 8: return tp_launch<8, 4>(p, RP, nseg, L, row_term, row_kind, work, stream, scan);
-    }
-    return PIORAN_ERR_UNSUPPORTED;
+    double* filter_disc = plan.filter_disc ? disc : nullptr;
+    const int check = p.opt ? p.opt->tp_check : 0;
+    hipLaunchKernelGGL(seg.filter, dim3((unsigned)nseg, (unsigned)B), dim3(64 * plan.NWV), 0, stream, N, RP, nseg, L, row_kind, (const TpRec*)rec, (const TpStep*)stp,
+                       (const double*)bnd, part, sval, filter_disc, check);
+    hipLaunchKernelGGL(tp_finish_kernel, dim3((unsigned)B), dim3(64), 0, stream, N, nseg, B, (const double*)part, p.out, p.status, check != 1 ? filter_disc : (double*)nullptr, check);      // (tp_check = 2 / 3: the raw distance on the innovation scale / the estimate alone: tools)
+    return hipGetLastError() == hipSuccess ? PIORAN_OK : PIORAN_ERR_HIP;
 }

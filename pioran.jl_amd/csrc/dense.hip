@@ -27,6 +27,7 @@
 #include "../../include/pioran_hip.h"
 #include "common.h"
 #include "device_util.h"
+#include "lds_grant.h"
 
 #include <cmath>
 #include <type_traits>
@@ -1257,17 +1258,9 @@ static void launch_build(int64_t N, int64_t Mp, int64_t ld, int32_t J, const dou
     // shared (c, d) (or one matrix): the transcendental part once per tile, the tiles themselves on the matrix cores
     bool tile_build = (nbatch == 1 || bt.cd_stride == 0) && sorted && J <= 64;
     if (tile_build && nt > 1) {
-        // dense_build_fast_batch_kernel needs 2 KB x roundup4(J) of dynamic LDS (80 KB at J = 40, 128 KB at J = 64): ask once per device,
-        // and take this path only where the device grants it — otherwise the entry-per-thread + per-tile pair below
-        static int granted[64] = {};    // 0 unknown, 1 granted, -1 refused; racing threads at worst ask twice
-        int dev = 0;
-        bool ok = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64;
-        if (ok && granted[dev] == 0) {
-            granted[dev] = hipFuncSetAttribute((const void*)dense_build_fast_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               4 * 64 * BT * (int)sizeof(double)) == hipSuccess ? 1 : -1;
-            if (granted[dev] < 0) (void)hipGetLastError();
-        }
-        tile_build = ok && granted[dev] == 1;
+        // dense_build_fast_batch_kernel needs 2 KB x roundup4(J) of dynamic LDS (80 KB at J = 40, 128 KB at J = 64): asked for once per device
+        // (at the size of J = 64), and this path taken only where the device grants it — otherwise the entry-per-thread + per-tile pair below
+        tile_build = pioran_grant_lds((const void*)dense_build_fast_batch_kernel, (size_t)4 * 64 * BT * sizeof(double)) == PIORAN_OK;
     }
     if (tile_build) {
         hipLaunchKernelGGL(dense_build_diag_batch_kernel, dim3(tiles, 4, (nbatch + ZC - 1) / ZC), dim3(256), 0, stream, N, Mp, ld, J, (int32_t)nbatch, a, b,

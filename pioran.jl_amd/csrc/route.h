@@ -4,8 +4,10 @@
 // their own are planned before the ladder: mixed_plan where only a few terms differ between the draws, perdraw_form where the caller says all do.
 // The other batched entries (prediction, gradient, simulation, posterior draws) have one rule, entry_plan.
 // One level down, the step-by-step families name the kernel instantiation a launch runs by the same kind of rule, at the end: scan_plan for the
-// throughput layout (celerite_scan.hip), wide_plan for the latency layout (celerite_wide.hip).  Those files look the plan's kernel up in a table
-// and launch it; they read no selection option themselves.  pioran_step_route names both plans without a GPU.
+// throughput layout (celerite_scan.hip), wide_plan for the latency layout (celerite_wide.hip), block_plan for the windowed kernels (celerite_block.hip),
+// tile_plan for their one-draw-per-wavefront form (celerite_tile.hip), tp_step_plan for the time-parallel family (celerite_tp.hip).  Those five files
+// look the plan's kernels up in a table and launch them; they read no selection option themselves.  pioran_step_route names the first two plans
+// without a GPU, pioran_window_route the other three.
 #pragma once
 #include "common.h"
 #include "scan_configs.h"
@@ -14,6 +16,8 @@
 
 // doubles of one step record of the shared table (table.hip): (v, x, phi) of R + 2 rows, then (y_n, sigma2_n)
 constexpr int64_t rec_stride_of(int64_t R) { return 3 * (int64_t)(R + 2) + 2; }
+// block columns of 16 rows of the windowed kernels (celerite_block.hip, celerite_tile.hip): the R rows and the y row
+constexpr int block_columns(int32_t R) { return (R + 1 + 15) / 16; }
 
 // What the rules read of a launch
 struct RouteQuery {
@@ -146,3 +150,78 @@ WidePlan wide_plan(WideMode mode, int32_t R, int32_t npd_rows, bool per_draw_tab
 // its name to pioran_celerite_config_name(0): "wide_rpl3", "wide2_rpl4", "wide2_rpl4_y"; gradient: "+adjoint" / "+adjoint2" behind the forward kernel's
 void wide_plan_name(const WidePlan& plan, WideMode mode, char* buf, size_t len);
 void pioran_note_wide_launch(const WidePlan& plan, WideMode mode);   // celerite_scan.hip pioran_scan_config_name(0): the thread's last launch was this one
+
+// ---- the windowed, tile and time-parallel kernels' instantiations --------------------------------------------------------------------------------
+
+// celerite_block.hip.  The forward kernel celerite_block_kernel<NB, emode, pdm, st>: NB block columns; emode: where the pair table E lives (0 one LDS
+// buffer, 1 two, 2 global memory); pdm: per-draw rows (0 none; 1 a helper wavefront prepares them, 320 threads; 2 the chain wavefront does); st: what
+// it stores per window (0 nothing, 1 the reverse pass's operands, 2 the prediction's, 3 the simulation's).  Behind it — gradient:
+// celerite_block_adjoint_kernel<NB, cd, tpt> (cd: d/dc or d/dd asked for; tpt: contraction threads per term, 8 up to 32 terms, else 4); solve:
+// celerite_block_backsolve_kernel<NB>; simulate: block_sim_xi_kernel<NB> and celerite_block_sim_kernel<NB>.
+enum class BlockMode { value, gradient, solve, simulate };
+constexpr int kBlockMaxTerms = 64;
+constexpr int kBlockMaxPdTerms = 2;
+constexpr size_t kBlockLdsMax = 160 * 1024;
+struct BlockPlan {
+    int rc = PIORAN_ERR_UNSUPPORTED;
+    int NB = 0, emode = 0, pdm = 0, st = 0;
+    int threads = 0;   // per workgroup of the forward kernel: 256, 320 or 512
+    size_t lds = 0;    // ... its dynamic LDS
+    bool cd = false;
+    int tpt = 0;
+};
+BlockPlan block_plan(BlockMode mode, int32_t R, int32_t J, int64_t B, int32_t npd_rows, bool want_cd, const ScanOptions* opt);
+// "block_nb3_e2_pd0"; gradient "block_nb2_e0+adjoint_cd_8" / "block_nb2_e0+adjoint_4"; "block_nb2_e0+backsolve"; "block_nb2_e0+sim"; "none": refused
+void block_plan_name(const BlockPlan& plan, BlockMode mode, char* buf, size_t len);
+size_t pioran_block_lds_bytes(int NB, int J, int emode, int npd_terms);    // celerite_block.hip: the forward kernel's dynamic LDS (no runtime call)
+bool pioran_block_kernel_exists(const BlockPlan& plan, BlockMode mode);   // ... its tables hold the plan's kernels
+
+// celerite_tile.hip.  Value: celerite_tile_kernel<NB, KL, false, SER> — KL live K-steps of four rows in the last row block, SER: a series per draw.
+// Gradient: celerite_tile_kernel<NB, 4, true, false>, then celerite_tile_adjoint_kernel<NB, cd> with adj_waves draws per workgroup and
+// tile_pairs_grad_kernel<cd>.
+enum class TileMode { value, gradient };
+constexpr int kTileMaxTerms = 64;
+constexpr int tile_adj_waves_of(int NB, bool cd) { return NB <= 3 ? 4 : (cd ? 2 : 3); }
+struct TilePlan {
+    int rc = PIORAN_ERR_UNSUPPORTED;
+    int NB = 0, KL = 0;
+    bool SER = false, cd = false;
+    int adj_waves = 0;
+};
+TilePlan tile_plan(TileMode mode, int32_t R, int32_t J, bool per_draw_series, bool want_cd);
+// "tile_nb3_kl2", "tile_nb3_kl2_ser"; gradient "tile_nb3_kl4_st+adjoint_cd_w4" / "tile_nb4_kl4_st+adjoint_w3"; "none": refused
+void tile_plan_name(const TilePlan& plan, TileMode mode, char* buf, size_t len);
+size_t pioran_tile_lds_bytes(int NB);                    // celerite_tile.hip: the forward kernel's dynamic LDS,
+size_t pioran_tile_adj_lds_bytes(int NB, bool cd);      // ... the adjoint's
+bool pioran_tile_kernel_exists(const TilePlan& plan, TileMode mode);
+
+// celerite_tp.hip: with which kernels the family runs (whether and how it runs at all: TpPlan, tp_mode above).  tp_element_kernel and
+// tp_filter_kernel<NP, NWV>; between them the boundary phase — the walk on tp_boundary_small_kernel<rows> (2 | 4 state rows),
+// tp_boundary_wave_kernel<rows> (6 .. 16) or tp_boundary_kernel<4, rt> (rt tiles of 16 rows), or the scan on tp_combine_kernel<rt, tw> /
+// tp_combine_lean_kernel<rt, tw> (tw wavefronts per combination); mode 1 only: the verification launch of the scan's kernel and behind it the walk,
+// on tp_boundary_wave_kernel<8 | 16> or tp_boundary_kernel<4, rt>, for the draws that fail.
+enum class TpPhase { none, small, wave, tiles, scan };
+struct TpStepPlan {
+    int rc = PIORAN_ERR_UNSUPPORTED;
+    int NP = 0, NWV = 0;
+    TpPhase boundary = TpPhase::none;
+    int rows = 0;                          // small, wave: the template argument
+    int rt = 0, tw = 0;                    // tiles, scan: tiles of rows; scan: wavefronts
+    bool lean = false;
+    size_t lds = 0;                        // dynamic LDS of the boundary phase's kernel
+    TpPhase verify = TpPhase::none;        // none, wave or tiles
+    int verify_rows = 0, verify_rt = 0;
+    size_t verify_lds = 0;
+    bool filter_disc = false;              // the filter makes the check on its way (its `disc`)
+};
+TpStepPlan tp_step_plan(int RP, int nseg, int mode /*pioran_launch_tp's: 0, 1, 2, 4*/, const ScanOptions* opt);
+// "tp_np1x1+small2", "tp_np4x1+wave8", "tp_np3x4+boundary_rt2", "tp_np5x4+combine_lean_rt4_w8"; mode 1: "...+verify_wave8" / "...+verify_boundary_rt3"
+void tp_step_plan_name(const TpStepPlan& plan, char* buf, size_t len);
+bool pioran_tp_kernel_exists(const TpStepPlan& plan);
+
+// The calling thread's last launch of one of these three families (pioran_celerite_config_name(-2)): the launchers note their plan, the name is
+// spelled when asked for
+void pioran_note_block_launch(const BlockPlan& plan, BlockMode mode);
+void pioran_note_tile_launch(const TilePlan& plan, TileMode mode);
+void pioran_note_tp_launch(const TpStepPlan& plan);
+const char* pioran_window_last_name();

@@ -547,3 +547,171 @@ void wide_plan_name(const WidePlan& plan, WideMode mode, char* buf, size_t len)
     std::snprintf(buf, len, "%s_rpl%d%s%s", plan.lean ? "wide2" : "wide", plan.rpl, plan.ycol ? "_y" : "",
                   mode != WideMode::gradient ? "" : (plan.lean_adjoint ? "+adjoint2" : "+adjoint"));
 }
+
+// ---- the windowed kernels (celerite_block.hip) --------------------------------------------------------------------------------------------------------
+// Where the pair table E lives (tools/sweep_block_emode.py, N = 1e4, late round 3): one LDS buffer is as fast as two or faster at every size measured
+// (SHO-20, 256 draws: 1.92 vs 2.10 ms — the second buffer was worth its LDS in round 2, before the shared block shrank), so two buffers are an option
+// only (block_emode = 1) — except with per-draw rows up to 256 draws, where they are taken when they fit; above 256 draws what counts is whether TWO
+// workgroups fit a CU — if they do not with E in LDS but do without, E is read from global memory (SHO-20, 512 draws: 2.68 instead of 3.75 ms).
+// 64 .. 95 rows (five and six block columns, round 4): value only, no per-draw rows; E in LDS where it fits, else from global memory.
+// Per-draw rows: a helper wavefront prepares them where the workgroup has room for one (up to three block columns); above 256 draws there, two
+// workgroups of four wavefronts per CU (the chain wavefront prepares the per-draw rows, E comes from global memory) instead of one of five.
+// Gradient above 256 chains: the forward pass with two workgroups per CU as well (up to three block columns; exp & 16 switches that off: tools); the
+// reverse pass stays at one (its LDS holds two copies of a window's block).
+BlockPlan block_plan(BlockMode mode, int32_t R, int32_t J, int64_t B, int32_t npd_rows, bool want_cd, const ScanOptions* opt)
+{
+    const ScanOptions& o = opt ? *opt : kDefaultOptions;
+    BlockPlan plan;
+    const int NB = plan.NB = block_columns(R), npd = npd_rows / 2;
+    const auto fits = [&](int emode, int workgroups = 1) { return workgroups * pioran_block_lds_bytes(NB, J, emode, npd) <= kBlockLdsMax; };
+    const auto take = [&](int emode, int pdm) {
+        plan.emode = emode;
+        plan.pdm = pdm;
+        plan.threads = NB < 4 ? (pdm == 1 ? 320 : 256) : 512;
+        plan.lds = pioran_block_lds_bytes(NB, J, emode, pdm ? npd : 0);
+        plan.rc = PIORAN_OK;
+        return plan;
+    };
+    if (mode != BlockMode::value) {
+        if (npd_rows != 0 || !pioran_block_fits(R, J)) return plan;
+        plan.st = (int)mode;
+        if (mode == BlockMode::gradient) {
+            plan.cd = want_cd;
+            plan.tpt = J <= 32 ? 8 : 4;
+            if (NB <= 3 && B > 256 && fits(2, 2) && !(o.exp & 16)) return take(2, 0);
+        }
+        return take(0, 0);
+    }
+    const int em = o.block_emode;   // diagnostics: force an E mode
+    if (npd_rows != 0) {
+        if ((npd_rows & 1) || !pioran_block_fits_pd(R, J, npd)) return plan;
+        const int helper = NB < 4 ? 1 : 2;
+        if (NB < 4 && (em == 2 || (em < 0 && B > 256)) && fits(2, 2)) return take(2, 2);
+        if (B <= 256 && fits(1)) return take(1, helper);
+        return fits(0) ? take(0, helper) : plan;
+    }
+    if (!pioran_block_fits_value(R, J)) return plan;
+    if (NB >= 5) return fits(0) ? take(0, 0) : (fits(2) ? take(2, 0) : plan);
+    if (em == 2 && NB < 4) return take(2, 0);
+    if (em == 1 && fits(1)) return take(1, 0);
+    if (NB < 4 && em < 0 && B > 256 && !fits(0, 2) && fits(2, 2)) return take(2, 0);
+    return fits(0) ? take(0, 0) : plan;
+}
+
+void block_plan_name(const BlockPlan& plan, BlockMode mode, char* buf, size_t len)
+{
+    if (plan.rc != PIORAN_OK) { std::snprintf(buf, len, "none"); return; }
+    if (mode == BlockMode::value) std::snprintf(buf, len, "block_nb%d_e%d_pd%d", plan.NB, plan.emode, plan.pdm);
+    else if (mode == BlockMode::gradient) std::snprintf(buf, len, "block_nb%d_e%d+adjoint%s_%d", plan.NB, plan.emode, plan.cd ? "_cd" : "", plan.tpt);
+    else std::snprintf(buf, len, "block_nb%d_e%d+%s", plan.NB, plan.emode, mode == BlockMode::solve ? "backsolve" : "sim");
+}
+
+// ---- one draw per wavefront (celerite_tile.hip) ------------------------------------------------------------------------------------------------------
+// NB = ceil((R + 1) / 16) block columns, KL = ceil((R - 16 (NB - 1)) / 4) live K-steps in the last row block (NB = 1: R >= 1, KL >= 1).  The reverse
+// mode's forward pass keeps all four K-steps; its adjoint runs four draws per workgroup up to three block columns, three at four (DRWCelerite-20),
+// two there with d/d(c, d).
+TilePlan tile_plan(TileMode mode, int32_t R, int32_t J, bool per_draw_series, bool want_cd)
+{
+    TilePlan plan;
+    plan.NB = block_columns(R);
+    if ((R >> 4) != plan.NB - 1) return plan;   // the kernels' compile-time y block column
+    if (mode == TileMode::gradient) {
+        if (per_draw_series || J > kTileMaxTerms || R < 1 || R > pioran_tile_grad_supported_rows()) return plan;
+        plan.KL = 4;
+        plan.cd = want_cd;
+        plan.adj_waves = tile_adj_waves_of(plan.NB, want_cd);
+    } else {
+        if (!pioran_tile_fits(R, J)) return plan;
+        plan.KL = (R - 16 * (plan.NB - 1) + 3) / 4;
+        plan.SER = per_draw_series;
+    }
+    plan.rc = PIORAN_OK;
+    return plan;
+}
+
+void tile_plan_name(const TilePlan& plan, TileMode mode, char* buf, size_t len)
+{
+    if (plan.rc != PIORAN_OK) std::snprintf(buf, len, "none");
+    else if (mode == TileMode::value) std::snprintf(buf, len, "tile_nb%d_kl%d%s", plan.NB, plan.KL, plan.SER ? "_ser" : "");
+    else std::snprintf(buf, len, "tile_nb%d_kl4_st+adjoint%s_w%d", plan.NB, plan.cd ? "_cd" : "", plan.adj_waves);
+}
+
+// ---- the time-parallel family's kernels (celerite_tp.hip) --------------------------------------------------------------------------------------------
+// Element and filter kernels: one wavefront per segment and two rows per step of NP up to 12 state rows, four wavefronts and eight rows above (at 16
+// rows four are 9 % ahead of one).  The boundary phase as a scan — modes 1 and 2, from two segments on, where pioran_tp_scan_rows — on the lean
+// combination at four tiles of rows (only that one fits the LDS) or on request (tp_scan_lean: tests), with eight wavefronts per combination from 17
+// rows on (three tiles of rows: nine product tiles and eight column tiles per elimination round — 48.9 -> 40.2 us; four tiles, lean: sixteen and
+// twelve) unless tp_scan_waves = 4.  Mode 2 leaves the check to the filter (the caller repairs the draws that fail it: capi.hip tp_dispatch), and so
+// does mode 4 behind its walk; mode 1 verifies with one more launch of the scan's kernel and walks the draws that fail.
+TpStepPlan tp_step_plan(int RP, int nseg, int mode, const ScanOptions* opt)
+{
+    const ScanOptions& o = opt ? *opt : kDefaultOptions;
+    TpStepPlan plan;
+    if (RP < 2 || RP > 64 || RP != pioran_tp_padded_rows(RP) || nseg < 1) return plan;
+    plan.NP = RP <= 12 ? RP / 2 : RP / 8;
+    plan.NWV = RP <= 12 ? 1 : 4;
+    const int rt = (RP + 15) / 16;
+    // the walk: two or four rows per thread of a wavefront's 64 draws, one wavefront per draw up to 16 rows, four wavefronts and rt tiles above
+    const auto walk = [&](TpPhase& phase, int& rows, int& tiles, size_t& lds) {
+        const size_t r16 = (size_t)rt * 16;
+        if (RP <= 4) { phase = TpPhase::small; rows = RP; }
+        else if (RP <= 16) { phase = TpPhase::wave; rows = RP; }
+        else { phase = TpPhase::tiles; tiles = rt; lds = (r16 * (2 * r16 + 3) + 2 * r16 * (r16 + 1) + 192 + 1024) * sizeof(double); }
+    };
+    plan.filter_disc = mode == 4;
+    if (mode != 0 && mode != 4 && nseg >= 2 && pioran_tp_scan_rows(RP)) {
+        const size_t r16 = (size_t)rt * 16;
+        plan.boundary = TpPhase::scan;
+        plan.rt = rt;
+        plan.lean = rt == 4 || o.tp_scan_lean;
+        plan.tw = rt >= 2 && o.tp_scan_waves != 4 ? 8 : 4;
+        plan.lds = plan.lean ? (r16 * (3 * r16 + 3) + r16 * (r16 + 1) + 7 * 64 + 32 + 256 * plan.tw) * sizeof(double)
+                             : (r16 * (3 * r16 + 3) + 4 * r16 * (r16 + 1) + 7 * 64 + 256 * plan.tw) * sizeof(double);
+        if (mode == 2) plan.filter_disc = true;
+        else walk(plan.verify, plan.verify_rows, plan.verify_rt, plan.verify_lds);
+    } else {
+        walk(plan.boundary, plan.rows, plan.rt, plan.lds);
+    }
+    plan.rc = PIORAN_OK;
+    return plan;
+}
+
+void tp_step_plan_name(const TpStepPlan& plan, char* buf, size_t len)
+{
+    if (plan.rc != PIORAN_OK) { std::snprintf(buf, len, "none"); return; }
+    int n = std::snprintf(buf, len, "tp_np%dx%d", plan.NP, plan.NWV);
+    const auto add = [&](const char* prefix, TpPhase phase, int rows, int rt) {
+        if (n < 0 || (size_t)n >= len) return;
+        if (phase == TpPhase::small) n += std::snprintf(buf + n, len - n, "+%ssmall%d", prefix, rows);
+        else if (phase == TpPhase::wave) n += std::snprintf(buf + n, len - n, "+%swave%d", prefix, rows);
+        else if (phase == TpPhase::tiles) n += std::snprintf(buf + n, len - n, "+%sboundary_rt%d", prefix, rt);
+        else if (phase == TpPhase::scan) n += std::snprintf(buf + n, len - n, "+combine%s_rt%d_w%d", plan.lean ? "_lean" : "", rt, plan.tw);
+    };
+    add("", plan.boundary, plan.rows, plan.rt);
+    add("verify_", plan.verify, plan.verify_rows, plan.verify_rt);
+}
+
+// the calling thread's last launch of these three families
+namespace {
+struct LastWindowLaunch {
+    int family = 0;   // 0 none yet, 1 block, 2 tile, 3 tp
+    int mode = 0;
+    BlockPlan block;
+    TilePlan tile;
+    TpStepPlan tp;
+};
+thread_local LastWindowLaunch g_last_window;
+}  // namespace
+void pioran_note_block_launch(const BlockPlan& plan, BlockMode mode) { g_last_window.family = 1; g_last_window.mode = (int)mode; g_last_window.block = plan; }
+void pioran_note_tile_launch(const TilePlan& plan, TileMode mode) { g_last_window.family = 2; g_last_window.mode = (int)mode; g_last_window.tile = plan; }
+void pioran_note_tp_launch(const TpStepPlan& plan) { g_last_window.family = 3; g_last_window.tp = plan; }
+const char* pioran_window_last_name()
+{
+    static thread_local char buf[96];
+    const LastWindowLaunch& l = g_last_window;
+    if (l.family == 1) block_plan_name(l.block, (BlockMode)l.mode, buf, sizeof(buf));
+    else if (l.family == 2) tile_plan_name(l.tile, (TileMode)l.mode, buf, sizeof(buf));
+    else if (l.family == 3) tp_step_plan_name(l.tp, buf, sizeof(buf));
+    else std::snprintf(buf, sizeof(buf), "none");
+    return buf;
+}

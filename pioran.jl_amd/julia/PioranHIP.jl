@@ -1071,4 +1071,24 @@ function step_route(family::AbstractString, R::Integer; standard_rows::Integer=0
     return (GC.@preserve(name, unsafe_string(pointer(name))), plan)
 end
 
+"""
+    window_route(family; R=0, J=0, B=1, npd_rows=0, per_draw_series=false, want_cd=false, tp_rows=0, tp_segments=0, tp_mode=0, options="")
+
+Diagnostics (no GPU needed): the kernel instantiations a launch of the windowed kernels (`family = "block"`, `"block_grad"`, `"block_solve"`,
+`"block_sim"`), of their one-draw-per-wavefront form (`"tile"`, `"tile_grad"`) or of the time-parallel family (`"tp"`) runs
+(`pioran_window_route`).  Returns `(name, plan)`: the name `pioran_celerite_config_name(-2)` reports after such a launch (`nothing` where it is
+refused) and the plan's twelve integers (`include/pioran_hip.h`).
+"""
+function window_route(family::AbstractString; R::Integer=0, J::Integer=0, B::Integer=1, npd_rows::Integer=0, per_draw_series::Bool=false,
+                      want_cd::Bool=false, tp_rows::Integer=0, tp_segments::Integer=0, tp_mode::Integer=0, options::AbstractString="")
+    name = zeros(UInt8, 96)
+    plan = zeros(Int32, 12)
+    rc = ccall((:pioran_window_route, LIB), Cint,
+               (Cstring, Int32, Int32, Int64, Int32, Cint, Cint, Int32, Int32, Cint, Cstring, Ptr{UInt8}, Cint, Ptr{Int32}),
+               family, R, J, B, npd_rows, per_draw_series, want_cd, tp_rows, tp_segments, tp_mode, options, name, length(name), plan)
+    rc == -4 && return (nothing, plan)
+    check(rc)
+    return (GC.@preserve(name, unsafe_string(pointer(name))), plan)
+end
+
 end # module

@@ -53,6 +53,9 @@ def test_argument_validation_without_gpu():
     assert L.pioran_ctx_set_option(None, b"no_wide", b"1") == -1
     assert L.pioran_step_route(None, 40, 1, 0, 1, 1, 0, 0, b"", ctypes.create_string_buffer(8), 8, None) == -1
     assert L.pioran_step_route(b"scan", 40, 1, 0, 1, 1, 0, 0, b"", None, 0, None) == -1 and L.pioran_step_route(b"tile", 40, 1, 0, 1, 1, 0, 0, b"", ctypes.create_string_buffer(8), 8, None) == -1
+    assert L.pioran_window_route(None, 40, 20, 1, 0, 0, 0, 0, 0, 0, b"", ctypes.create_string_buffer(8), 8, None) == -1
+    assert L.pioran_window_route(b"block", 40, 20, 1, 0, 0, 0, 0, 0, 0, b"", None, 0, None) == -1
+    assert L.pioran_window_route(b"scan", 40, 20, 1, 0, 0, 0, 0, 0, 0, b"", ctypes.create_string_buffer(8), 8, None) == -1
     assert L.pioran_dense_nll_timed(None, 4, 1, None, None, None, None, None, None, None, None, None, None) == -1
 
 

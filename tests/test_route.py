@@ -3,7 +3,8 @@ takes when every resource is granted.  Routes the GPU tests already assert, tran
 time-parallel plans against the conditions pioran_launch_tp refuses on.  Likewise pioran_value_route_cd for draws with (c, d) of their own, and
 pioran_entry_route for the other batched entries (route.hip entry_plan) against the rules written out in entry_truth.  One level down,
 pioran_step_route (scan_plan, wide_plan: the kernel instantiation of a step-by-step launch) against the listing recorded before those rules
-existed, the names the GPU tests assert, and properties over the listing's grid."""
+existed, the names the GPU tests assert, and properties over the listing's grid; pioran_window_route (block_plan, tile_plan, tp_step_plan) against
+the listing recorded before those."""
 import importlib.util
 import itertools
 import json
@@ -739,3 +740,62 @@ def test_step_route_properties_over_the_grid():
                 assert lean == (R > 95 or per_draw_tables)               # (store, simulate: per-draw tables are refused above)
             if mode in ("store", "simulate"):
                 assert not per_draw_tables and (not lean or npd == 0) and (options != "wide2=1" or lean == (R >= 64 and npd == 0))
+
+
+# ---- the windowed, tile and time-parallel kernels' instantiations: pioran_window_route (route.hip block_plan, tile_plan, tp_step_plan) -----------------
+
+def test_window_route_reproduces_the_listing_recorded_before_the_rules():
+    """tests/golden/window_route_listing.json: the kernels, threads per workgroup and dynamic LDS bytes the launch code of celerite_block.hip,
+    celerite_tile.hip and celerite_tp.hip chose before block_plan / tile_plan / tp_step_plan existed (tools/experiments/window_route_listing.py), over
+    the grid of route_grid.window_keys: the rules give the same return code, the same kernel instantiations in the same order and, for the kernel the
+    plan sizes (the forward kernel; the tile adjoint, the time-parallel boundary phase), the same threads and LDS bytes for every entry, and the files'
+    tables hold a kernel for every plan that is not refused.  The threads of the kernels that run behind the forward one are fixed in the launch code and
+    in route_grid.window_kernels alike: this test holds the rule, not the launcher's lookup, which tests/test_gpu_window_route.py runs."""
+    listing = json.loads((ROOT / "tests" / "golden" / "window_route_listing.json").read_text())
+    n = 0
+    for family, (keys, xs_of) in G.window_keys().items():
+        assert len(listing[family]) == len(keys)
+        for key in keys:
+            xs = list(xs_of(key))
+            for x, want in G.window_expand(listing["runs"][listing[family]["|".join(map(str, key))]], xs):
+                q = G.window_query(family, key, x)
+                rc, name, plan = G.window_route(family, **q)
+                got = rc if rc else G.window_kernels(family, plan, q.get("tp_segments", 2))
+                assert got == want, (family, key, x, name)
+                assert (name == "none") == (rc != 0)
+                if rc == 0:
+                    assert plan[11 if family == "tp" else 8] == 1, (family, key, x, name)       # *_kernel_exists
+                n += 1
+    assert n == 268864
+    # the shapes of the benchmarks are on the grid: SHO-20 and DRWCelerite-20 at 512 draws, pair table from global memory, two workgroups per CU
+    assert G.window_route("block", R=40, J=20, B=512)[1] == "block_nb3_e2_pd0" and G.window_route("block", R=60, J=40, B=512)[1] == "block_nb4_e0_pd0"
+
+
+def test_window_route_names_are_one_to_one_with_the_kernels():
+    """Two entries of the grid have the same name exactly where they run the same kernel instantiations."""
+    by_name = {}
+    for family, (keys, xs_of) in G.window_keys().items():
+        for key in keys[::7]:
+            for x in xs_of(key):
+                q = G.window_query(family, key, x)
+                rc, name, plan = G.window_route(family, **q)
+                if rc == 0:
+                    kernels = tuple(k[0] for k in G.window_kernels(family, plan, 2))
+                    assert by_name.setdefault(name, kernels) == kernels, name
+    assert len(set(by_name.values())) == len(by_name) > 100
+
+
+def test_launchers_read_no_selection_option():
+    """celerite_block.hip, celerite_tile.hip and celerite_tp.hip ask the rules: none names an option the choice goes by."""
+    for f in ("celerite_block.hip", "celerite_tile.hip", "celerite_tp.hip"):
+        text = (ROOT / "pioran.jl_amd" / "csrc" / f).read_text()
+        for word in ("block_emode", "exp & 16", "tp_scan_lean", "tp_scan_waves"):
+            assert word not in text, (f, word)
+
+
+def test_window_route_argument_validation():
+    name = __import__("ctypes").create_string_buffer(96)
+    L = pj._lib.lib()
+    assert L.pioran_window_route(b"block", 40, 20, 1, 0, 0, 0, 0, 0, 0, b"block_emode", name, len(name), None) == -1     # an option without a value
+    assert L.pioran_window_route(b"wide", 40, 20, 1, 0, 0, 0, 0, 0, 0, b"", name, len(name), None) == -1
+    assert L.pioran_window_route(b"block", 144, 72, 1, 0, 0, 0, 0, 0, 0, b"", name, len(name), None) == -4 and name.value == b"none"

@@ -18,6 +18,10 @@ arrays — a different segment count, mode or chunking changes bits, so two libr
 instead: name, return code and a hash of the outputs per point; the gradient arrays are saved / compared with the saved ones
 (--before-entry-route: the library is from before pioran_entry_route existed).  `--steps` lists step_points() the same way
 (--before-step-route: the library is from before pioran_step_route existed).
+
+`window_route` asks pioran_window_route: the instantiations of the windowed kernels, their one-draw-per-wavefront form and the time-parallel family;
+`window_points()` / `run_window_point` are the launches of tests/test_gpu_window_route.py, listed behind the others by `--steps`
+(--before-window-route: the library is from before pioran_window_route existed; the name that ran, pioran_celerite_config_name(-2), is then not listed).
 """
 import ctypes
 import hashlib
@@ -372,6 +376,219 @@ def run_step_point(ctx, pt):
         ds.close()
 
 
+# ---- the windowed, tile and time-parallel kernels' instantiations (route.hip block_plan, tile_plan, tp_step_plan): the grid
+# tests/golden/window_route_listing.json was recorded over, from the commit before those rules (tools/experiments/window_route_listing.py) --------------
+WINDOW_MAX_TERMS = 64
+WINDOW_EMODES = ("", "block_emode=0", "block_emode=1", "block_emode=2")
+
+
+def window_route(family, R=0, J=0, B=1, npd_rows=0, per_draw_series=False, want_cd=False, tp_rows=0, tp_segments=0, tp_mode=0, options=""):
+    """(rc, name, plan) of pioran_window_route — family "block", "block_grad", "block_solve", "block_sim", "tile", "tile_grad" or "tp"; name: what
+    pioran_celerite_config_name(-2) reports after the launch, "none" where it is refused (rc -4); plan: the 12 integers include/pioran_hip.h documents."""
+    import pioran_jl_amd as pj
+    name = ctypes.create_string_buffer(96)
+    plan = (ctypes.c_int32 * 12)()
+    rc = pj._lib.lib().pioran_window_route(family.encode(), R, J, B, npd_rows, int(per_draw_series), int(want_cd), tp_rows, tp_segments, tp_mode,
+                                           options.encode(), name, len(name), plan)
+    if rc not in (0, -4):
+        raise ValueError(f"pioran_window_route: error {rc}")
+    return rc, name.value.decode(), tuple(plan)
+
+
+def window_keys():
+    """family -> (keys, the values of the variable every key is asked over): the terms J for the windowed families (key[0] is R: J from ceil(R / 2)
+    on), the rows R for the tile family (J = ceil(R / 2)), the padded state rows for the time-parallel one, valid or not."""
+    value = [(R, B, npd, em) for R in range(1, 97) for B in (1, 256, 257, 512, 513) for npd in (0, 2, 4) for em in WINDOW_EMODES]
+    grad = [(R, B, cd, ex) for R in range(1, 65) for B in (256, 257) for cd in (0, 1) for ex in ("", "exp=16")]
+    terms = lambda key: range((key[0] + 1) // 2, WINDOW_MAX_TERMS + 1)
+    return {"block": (value, terms), "block_grad": (grad, terms), "block_solve": ([(R,) for R in range(1, 65)], terms),
+            "block_sim": ([(R,) for R in range(1, 65)], terms),
+            "tile": ([(0,), (1,)], lambda key: range(1, 97)), "tile_grad": ([(0,), (1,)], lambda key: range(1, 65)),
+            "tp": ([(nseg, mode, lean, waves) for nseg in (1, 2, 3, 9) for mode in (0, 1, 2, 4) for lean in ("", "tp_scan_lean=1")
+                    for waves in ("", "tp_scan_waves=4")], lambda key: range(1, 67))}
+
+
+def window_query(family, key, x):
+    """The arguments of window_route for one entry of the grid."""
+    if family == "block":
+        return dict(R=key[0], J=x, B=key[1], npd_rows=key[2], options=key[3])
+    if family == "block_grad":
+        return dict(R=key[0], J=x, B=key[1], want_cd=bool(key[2]), options=key[3])
+    if family in ("block_solve", "block_sim"):
+        return dict(R=key[0], J=x, B=3)
+    if family == "tile":
+        return dict(R=x, J=(x + 1) // 2, B=5, per_draw_series=bool(key[0]))
+    if family == "tile_grad":
+        return dict(R=x, J=(x + 1) // 2, B=7, want_cd=bool(key[0]))
+    return dict(tp_rows=x, tp_segments=key[0], tp_mode=key[1], options=";".join(o for o in key[2:] if o))
+
+
+def window_kernels(family, plan, tp_segments=2):
+    """The launches a plan of pioran_window_route stands for, as the listing holds them: [[kernel<template arguments>, threads per workgroup, dynamic
+    LDS bytes], ...] in launch order.  The forward kernel's threads and LDS bytes, and every kernel's template arguments, are the plan's; the threads of the
+    kernels behind it are written out here as the launch code has them (the launches themselves are held by the GPU tests).  Not listed, because no rule chooses them: the tile family's pair pre-pass, tp_records_kernel, tp_finish_kernel."""
+    tf = ("false", "true")
+    if family.startswith("block"):
+        NB, e, pd, st, threads, lds, cd, tpt = plan[:8]
+        out = [[f"celerite_block_kernel<{NB},{e},{pd},{st}>", threads, lds]]
+        if family == "block_grad":
+            out.append([f"celerite_block_adjoint_kernel<{NB},{tf[cd]},{tpt}>", 256, 0])
+        elif family == "block_solve":
+            out.append([f"celerite_block_backsolve_kernel<{NB}>", 64, 0])
+        elif family == "block_sim":
+            out += [[f"block_sim_xi_kernel<{NB}>", 256, 0], [f"celerite_block_sim_kernel<{NB}>", 64, 0]]
+        return out
+    if family == "tile":
+        NB, KL, ser, _, _, threads, lds = plan[:7]
+        return [[f"celerite_tile_kernel<{NB},{KL},false,{tf[ser]}>", threads, lds]]
+    if family == "tile_grad":
+        NB, KL, _, cd, waves, threads, lds, adj_lds = plan[:8]
+        return [[f"celerite_tile_kernel<{NB},{KL},true,false>", threads, lds], [f"celerite_tile_adjoint_kernel<{NB},{tf[cd]}>", 64 * waves, adj_lds],
+                [f"tile_pairs_grad_kernel<{tf[cd]}>", 512, 0]]
+    NP, NWV, boundary, arg, lean, tw, lds, verify, varg, vlds, _, _ = plan
+    walk = {1: lambda a, l: [f"tp_boundary_small_kernel<{a}>", 64, 0], 2: lambda a, l: [f"tp_boundary_wave_kernel<{a}>", 64, 0],
+            3: lambda a, l: [f"tp_boundary_kernel<4,{a}>", 256, l]}
+    out = [[f"tp_element_kernel<{NP},{NWV}>", 64 * NWV, 0]] if tp_segments > 1 else []
+    out.append([f"tp_combine{'_lean' if lean else ''}_kernel<{arg},{tw}>", 64 * tw, lds] if boundary == 4 else walk[boundary](arg, lds))
+    if verify:
+        out.append(walk[verify](varg, vlds))
+    return out + [[f"tp_filter_kernel<{NP},{NWV}>", 64 * NWV, 0]]
+
+
+def window_answer(family, key, x):
+    """What the listing holds per entry: the kernels of the plan, or the return code where the launch is refused."""
+    q = window_query(family, key, x)
+    rc, _, plan = window_route(family, **q)
+    return rc if rc else window_kernels(family, plan, q.get("tp_segments", 2))
+
+
+def window_runs(answers):
+    """[(x, answer), ...] over consecutive x as runs [last x, answer] (the first run starts at the first x).  Within a run the kernels keep their names
+    and threads and every dynamic LDS size is affine in x: a kernel of a run is [name, threads, LDS bytes at x = 0, LDS bytes per unit of x]."""
+    runs = []        # [last x, answer, entries]
+    for x, a in answers:
+        r = runs[-1] if runs else None
+        if r is not None and isinstance(a, int) and a == r[1]:
+            r[0] = x
+            continue
+        if r is not None and not isinstance(a, int) and not isinstance(r[1], int) and [k[:2] for k in a] == [k[:2] for k in r[1]]:
+            if r[2] == 1:        # the run's second entry sets the slopes
+                for k, held in zip(a, r[1]):
+                    held[3] = k[2] - held[2]
+                    held[2] = k[2] - held[3] * x
+            if all(held[2] + held[3] * x == k[2] for k, held in zip(a, r[1])):
+                r[0], r[2] = x, r[2] + 1
+                continue
+        runs.append([x, a if isinstance(a, int) else [[k[0], k[1], k[2], 0] for k in a], 1])
+    return [r[:2] for r in runs]
+
+
+def window_expand(runs, xs):
+    """The inverse of window_runs: [(x, answer), ...]."""
+    out, i = [], 0
+    for x in xs:
+        while runs[i][0] < x:
+            i += 1
+        a = runs[i][1]
+        out.append((x, a if isinstance(a, int) else [[k[0], k[1], k[2] + k[3] * x] for k in a]))
+    return out
+
+
+# ---- the launches of tests/test_gpu_window_route.py: one on each side of every rule of block_plan / tile_plan / tp_step_plan -----------------------------
+WindowPoint = namedtuple("WindowPoint", "family rows J B npd_rows series cd options")
+WINDOW_N, WINDOW_TP_N, WINDOW_M = 37, 64, 5
+WINDOW_TO_BLOCK = "scan_config=block"
+WINDOW_TO_TILE = "scan_config=tile"
+
+
+def window_points():
+    def pt(family, rows, B, npd_rows=0, series=False, cd=False, options="", J=None):
+        return WindowPoint(family, rows, J or (rows + 1) // 2, B, npd_rows, series, cd, options)
+    pts = []
+    # the windowed value kernel: a point per block-column count, three draws and 257 (where the rule reads B > 256; five and six block columns have no such rule)
+    pts += [pt("block", rows, B, options=WINDOW_TO_BLOCK) for rows in (5, 20, 40, 60, 70, 90) for B in ((3, 257) if rows < 64 else (3,))]
+    # ... the forced E modes, where the kernel has them (three block columns) and where it does not (four: two LDS buffers do not fit, none is no option)
+    pts += [pt("block", 40, 3, options=WINDOW_TO_BLOCK + f";block_emode={e}") for e in (0, 1, 2)]
+    pts += [pt("block", 60, 3, options=WINDOW_TO_BLOCK + ";block_emode=1"), pt("block", 60, 3, options=WINDOW_TO_BLOCK + ";block_emode=2")]
+    # ... per-draw rows (the last one or two terms per draw) at two and four block columns, either side of 256 draws
+    pts += [pt("block", rows, B, npd_rows=npd) for rows in (20, 60) for npd in (2, 4) for B in (3, 257)]
+    # gradient, solve (the prediction), simulate
+    pts += [pt("block_grad", rows, B, cd=cd, options="no_tile=1") for rows in (5, 20, 40, 60) for B in (3, 257) for cd in (False, True)]
+    pts.append(pt("block_grad", 40, 3, J=36, options="no_tile=1"))        # more than 32 terms: four contraction threads per term (32 of them with one row)
+    pts += [pt(f, rows, 3) for f in ("block_solve", "block_sim") for rows in (5, 20, 40, 60)]
+    # the tile family, five draws (the second workgroup ragged): a point per block-column count, the K-step edges of three block columns, a series per draw
+    pts += [pt("tile", rows, 5, options=WINDOW_TO_TILE) for rows in (5, 20, 40, 60, 70, 90, 32, 33, 36, 37, 44, 47)]
+    pts.append(pt("tile", 40, 5, series=True, options=WINDOW_TO_TILE))
+    # its gradient, seven draws (ragged for two, three and four adjoint wavefronts)
+    pts += [pt("tile_grad", rows, 7, cd=cd, options=WINDOW_TO_TILE) for rows in (5, 20, 40, 60) for cd in (False, True)]
+    # the time-parallel family, one draw of 64 steps in four segments (two scan levels): the walk unchecked, the scan with its verification launch, and the
+    # default repair pass (the scan or, below eight rows, the walk checked by the filter) — after that one the last launch is the windowed kernel's
+    for rows in (2, 4, 8, 12, 16, 24, 64):
+        base = "scan_config=tp;tp_segments=4"
+        pts += [pt("tp", rows, 1, options=base + ";tp_scan=0;tp_unchecked=1"), pt("tp", rows, 1, options=base + ";tp_walk_repair=1"), pt("tp", rows, 1, options=base)]
+    pts.append(pt("tp", 24, 1, options="scan_config=tp;tp_segments=4;tp_walk_repair=1;tp_scan_lean=1"))
+    return pts
+
+
+def _option(pt, key):
+    return dict(kv.split("=") for kv in pt.options.split(";") if kv).get(key)
+
+
+def window_expected(pt):
+    """The name pioran_window_route gives the point's LAST launch of the three families — pioran_celerite_config_name(-2) after the call."""
+    terms_options = ";".join(kv for kv in pt.options.split(";") if kv.split("=")[0] in ("block_emode", "exp", "tp_scan_lean", "tp_scan_waves"))
+    if pt.family != "tp":
+        # (the gradient of the Python API asks for d/dc and d/dd together; per-draw rows: the draws' own kernel has them, npd_rows of them)
+        return window_route(pt.family, R=pt.rows, J=pt.J, B=pt.B, npd_rows=pt.npd_rows, per_draw_series=pt.series, want_cd=pt.cd, options=terms_options)[1]
+    _, (scan, RP, nseg, _) = value_route(pt.rows, pt.J, 0, pt.B, WINDOW_TP_N, options=pt.options)
+    repair = not _option(pt, "tp_walk_repair") and not _option(pt, "tp_unchecked")
+    if repair:      # the serial-chain kernel runs last, over the draws that failed the check
+        return window_route("block", R=pt.rows, J=pt.J, B=pt.B)[1]
+    return window_route("tp", tp_rows=RP, tp_segments=nseg, tp_mode=1 if scan and _option(pt, "tp_walk_repair") else 0, options=terms_options)[1]
+
+
+def run_window_point(ctx, pt):
+    """One call that reaches the point's launch: (family that ran, pioran_celerite_config_name(-2) after it, the outputs that are one workgroup's or
+    one wavefront's sums — the gradient arrays are left out)."""
+    import pioran_jl_amd as pj
+    N = WINDOW_TP_N if pt.family == "tp" else WINDOW_N
+    npd = pt.npd_rows // 2
+    n_one = 2 * pt.J - pt.rows
+    t, y, s2, A, Bc, C, Dd, mu, nu = inputs_cd(CdPoint(pt.J, npd, pt.B, N, "")) if npd else inputs(Point(pt.J, 0, pt.B, N, ""))
+    if n_one:          # the one-row terms are the LAST ones
+        Bc[:, -n_one:] = 0.0
+        Dd[-n_one:] = 0.0
+    rng = np.random.default_rng([pt.J, pt.rows, pt.B, N, 6])
+    opts = [kv.split("=") for kv in pt.options.split(";") if kv]
+    ds = pj.Dataset(t, y, s2, ctx)
+    try:
+        for k, v in opts:
+            ctx.set_option(k, v)
+        if pt.family in ("block", "tile", "tp"):
+            if pt.series:      # a series per draw: the shifted log-flux form on a positive series
+                ds.close()
+                ds = pj.Dataset(t, np.exp(0.5 * y), s2, ctx)
+                out, st = ds.logl_batch(A, Bc, C, Dd, mu=mu, nu=nu, shift=np.exp(0.5 * y).min() * np.linspace(0.1, 0.9, pt.B), return_status=True)
+            else:
+                out, st = ds.logl_batch(A, Bc, C, Dd, mu=mu, nu=nu, return_status=True)
+            out = dict(logl=out, status=st)
+        elif pt.family == "block_solve":
+            mean, st = ds.predict(A, Bc, C, Dd, rng.uniform(t[0] - 1, t[-1] + 1, WINDOW_M), mu=mu, nu=nu, return_status=True)
+            out = dict(mean=mean, status=st)
+        elif pt.family == "block_sim":
+            out = dict(y=ctx.simulate(A, Bc, C, Dd, t, s2, rng.standard_normal((pt.B, N))))
+        else:
+            g = ds.logl_grad(A, Bc, C, Dd, mu=mu, nu=nu, cd_grad=pt.cd)
+            out = dict(logl=g["logl"], status=g["status"])
+        L = pj._lib.lib()
+        ran = L.pioran_celerite_config_name(-2).decode() if "pioran_window_route" in pj._lib.SIGNATURES else ""
+        return L.pioran_celerite_config_name(-1).decode(), ran, out
+    finally:
+        for k, _ in opts:
+            ctx.set_option(k, None)
+        ds.close()
+
+
 def expected(pt):
     """The family the rules name for a point of any of the three kinds."""
     if isinstance(pt, CdPoint):
@@ -522,6 +739,8 @@ def main():
         pj._lib.SIGNATURES.pop("pioran_entry_route", None)
     if "--before-step-route" in sys.argv:
         pj._lib.SIGNATURES.pop("pioran_step_route", None)
+    if "--before-window-route" in sys.argv:
+        pj._lib.SIGNATURES.pop("pioran_window_route", None)
     ctx = pj.Context(0)
     if "--entries" in sys.argv:
         arg = lambda flag: sys.argv[sys.argv.index(flag) + 1] if flag in sys.argv else None
@@ -531,6 +750,11 @@ def main():
             fam, _, out = run_step_point(ctx, pt)
             digest = hashlib.sha256(b"".join(np.ascontiguousarray(v).tobytes() for _, v in sorted(out.items()))).hexdigest()[:16]
             print(f"step {pt.family:8s} rows {2 * pt.J - pt.n_one:3d} J {pt.J:2d} B {pt.B:4d} N {STEP_N} [{pt.options}] {fam} {digest}", flush=True)
+        for pt in window_points():     # (the instantiation's name last: empty from a library before pioran_window_route)
+            fam, ran, out = run_window_point(ctx, pt)
+            digest = hashlib.sha256(b"".join(np.ascontiguousarray(v).tobytes() for _, v in sorted(out.items()))).hexdigest()[:16]
+            print(f"window {pt.family:11s} rows {pt.rows:3d} J {pt.J:2d} B {pt.B:4d} per-draw rows {pt.npd_rows} series {int(pt.series)} cd {int(pt.cd)} "
+                  f"[{pt.options}] {fam} {digest} {ran}", flush=True)
         return
     for pt in carma_points():
         fam, out, st, _ = run_carma_point(ctx, pt)
