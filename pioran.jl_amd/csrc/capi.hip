@@ -13,7 +13,45 @@
 #include <thread>
 #include <vector>
 
+// One device allocation and its owner: freed when the owner goes.  Grown by ensure (context buffers: with slack) or ensure_exact; every hipMalloc and
+// hipFree of the library is in its two functions.
+struct DevMem {
+    void* p = nullptr;
+    size_t cap = 0;   // bytes
+    DevMem() = default;
+    DevMem(const DevMem&) = delete;
+    DevMem& operator=(const DevMem&) = delete;
+    ~DevMem() { (void)release(); }
+    hipError_t release()        // frees; p = nullptr, cap = 0 whatever the runtime says
+    {
+        const hipError_t e = p ? hipFree(p) : hipSuccess;
+        p = nullptr;
+        cap = 0;
+        return e;
+    }
+    bool alloc(size_t bytes)    // of an empty one; false: no memory
+    {
+        if (hipMalloc(&p, bytes) != hipSuccess) {
+            (void)hipGetLastError();   // the failure is reported through the return code: do not leave it sticky for the callers'
+                                       // shrink-and-retry loops (a later launch wrapper would read it as its own error)
+            p = nullptr;
+            return false;
+        }
+        cap = bytes;
+        return true;
+    }
+};
+
+// ... seen as an array of T
+template <class T>
+struct DevArray : DevMem {
+    operator T*() const { return (T*)p; }
+};
+
 struct pioran_ctx {
+    pioran_ctx() = default;
+    pioran_ctx(const pioran_ctx&) = delete;
+    ~pioran_ctx();   // everything the context owns; the caller has set the device and drained the stream
     int device = 0;
     int ncu = 0;                    // compute units of the device (read once, at creation: the dispatch functions must not call into the runtime per launch)
     hipStream_t stream = nullptr;
@@ -35,29 +73,32 @@ struct pioran_ctx {
     // second stream + events of the gradient's reverse pass (replay of one segment overlaps the adjoint of the next); lazy
     hipStream_t aux = nullptr;
     hipEvent_t gev[5] = {};
-    // growable device staging for the host-pointer entry points
-    struct Buf {
-        void* p = nullptr;
-        size_t cap = 0;
+    // growable device staging for the host-pointer entry points.  A Buf enters `bufs` as it is constructed, and cannot be constructed otherwise:
+    // `bufs` is the one list of them, what pioran_ctx_trim and the destructor walk.  A new buffer is one more name below.
+    struct Buf : DevMem {
+        explicit Buf(pioran_ctx* owner) { owner->bufs.push_back(this); }
     };
-    Buf bA, bB, bC, bD, bmu, bnu, bY, bS2, bout, bst, bscratch, bK, bwork, bshift, bgtab, bq, bpair, btp, btprow;
-    Buf blstab, blsaux;   // periodogram: the cos/sin table of a frequency chunk | weights and per-draw scalars
+    std::vector<Buf*> bufs;
+    Buf bA{this}, bB{this}, bC{this}, bD{this}, bmu{this}, bnu{this}, bY{this}, bS2{this}, bout{this}, bst{this}, bscratch{this}, bK{this},
+        bwork{this}, bshift{this}, bgtab{this}, bq{this}, bpair{this}, btp{this}, btprow{this};
+    Buf blstab{this}, blsaux{this};   // periodogram: the cos/sin table of a frequency chunk | weights and per-draw scalars
     // posterior draws (rand_posterior_batch): what the chain holds BESIDE the prediction's buffers, which keep their roles there —
     // the caller's normals q_data | q_new | eps, the normals on the merged grid, the simulation's stores | xi | realisations | log L | status,
     // the index maps, the residual series Y | S2, the shifts, a chunk's draws | their status
-    Buf brqd, brqn, breps, brqT, brstores, brxi, brf, brsout, brsst, brmaps, brY, brS2, brshift, brres, brst;
+    Buf brqd{this}, brqn{this}, breps{this}, brqT{this}, brstores{this}, brxi{this}, brf{this}, brsout{this}, brsst{this}, brmaps{this}, brY{this},
+        brS2{this}, brshift{this}, brres{this}, brst{this};
     // quantiles over draws (quantiles.hip): the resident draws [B][M] | their status [B] (the summary entry's sink; the host form's staged X and
     // status), the small inputs probs | shift | ref | scale, the indices cols | kept, the results quant | mean
-    Buf bqX, bqst, bqin, bqidx, bqout;
+    Buf bqX{this}, bqst{this}, bqin{this}, bqidx{this}, bqout{this};
     // approx and its reverse mode as the two ends of the gradient (ThetaDraws): the grid's sp | w | LU | piv and the batch's theta | norm, a chunk's
     // grad_theta | grad_norm | the kernel's scratch
-    Buf bthin, bthout;
+    Buf bthin{this}, bthout{this};
     // PSD check (psd_check.hip): the grid's sp | LU | piv, the host forms' theta | norm | freq, a chunk's amp | integ | pf0 | status, a chunk's
     // (the summary: the batch's) arrays psd | psd_approx | residuals | ratios, the summary's transposed copies | partials, its small inputs and results
-    Buf bpcgrid, bpcin, bpcdraw, bpcout, bpcT, bpcq;
+    Buf bpcgrid{this}, bpcin{this}, bpcdraw{this}, bpcout{this}, bpcT{this}, bpcq{this};
     // CARMA entries (carma.hip): the batch's sampled parameters in1 | in2 | norm | flags, and what the kernels leave beside the coefficients (which
     // land where the value and gradient bodies read them, bA .. bD): the reverse mode's results, the PSD's per-draw roots | beta | factor | status
-    Buf bcarma, bcarmaout;
+    Buf bcarma{this}, bcarmaout{this};
     std::vector<double> pcgrid_host;   // what bpcgrid is filled from: the device form returns before the copy has run
     double pcgrid_key[6] = {};         // ... and the (J, basis, f_min, f_max, S_low, S_high) it was built for
     // scalar entry point: the last series' time stamps stay resident (samplers call logl with the same t)
@@ -72,28 +113,26 @@ struct PrepState {
     int32_t J = 0, R = 0;
     std::vector<double> c_host, d_host;
     std::vector<int32_t> real_host;
-    double* tab = nullptr;
-    size_t tab_cap = 0;
-    int32_t* rowmap = nullptr;
-    size_t rowmap_cap = 0;
-    double *dc = nullptr, *dd = nullptr;
-    size_t dcd_cap = 0;
+    DevArray<double> tab;
+    DevArray<int32_t> rowmap;
+    DevArray<double> dc;    // c | d
+    double* dd = nullptr;   // ... the second half of it
     bool prepared = false;
     // mixed mode (term kind 2): indices of the per-draw terms, on the device
     int32_t npd_terms = 0;
-    int32_t* dpd_terms = nullptr;
+    DevArray<int32_t> dpd_terms;
     // row layout class for the scan's configuration choice (ScanParams::standard_rows / n_complex)
     int32_t row_layout = 0, n_complex = 0;
     // table of the windowed kernel (celerite_block.hip), built on first use for the prepared (c, d)
-    double* btab = nullptr;
-    size_t btab_cap = 0;
+    DevArray<double> btab;
     bool btab_ready = false;
 };
 
 struct pioran_ds {
     pioran_ctx* ctx = nullptr;
     int64_t N = 0;
-    double *t = nullptr, *y = nullptr, *s2 = nullptr;  // device
+    DevMem series;                                     // t | y | s2
+    double *t = nullptr, *y = nullptr, *s2 = nullptr;  // ... and where each begins
     PrepState user, host;
 };
 
@@ -138,23 +177,24 @@ static bool ws_fits(pioran_ctx* ctx, const pioran_ctx::Buf& b, size_t bytes)
     return device_free_bytes(free_b) && bytes <= ws_allow(ctx, free_b) + b.cap;
 }
 
+// `m` holds at least `bytes`: what it held is freed and `want` >= bytes allocated where it did not.  PIORAN_ERR_HIP: the runtime refused the free;
+// PIORAN_ERR_ALLOC: there is no memory, and `m` is empty.
+int grow(pioran_ctx* ctx, DevMem& m, size_t bytes, size_t want)
+{
+    if (bytes <= m.cap) return PIORAN_OK;
+    HIPCHK(ctx, m.release());
+    return m.alloc(want) ? PIORAN_OK : PIORAN_ERR_ALLOC;
+}
+
 int ensure(pioran_ctx* ctx, pioran_ctx::Buf& b, size_t bytes)
 {
-    if (bytes <= b.cap) return PIORAN_OK;
-    if (b.p) HIPCHK(ctx, hipFree(b.p));
-    b.p = nullptr;
-    b.cap = 0;
-    size_t want = bytes + (bytes < (size_t(1) << 28) ? bytes / 4 : 0) + 256;   // growth slack for small buffers only
-    if (hipMalloc(&b.p, want) != hipSuccess) {
-        (void)hipGetLastError();   // the failure is reported through the return code: do not leave it sticky for the callers'
-                                   // shrink-and-retry loops (a later launch wrapper would read it as its own error)
-        b.p = nullptr;
-        ctx->last_err = "hipMalloc failed";
-        return PIORAN_ERR_ALLOC;
-    }
-    b.cap = want;
-    return PIORAN_OK;
+    const int rc = grow(ctx, b, bytes, bytes + (bytes < (size_t(1) << 28) ? bytes / 4 : 0) + 256);   // growth slack for small buffers only
+    if (rc == PIORAN_ERR_ALLOC) ctx->last_err = "hipMalloc failed";
+    return rc;
 }
+
+// ... with no slack: the prepared states' tables and the data set's series keep the size they are asked for
+int ensure_exact(pioran_ctx* ctx, DevMem& m, size_t bytes) { return grow(ctx, m, bytes, bytes); }
 
 struct BufNeed { pioran_ctx::Buf* b; size_t bytes; };
 int ensure_each(pioran_ctx* ctx, std::initializer_list<BufNeed> needs)
@@ -206,6 +246,14 @@ struct PendingGuard {
 
 constexpr size_t kPinMaxRequest = size_t(32) << 20;   // larger transfers go straight from / to the caller's memory
 
+// the pinned staging area back to the runtime (nothing in flight uses it: the callers have synchronised)
+void pin_release(pioran_ctx* ctx)
+{
+    if (ctx->pin) (void)hipHostFree(ctx->pin);
+    ctx->pin = nullptr;
+    ctx->pin_cap = ctx->pin_off = 0;
+}
+
 // bytes of pinned staging, 256-byte aligned; nullptr when the request is too large for staging (or pinning fails)
 void* pin_reserve(pioran_ctx* ctx, size_t bytes)
 {
@@ -214,9 +262,7 @@ void* pin_reserve(pioran_ctx* ctx, size_t bytes)
     if (ctx->pin_off + need > ctx->pin_cap) {
         if (ctx_sync(ctx) != PIORAN_OK) return nullptr;           // nothing in flight uses the old buffer any more
         if (need > ctx->pin_cap) {
-            if (ctx->pin) (void)hipHostFree(ctx->pin);
-            ctx->pin = nullptr;
-            ctx->pin_cap = 0;
+            pin_release(ctx);
             size_t want = need * 4 < (size_t(8) << 20) ? (size_t(8) << 20) : need * 4;
             if (hipHostMalloc((void**)&ctx->pin, want, hipHostMallocDefault) != hipSuccess) { ctx->pin = nullptr; return nullptr; }
             ctx->pin_cap = want;
@@ -554,12 +600,7 @@ std::vector<int32_t> build_rowmap(int64_t J, const int32_t* kind)
 int set_rowmap(pioran_ds* ds, PrepState& s, const std::vector<int32_t>& rm)
 {
     pioran_ctx* ctx = ds->ctx;
-    if (rm.size() > s.rowmap_cap) {
-        if (s.rowmap) HIPCHK(ctx, hipFree(s.rowmap));
-        s.rowmap = nullptr;
-        if (hipMalloc((void**)&s.rowmap, rm.size() * sizeof(int32_t)) != hipSuccess) return PIORAN_ERR_ALLOC;
-        s.rowmap_cap = rm.size();
-    }
+    if (const int rc = ensure_exact(ctx, s.rowmap, rm.size() * sizeof(int32_t))) return rc;
     HIPCHK(ctx, hipMemcpyAsync(s.rowmap, rm.data(), rm.size() * sizeof(int32_t), hipMemcpyHostToDevice,
                                ctx->stream));
     // the host vector is about to go out of scope in the callers: finish the copy first
@@ -638,17 +679,9 @@ int ensure_btab(pioran_ds* ds, PrepState& s)
     // 60 KB per 16 time stamps at J = 20: very long series (or a device short of memory) stay on the other kernels
     const size_t need = pioran_block_table_doubles(ds->N, s.R, s.J);
     if (need * sizeof(double) > (size_t(2) << 30)) return PIORAN_ERR_UNSUPPORTED;
-    if (need > s.btab_cap) {
-        if (s.btab) HIPCHK(ctx, hipFree(s.btab));
-        s.btab = nullptr;
-        s.btab_cap = 0;
-        if (hipMalloc((void**)&s.btab, need * sizeof(double)) != hipSuccess) {
-            (void)hipGetLastError();
-            return PIORAN_ERR_UNSUPPORTED;
-        }
-        s.btab_cap = need;
-    }
-    int rc = ctx->opt.btab_reference
+    int rc = ensure_exact(ctx, s.btab, need * sizeof(double));
+    if (rc) return rc == PIORAN_ERR_ALLOC ? PIORAN_ERR_UNSUPPORTED : rc;
+    rc = ctx->opt.btab_reference
                  ? pioran_launch_block_table_reference(ds->N, s.R, s.J, s.rowmap, ds->t, s.dc, s.dd, ds->y, ds->s2, s.btab, ctx->stream)
                  : pioran_launch_block_table(ds->N, s.R, s.J, s.rowmap, ds->t, s.dc, s.dd, ds->y, ds->s2, s.btab, ctx->stream);
     if (rc) return rc;
@@ -1143,27 +1176,26 @@ int pioran_ctx_destroy(pioran_ctx* ctx)
     if (!ctx) return PIORAN_ERR_ARG;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->scalar_ds) pioran_dataset_destroy(ctx->scalar_ds);
-    ctx->scalar_ds = nullptr;
-    pioran_ctx::Buf* bufs[] = {&ctx->bA, &ctx->bB, &ctx->bC, &ctx->bD, &ctx->bmu, &ctx->bnu, &ctx->bY,
-                               &ctx->bS2, &ctx->bout, &ctx->bst, &ctx->bscratch, &ctx->bK, &ctx->bwork, &ctx->bshift, &ctx->bgtab, &ctx->bq, &ctx->bpair, &ctx->btp, &ctx->btprow, &ctx->brqd, &ctx->brqn, &ctx->breps, &ctx->brqT, &ctx->brstores, &ctx->brxi, &ctx->brf, &ctx->brsout, &ctx->brsst, &ctx->brmaps,
-                               &ctx->brY, &ctx->brS2, &ctx->brshift, &ctx->brres, &ctx->brst, &ctx->bqX, &ctx->bqst, &ctx->bqin, &ctx->bqidx, &ctx->bqout,
-                               &ctx->bthin, &ctx->bthout, &ctx->bpcgrid, &ctx->bpcin, &ctx->bpcdraw, &ctx->bpcout, &ctx->bpcT, &ctx->bpcq, &ctx->bcarma, &ctx->bcarmaout};
-    for (auto* b : bufs)
-        if (b->p) (void)hipFree(b->p);
-    for (auto& e : ctx->ev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& e : ctx->gev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& e : ctx->dev_)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& st : ctx->dstream)
-        if (st) (void)hipStreamDestroy(st);
-    if (ctx->pin) (void)hipHostFree(ctx->pin);
-    if (ctx->aux) (void)hipStreamDestroy(ctx->aux);
-    if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return PIORAN_OK;
+}
+
+// (a context whose creation failed half-way comes here too: what was never created is null)
+pioran_ctx::~pioran_ctx()
+{
+    if (scalar_ds) pioran_dataset_destroy(scalar_ds);
+    for (Buf* b : bufs) (void)b->release();   // before the streams go, as ever; the buffers' own destructors find nothing left
+    for (auto& e : ev)
+        if (e) (void)hipEventDestroy(e);
+    for (auto& e : gev)
+        if (e) (void)hipEventDestroy(e);
+    for (auto& e : dev_)
+        if (e) (void)hipEventDestroy(e);
+    for (auto& st : dstream)
+        if (st) (void)hipStreamDestroy(st);
+    pin_release(this);
+    if (aux) (void)hipStreamDestroy(aux);
+    if (own_stream && stream) (void)hipStreamDestroy(stream);
 }
 
 int pioran_ctx_trim(pioran_ctx* ctx)
@@ -1171,19 +1203,8 @@ int pioran_ctx_trim(pioran_ctx* ctx)
     if (!ctx) return PIORAN_ERR_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     SYNC(ctx);
-    pioran_ctx::Buf* bufs[] = {&ctx->bA, &ctx->bB, &ctx->bC, &ctx->bD, &ctx->bmu, &ctx->bnu, &ctx->bY,
-                               &ctx->bS2, &ctx->bout, &ctx->bst, &ctx->bscratch, &ctx->bK, &ctx->bwork, &ctx->bshift, &ctx->bgtab, &ctx->bq, &ctx->bpair, &ctx->btp, &ctx->btprow,
-                               &ctx->blstab, &ctx->blsaux, &ctx->brqd, &ctx->brqn, &ctx->breps, &ctx->brqT, &ctx->brstores, &ctx->brxi, &ctx->brf, &ctx->brsout, &ctx->brsst, &ctx->brmaps,
-                               &ctx->brY, &ctx->brS2, &ctx->brshift, &ctx->brres, &ctx->brst, &ctx->bqX, &ctx->bqst, &ctx->bqin, &ctx->bqidx, &ctx->bqout,
-                               &ctx->bthin, &ctx->bthout, &ctx->bpcgrid, &ctx->bpcin, &ctx->bpcdraw, &ctx->bpcout, &ctx->bpcT, &ctx->bpcq, &ctx->bcarma, &ctx->bcarmaout};
-    for (auto* b : bufs) {
-        if (b->p) (void)hipFree(b->p);
-        b->p = nullptr;
-        b->cap = 0;
-    }
-    if (ctx->pin) (void)hipHostFree(ctx->pin);
-    ctx->pin = nullptr;
-    ctx->pin_cap = ctx->pin_off = 0;
+    for (pioran_ctx::Buf* b : ctx->bufs) (void)b->release();
+    pin_release(ctx);
     return PIORAN_OK;
 }
 
@@ -1220,8 +1241,8 @@ int pioran_dataset_create(pioran_ctx* ctx, int64_t N, const double* t, const dou
     ds->ctx = ctx;
     ds->N = N;
     const size_t bytes = (size_t)N * sizeof(double);
-    double* base = nullptr;
-    if (hipMalloc((void**)&base, 3 * bytes) != hipSuccess) { delete ds; return PIORAN_ERR_ALLOC; }
+    if (const int rc = ensure_exact(ctx, ds->series, 3 * bytes)) { delete ds; return rc; }
+    double* base = (double*)ds->series.p;
     ds->t = base;
     ds->y = base + N;
     ds->s2 = base + 2 * N;
@@ -1231,7 +1252,6 @@ int pioran_dataset_create(pioran_ctx* ctx, int64_t N, const double* t, const dou
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) {
         ctx->last_err = hipGetErrorString(e);
-        (void)hipFree(base);
         delete ds;
         return PIORAN_ERR_HIP;
     }
@@ -1244,14 +1264,6 @@ int pioran_dataset_destroy(pioran_ds* ds)
     if (!ds) return PIORAN_ERR_ARG;
     (void)hipSetDevice(ds->ctx->device);
     (void)hipStreamSynchronize(ds->ctx->stream);
-    if (ds->t) (void)hipFree(ds->t);
-    for (PrepState* s : {&ds->user, &ds->host}) {
-        if (s->tab) (void)hipFree(s->tab);
-        if (s->btab) (void)hipFree(s->btab);
-        if (s->rowmap) (void)hipFree(s->rowmap);
-        if (s->dc) (void)hipFree(s->dc);
-        if (s->dpd_terms) (void)hipFree(s->dpd_terms);
-    }
     delete ds;
     return PIORAN_OK;
 }
@@ -1277,34 +1289,23 @@ static int prepare_state(pioran_ds* ds, PrepState& s, int64_t J, const double* c
     if (same) return PIORAN_OK;
     s.prepared = false;
     s.btab_ready = false;
-    if ((size_t)J > s.dcd_cap) {
-        if (s.dc) HIPCHK(ctx, hipFree(s.dc));
-        s.dc = nullptr;
-        if (hipMalloc((void**)&s.dc, 2 * (size_t)J * sizeof(double)) != hipSuccess) return PIORAN_ERR_ALLOC;
-        s.dcd_cap = (size_t)J;
-    }
+    int rc = ensure_exact(ctx, s.dc, 2 * (size_t)J * sizeof(double));
+    if (rc) return rc;
     s.dd = s.dc + J;
     s.c_host.assign(c, c + J);
     s.d_host.assign(d, d + J);
     HIPCHK(ctx, hipMemcpyAsync(s.dc, s.c_host.data(), J * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(s.dd, s.d_host.data(), J * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    int rc = set_rowmap(ds, s, build_rowmap(J, real.data()));   // sets s.R
+    rc = set_rowmap(ds, s, build_rowmap(J, real.data()));   // sets s.R
     if (rc) return rc;
     s.npd_terms = (int32_t)pdlist.size();
     if (!pdlist.empty()) {
-        if (!s.dpd_terms && hipMalloc((void**)&s.dpd_terms, 256 * sizeof(int32_t)) != hipSuccess) return PIORAN_ERR_ALLOC;
+        if ((rc = ensure_exact(ctx, s.dpd_terms, 256 * sizeof(int32_t)))) return rc;
         HIPCHK(ctx, hipMemcpyAsync(s.dpd_terms, pdlist.data(), pdlist.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
         SYNC(ctx);
     }
     // the table is per ROW (v, x, phi) + (y_n, sigma2_n) per step, see table.hip
-    const size_t need = pioran_table_doubles(ds->N, s.R);
-    if (need > s.tab_cap) {
-        if (s.tab) HIPCHK(ctx, hipFree(s.tab));
-        s.tab = nullptr;
-        s.tab_cap = 0;
-        if (hipMalloc((void**)&s.tab, need * sizeof(double)) != hipSuccess) return PIORAN_ERR_ALLOC;
-        s.tab_cap = need;
-    }
+    if ((rc = ensure_exact(ctx, s.tab, pioran_table_doubles(ds->N, s.R) * sizeof(double)))) return rc;
     rc = pioran_launch_table(ds->N, s.R, s.rowmap, ds->t, s.dc, s.dd, ds->y, ds->s2, s.tab,
                              rec_stride_of(s.R), ctx->stream);
     if (rc) return rc;

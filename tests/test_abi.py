@@ -69,6 +69,35 @@ def test_launch_path_never_reads_the_environment():
     assert capi.count("getenv(") == body.count("getenv(")     # every read sits inside context creation
 
 
+def _braced(text, head):
+    """the text of the one definition that starts with `head`, up to the brace that closes it"""
+    assert text.count(head) == 1, head
+    start = text.index(head)
+    i = text.index("{", start)
+    depth = 0
+    for j in range(i, len(text)):
+        depth += {"{": 1, "}": -1}.get(text[j], 0)
+        if depth == 0:
+            return text[start:j + 1]
+    raise AssertionError(f"unbalanced braces after {head}")
+
+
+def test_device_memory_has_one_owner():
+    """Every allocation and release of device or pinned memory sits in the owning buffer type (DevMem) or in the two functions of the pinned-staging
+    allocator: what the context, a data set and its prepared states hold is freed by their destructors, and no entry allocates on its own."""
+    csrc = ROOT / "pioran.jl_amd" / "csrc"
+    calls = ("hipMalloc(", "hipFree(", "hipHostMalloc(", "hipHostFree(")
+    hits = [(f.name, i + 1) for f in csrc.glob("*") if f.is_file() for i, line in enumerate(f.read_text().splitlines()) if any(c in line for c in calls)]
+    assert hits and all(name == "capi.hip" for name, _ in hits)
+    capi = (csrc / "capi.hip").read_text()
+    owner = _braced(capi, "struct DevMem {")
+    pinned = _braced(capi, "void pin_release(pioran_ctx* ctx)") + _braced(capi, "void* pin_reserve(pioran_ctx* ctx, size_t bytes)")
+    for c in calls:
+        assert capi.count(c) == owner.count(c) + pinned.count(c)
+    assert owner.count("hipMalloc(") == 1 and owner.count("hipFree(") == 1 and pinned.count("hipHostMalloc(") == 1 and pinned.count("hipHostFree(") == 1
+    assert not any(c in owner for c in calls[2:]) and not any(c in pinned for c in calls[:2])
+
+
 def test_fails_loudly_without_gpu():
     import torch
     if torch.cuda.is_available():

@@ -173,6 +173,37 @@ def test_draw_chunks_share_one_frequency_chunking(irregular):
     assert np.array_equal(parts, whole) and np.array_equal(again, whole)
 
 
+def test_closing_a_context_frees_the_frequency_table():
+    """N = F = 2048, B = 4: the table of the frequency chunk (blstab) is 2 * 2048 * 2048 doubles = 64 MiB before the growth slack.  Contexts that are
+    closed without trim() must give it back: after a warm-up cycle (code object, the runtime's pools), three more cycles of Context, lombscargle,
+    close() may not lower the device's free memory by more than 64 MiB (the margin test_gradient_workspace_is_small leaves for other tenants),
+    where a context that kept its table would lose 192 MiB.  The free memory is device-wide: another process allocating meanwhile can fail this."""
+    import torch
+    N = F = 2048
+    rng = np.random.default_rng(2048)
+    t = np.cumsum(0.05 + rng.exponential(0.95, N))
+    yerr = rng.uniform(0.05, 0.2, N)
+    Y = rng.standard_normal((4, N)) + np.sin(0.3 * t)[None, :]
+    freq = P.reference_grid(t, F + 1)[:-1]
+
+    def cycle():
+        c = pj.Context(0)
+        try:
+            return c.lombscargle(t, Y, yerr, freq)
+        finally:
+            c.close()
+
+    first = cycle()
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    for _ in range(3):
+        last = cycle()
+    free1 = torch.cuda.mem_get_info()[0]
+    print(f"free memory before / after three cycles without trim(): {free0} / {free1} bytes, lost {(free0 - free1) / 2**20:.1f} MiB")
+    assert free1 >= free0 - (64 << 20)
+    assert np.all(np.isfinite(first)) and np.array_equal(last, first)
+
+
 def test_device_form_equals_host_form(ctx, irregular):
     import torch
     t, Y, yerr, freq = irregular
